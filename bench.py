@@ -8,17 +8,24 @@ already resident in HBM: target index build (the reference rebuilds both kd-tree
 odomEstimationNode.cpp:602-603; here once per batch because the submap is shared), 10 x {correspondence +
 normal-equation kernel, solve kernel}, finalize.
 
-  python bench.py --gpus N --steps K --warmup W [--workload cfg1|cfg2|cfg3|cfg4|cfg5|odom]
+  python bench.py --gpus N --steps K --warmup W [--workload cfg1|cfg2|cfg3|cfg4|cfg5|odom] [--dump-outputs DIR] [--full]
 
 Multi-GPU: one process per GPU, independent batches per rank (weak scaling), one RCCL all-gather of the result
 blocks per step.  `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-launches this script under
 `python -m torch.distributed.run --nproc-per-node N` (rendezvous on 127.0.0.1); under a launcher, WORLD_SIZE must
 equal N and N devices must be visible, otherwise the script exits non-zero — it never reports a 1-GPU figure as N.
 
-Prints ONE JSON line (rank 0).  `value` = registrations of all ranks / time of K steps (device-resident inputs).
-If K steps take less than --min-seconds (default 2 s) the K-step loop is repeated R times back to back inside the
-same timed bracket so that samplers see a busy GPU; `ms_per_step` is then the mean over R x K steps and
-`timed_region_s` / `step_loop_repeats` say so.
+Prints ONE JSON line (rank 0).  `value` = registrations of all ranks / time of K steps (device-resident inputs);
+`ms_per_step` = the time of one timed step.  A plain run sets up, warms up, times exactly K steps and prints the line.
+--min-seconds S (default 0: off) repeats the K-step loop R times back to back inside the same timed bracket until it
+lasts S seconds; `ms_per_step` is then the mean over R x K steps and `timed_region_s` / `step_loop_repeats` say so.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy in float32 / float64: rank 0's poses and
+per-registration stats and, at N > 1 ranks, the all-gathered result block of every rank (the trajectory of a sequence
+workload); the inputs are seeded, so two builds can be compared output for output.  Past 64 MB in all, a fixed, seeded
+sample of the rows is written instead, with the sampled row numbers next to each array.
+--full adds everything beside the headline: `roofline` (HIP events around the kernels of the timed loop), and, after the
+timed region, `cpu_baseline` with the oracle parity, `exact_build`, `two_batches_in_flight`, `interleaved_halves` and
+`pcie_inclusive` (--cpu-regs / --no-profile / --no-pcie trim these).
 `roofline.achieved` = algorithmic bytes per launch of the dominant kernel (96 B x point-iterations in the launch,
 BASELINE.md §3) / its average duration measured with HIP events on the library's stream inside the timed region.
 `cpu_baseline` = the CPU oracle (a port of the reference path, kd-tree build included) timed on this host on a
@@ -81,14 +88,25 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=0, help="registrations per GPU per step (0 = the workload's own)")
-    ap.add_argument("--cpu-regs", type=int, default=12, help="registrations per CPU-baseline leg (0 = skip the CPU baseline)")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive leg")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the K-step loop until the timed region is this long")
+    ap.add_argument("--cpu-regs", type=int, default=12, help="with --full: registrations per CPU-baseline leg (0 = skip the CPU baseline)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not record per-kernel HIP events")
+    ap.add_argument("--no-pcie", action="store_true", help="with --full: skip the PCIe-inclusive leg")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the K-step loop until the timed region is this long (default 0: exactly --steps timed steps)")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64): rank 0's outputs, "
+                         "and at N > 1 ranks the all-gathered block of every rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (roofline, CPU baseline and oracle parity, "
+                         "exact-arithmetic build, two batches in flight, interleaved halves, PCIe-inclusive leg)")
     args = ap.parse_args()
+    if not args.full:                   # a plain run: set-up, warm-up, the timed steps, the outputs, the line
+        args.cpu_regs, args.no_profile, args.no_pcie = 0, True, True
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(relaunch_under_torchrun(args.gpus, sys.argv[1:]))
 
@@ -175,11 +193,13 @@ def main():
     if args.workload in ("cfg3", "odom"):
         from lisreg import replay
         fn = replay.bench_sequence if args.workload == "cfg3" else replay.bench_odometry
-        out = fn(dev_index, steps=args.steps, warmup=args.warmup) if rank == 0 else None
+        out = fn(dev_index, steps=args.steps, warmup=args.warmup, roofline=args.full) if rank == 0 else None
         if out is not None:
             frames, recs = out.pop("_frames"), out.pop("_recs")
+            if args.dump_outputs:           # a frame's pose depends on every frame before it: the whole trajectory, the last step's pose last
+                dump_outputs(args.dump_outputs, dict(poses=np.array([rec["T"] for rec in recs])))
             out["cpu_baseline"] = chain_cpu_baseline(args.workload, frames, recs, np) if args.cpu_regs > 0 else None
-            out["pcl_reference"] = pcl_reference_note()
+            out["pcl_reference"] = pcl_reference_note() if args.full else None
         if use_dist:
             dist.barrier(); dist.destroy_process_group()
         if out is not None:
@@ -268,10 +288,12 @@ def main():
         step()
     barrier()
     # how many times the K-step loop must run to fill --min-seconds (decided from a short untimed probe; all ranks agree)
-    t_probe = time.perf_counter()
-    step(); barrier()
-    per_step = max(time.perf_counter() - t_probe, 1e-5)
-    repeats = max(1, int(np.ceil(args.min_seconds / (per_step * args.steps)))) if args.min_seconds > 0 else 1
+    repeats = 1
+    if args.min_seconds > 0:
+        t_probe = time.perf_counter()
+        step(); barrier()
+        per_step = max(time.perf_counter() - t_probe, 1e-5)
+        repeats = max(1, int(np.ceil(args.min_seconds / (per_step * args.steps))))
     ctl_dev = "cpu" if (use_dist and dist.get_backend() == "gloo") else dev
     if use_dist:
         rt = torch.tensor([repeats], dtype=torch.int64, device=ctl_dev)
@@ -302,6 +324,11 @@ def main():
         parts = [torch.empty((batch, lisreg.RESULT_SIZE)) for _ in range(world)]
         dist.all_gather(parts, local_view.cpu())
         gathered = torch.stack(parts)
+    if args.dump_outputs and rank == 0:      # this rank's poses + stats; at N > 1 also every rank's result block as gathered
+        outs = dict(poses=T_gpu, **{f"stats_{k}": [s[k] for s in st_gpu] for k in st_gpu[0]})
+        if use_dist:
+            outs["gathered_results"] = gathered.cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
 
     total_steps = repeats * args.steps
     regs = n_gpus * batch * total_steps
@@ -408,7 +435,7 @@ def main():
 
     # ---- the exact-arithmetic build on the SAME device-resident batch (the parity anchor of tests/test_exact.py), timed ----------
     exact_leg = None
-    if rank == 0 and n_gpus == 1 and not own_targets and not os.environ.get("LISREG_BENCH_NO_EXACT"):
+    if args.full and rank == 0 and n_gpus == 1 and not own_targets and not os.environ.get("LISREG_BENCH_NO_EXACT"):
         cx = lisreg.Context(dev_index)
         cx.set_stream(stream.cuda_stream)
         cx.set_option("rebuild_targets_each_run", 1)
@@ -435,7 +462,7 @@ def main():
     # workgroup per registration; launch gaps) or half busy (the index / row build: latency- and LDS-bound); a second, independent batch on
     # another stream fills them.  Reported next to `value`, never as `value`; poses must equal the single-stream ones.
     overlap_leg = None
-    if rank == 0 and n_gpus == 1 and not own_targets and not os.environ.get("LISREG_BENCH_NO_OVERLAP"):
+    if args.full and rank == 0 and n_gpus == 1 and not own_targets and not os.environ.get("LISREG_BENCH_NO_OVERLAP"):
         lanes = []
         for _ in range(2):
             cx = lisreg.Context(dev_index)
@@ -469,7 +496,7 @@ def main():
     # (bit-identical results).  Off by default — a half-launch's duration is then no longer its own, and `roofline` is made of launch
     # durations — and reported here, next to `value`, with the whole-step fraction it reaches.
     interleave_leg = None
-    if rank == 0 and n_gpus == 1 and not own_targets and not os.environ.get("LISREG_BENCH_NO_OVERLAP"):
+    if args.full and rank == 0 and n_gpus == 1 and not own_targets and not os.environ.get("LISREG_BENCH_NO_OVERLAP"):
         cx = lisreg.Context(dev_index)
         sx = torch.cuda.Stream(device=dev)
         cx.set_stream(sx.cuda_stream)
@@ -543,7 +570,7 @@ def main():
                        "process_group": None if not use_dist else {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                                                                    "pose_gather": "lisreg_comm_init / lisreg_gather_results (the library's own RCCL all-gather)" if native_gather else "torch.distributed " + dist.get_backend(),
                                                                    "comm_nranks": comm_nranks, "ranks": rank_devices}},
-            "roofline": roof, "cpu_baseline": cpu, "pcl_reference": pcl_reference_note(), "pcie_inclusive": pcie, "two_batches_in_flight": overlap_leg, "interleaved_halves": interleave_leg, "exact_build": exact_leg,
+            "roofline": roof, "cpu_baseline": cpu, "pcl_reference": pcl_reference_note() if args.full else None, "pcie_inclusive": pcie, "two_batches_in_flight": overlap_leg, "interleaved_halves": interleave_leg, "exact_build": exact_leg,
             "accuracy": {"max_rot_err_vs_truth_rad": float(err_truth[:, :3].max()),
                          "max_trans_err_vs_truth_m": float(err_truth[:, 3:].max()),
                          "vs_cpu_oracle": parity,
@@ -634,11 +661,11 @@ def bench_icp(args, lisreg, torch, np, synth, synth_torch, dev, dev_index, rank,
             dist.barrier()
         torch.cuda.synchronize()
 
-    warm = max(1, min(args.warmup, 2))
+    warm = args.warmup
     for _ in range(warm):
         step()
     barrier()
-    steps = max(1, min(args.steps, 10))
+    steps = args.steps
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
@@ -649,24 +676,31 @@ def bench_icp(args, lisreg, torch, np, synth, synth_torch, dev, dev_index, rank,
         dist.all_reduce(tt_, op=dist.ReduceOp.MAX)
         elapsed = float(tt_.item())
     res = last["res"]
-    # one more call with HIP events around every k_icp_assoc launch (and chain off, so that the events of ONE run are read)
-    ctx.set_profiling(True)
-    res_p = ctx.icp_align_batch(items, prm, chain_prev_mse=False)
-    timing = ctx.timing()
-    ctx.set_profiling(False)
-    it_sum = int(sum(r["iters"] for r in res_p))
-    launches = int(timing["assoc_launches"])
-    # a launch works on the candidates still iterating: point-iterations actually done = sum over candidates of iterations x points
-    pt_iters = int(sum(r["iters"] * items[k][1][1] for k, r in enumerate(res_p)))
-    avg_ms = timing["assoc_ms"] / max(launches, 1)
-    alg_bytes_launch = ICP_ALG_BYTES_PER_POINT_ITER * pt_iters / max(launches, 1)
-    achieved = alg_bytes_launch / (avg_ms * 1e-3) / 1e9
-    roof = dict(bound="hbm", kernel="k_icp_assoc", achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 5),
-                traffic=None, avg_launch_ms=round(avg_ms, 4), launches=launches,
-                algorithmic_bytes_per_launch=int(alg_bytes_launch),
-                note=f"{ICP_ALG_BYTES_PER_POINT_ITER} B per source point and ICP iteration (16 B read + 16 B working copy written + one 16 B neighbour gather) x the "
-                     f"point-iterations of the candidates still running ({pt_iters} over {launches} launches, {it_sum} candidate-iterations); "
-                     "k = 1 search traffic (grid cells, candidates) is overhead and not counted")
+    if args.dump_outputs and rank == 0:      # this rank's results; at N > 1 also every rank's poses as gathered
+        outs = {k: [r[k] for r in res] for k in res[0]}
+        if use_dist and (native_gather or dist.get_backend() == "nccl"):
+            outs["gathered_poses"] = gathered.cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
+    roof = None
+    if args.full and not args.no_profile:
+        # one more call with HIP events around every k_icp_assoc launch (and chain off, so that the events of ONE run are read)
+        ctx.set_profiling(True)
+        res_p = ctx.icp_align_batch(items, prm, chain_prev_mse=False)
+        timing = ctx.timing()
+        ctx.set_profiling(False)
+        it_sum = int(sum(r["iters"] for r in res_p))
+        launches = int(timing["assoc_launches"])
+        # a launch works on the candidates still iterating: point-iterations actually done = sum over candidates of iterations x points
+        pt_iters = int(sum(r["iters"] * items[k][1][1] for k, r in enumerate(res_p)))
+        avg_ms = timing["assoc_ms"] / max(launches, 1)
+        alg_bytes_launch = ICP_ALG_BYTES_PER_POINT_ITER * pt_iters / max(launches, 1)
+        achieved = alg_bytes_launch / (avg_ms * 1e-3) / 1e9
+        roof = dict(bound="hbm", kernel="k_icp_assoc", achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 5),
+                    traffic=None, avg_launch_ms=round(avg_ms, 4), launches=launches,
+                    algorithmic_bytes_per_launch=int(alg_bytes_launch),
+                    note=f"{ICP_ALG_BYTES_PER_POINT_ITER} B per source point and ICP iteration (16 B read + 16 B working copy written + one 16 B neighbour gather) x the "
+                         f"point-iterations of the candidates still running ({pt_iters} over {launches} launches, {it_sum} candidate-iterations); "
+                         "k = 1 search traffic (grid cells, candidates) is overhead and not counted")
     # accuracy: the correction ICP should find moves the mis-placed key frame onto the map
     err_t = max(float(np.abs(res[k]["T"][:3, 3] - T_fix[k % n_distinct][:3, 3]).max()) for k in range(batch))
     n_conv = int(sum(1 for r in res if r["converged"]))
@@ -710,6 +744,32 @@ def bench_icp(args, lisreg, torch, np, synth, synth_torch, dev, dev_index, rank,
             "roofline": roof, "cpu_baseline": cpu,
             "accuracy": {"converged": n_conv, "candidates": batch, "max_translation_err_vs_truth_m": err_t, "vs_cpu_oracle": parity,
                          "iterations_min_max": [int(min(r["iters"] for r in res)), int(max(r["iters"] for r in res))]}}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy — float32 / float64 as computed, integer and boolean fields as float64 (exact)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {name: np.asarray(a) for name, a in arrays.items()}
+    arrays = {name: a if a.dtype in (np.float32, np.float64) else a.astype(np.float64) for name, a in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        # a fixed, seeded sample of the rows (the same rows in every run of the same arguments), each array next to its row numbers
+        # (float64): the fraction keeps data + row numbers + .npy headers (< 1 KiB a file) within the limit
+        budget = DUMP_LIMIT_BYTES - 2048 * len(arrays)
+        frac = budget / sum(a.nbytes + 8 * len(a) for a in arrays.values() if a.ndim)
+        sampled = {}
+        for name, a in arrays.items():
+            if a.ndim == 0:
+                sampled[name] = a
+                continue
+            rows = np.sort(np.random.default_rng(0).choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            sampled[name], sampled[f"{name}_sample_rows"] = a[rows], rows.astype(np.float64)
+        arrays = sampled
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
 
 
 def pcl_reference_note():

@@ -448,12 +448,12 @@ def _chain_roofline(ctx, make_replayer, frames, src_points_of):
                      "finished-counter")
 
 
-def bench_sequence(device: int, steps: int = 20, warmup: int = 2) -> dict:
+def bench_sequence(device: int, steps: int = 20, warmup: int = 2, roofline: bool = True) -> dict:
     """bench.py --workload cfg3: frames/s of the synthetic drive on the HIP chain (host-inclusive: every frame's sweep crosses
     PCIe, as in the reference's node).  Returns the bench line plus `_frames` / `_recs` (the inputs and the HIP chain's records)
-    for bench.py's CPU-baseline leg."""
+    for bench.py's CPU-baseline leg.  roofline=False skips the second, profiled pass over the frames."""
     import lisreg
-    n = max(steps, 2) + warmup
+    n = max(steps, 1) + warmup                  # exactly `steps` timed frames after the warm-up ones
     frames = [c for c, _ in synthetic_drive(n)]
     truth = [t for _, t in synthetic_drive(n)]
     ctx = lisreg.Context(device)
@@ -471,7 +471,7 @@ def bench_sequence(device: int, steps: int = 20, warmup: int = 2) -> dict:
     dt = time.perf_counter() - t0
     gc.enable()
     err = max(float(np.abs(np.asarray(rec["T"], np.float64)[3:5] - truth[rec["frame"]][3:5]).max()) for rec in recs)
-    roof = _chain_roofline(ctx, lambda: DeviceReplayer(ctx, 2), frames, lambda rec: int(rec["n_src_corner"]) + int(rec["n_src_surf"]))
+    roof = _chain_roofline(ctx, lambda: DeviceReplayer(ctx, 2), frames, lambda rec: int(rec["n_src_corner"]) + int(rec["n_src_surf"])) if roofline else None
     ctx.close()
     # (the CPU baseline of this line — the oracle chain on the first frames — is timed by bench.py: this package never touches oracle/)
     cpu = None
@@ -486,11 +486,11 @@ def bench_sequence(device: int, steps: int = 20, warmup: int = 2) -> dict:
             "_frames": list(frames), "_recs": recs}
 
 
-def bench_odometry(device: int, steps: int = 20, warmup: int = 2) -> dict:
+def bench_odometry(device: int, steps: int = 20, warmup: int = 2, roofline: bool = True) -> dict:
     """bench.py --workload odom: frames/s of the raw-sweep odometry chain on the HIP path (host-inclusive: every sweep crosses
-    PCIe, features and keyframes come back to the host driver as in the reference's node graph)."""
+    PCIe, features and keyframes come back to the host driver as in the reference's node graph).  roofline: see bench_sequence."""
     import lisreg
-    n = max(steps, 2) + warmup
+    n = max(steps, 1) + warmup                  # exactly `steps` timed frames after the warm-up ones
     frames, truth = zip(*synthetic_raw_drive(n))
     ctx = lisreg.Context(device)
     r = DeviceOdomReplayer(ctx)
@@ -504,7 +504,8 @@ def bench_odometry(device: int, steps: int = 20, warmup: int = 2) -> dict:
     dt = time.perf_counter() - t0
     gc.enable()
     err = max(float(np.abs(np.asarray(rec["T"], np.float64)[3:5] - truth[rec["frame"]][3:5]).max()) for rec in recs)
-    roof = _chain_roofline(ctx, lambda: DeviceOdomReplayer(ctx), frames, lambda rec: int(rec.get("n_src_corner", 0)) + int(rec.get("n_src_surf", 0)))
+    roof = (_chain_roofline(ctx, lambda: DeviceOdomReplayer(ctx), frames, lambda rec: int(rec.get("n_src_corner", 0)) + int(rec.get("n_src_surf", 0)))
+            if roofline else None)
     ctx.close()
     cpu = None                                  # timed by bench.py (see bench_sequence)
     return {"metric": "sequential scan-to-map odometry frames/sec (synthetic raw drive, no labels)",

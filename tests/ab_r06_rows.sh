@@ -7,9 +7,9 @@ for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); r=d['roofline']; print('$1', d['value'], d['ms_per_step'], 'frac', r.get('frac'), 'step_frac', r.get('step_frac'), 'front_end', d['config'].get('front_end', d['config'].get('search')))"; }
 for b in 8 12 16 24 32; do for m in 3 5; do
-  LISREG_SEARCH_MODE=$m python bench.py --batch $b --cpu-regs 0 --no-pcie --steps 20 --warmup 5 2>/dev/null | pr "cfg2 batch $b mode $m"
+  LISREG_SEARCH_MODE=$m python bench.py --full --batch $b --cpu-regs 0 --no-pcie --steps 20 --warmup 5 2>/dev/null | pr "cfg2 batch $b mode $m"
 done; done
 for b in 8 16 32; do for m in 3 5; do
-  LISREG_SEARCH_MODE=$m python bench.py --workload cfg5 --batch $b --cpu-regs 0 --no-pcie --steps 8 --warmup 2 2>/dev/null | pr "cfg5 batch $b mode $m"
+  LISREG_SEARCH_MODE=$m python bench.py --full --workload cfg5 --batch $b --cpu-regs 0 --no-pcie --steps 8 --warmup 2 2>/dev/null | pr "cfg5 batch $b mode $m"
 done; done
-LISREG_SEARCH_MODE=5 LISREG_ROW_REACH=0 python bench.py --workload cfg5 --batch 8 --cpu-regs 0 --no-pcie --steps 8 --warmup 2 2>/dev/null | pr "cfg5 batch 8 mode 5 no reach"
+LISREG_SEARCH_MODE=5 LISREG_ROW_REACH=0 python bench.py --full --workload cfg5 --batch 8 --cpu-regs 0 --no-pcie --steps 8 --warmup 2 2>/dev/null | pr "cfg5 batch 8 mode 5 no reach"

@@ -1,11 +1,11 @@
 #!/bin/bash
 # regenerates the bench lines / kernel tables kept under profiles/ (on the GPU box): tests/final_profiles.sh <tag>
 TAG=${1:-r03}; R=$(pwd); O=$R/gpurun_out/final_$TAG; rm -rf $O; mkdir -p $O
-for w in cfg1 cfg3 odom cfg4 cfg5 cfg4_icp; do timeout 300 python bench.py --workload $w 2>/dev/null | tail -1 > $O/${TAG}_bench_$w.json; done
-timeout 300 python bench.py --workload cfg5 --batch 32 2>/dev/null | tail -1 > $O/${TAG}_bench_cfg5_b32.json        # "B >= 8" — both ends reported
-timeout 300 python bench.py 2>/dev/null | tail -1 > $O/${TAG}_bench.json
-LISREG_BENCH_FORCE_DIST=1 timeout 300 python bench.py --steps 10 --warmup 2 --cpu-regs 0 --no-pcie 2>/dev/null | tail -1 > $O/${TAG}_bench_force_dist_1rank.json
-( cd /tmp; export TMPDIR=/tmp; rocprofv3 --output-format csv --kernel-trace --stats -d $O/icp_trace -o trace -- python $R/bench.py --workload cfg4_icp --steps 2 --warmup 1 --cpu-regs 0 > $O/icp_trace.log 2>&1 )
+for w in cfg1 cfg3 odom cfg4 cfg5 cfg4_icp; do timeout 300 python bench.py --full --workload $w 2>/dev/null | tail -1 > $O/${TAG}_bench_$w.json; done
+timeout 300 python bench.py --full --workload cfg5 --batch 32 2>/dev/null | tail -1 > $O/${TAG}_bench_cfg5_b32.json        # "B >= 8" — both ends reported
+timeout 300 python bench.py --full 2>/dev/null | tail -1 > $O/${TAG}_bench.json
+LISREG_BENCH_FORCE_DIST=1 timeout 300 python bench.py --full --steps 10 --warmup 2 --cpu-regs 0 --no-pcie 2>/dev/null | tail -1 > $O/${TAG}_bench_force_dist_1rank.json
+( D=$(mktemp -d); cd $D; export TMPDIR=$D; rocprofv3 --output-format csv --kernel-trace --stats -d $O/icp_trace -o trace -- python $R/bench.py --full --workload cfg4_icp --steps 2 --warmup 1 --cpu-regs 0 > $O/icp_trace.log 2>&1 )
 python - "$O" "$TAG" <<'PY'
 import csv, glob, sys
 O, TAG = sys.argv[1], sys.argv[2]
@@ -55,5 +55,5 @@ PY
 done
 timeout 300 bash tests/timeline.sh > $O/${TAG}_step_timeline.txt 2>&1                  # the kernels of one configs[1] step in order
 timeout 600 python -m pytest tests/test_fit_device.py tests/test_round6_edges.py tests/test_configs.py -m gpu -q -s 2>&1 | grep -E "^\[|\|p\||unit normal|planes through|passed|failed" > $O/${TAG}_new_tests_output.txt
-LISREG_BENCH_OVERSUBSCRIBE=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 10 --warmup 2 2>/dev/null | tail -1 > $O/${TAG}_bench_2ranks_one_gpu.json
+LISREG_BENCH_OVERSUBSCRIBE=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 10 --warmup 2 --full 2>/dev/null | tail -1 > $O/${TAG}_bench_2ranks_one_gpu.json
 ls $O

@@ -2,7 +2,7 @@
 # VALU instruction count and lane utilisation of the lisreg kernels (one rocprofv3 --pmc pass, no tracing).
 set -u
 REPO=$(pwd); OUT=$REPO/gpurun_out/pmc_lanes; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-rocprofv3 --output-format csv --pmc SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS -d $OUT -o pmc -- python $REPO/bench.py --steps 2 --warmup 1 --cpu-regs 0 --no-profile > $OUT/log.txt 2>&1
+rocprofv3 --output-format csv --pmc SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS -d $OUT -o pmc -- python $REPO/bench.py --full --steps 2 --warmup 1 --cpu-regs 0 --no-profile > $OUT/log.txt 2>&1
 cd $REPO
 python - <<'PY'
 import csv,glob,collections

@@ -1,9 +1,15 @@
 """N > 1 path on CPU: world_size-2 gloo run of the sharding + result all-gather used by bench.py on RCCL.
 Each rank registers its shard with the CPU oracle (stand-in for its GPU), the gathered block must equal the
-single-process result for all items, in item order."""
+single-process result for all items, in item order.
+The ranks are started with the standard library's spawn context, so torch is imported in the rank processes only: imported
+into the pytest process after liblisreg.so, torch's wheel maps its own HIP runtime and RCCL next to the system's, and the
+GPU tests that follow in the same process (lisreg_comm_init reuses an RCCL already loaded) would run RCCL on the wrong runtime."""
+import multiprocessing
+import multiprocessing.connection
 import os
 import socket
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -49,18 +55,40 @@ def test_shard_range_partitions():
             assert max(sizes) - min(sizes) <= 1
 
 
+def _spawn(world, port, n_items, out_path, timeout=120.0):
+    """Start the ranks; as soon as one fails (or the time is up) stop the others instead of leaving them blocked in a collective.
+    A failing rank's traceback is on the captured stderr."""
+    ctx = multiprocessing.get_context("spawn")
+    procs = [ctx.Process(target=_worker, args=(rank, world, port, n_items, out_path)) for rank in range(world)]
+    for p in procs:
+        p.start()
+    deadline = time.monotonic() + timeout
+    try:
+        running = {p.sentinel: p for p in procs}
+        while running and time.monotonic() < deadline:
+            for s in multiprocessing.connection.wait(list(running), timeout=max(0.0, deadline - time.monotonic())):
+                running.pop(s).join()
+            if any(p.exitcode not in (None, 0) for p in procs):
+                break
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+            p.join(10)
+    assert [p.exitcode for p in procs] == [0] * world, f"rank exit codes {[p.exitcode for p in procs]} (timeout {timeout} s)"
+
+
 @pytest.mark.timeout(300)
 def test_two_rank_gather_equals_single_process(tmp_path):
-    import torch.multiprocessing as mp
     n_items = 5                      # ragged: 3 + 2
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]
     out2 = str(tmp_path / "w2.npy")
-    mp.spawn(_worker, args=(2, port, n_items, out2), nprocs=2, join=True)
+    _spawn(2, port, n_items, out2)
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]
     out1 = str(tmp_path / "w1.npy")
-    mp.spawn(_worker, args=(1, port, n_items, out1), nprocs=1, join=True)
+    _spawn(1, port, n_items, out1)
     a, b = np.load(out2), np.load(out1)
     assert a.shape == (n_items, 12) and np.array_equal(a, b)
     assert np.all(a[:, 6] == 3) and np.all(np.isin(a[:, 11], (0, 2)))
