@@ -657,6 +657,66 @@ int  lisreg_icp_gn_match(lisreg_ctx* ctx, int slot, const void* source, int n, i
                          unsigned max_iterations, float max_correspond_distance, const float predict_pose[16],
                          lisreg_icpgn_result* result, void* transformed_out);
 
+/* ---- loop-closure candidate detection: FEPSC (src/core/epscGeneration.cpp) -------------------------------------------
+ * EPSCGeneration::loopDetection (:663-992) with UsingFEPSCFlag (config/params.yaml:22-28), as loopClosureThread calls it for every
+ * key frame (subMapOptmizationNode.cpp:2328-2362): its matched_frame_id / matched_frame_transform become loopKeyPre and the EPSC
+ * init pose that seeds the verification ICP (:2796-2805, lisreg_icp_align_batch).  Per key frame: pose and travel gate (:686-745,
+ * in double on the host), then on the device for every gated history frame the 1 x 360 projection yaw search + 2-D ICP (globalICP,
+ * :258-401), the three current clouds moved by its result and binned into the 20 x 80 FEPSC (:478-607), the 20-shift score
+ * (calculateDistance, :633-660), and the first strict maximum above the threshold.  One deliberate deviation: the yaw search wraps
+ * the shifted column modulo 360 (the reference wraps once and reads past its 360-entry row for yaw shifts above 331 sectors).
+ * Clouds: corner / surf LISREG_FMT_XYZI host structs, semantic LISREG_FMT_XYZIL host structs (label = the uint16 at byte 20), or
+ * all three LISREG_FMT_DEVICE records (label in the payload); one format and stride per call. */
+#define LISREG_LOOPDET_MAX_DB   16
+#define LISREG_LOOPDET_NO_SHIFT (-2147483647 - 1)   /* yaw_shift when no shift beat the initial 100000 */
+typedef struct lisreg_loopdet_params {
+    double skip_neighbour_distance;     /* SKIP_NEIBOUR_DISTANCE 20: delta_travel > this */
+    double inflation_covariance;        /* INFLATION_COVARIANCE 0.01: pos_distance < delta_travel * this */
+    double distance_threshold;          /* DISTANCE_THRESHOLD 0.75: score > this */
+} lisreg_loopdet_params;
+typedef struct lisreg_loopdet_frame {
+    const void* corner;  int n_corner;  /* cloud_corner (XYZI) */
+    const void* surf;    int n_surf;    /* cloud_surface (XYZI) */
+    const void* semantic; int n_semantic; /* semantic_raw (XYZIL) */
+    float odom[12];                     /* pclPointToAffine3f(optimized_pose) as a row-major 3 x 4 (lisreg_pose_to_matrix) */
+} lisreg_loopdet_frame;
+typedef struct lisreg_loopdet_result {
+    int    current_frame_id;            /* frames stored before this one */
+    int    n_candidates;                /* gated history frames */
+    int    matched_frame_id;            /* -1: none */
+    int    reserved;
+    float  matched_transform[16];       /* row-major 4 x 4: translation (diff_x, diff_y, 0), rotation about z by the ICP's yaw */
+    double score;                       /* best FEPSC score (0 when none) */
+} lisreg_loopdet_result;
+typedef struct lisreg_loopdet_candidate {
+    int    history_id;
+    int    yaw_shift;                   /* winning column shift of the 1 x 360 search, or LISREG_LOOPDET_NO_SHIFT */
+    float  yaw_angle;                   /* the angle the ICP source is rotated by (shift * step, or the wrapped yaw * step) */
+    int    icp_state, icp_iters, icp_n_corr; /* LISREG_ICP_*, iterations, correspondences of the last one */
+    float  transform[16];               /* trans * trans1, row-major 4 x 4 */
+    int    score_shift;                 /* -10 .. 9, the first strict minimum (0 when none) */
+    int    reserved;
+    double score;                       /* 1 - min difference */
+} lisreg_loopdet_candidate;
+int  lisreg_loopdet_default_params(lisreg_loopdet_params* p);
+/* forget every frame of database db_id (0 .. LISREG_LOOPDET_MAX_DB - 1); databases are independent */
+int  lisreg_loopdet_reset(lisreg_ctx* ctx, int db_id);
+/* loopDetection for frames[0 .. n_frames) in order (frame k sees frames 0 .. k - 1 as history); params NULL = defaults.  results[k]
+ * equals, to the bit, what a call with frame k alone returns after frames 0 .. k - 1.  stride: of the host structs (ignored for
+ * LISREG_FMT_DEVICE); corner / surf may be XYZIL structs too (the label is not read). */
+int  lisreg_loopdet_detect(lisreg_ctx* ctx, int db_id, const lisreg_loopdet_frame* frames, int n_frames, int stride_bytes, int fmt,
+                           const lisreg_loopdet_params* params, lisreg_loopdet_result* results);
+/* every gated candidate of frame k of the last lisreg_loopdet_detect on db_id, in history order: *n_out = their count, at most
+ * cap are written */
+int  lisreg_loopdet_candidates(lisreg_ctx* ctx, int db_id, int k, lisreg_loopdet_candidate* out, int cap, int* n_out);
+/* the stored descriptors of frame frame_id: FEPSC [20 x 80] (row = ring) and the projection [360 x 4] (count, x, y, label) */
+int  lisreg_loopdet_get(lisreg_ctx* ctx, int db_id, int frame_id, uint8_t* fepsc, float* projection);
+/* one frame's descriptors under M (row-major 4 x 4, NULL = the clouds as they are): FEPSC, EPSC, SEPSC [20 x 80] and the
+ * projection [360 x 4] of the moved semantic cloud; any output may be NULL */
+int  lisreg_loop_descriptor(lisreg_ctx* ctx, const void* corner, int n_corner, const void* surf, int n_surf, const void* semantic,
+                            int n_semantic, int stride_bytes, int fmt, const float* M, uint8_t* fepsc, uint8_t* epsc,
+                            uint8_t* sepsc, float* projection);
+
 /* ---- helpers that mirror src/core/common.cpp ------------------------------------------------------------- */
 /* trans2Affine3f (common.cpp:54-57): row-major 3x4 [R|t]. */
 void lisreg_pose_to_matrix(const float T[6], float M[12]);

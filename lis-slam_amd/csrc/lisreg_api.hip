@@ -420,6 +420,7 @@ void lisreg_destroy(lisreg_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     lisreg_comm_destroy(c);
     feeder_destroy(c);
+    loopdet_destroy(c);
     for (auto& t : c->targets) for (int k = 0; k < 2; ++k) { t.raw[k].release(); t.sorted[k].release(); t.cell_start[k].release(); t.nbr[k].release(); t.nbr_meta[k].release();
         t.crow[k].release(); t.crow_meta[k].release(); t.crow_tab[k].release(); t.crow_need[k].release(); t.crow_omask[k].release(); t.crow_scan[k].release(); t.crow_scan_tmp[k].release(); t.crow_qmark[k].release(); t.crow_reach[k].release(); }
     DevBuf* bufs[] = { &c->grids_dev, &c->hist, &c->bucket_start, &c->scan_tmp, &c->elem_bucket, &c->elem_sub,

@@ -92,6 +92,7 @@ struct KeyframeRing {
 };
 
 struct PackPool;           // host feeder threads (lisreg_api_feed.hip)
+struct LoopDet;            // loop-closure candidate databases and their scratch (lisreg_loop.hip)
 struct PackChunk { const unsigned char* src; lisreg_dpoint* dst; int n, stride, fmt; int pinned; };      // <= 64 k points of one host cloud; pinned: the DMA engine may read src
 
 struct RcclApi {
@@ -244,10 +245,13 @@ struct lisreg_ctx {
     lisreg::RcclApi   rccl;
     void*     comm = nullptr;
     int       comm_nranks = 0;
+    // FEPSC loop-closure candidate detection (lisreg_loop.hip): created on first use, released by loopdet_destroy
+    lisreg::LoopDet* loopdet = nullptr;
 };
 
 namespace lisreg {
 void feeder_destroy(lisreg_ctx* c);
+void loopdet_destroy(lisreg_ctx* c);
 int  ctx_fail(lisreg_ctx* c, int code, const std::string& msg);
 // pack PCL structs (stride/format of common.h:9,25-35) into 16-B device records
 void pack_cloud(const void* cloud, int n, int stride, int fmt, lisreg_dpoint* out);

@@ -164,6 +164,38 @@ int main()
         std::printf("updateInitialGuess: T = [%g %g %g %g %g %g]\n", T[0], T[1], T[2], T[3], T[4], T[5]);
         ok = ok && std::fabs(std::sqrt(T[3] * T[3] + T[4] * T[4] + T[5] * T[5]) - 1.f) < 1e-4f && pred[3] == T[3];
     }
+    // EPSCGeneration::loopDetection: two laps of a square drive past the same walls; the second lap's frames are gated against the
+    // first lap's and their FEPSC matches the revisited frame
+    {
+        EPSCGeneration epsc(reg.handle(), 1);
+        auto frame_at = [&](float px, float py, PointCloud<PointXYZI>& c, PointCloud<PointXYZI>& s, PointCloud<PointXYZIL>& m) {
+            for (int k = 0; k < 4000; ++k) {                       // walls of a 60 x 60 m room and 40 poles, seen from (px, py)
+                const float u = -30.f + 60.f * (float)((k * 7919) % 4000) / 4000.f, h = (float)(k % 7);
+                const int side = k % 4;
+                PointXYZIL q{}; q.x = side == 0 ? 30.f : side == 1 ? -30.f : u; q.y = side == 2 ? 30.f : side == 3 ? -30.f : u; q.z = h;
+                q.x -= px; q.y -= py; q.label = 13;
+                m.push_back(q);
+                PointXYZI p{}; p.x = q.x; p.y = q.y; p.z = q.z; s.push_back(p);
+                if (k % 10 == 0) { PointXYZIL r = q; r.x = -20.f + (float)(k % 400) / 10.f - px; r.y = (float)((k / 400) % 10) * 4.f - 18.f - py; r.label = 18; m.push_back(r); p.x = r.x; p.y = r.y; c.push_back(p); }
+            }
+        };
+        int matches = 0, last_id = -1;
+        for (int lap = 0; lap < 2; ++lap)
+            for (int k = 0; k < 12; ++k) {
+                const float a = 6.2831853f * (float)k / 12.f, px = 10.f * std::cos(a), py = 10.f * std::sin(a);
+                PointCloud<PointXYZI> c, s; PointCloud<PointXYZIL> m;
+                frame_at(px, py, c, s, m);
+                const float odom[12] = { 1, 0, 0, px, 0, 1, 0, py, 0, 0, 1, 0 };
+                epsc.loopDetection(c, s, m, odom);
+                last_id = epsc.current_frame_id;
+                if (!epsc.matched_frame_id.empty()) ++matches;
+                if (lap == 0) ok = ok && epsc.matched_frame_id.empty();
+            }
+        std::printf("EPSCGeneration: %d frames, %d loop candidates (last score %g)\n", last_id + 1, matches, epsc.last_score);
+        const bool eok = last_id == 23 && matches >= 6;
+        std::printf(eok ? "EPSCGeneration ok\n" : "EPSCGeneration FAILED\n");
+        ok = ok && eok;
+    }
     std::printf(ok ? "host_smoke ok\n" : "host_smoke FAILED\n");
     return ok ? 0 : 1;
 }

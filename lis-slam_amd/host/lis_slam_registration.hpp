@@ -539,4 +539,41 @@ inline std::vector<lisreg_icp_result> alignLoopCandidates(lisreg_ctx* ctx, const
     return res;
 }
 
+// EPSCGeneration (src/include/epscGeneration.h, src/core/epscGeneration.cpp:663-992) with UsingFEPSCFlag: loopDetection per key frame,
+// the public current_frame_id / matched_frame_id / matched_frame_transform that loopClosureThread reads (subMapOptmizationNode.cpp:
+// 2328-2362).  odom is the row-major 3 x 4 of pclPointToAffine3f(optimized_pose) (lisreg_pose_to_matrix); matched_frame_transform
+// holds row-major 4 x 4 matrices (the EPSC init pose of detectLoopClosureForSubMap, :2796-2805).  The history lives in database
+// db_id of the context, so several generators may share one context.
+class EPSCGeneration {
+public:
+    explicit EPSCGeneration(lisreg_ctx* ctx, int db_id = 0) : ctx_(ctx), db_(db_id) { check(lisreg_loopdet_reset(ctx_, db_)); }
+    void loopDetection(const PointCloud<PointXYZI>& corner_pc, const PointCloud<PointXYZI>& surf_pc, const PointCloud<PointXYZIL>& semantic_pc,
+                       const float odom[12]) {
+        lisreg_loopdet_frame f;
+        f.corner = corner_pc.points.data(); f.n_corner = (int)corner_pc.size();
+        f.surf = surf_pc.points.data(); f.n_surf = (int)surf_pc.size();
+        f.semantic = semantic_pc.points.data(); f.n_semantic = (int)semantic_pc.size();
+        std::memcpy(f.odom, odom, sizeof f.odom);
+        lisreg_loopdet_result r;
+        check(lisreg_loopdet_detect(ctx_, db_, &f, 1, (int)sizeof(PointXYZIL), LISREG_FMT_XYZIL, nullptr, &r));
+        current_frame_id = r.current_frame_id;
+        matched_frame_id.clear();
+        matched_frame_transform.clear();
+        if (r.matched_frame_id >= 0) {
+            matched_frame_id.push_back(r.matched_frame_id);
+            std::vector<float> T(r.matched_transform, r.matched_transform + 16);
+            matched_frame_transform.push_back(T);
+            last_score = r.score;
+        }
+    }
+    int current_frame_id = 0;
+    std::vector<int> matched_frame_id;
+    std::vector<std::vector<float>> matched_frame_transform;
+    double last_score = 0.0;
+private:
+    void check(int rc) { if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_)); }
+    lisreg_ctx* ctx_;
+    int db_;
+};
+
 }  // namespace lis_slam

@@ -38,6 +38,8 @@ ABI_SYMBOLS = [
     "lisreg_localmap_default_params", "lisreg_localmap_reset", "lisreg_localmap_insert", "lisreg_localmap_extract",
     "lisreg_localmap_get", "lisreg_predict_pose", "lisreg_guess_state_init", "lisreg_update_initial_guess", "lisreg_submap_insert", "lisreg_submap_extract", "lisreg_submap_crop_boxes",
     "lisreg_icp_default_params", "lisreg_icp_align", "lisreg_icp_align_batch", "lisreg_icp_gn_match",
+    "lisreg_loopdet_default_params", "lisreg_loopdet_reset", "lisreg_loopdet_detect", "lisreg_loopdet_candidates",
+    "lisreg_loopdet_get", "lisreg_loop_descriptor",
 ]
 
 
@@ -73,6 +75,45 @@ class GuessState(C.Structure):
 
 class IcpItem(C.Structure):
     _fields_ = [("source", C.c_void_p), ("n", C.c_int), ("slot", C.c_int), ("guess", C.POINTER(C.c_float))]
+
+
+LOOPDET_MAX_DB = 16
+LOOPDET_NO_SHIFT = -2 ** 31
+
+
+class LoopdetParams(C.Structure):
+    _fields_ = [("skip_neighbour_distance", C.c_double), ("inflation_covariance", C.c_double), ("distance_threshold", C.c_double)]
+
+
+class LoopdetFrame(C.Structure):
+    _fields_ = [("corner", C.c_void_p), ("n_corner", C.c_int), ("surf", C.c_void_p), ("n_surf", C.c_int),
+                ("semantic", C.c_void_p), ("n_semantic", C.c_int), ("odom", C.c_float * 12)]
+
+
+class LoopdetResult(C.Structure):
+    _fields_ = [("current_frame_id", C.c_int), ("n_candidates", C.c_int), ("matched_frame_id", C.c_int), ("reserved", C.c_int),
+                ("matched_transform", C.c_float * 16), ("score", C.c_double)]
+
+    def as_dict(self):
+        return dict(current_frame_id=self.current_frame_id, n_candidates=self.n_candidates, matched_frame_id=self.matched_frame_id,
+                    matched_transform=np.array(list(self.matched_transform), np.float32).reshape(4, 4), score=self.score)
+
+
+class LoopdetCandidate(C.Structure):
+    _fields_ = [("history_id", C.c_int), ("yaw_shift", C.c_int), ("yaw_angle", C.c_float), ("icp_state", C.c_int),
+                ("icp_iters", C.c_int), ("icp_n_corr", C.c_int), ("transform", C.c_float * 16), ("score_shift", C.c_int),
+                ("reserved", C.c_int), ("score", C.c_double)]
+
+    def as_dict(self):
+        return dict(history_id=self.history_id, yaw_shift=self.yaw_shift, yaw_angle=self.yaw_angle, icp_state=self.icp_state,
+                    icp_iters=self.icp_iters, icp_n_corr=self.icp_n_corr,
+                    transform=np.array(list(self.transform), np.float32).reshape(4, 4), score_shift=self.score_shift, score=self.score)
+
+
+def loopdet_default_params() -> LoopdetParams:
+    p = LoopdetParams()
+    lib().lisreg_loopdet_default_params(C.byref(p))
+    return p
 
 
 class Deskew(C.Structure):
@@ -276,6 +317,14 @@ def lib():
         L.lisreg_icp_gn_match.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_float, fp, C.POINTER(IcpGnResult), vp]
         L.lisreg_icp_align.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams), fp, C.POINTER(IcpResult), vp]
         L.lisreg_icp_align_batch.argtypes = [vp, C.POINTER(IcpItem), C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams), C.c_int, C.POINTER(IcpResult)]
+        u8p = C.POINTER(C.c_uint8)
+        L.lisreg_loopdet_default_params.argtypes = [C.POINTER(LoopdetParams)]
+        L.lisreg_loopdet_reset.argtypes = [vp, C.c_int]
+        L.lisreg_loopdet_detect.argtypes = [vp, C.c_int, C.POINTER(LoopdetFrame), C.c_int, C.c_int, C.c_int, C.POINTER(LoopdetParams),
+                                            C.POINTER(LoopdetResult)]
+        L.lisreg_loopdet_candidates.argtypes = [vp, C.c_int, C.c_int, C.POINTER(LoopdetCandidate), C.c_int, ip]
+        L.lisreg_loopdet_get.argtypes = [vp, C.c_int, C.c_int, u8p, fp]
+        L.lisreg_loop_descriptor.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, fp, u8p, u8p, u8p, fp]
         _lib = L
     return _lib
 
@@ -922,6 +971,75 @@ class Context:
         self._chk(self._L.lisreg_icp_align_batch(self._h, arr, n, stride, FMT_DEVICE if fmt is None else fmt, C.byref(params),
                                                  1 if chain_prev_mse else 0, res))
         return [res[k].as_dict() for k in range(n)]
+
+    # ---- FEPSC loop-closure candidate detection (EPSCGeneration::loopDetection) ----
+    @staticmethod
+    def _loop_clouds(clouds):
+        """(corner, surf, semantic): host PCL struct arrays (one itemsize), or (device_ptr, n) tuples of LISREG_FMT_DEVICE records."""
+        ptrs, ns, fmt, stride = [], [], None, 32
+        for cl in clouds:
+            if isinstance(cl, tuple):
+                ptrs.append(C.c_void_p(cl[0])); ns.append(int(cl[1])); f, st = FMT_DEVICE, 16
+            else:
+                ptrs.append(C.c_void_p(cl.ctypes.data if len(cl) else 0)); ns.append(len(cl)); f, st = FMT_XYZIL, cl.dtype.itemsize
+            if fmt is None:
+                fmt, stride = f, st
+            elif (fmt, stride) != (f, st):
+                raise ValueError("loop detection: one point format per call")
+        return ptrs, ns, fmt, stride
+
+    def loopdet_reset(self, db_id: int = 0):
+        """lisreg_loopdet_reset: forget every frame of database db_id."""
+        self._chk(self._L.lisreg_loopdet_reset(self._h, db_id))
+
+    def loopdet_detect(self, frames, db_id: int = 0, params: "LoopdetParams" = None):
+        """lisreg_loopdet_detect: frames = [(corner, surf, semantic, odom), ...] with odom a row-major 3 x 4 (or 4 x 4) matrix.
+        Returns one result dict per frame."""
+        n = len(frames)
+        arr = (LoopdetFrame * max(n, 1))()
+        keep, fmt, stride = [], FMT_XYZIL, 32
+        for k, (corner, surf, semantic, odom) in enumerate(frames):
+            clouds = [c if isinstance(c, tuple) else np.ascontiguousarray(c) for c in (corner, surf, semantic)]
+            keep.extend(clouds)
+            (p0, p1, p2), (n0, n1, n2), f, st = self._loop_clouds(clouds)
+            if k == 0:
+                fmt, stride = f, st
+            elif (fmt, stride) != (f, st):
+                raise ValueError("loopdet_detect: one point format per call")
+            arr[k].corner, arr[k].n_corner, arr[k].surf, arr[k].n_surf, arr[k].semantic, arr[k].n_semantic = p0, n0, p1, n1, p2, n2
+            o = np.asarray(odom, np.float32).reshape(-1, 4)[:3].ravel()
+            for i in range(12):
+                arr[k].odom[i] = float(o[i])
+        res = (LoopdetResult * max(n, 1))()
+        self._chk(self._L.lisreg_loopdet_detect(self._h, db_id, arr, n, stride, fmt, C.byref(params) if params is not None else None, res))
+        return [res[k].as_dict() for k in range(n)]
+
+    def loopdet_candidates(self, k: int, db_id: int = 0):
+        """lisreg_loopdet_candidates: every gated candidate of frame k of the last detect call, in history order."""
+        cnt = C.c_int(0)
+        self._chk(self._L.lisreg_loopdet_candidates(self._h, db_id, k, None, 0, C.byref(cnt)))
+        out = (LoopdetCandidate * max(cnt.value, 1))()
+        self._chk(self._L.lisreg_loopdet_candidates(self._h, db_id, k, out, cnt.value, C.byref(cnt)))
+        return [out[j].as_dict() for j in range(cnt.value)]
+
+    def loopdet_get(self, frame_id: int, db_id: int = 0):
+        """lisreg_loopdet_get: (FEPSC uint8 [20, 80], projection float32 [360, 4]) stored for frame_id."""
+        d = np.zeros((20, 80), np.uint8)
+        pr = np.zeros((360, 4), np.float32)
+        self._chk(self._L.lisreg_loopdet_get(self._h, db_id, frame_id, d.ctypes.data_as(C.POINTER(C.c_uint8)), pr.ctypes.data_as(C.POINTER(C.c_float))))
+        return d, pr
+
+    def loop_descriptor(self, corner, surf, semantic, M=None):
+        """lisreg_loop_descriptor: dict of fepsc / epsc / sepsc (uint8 [20, 80]) and projection (float32 [360, 4]) under M."""
+        clouds = [c if isinstance(c, tuple) else np.ascontiguousarray(c) for c in (corner, surf, semantic)]
+        (p0, p1, p2), (n0, n1, n2), fmt, stride = self._loop_clouds(clouds)
+        m = None if M is None else np.ascontiguousarray(M, np.float32).ravel()
+        out = {k: np.zeros((20, 80), np.uint8) for k in ("fepsc", "epsc", "sepsc")}
+        out["projection"] = np.zeros((360, 4), np.float32)
+        u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._chk(self._L.lisreg_loop_descriptor(self._h, p0, n0, p1, n1, p2, n2, stride, fmt, None if m is None else m.ctypes.data_as(C.POINTER(C.c_float)),
+                                                 u8(out["fepsc"]), u8(out["epsc"]), u8(out["sepsc"]), out["projection"].ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     def icp_gn_match(self, slot: int, source: np.ndarray, max_iterations: int, max_correspond_distance: float, predict_pose,
                      want_transformed: bool = False):

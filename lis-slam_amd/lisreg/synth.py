@@ -241,3 +241,21 @@ def make_raw_scan(h: int, w: int, seed: int, scene_seed: int = 1234, dup_fractio
     out["ring"] = ring
     out["time"] = np.linspace(0, 0.1, len(xyz), dtype=np.float32)
     return out
+
+
+def make_loop_drive(n_per_lap: int, laps: int, radius: float = 12.0, h: int = 16, w: int = 360, seed: int = 0,
+                    scene_seed: int = 1234, lap_offset: float = 0.05):
+    """Key frames of a multi-lap drive on a circle through the room (loop-closure candidate detection): a list of
+    dict(corner, surf, semantic, odom) — the corner (label 18) / surf (labels 9, 13) clouds of make_scan(labelled=True), their
+    concatenation as the semantic cloud, and odom = the float32 row-major 3 x 4 pose.  Lap l is shifted outwards by l * lap_offset
+    metres and a quarter key-frame spacing along the circle, so revisits are near but never exact."""
+    frames = []
+    for lap in range(laps):
+        for k in range(n_per_lap):
+            th = 2 * np.pi * (k + 0.25 * (lap % 2)) / n_per_lap
+            r = radius + lap * lap_offset
+            T = np.array([0.0, 0.0, th + np.pi / 2, r * np.cos(th), r * np.sin(th), SENSOR_Z], np.float64)
+            s = make_scan(h, w, seed=seed + 1000 * lap + k, scene_seed=scene_seed, labelled=True, T_true=T)
+            frames.append(dict(corner=s["corner"], surf=s["surf"], semantic=concat_clouds([s["corner"], s["surf"]]),
+                               odom=pose_matrix(T)[:3].astype(np.float32)))
+    return frames
