@@ -717,6 +717,47 @@ int  lisreg_loop_descriptor(lisreg_ctx* ctx, const void* corner, int n_corner, c
                             int n_semantic, int stride_bytes, int fmt, const float* M, uint8_t* fepsc, uint8_t* epsc,
                             uint8_t* sepsc, float* projection);
 
+/* ---- loop-closure candidate selectors: the seven Using*Flag of loopDetection (src/include/utility.h:446-452) ---------------
+ * A database detects with the kinds it was configured with; each enabled kind contributes its own best match, and the matched list
+ * is pushed in this bit order (:894-990).  ISC, SC, SSC are computed from the semantic cloud moved by the pair's globalICP
+ * transform (calculateISC / calculateSC / calculateSSC, :403-476, 564-589); EPSC, SEPSC, FEPSC as above.  ISC, SC, EPSC, SEPSC,
+ * FEPSC score with calculateDistance (threshold distance_threshold), SSC with calculateLabelSim (threshold label_threshold; an empty
+ * pair of descriptors scores NaN and is never selected), POSE takes the smallest gate distance.  Deviation: SSC treats labels >= 20
+ * (past order_vec) as order 0.  ISC reads the float intensity at byte 16 of the semantic host structs: ISC with LISREG_FMT_DEVICE
+ * clouds is LISREG_ERR_ARG. */
+#define LISREG_LOOP_ISC   1u
+#define LISREG_LOOP_SC    2u
+#define LISREG_LOOP_EPSC  4u
+#define LISREG_LOOP_SEPSC 8u
+#define LISREG_LOOP_FEPSC 16u
+#define LISREG_LOOP_SSC   32u
+#define LISREG_LOOP_POSE  64u
+#define LISREG_LOOP_KINDS 7                 /* kind index = bit position: ISC 0 .. POSE 6 */
+#define LISREG_LOOP_LABEL_THRESHOLD 0.79    /* LABEL_THRESHOLD (epscGeneration.h:17) */
+typedef struct lisreg_loopdet_match {
+    int    kind;                            /* one LISREG_LOOP_* bit */
+    int    history_id;
+    float  transform[16];                   /* row-major 4 x 4: (diff_x, diff_y, 0) rotated by the kind's angle; SSC / POSE: trans * trans1 */
+    double score;                           /* the kind's score; POSE: the gate's pos_distance */
+} lisreg_loopdet_match;
+typedef struct lisreg_loopdet_kind_scores {
+    int    history_id;
+    int    shift[LISREG_LOOP_KINDS];        /* calculateDistance's first strict minimum, -10 .. 9 (0 for SSC, POSE and disabled kinds) */
+    double score[LISREG_LOOP_KINDS];        /* per kind index; POSE: pos_distance; 0 for disabled kinds */
+} lisreg_loopdet_kind_scores;
+/* select the kinds (a nonzero mask of LISREG_LOOP_* below 128) of database db_id and SSC's threshold; only while the database is
+ * empty (lisreg_loopdet_reset keeps the configuration).  A database never configured is LISREG_LOOP_FEPSC. */
+int  lisreg_loopdet_configure(lisreg_ctx* ctx, int db_id, unsigned kinds, double label_threshold);
+/* the matched list of frame k of the last lisreg_loopdet_detect on db_id (matched_frame_id / matched_frame_transform), push order */
+int  lisreg_loopdet_matches(lisreg_ctx* ctx, int db_id, int k, lisreg_loopdet_match* out, int cap, int* n_out);
+/* every gated candidate of frame k of the last detect, in history order, with the score of every enabled kind */
+int  lisreg_loopdet_candidate_scores(lisreg_ctx* ctx, int db_id, int k, lisreg_loopdet_kind_scores* out, int cap, int* n_out);
+/* the stored (untransformed) descriptor of one enabled kind (ISC .. SSC) of frame frame_id: uint8 [20 x 80], row = ring */
+int  lisreg_loopdet_get_descriptor(lisreg_ctx* ctx, int db_id, int frame_id, unsigned kind, uint8_t* out);
+/* one frame's descriptor of one kind (ISC .. SSC) under M (NULL = the clouds as they are) */
+int  lisreg_loop_descriptor_kind(lisreg_ctx* ctx, unsigned kind, const void* corner, int n_corner, const void* surf, int n_surf,
+                                 const void* semantic, int n_semantic, int stride_bytes, int fmt, const float* M, uint8_t* out);
+
 /* ---- helpers that mirror src/core/common.cpp ------------------------------------------------------------- */
 /* trans2Affine3f (common.cpp:54-57): row-major 3x4 [R|t]. */
 void lisreg_pose_to_matrix(const float T[6], float M[12]);

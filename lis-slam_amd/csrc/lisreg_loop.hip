@@ -1,6 +1,7 @@
-// lisreg_loop.hip — FEPSC loop-closure candidate detection: EPSCGeneration::loopDetection (src/core/epscGeneration.cpp:663-992)
-// with UsingFEPSCFlag, the only descriptor config/params.yaml:22-28 enables.  The host applies the pose / travel gate (:686-745)
-// in double; everything after it is one launch sequence over every (frame, candidate) pair of a call:
+// lisreg_loop.hip — loop-closure candidate detection: EPSCGeneration::loopDetection (src/core/epscGeneration.cpp:663-992) with
+// any of its seven selectors (ISC, SC, EPSC, SEPSC, FEPSC, SSC, Pose; FEPSC alone is config/params.yaml:22-28's default).  The host
+// applies the pose / travel gate (:686-745) in double; everything after it is one launch sequence over every (frame, candidate) pair
+// of a call:
 //   k_loop_project  one workgroup per frame: project() (:84-120), the 1 x 360 table of (count, x, y, label) of labels
 //                   {13, 14, 16, 18, 19}; "the last point wins" is the largest point index per sector, gathered afterwards;
 //   k_loop_icp      one workgroup per gated pair: globalICP (:258-401) — the 60-shift yaw search on the counts, the two sector
@@ -8,16 +9,23 @@
 //                   epsilon 0, relative MSE -DBL_MAX) by brute-force k = 1 (FLANN L2_Simple order, ties to the smaller index) and
 //                   the shared Umeyama step (lisreg_icp_step.hpp); result trans * trans1;
 //   k_loop_bin      the hot path: the whole current frame (corner, surf, semantic) moved by the pair's matrix and binned into four
-//                   20 x 80 integer histograms in LDS (EPSC corner / surf, SEPSC 40|50 / 81), merged with integer atomics;
+//                   20 x 80 integer histograms in LDS (EPSC corner / surf, SEPSC 40|50 / 81), merged with integer atomics; with SC,
+//                   ISC or SSC enabled (the template instance k_loop_bin<true>) also, per cell, the last point whose SC / ISC value
+//                   resets the cell (an index-keyed atomicMax) and the largest SSC order;
+//   k_loop_fold     (SC or ISC only) the semantic cloud again: per cell the largest in-range value after the last reset;
 //   k_loop_finish   the uchar counters (mod 256), 100 * psc / (1 + esc) in int (mod 256), FEPSC = (uchar)(0.4 s + 0.6 e) in double;
-//   k_loop_score    calculateDistance (:633-660): shifts -10 .. 9, first strict minimum;
-//   k_loop_select   per frame, the first strict maximum above the threshold, and the transform of :860-870.
+//                   SC / ISC = max(the reset value or 0, the later in-range maximum), SSC = the label of the largest order;
+//   k_loop_score    per (pair, enabled kind): calculateDistance (:633-660), shifts -10 .. 9, first strict minimum, or
+//                   calculateLabelSim (:611-631) for SSC;
+//   k_loop_select   per frame and kind, the first strict maximum above the threshold (Pose: the first strict minimum of the gate
+//                   distance), the transforms of :771-890 and the matched list in push order (:894-990).
 // The frame's own (untransformed) descriptor is the identity pair of the same launch and goes straight into the database, so a
 // batch of K frames can match frames earlier in the same batch.  Compiled -ffp-contract=off: every float / double operation rounds
 // on its own like the reference's x86 build.
 // Deviation from the reference: globalICP wraps j + i once (`if (new_col >= sectors) new_col -= sectors`), which for a
 // wrapped yaw above 331 sectors (a slightly negative yaw difference) reads past the 360-entry row — undefined behaviour.  Here the
-// column is wrapped modulo 360.
+// column is wrapped modulo 360.  SSC labels >= 20 (past order_vec, undefined behaviour) count as order 0; ISC needs host structs
+// (device records carry the label, not the intensity).
 #include "lisreg_ctx.hpp"
 #include "lisreg_icp_step.hpp"
 
@@ -43,25 +51,50 @@ constexpr unsigned kPscLabels = (1u << 9) | (1u << 10) | (1u << 11) | (1u << 13)
 constexpr unsigned kEscLabels = (1u << 16) | (1u << 18) | (1u << 19);
 constexpr unsigned kProjLabels = (1u << 13) | (1u << 14) | (1u << 16) | (1u << 18) | (1u << 19);
 
+// the seven selectors by kind index (bit position of LISREG_LOOP_*), and the descriptor slots of a pair: FEPSC, EPSC, SEPSC are
+// always computed (slots 0 - 2); SC, ISC, SSC (slots 3 - 5) only when one of them is enabled
+enum { kIsc = 0, kSc, kEpsc, kSepsc, kFepsc, kSsc, kPose, kKinds };
+constexpr int      kDescKinds = 6;
+constexpr int      kSlotOf[kDescKinds] = { 4, 3, 1, 2, 0, 5 };                     // kind index -> descriptor slot
+constexpr unsigned kFoldKinds = LISREG_LOOP_ISC | LISREG_LOOP_SC | LISREG_LOOP_SSC;  // the kinds k_loop_bin<true> is for
+// order_vec (epscGeneration.h:24-25) for labels 0 .. 19; labels >= 20 (past the vector: undefined behaviour) count as order 0
+__constant__ int kOrder[20] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 10, 11, 12, 13, 15, 16, 14, 17, 9, 18, 19 };
+__constant__ int kLabelOfOrder[20] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 17, 9, 10, 11, 12, 15, 13, 14, 16, 18, 19 };
+// per pair, the fold state of k_loop_bin<true> / k_loop_fold (zeroed each call; 0 = nothing yet)
+struct LoopFold {
+    unsigned           reset[2][kCells];     // SC, ISC: ((index + 1) << 8) | the byte the last resetting point stores
+    int                maxv[2][kCells];      // SC: value + 129, ISC: value + 1 — the largest in-range value after that reset
+    int                order[kCells];        // SSC: the largest order_vec value of a point in the cell
+};
+
 struct LoopFrame {
     const float4* pts[3];    // corner, surf, semantic (16-B records, label in the payload of the semantic ones)
+    const float*  inten;     // ISC: the semantic cloud's intensities (host structs only), or null
     float4*       proj;      // where k_loop_project writes the frame's 360 sectors
-    uint8_t*      fepsc;     // where the identity pair's FEPSC goes (the database), or null
+    uint8_t*      db[kDescKinds];     // per descriptor slot, where the identity pair's descriptor goes (the database), or null
     int           n[3];
     int           has_M;     // lisreg_loop_descriptor with a matrix: the identity pair moves the clouds by M
     int           frame_id, cand0, n_cand, pad_;
     float         M[16];
 };
 struct LoopPair {
-    int   frame, hist, kind, tmp_id;                     // kind 0: the frame's own descriptor, 1: a gated candidate
-    float yaw;                                           // yaw difference wrapped into [0, 2 pi) (float, as globalICP)
-    int   pad_[3];
+    int    frame, hist, kind, tmp_id;                    // kind 0: the frame's own descriptor, 1: a gated candidate
+    float  yaw;                                          // yaw difference wrapped into [0, 2 pi) (float, as globalICP)
+    float  yaw_diff;                                     // the same, unwrapped (EPSC's initial angle, :817)
+    double pos_distance;                                 // the gate's distance (Pose)
 };
 struct LoopPairOut {
     float  T[16];
     float  yaw_angle;
     int    yaw_shift, state, iters, n_corr, score_shift;
     double score;
+    double kscore[kDescKinds];                           // per kind index ISC .. SSC (enabled kinds only)
+    int    kshift[kDescKinds];
+};
+// what k_loop_score scores: the enabled descriptor kinds and their databases
+struct LoopScoreKinds {
+    const uint8_t* db[kDescKinds];                       // per kind index
+    int            kind[kDescKinds];                     // blockIdx.y -> kind index
 };
 
 __device__ __forceinline__ void apply_m(const float* M, float x, float y, float z, float& ox, float& oy, float& oz)
@@ -238,9 +271,33 @@ __global__ __launch_bounds__(256) void k_loop_icp(const LoopPair* __restrict__ p
     }
 }
 
-// the three clouds of a pair's frame, moved by the pair's matrix, into 4 x 1600 integer counters (LDS, then global atomics)
+// calculateEPSC's bin of a moved point (ring * 80 + sector), or -1 when it is skipped
+__device__ __forceinline__ int bin_of(float x, float y)
+{
+    const double d = (double)sqrtf(x * x + y * y);
+    if (!(d == d) || d >= kMaxDis || d < kMinDis) return -1;
+    const int ring = (int)floor((d - kMinDis) / kRingStep);
+    const double angle = M_PI + (double)atan2f(y, x);
+    const int sector = (int)floor(angle / kSectorStep);
+    if (ring >= kRings || ring < 0 || sector >= kSectors || sector < 0) return -1;
+    return ring * kSectors + sector;
+}
+
+// (int) of a double / float as the reference's x86 build converts it (cvttsd2si / cvttss2si): NaN and out-of-range give INT_MIN.
+// gfx950's v_cvt_i32_f* saturate and map NaN to 0, so the range is tested first.
+__device__ __forceinline__ int x86_int(double t) { return (t > -2147483649.0 && t < 2147483648.0) ? (int)t : INT_MIN; }
+__device__ __forceinline__ int x86_int(float t) { return (t >= -2147483648.f && t < 2147483648.f) ? (int)t : INT_MIN; }
+// calculateSC's z_temp (LIDAR_HEIGHT 5.0, in double) and calculateISC's intensity_temp (255 * intensity, a float product)
+__device__ __forceinline__ int sc_value(float z) { return x86_int(100.0 * ((double)z + 5.0) / 8.0); }
+__device__ __forceinline__ int isc_value(float intensity) { return x86_int(255.f * intensity); }
+
+// the three clouds of a pair's frame, moved by the pair's matrix, into 4 x 1600 integer counters (LDS, then global atomics).
+// kFold (SC, ISC or SSC enabled): every semantic point is binned, and per cell the last resetting SC / ISC point (`(signed char)
+// s < v` with v >= 128, `(uchar) s < v` with v >= 256 always store v's low byte) and the largest SSC order are kept as well.
+template <bool kFold>
 __global__ __launch_bounds__(256) void k_loop_bin(const LoopPair* __restrict__ pairs, const LoopFrame* __restrict__ frames,
-                                                  const LoopPairOut* __restrict__ pout, int* __restrict__ hist)
+                                                  const LoopPairOut* __restrict__ pout, int* __restrict__ hist, LoopFold* __restrict__ fold,
+                                                  unsigned kinds)
 {
     __shared__ int h[kHist];
     __shared__ float sM[16];
@@ -254,33 +311,72 @@ __global__ __launch_bounds__(256) void k_loop_bin(const LoopPair* __restrict__ p
     const bool moved = P.kind == 1 || F.has_M;
     for (int k = threadIdx.x; k < kHist; k += 256) h[k] = 0;
     if (threadIdx.x < 16) sM[threadIdx.x] = P.kind == 1 ? pout[p].T[threadIdx.x] : F.M[threadIdx.x];
-    __syncthreads();
-    const int end = (int)(total - base < kBinChunk ? total - base : kBinChunk);
-    for (int l = threadIdx.x; l < end; l += 256) {
-        const long long g = base + l;
-        int cl, i;
-        if (g < n0) { cl = 0; i = (int)g; } else if (g < (long long)n0 + n1) { cl = 1; i = (int)(g - n0); } else { cl = 2; i = (int)(g - n0 - n1); }
-        const float4 q = F.pts[cl][i];
-        int slot;
-        if (cl == 2) {
-            const int lab = label_of(q);
-            if (lab >= 32) continue;
-            slot = ((kPscLabels >> lab) & 1u) ? 2 : (((kEscLabels >> lab) & 1u) ? 3 : -1);
-            if (slot < 0) continue;
-        } else {
-            slot = cl;
+    if constexpr (!kFold) {
+        __syncthreads();
+        const int end = (int)(total - base < kBinChunk ? total - base : kBinChunk);
+        for (int l = threadIdx.x; l < end; l += 256) {
+            const long long g = base + l;
+            int cl, i;
+            if (g < n0) { cl = 0; i = (int)g; } else if (g < (long long)n0 + n1) { cl = 1; i = (int)(g - n0); } else { cl = 2; i = (int)(g - n0 - n1); }
+            const float4 q = F.pts[cl][i];
+            int slot;
+            if (cl == 2) {
+                const int lab = label_of(q);
+                if (lab >= 32) continue;
+                slot = ((kPscLabels >> lab) & 1u) ? 2 : (((kEscLabels >> lab) & 1u) ? 3 : -1);
+                if (slot < 0) continue;
+            } else {
+                slot = cl;
+            }
+            float x = q.x, y = q.y, z = q.z;
+            if (moved) apply_m(sM, q.x, q.y, q.z, x, y, z);
+            const int cell = bin_of(x, y);
+            if (cell < 0) continue;
+            atomicAdd(&h[slot * kCells + cell], 1);
         }
-        float x = q.x, y = q.y, z = q.z;
-        if (moved) apply_m(sM, q.x, q.y, q.z, x, y, z);
-        const double d = (double)sqrtf(x * x + y * y);
-        if (!(d == d) || d >= kMaxDis || d < kMinDis) continue;
-        const int ring = (int)floor((d - kMinDis) / kRingStep);
-        const double angle = M_PI + (double)atan2f(y, x);
-        const int sector = (int)floor(angle / kSectorStep);
-        if (ring >= kRings || ring < 0 || sector >= kSectors || sector < 0) continue;
-        atomicAdd(&h[slot * kCells + ring * kSectors + sector], 1);
+        __syncthreads();
+    } else {
+        __shared__ unsigned rk[2][kCells];
+        __shared__ int ord[kCells];
+        for (int k = threadIdx.x; k < kCells; k += 256) { rk[0][k] = 0; rk[1][k] = 0; ord[k] = 0; }
+        __syncthreads();
+        const bool want_sc = kinds & LISREG_LOOP_SC, want_isc = kinds & LISREG_LOOP_ISC, want_ssc = kinds & LISREG_LOOP_SSC;
+        const int end = (int)(total - base < kBinChunk ? total - base : kBinChunk);
+        for (int l = threadIdx.x; l < end; l += 256) {
+            const long long g = base + l;
+            int cl, i;
+            if (g < n0) { cl = 0; i = (int)g; } else if (g < (long long)n0 + n1) { cl = 1; i = (int)(g - n0); } else { cl = 2; i = (int)(g - n0 - n1); }
+            const float4 q = F.pts[cl][i];
+            int slot = cl, lab = 0;
+            if (cl == 2) {
+                lab = label_of(q);
+                slot = lab >= 32 ? -1 : ((kPscLabels >> lab) & 1u) ? 2 : (((kEscLabels >> lab) & 1u) ? 3 : -1);
+            }
+            float x = q.x, y = q.y, z = q.z;
+            if (moved) apply_m(sM, q.x, q.y, q.z, x, y, z);
+            const int cell = bin_of(x, y);
+            if (cell < 0) continue;
+            if (slot >= 0) atomicAdd(&h[slot * kCells + cell], 1);
+            if (cl != 2) continue;
+            const unsigned key = (unsigned)(i + 1) << 8;                  // i + 1 < 2^24 (run_launch)
+            if (want_sc) {
+                const int v = sc_value(z);
+                if (v >= 128) atomicMax(&rk[0][cell], key | (unsigned)(v & 255));
+            }
+            if (want_isc) {
+                const int v = isc_value(F.inten[i]);
+                if (v >= 256) atomicMax(&rk[1][cell], key | (unsigned)(v & 255));
+            }
+            if (want_ssc && lab < 20 && kOrder[lab] > 0) atomicMax(&ord[cell], kOrder[lab]);
+        }
+        __syncthreads();
+        LoopFold& fo = fold[p];
+        for (int k = threadIdx.x; k < kCells; k += 256) {
+            if (rk[0][k]) atomicMax(&fo.reset[0][k], rk[0][k]);
+            if (rk[1][k]) atomicMax(&fo.reset[1][k], rk[1][k]);
+            if (ord[k]) atomicMax(&fo.order[k], ord[k]);
+        }
     }
-    __syncthreads();
     int* out = hist + (size_t)p * kHist;
     for (int k = threadIdx.x; k < kHist; k += 256) {
         const int v = h[k];
@@ -288,37 +384,117 @@ __global__ __launch_bounds__(256) void k_loop_bin(const LoopPair* __restrict__ p
     }
 }
 
-// calculateEPSC / calculateSEPSC / calculateFEPSC from the counters: desc[p] = FEPSC, EPSC, SEPSC (1600 bytes each)
+// SC / ISC after k_loop_bin<true>: per cell the largest in-range value (SC -128 .. 127, ISC 0 .. 255) of the points after the cell's
+// last reset (every point when none).  Values below the range (v <= -129, v < 0, INT_MIN) never change a cell.
+__global__ __launch_bounds__(256) void k_loop_fold(const LoopPair* __restrict__ pairs, const LoopFrame* __restrict__ frames,
+                                                   const LoopPairOut* __restrict__ pout, LoopFold* __restrict__ fold, unsigned kinds)
+{
+    __shared__ int after[2][kCells], mx[2][kCells];
+    __shared__ float sM[16];
+    const int p = blockIdx.x;
+    const LoopPair P = pairs[p];
+    const LoopFrame& F = frames[P.frame];
+    const int n = F.n[2];
+    const int base = (int)blockIdx.y * kBinChunk;
+    if (base >= n) return;
+    const bool moved = P.kind == 1 || F.has_M;
+    LoopFold& fo = fold[p];
+    for (int k = threadIdx.x; k < kCells; k += 256) {
+        after[0][k] = (int)(fo.reset[0][k] >> 8); after[1][k] = (int)(fo.reset[1][k] >> 8);     // index + 1 of the last reset, or 0
+        mx[0][k] = 0; mx[1][k] = 0;
+    }
+    if (threadIdx.x < 16) sM[threadIdx.x] = P.kind == 1 ? pout[p].T[threadIdx.x] : F.M[threadIdx.x];
+    __syncthreads();
+    const bool want_sc = kinds & LISREG_LOOP_SC, want_isc = kinds & LISREG_LOOP_ISC;
+    const int end = n - base < kBinChunk ? n - base : kBinChunk;
+    for (int l = threadIdx.x; l < end; l += 256) {
+        const int i = base + l;
+        const float4 q = F.pts[2][i];
+        float x = q.x, y = q.y, z = q.z;
+        if (moved) apply_m(sM, q.x, q.y, q.z, x, y, z);
+        const int cell = bin_of(x, y);
+        if (cell < 0) continue;
+        if (want_sc && i >= after[0][cell]) {
+            const int v = sc_value(z);
+            if (v >= -128 && v <= 127) atomicMax(&mx[0][cell], v + 129);
+        }
+        if (want_isc && i >= after[1][cell]) {
+            const int v = isc_value(F.inten[i]);
+            if (v >= 0 && v <= 255) atomicMax(&mx[1][cell], v + 1);
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < kCells; k += 256) {
+        if (mx[0][k]) atomicMax(&fo.maxv[0][k], mx[0][k]);
+        if (mx[1][k]) atomicMax(&fo.maxv[1][k], mx[1][k]);
+    }
+}
+
+// calculateEPSC / calculateSEPSC / calculateFEPSC from the counters, and with fold state calculateSC / calculateISC / calculateSSC:
+// desc[p] = nd descriptor slots of 1600 bytes (FEPSC, EPSC, SEPSC [, SC, ISC, SSC])
 __global__ __launch_bounds__(256) void k_loop_finish(const LoopPair* __restrict__ pairs, const LoopFrame* __restrict__ frames,
-                                                     const int* __restrict__ hist, uint8_t* __restrict__ desc)
+                                                     const int* __restrict__ hist, const LoopFold* __restrict__ fold, int nd,
+                                                     uint8_t* __restrict__ desc)
 {
     const int p = blockIdx.x;
     const LoopPair P = pairs[p];
-    uint8_t* fepsc_db = P.kind == 0 ? frames[P.frame].fepsc : nullptr;
+    const LoopFrame& F = frames[P.frame];
+    const bool own = P.kind == 0;
     const int* h = hist + (size_t)p * kHist;
-    uint8_t* d = desc + (size_t)p * 3 * kCells;
+    uint8_t* d = desc + (size_t)p * nd * kCells;
     for (int c = threadIdx.x; c < kCells; c += 256) {
         const int e1 = h[c] & 255, p1 = h[kCells + c] & 255, p2 = h[2 * kCells + c] & 255, e2 = h[3 * kCells + c] & 255;   // uchar ++
         const uint8_t epsc = (uint8_t)(100 * p1 / (1 + e1)), sepsc = (uint8_t)(100 * p2 / (1 + e2));
         const uint8_t fepsc = (uint8_t)(sepsc * 0.4 + epsc * 0.6);
-        d[c] = fepsc; d[kCells + c] = epsc; d[2 * kCells + c] = sepsc;
-        if (fepsc_db) fepsc_db[c] = fepsc;
+        uint8_t v[kDescKinds] = { fepsc, epsc, sepsc, 0, 0, 0 };
+        if (nd > 3) {
+            const LoopFold& fo = fold[p];
+            const unsigned r0 = fo.reset[0][c], r1 = fo.reset[1][c];
+            int sc = r0 ? (int)(signed char)(uint8_t)(r0 & 255) : 0;          // the resetting point's byte, read as a signed char
+            if (fo.maxv[0][c]) sc = max(sc, fo.maxv[0][c] - 129);
+            int isc = r1 ? (int)(r1 & 255) : 0;
+            if (fo.maxv[1][c]) isc = max(isc, fo.maxv[1][c] - 1);
+            v[3] = (uint8_t)sc; v[4] = (uint8_t)isc; v[5] = (uint8_t)kLabelOfOrder[fo.order[c]];
+        }
+        for (int s = 0; s < nd; ++s) {
+            d[s * kCells + c] = v[s];
+            if (own && F.db[s]) F.db[s][c] = v[s];
+        }
     }
 }
 
-// calculateDistance(FEPSCArr[hist], FEPSC_cur): shifts -10 .. 9 of the current descriptor's columns
-__global__ __launch_bounds__(256) void k_loop_score(int cand0, const LoopPair* __restrict__ pairs, const uint8_t* __restrict__ db_fepsc,
+// per (gated pair, enabled kind): calculateDistance(desc_db[hist], desc_cur) — shifts -10 .. 9 of the current descriptor's columns —
+// or, for SSC, calculateLabelSim (no shift; 0 / 0 = NaN when both descriptors are empty)
+__global__ __launch_bounds__(256) void k_loop_score(int cand0, const LoopPair* __restrict__ pairs, LoopScoreKinds ks, int nd,
                                                     const uint8_t* __restrict__ desc, LoopPairOut* __restrict__ pout)
 {
     __shared__ uint8_t d1[kCells], d2[kCells];
     __shared__ int cnt[20];
     const int p = cand0 + (int)blockIdx.x;
+    const int kind = ks.kind[blockIdx.y];
     const LoopPair P = pairs[p];
-    const uint8_t* a = db_fepsc + (size_t)P.hist * kCells;
-    const uint8_t* b = desc + (size_t)p * 3 * kCells;
+    const uint8_t* a = ks.db[kind] + (size_t)P.hist * kCells;
+    const uint8_t* b = desc + ((size_t)p * nd + kSlotOf[kind]) * kCells;
     for (int c = threadIdx.x; c < kCells; c += 256) { d1[c] = a[c]; d2[c] = b[c]; }
     if (threadIdx.x < 20) cnt[threadIdx.x] = 0;
     __syncthreads();
+    if (kind == kSsc) {
+        int valid = 0, same = 0;
+        for (int c = threadIdx.x; c < kCells; c += 256) {
+            const int v1 = d1[c], v2 = d2[c];
+            if (v1 == 0 && v2 == 0) continue;
+            ++valid;
+            same += v1 == v2;
+        }
+        for (int m = 32; m >= 1; m >>= 1) { valid += __shfl_xor(valid, m, 64); same += __shfl_xor(same, m, 64); }
+        if ((threadIdx.x & 63) == 0) { atomicAdd(&cnt[0], valid); atomicAdd(&cnt[1], same); }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            pout[p].kscore[kSsc] = (double)cnt[1] / (double)cnt[0];
+            pout[p].kshift[kSsc] = 0;
+        }
+        return;
+    }
     int part[20];
 #pragma unroll
     for (int s = 0; s < 20; ++s) part[s] = 0;
@@ -346,35 +522,75 @@ __global__ __launch_bounds__(256) void k_loop_score(int cand0, const LoopPair* _
             const double t = ((double)cnt[s]) / (kSectors * kRings * 255);
             if (t < difference) { difference = t; shift = s - 10; }
         }
-        pout[p].score = 1 - difference;
-        pout[p].score_shift = shift;
+        pout[p].kscore[kind] = 1 - difference;
+        pout[p].kshift[kind] = shift;
+        if (kind == kFepsc) {
+            pout[p].score = 1 - difference;
+            pout[p].score_shift = shift;
+        }
     }
 }
 
-// best FEPSC candidate per frame (score > threshold && score > best: the first strict maximum) and its transform (:860-870)
+// Identity().translation() << x, y, 0; rotate(AngleAxisf(angle, UnitZ())): row-major 4 x 4
+__device__ void planar_transform(float x, float y, float angle, float* M)
+{
+    const float c = cosf(angle), s = sinf(angle);
+    for (int i = 0; i < 16; ++i) M[i] = (i % 5 == 0) ? 1.f : 0.f;
+    M[0] = c; M[1] = -s; M[3] = x;
+    M[4] = s; M[5] = c;  M[7] = y;
+    M[10] = (1.f - c) + c;
+}
+
+// per frame: every enabled kind's first strict maximum above its threshold (Pose: the first strict minimum of the gate distance
+// below 1000000), the transforms of :771-890, the matched list in push order (ISC, SC, EPSC, SEPSC, FEPSC, SSC, Pose) and the FEPSC
+// result of lisreg_loopdet_detect (-1 / identity / 0 when FEPSC is not enabled)
 __global__ __launch_bounds__(64) void k_loop_select(const LoopFrame* __restrict__ frames, int n_frames, const LoopPair* __restrict__ pairs,
-                                                    const LoopPairOut* __restrict__ pout, double threshold, lisreg_loopdet_result* __restrict__ res)
+                                                    const LoopPairOut* __restrict__ pout, unsigned kinds, double threshold, double label_threshold,
+                                                    lisreg_loopdet_result* __restrict__ res, lisreg_loopdet_match* __restrict__ match,
+                                                    int* __restrict__ n_match)
 {
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= n_frames) return;
     const LoopFrame& F = frames[k];
-    double best = 0.0;
-    int id = -1, at = -1;
-    for (int c = F.cand0; c < F.cand0 + F.n_cand; ++c) {
-        const double s = pout[c].score;
-        if (s > threshold && s > best) { best = s; id = pairs[c].hist; at = c; }
-    }
     lisreg_loopdet_result r;
-    r.current_frame_id = F.frame_id; r.n_candidates = F.n_cand; r.matched_frame_id = id; r.reserved = 0; r.score = best;
+    r.current_frame_id = F.frame_id; r.n_candidates = F.n_cand; r.matched_frame_id = -1; r.reserved = 0; r.score = 0.0;
     for (int i = 0; i < 16; ++i) r.matched_transform[i] = (i % 5 == 0) ? 1.f : 0.f;
-    if (at >= 0) {
-        // getTranslationAndEulerAngles(transform): x, y, yaw = atan2(m10, m00); Identity().translation() << x, y, 0; rotate(yaw about z)
+    int nm = 0;
+    for (int kind = 0; kind < kKinds; ++kind) {
+        if (!((kinds >> kind) & 1u)) continue;
+        double best = kind == kPose ? 1000000.0 : 0.0;
+        int at = -1;
+        for (int c = F.cand0; c < F.cand0 + F.n_cand; ++c) {
+            if (kind == kPose) {
+                const double s = pairs[c].pos_distance;
+                if (s < best) { best = s; at = c; }
+            } else {
+                const double s = pout[c].kscore[kind];
+                if (s > (kind == kSsc ? label_threshold : threshold) && s > best) { best = s; at = c; }
+            }
+        }
+        if (at < 0) continue;
+        lisreg_loopdet_match& m = match[(size_t)k * kKinds + nm++];
+        m.kind = 1 << kind; m.history_id = pairs[at].hist; m.score = best;
         const float* T = pout[at].T;
-        const float yaw = atan2f(T[4], T[0]), c = cosf(yaw), s = sinf(yaw);
-        r.matched_transform[0] = c; r.matched_transform[1] = -s; r.matched_transform[3] = T[3];
-        r.matched_transform[4] = s; r.matched_transform[5] = c;  r.matched_transform[7] = T[7];
-        r.matched_transform[10] = (1.f - c) + c;
+        if (kind == kSsc || kind == kPose) {
+            for (int i = 0; i < 16; ++i) m.transform[i] = T[i];
+            continue;
+        }
+        // getTranslationAndEulerAngles(transform): x, y, angle = atan2(m10, m00).  ISC, SC, SEPSC: calculateDistance refines the
+        // double angle by shift * sector_step (every selected score improved on 1.0); EPSC starts from the unwrapped yaw_diff
+        // instead; FEPSC keeps the ICP's angle
+        const float angle = atan2f(T[4], T[0]);
+        float a = angle;
+        if (kind == kEpsc) a = (float)((double)pairs[at].yaw_diff + pout[at].kshift[kind] * kSectorStep);
+        else if (kind != kFepsc) a = (float)((double)angle + pout[at].kshift[kind] * kSectorStep);
+        planar_transform(T[3], T[7], a, m.transform);
+        if (kind == kFepsc) {
+            r.matched_frame_id = m.history_id; r.score = best;
+            for (int i = 0; i < 16; ++i) r.matched_transform[i] = m.transform[i];
+        }
     }
+    n_match[k] = nm;
     res[k] = r;
 }
 
@@ -387,23 +603,34 @@ int bad(lisreg_ctx* c, const char* msg) { return ctx_fail(c, LISREG_ERR_ARG, msg
 struct LoopDb {
     std::vector<double> px, py, travel;       // posArr (x, y; z is 0), travelDistanceArr
     std::vector<float>  yaw;                  // yawArr
-    DevBuf proj, fepsc;                       // ProjectArr (float4 [360] per frame), FEPSCArr (uchar [1600] per frame)
+    DevBuf proj, desc[kDescKinds];            // ProjectArr (float4 [360] per frame); per descriptor slot of an enabled kind, its
+                                              // *Arr (uchar [1600] per frame)
     int cap = 0;
-    std::vector<std::vector<lisreg_loopdet_candidate>> last;     // candidates of every frame of the last detect call
+    unsigned kinds = LISREG_LOOP_FEPSC;       // lisreg_loopdet_configure
+    double label_threshold = LISREG_LOOP_LABEL_THRESHOLD;
+    std::vector<std::vector<lisreg_loopdet_candidate>> last;       // candidates of every frame of the last detect call
+    std::vector<std::vector<lisreg_loopdet_kind_scores>> last_scores;
+    std::vector<std::vector<lisreg_loopdet_match>> last_match;     // matched lists of every frame of the last detect call
     int n() const { return (int)px.size(); }
+    bool stores(int slot) const
+    {
+        for (int k = 0; k < kDescKinds; ++k) if (kSlotOf[k] == slot) return (kinds >> k) & 1u;
+        return false;
+    }
 };
 
 struct LoopDet {
     LoopDb db[LISREG_LOOPDET_MAX_DB];
-    DevBuf in, hist, desc, out, proj_tmp;     // the call's upload (tables + host clouds), counters, descriptors, results
+    DevBuf in, hist, desc, out, proj_tmp, fold;   // the call's upload (tables + host clouds), counters, descriptors, results, fold state
     std::vector<unsigned char> h_in, h_out;
 };
 
 void loopdet_destroy(lisreg_ctx* c)
 {
     if (!c->loopdet) return;
-    for (auto& d : c->loopdet->db) { d.proj.release(); d.fepsc.release(); }
+    for (auto& d : c->loopdet->db) { d.proj.release(); for (auto& b : d.desc) b.release(); }
     c->loopdet->in.release(); c->loopdet->hist.release(); c->loopdet->desc.release(); c->loopdet->out.release(); c->loopdet->proj_tmp.release();
+    c->loopdet->fold.release();
     delete c->loopdet;
     c->loopdet = nullptr;
 }
@@ -421,21 +648,25 @@ int db_reserve(lisreg_ctx* c, LoopDb& d, int need)
 {
     if (need <= d.cap) return LISREG_OK;
     const int cap = std::max(need, std::max(64, 2 * d.cap));
-    DevBuf np, nf;
-    if (np.ensure(sizeof(float4) * kProj * (size_t)cap) != hipSuccess || nf.ensure((size_t)kCells * cap) != hipSuccess) {
-        np.release(); nf.release();
-        return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: device allocation failed");
-    }
+    DevBuf np, nd[kDescKinds];
+    auto drop = [&]() { np.release(); for (auto& b : nd) b.release(); };
+    bool ok = np.ensure(sizeof(float4) * kProj * (size_t)cap) == hipSuccess;
+    for (int s = 0; s < kDescKinds && ok; ++s)
+        if (d.stores(s)) ok = nd[s].ensure((size_t)kCells * cap) == hipSuccess;
+    if (!ok) { drop(); return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: device allocation failed"); }
     const int n = d.n();
     hipError_t e = hipSuccess;
     if (n > 0) {
         e = hipMemcpyAsync(np.p, d.proj.p, sizeof(float4) * kProj * (size_t)n, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(nf.p, d.fepsc.p, (size_t)kCells * n, hipMemcpyDeviceToDevice, c->stream);
+        for (int s = 0; s < kDescKinds && e == hipSuccess; ++s)
+            if (d.stores(s)) e = hipMemcpyAsync(nd[s].p, d.desc[s].p, (size_t)kCells * n, hipMemcpyDeviceToDevice, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { np.release(); nf.release(); return ctx_fail(c, LISREG_ERR_HIP, std::string("loopdet: ") + hipGetErrorString(e)); }
-    d.proj.release(); d.fepsc.release();
-    d.proj = np; d.fepsc = nf; d.cap = cap;
+    if (e != hipSuccess) { drop(); return ctx_fail(c, LISREG_ERR_HIP, std::string("loopdet: ") + hipGetErrorString(e)); }
+    d.proj.release();
+    d.proj = np;
+    for (int s = 0; s < kDescKinds; ++s) { d.desc[s].release(); d.desc[s] = nd[s]; }
+    d.cap = cap;
     return LISREG_OK;
 }
 
@@ -453,34 +684,45 @@ size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 struct FrameIn { const void* ptr[3]; int n[3]; };
 
 // the launch sequence of one call: K frames (their own descriptors = pairs 0 .. K - 1), then the gated pairs.  frames / pairs are
-// filled except for the cloud and output pointers, which are set here.  Results are read back into h_out: LoopPairOut [P] then
-// lisreg_loopdet_result [K] (detect) — the caller has synchronised when this returns OK.
+// filled except for the cloud and output pointers, which are set here.  kinds: the enabled selectors (the descriptors computed and,
+// with a database, stored and scored).  Results are read back into h_out: LoopPairOut [P], lisreg_loopdet_result [K],
+// lisreg_loopdet_match [K][7], int [K] (detect) — the caller has synchronised when this returns OK.
 int run_launch(lisreg_ctx* c, LoopDet* L, std::vector<LoopFrame>& frames, std::vector<LoopPair>& pairs, const std::vector<FrameIn>& fin,
-               int stride, int fmt, LoopDb* db, double threshold)
+               int stride, int fmt, LoopDb* db, unsigned kinds, double threshold, double label_threshold)
 {
     const int K = (int)frames.size(), P = (int)pairs.size(), C = P - K;
+    const bool fold = kinds & kFoldKinds, want_int = kinds & LISREG_LOOP_ISC;
+    const int nd = fold ? kDescKinds : 3;
     hipStream_t st = c->stream;
-    // one upload: frame table, pair table, host clouds packed as 16-B records
-    size_t pts_total = 0;
-    long long max_total = 0;
+    // one upload: frame table, pair table, host clouds packed as 16-B records (then, for ISC, the semantic intensities)
+    size_t pts_total = 0, sem_total = 0;
+    long long max_total = 0, max_sem = 0;
     for (int k = 0; k < K; ++k) {
         long long t = 0;
         for (int j = 0; j < 3; ++j) { t += fin[(size_t)k].n[j]; if (fmt != LISREG_FMT_DEVICE) pts_total += (size_t)fin[(size_t)k].n[j]; }
         max_total = std::max(max_total, t);
+        max_sem = std::max<long long>(max_sem, fin[(size_t)k].n[2]);
+        sem_total += (size_t)fin[(size_t)k].n[2];
     }
     const long long chunks = std::max<long long>(1, (max_total + kBinChunk - 1) / kBinChunk);
+    const long long sem_chunks = std::max<long long>(1, (max_sem + kBinChunk - 1) / kBinChunk);
     if (chunks > 65535) return bad(c, "loopdet: a frame holds more than 268 M points");
+    if (fold && max_sem >= (1 << 24) - 1) return bad(c, "loopdet: SC / ISC / SSC take semantic clouds below 16 M points");
     const size_t off_pairs = align16(sizeof(LoopFrame) * K), off_pts = off_pairs + align16(sizeof(LoopPair) * P);
-    const size_t in_bytes = off_pts + sizeof(float4) * pts_total;
-    const size_t out_bytes = align16(sizeof(LoopPairOut) * P) + sizeof(lisreg_loopdet_result) * K;
+    const size_t off_int = off_pts + sizeof(float4) * pts_total;
+    const size_t in_bytes = off_int + (want_int ? sizeof(float) * sem_total : 0);
+    const size_t off_res = align16(sizeof(LoopPairOut) * P), off_match = off_res + align16(sizeof(lisreg_loopdet_result) * K);
+    const size_t off_nmatch = off_match + sizeof(lisreg_loopdet_match) * kKinds * K;
+    const size_t out_bytes = off_nmatch + sizeof(int) * K;
     HIPCHK(c, L->in.ensure(in_bytes));
     HIPCHK(c, L->hist.ensure(sizeof(int) * kHist * (size_t)P));
-    HIPCHK(c, L->desc.ensure((size_t)3 * kCells * P));
+    HIPCHK(c, L->desc.ensure((size_t)nd * kCells * P));
     HIPCHK(c, L->out.ensure(out_bytes));
+    if (fold) HIPCHK(c, L->fold.ensure(sizeof(LoopFold) * (size_t)P));
     if (!db) HIPCHK(c, L->proj_tmp.ensure(sizeof(float4) * kProj * (size_t)K));
     L->h_in.resize(in_bytes);
     unsigned char* base = L->in.as<unsigned char>();
-    size_t at = 0;
+    size_t at = 0, at_int = 0;
     for (int k = 0; k < K; ++k) {
         LoopFrame& F = frames[(size_t)k];
         for (int j = 0; j < 3; ++j) {
@@ -491,35 +733,66 @@ int run_launch(lisreg_ctx* c, LoopDet* L, std::vector<LoopFrame>& frames, std::v
             F.pts[j] = reinterpret_cast<const float4*>(base + off_pts) + at;
             at += (size_t)F.n[j];
         }
+        if (want_int) {
+            // the float intensity of PointXYZIL (byte 16)
+            float* dst = reinterpret_cast<float*>(L->h_in.data() + off_int) + at_int;
+            const unsigned char* src = static_cast<const unsigned char*>(fin[(size_t)k].ptr[2]);
+            for (int i = 0; i < F.n[2]; ++i) memcpy(dst + i, src + (size_t)i * stride + 16, sizeof(float));
+            F.inten = reinterpret_cast<const float*>(base + off_int) + at_int;
+            at_int += (size_t)F.n[2];
+        }
+        for (int s = 0; s < kDescKinds; ++s) F.db[s] = nullptr;
         if (db) {
             F.proj = db->proj.as<float4>() + (size_t)F.frame_id * kProj;
-            F.fepsc = db->fepsc.as<uint8_t>() + (size_t)F.frame_id * kCells;
+            for (int s = 0; s < kDescKinds; ++s)
+                if (db->stores(s)) F.db[s] = db->desc[s].as<uint8_t>() + (size_t)F.frame_id * kCells;
         } else {
             F.proj = L->proj_tmp.as<float4>() + (size_t)k * kProj;
-            F.fepsc = nullptr;
         }
     }
     memcpy(L->h_in.data(), frames.data(), sizeof(LoopFrame) * K);
     if (P) memcpy(L->h_in.data() + off_pairs, pairs.data(), sizeof(LoopPair) * P);
     const LoopFrame* d_frames = reinterpret_cast<const LoopFrame*>(base);
     const LoopPair* d_pairs = reinterpret_cast<const LoopPair*>(base + off_pairs);
-    LoopPairOut* d_pout = L->out.as<LoopPairOut>();
-    lisreg_loopdet_result* d_res = reinterpret_cast<lisreg_loopdet_result*>(L->out.as<unsigned char>() + align16(sizeof(LoopPairOut) * P));
+    unsigned char* d_out = L->out.as<unsigned char>();
+    LoopPairOut* d_pout = reinterpret_cast<LoopPairOut*>(d_out);
+    LoopFold* d_fold = fold ? L->fold.as<LoopFold>() : nullptr;
     HIPCHK(c, hipMemcpyAsync(base, L->h_in.data(), in_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemsetAsync(L->hist.p, 0, sizeof(int) * kHist * (size_t)P, st));
+    if (fold) HIPCHK(c, hipMemsetAsync(L->fold.p, 0, sizeof(LoopFold) * (size_t)P, st));
     const float4* db_proj = db ? db->proj.as<float4>() : nullptr;
-    const uint8_t* db_fepsc = db ? db->fepsc.as<uint8_t>() : nullptr;
+    // the kinds scored per gated pair (blockIdx.y of k_loop_score): the enabled descriptor kinds
+    LoopScoreKinds sk;
+    memset(&sk, 0, sizeof sk);
+    int n_score = 0;
+    for (int k = 0; k < kDescKinds && db; ++k)
+        if ((kinds >> k) & 1u) { sk.db[k] = db->desc[kSlotOf[k]].as<uint8_t>(); sk.kind[n_score++] = k; }
+    // without FEPSC nothing else writes a candidate's score / score_shift (lisreg_loopdet_candidate)
+    if (C > 0 && !(kinds & LISREG_LOOP_FEPSC)) HIPCHK(c, hipMemsetAsync(d_pout, 0, sizeof(LoopPairOut) * (size_t)P, st));
     k_loop_project<<<K, 1024, 0, st>>>(d_frames);
     if (C > 0) k_loop_icp<<<C, 256, 0, st>>>(d_pairs, K, d_frames, db_proj, d_pout);
-    k_loop_bin<<<dim3((unsigned)P, (unsigned)chunks), 256, 0, st>>>(d_pairs, d_frames, d_pout, L->hist.as<int>());
-    k_loop_finish<<<P, 256, 0, st>>>(d_pairs, d_frames, L->hist.as<int>(), L->desc.as<uint8_t>());
-    if (C > 0) k_loop_score<<<C, 256, 0, st>>>(K, d_pairs, db_fepsc, L->desc.as<uint8_t>(), d_pout);
-    if (db) k_loop_select<<<(K + 63) / 64, 64, 0, st>>>(d_frames, K, d_pairs, d_pout, threshold, d_res);
+    if (fold) k_loop_bin<true><<<dim3((unsigned)P, (unsigned)chunks), 256, 0, st>>>(d_pairs, d_frames, d_pout, L->hist.as<int>(), d_fold, kinds);
+    else k_loop_bin<false><<<dim3((unsigned)P, (unsigned)chunks), 256, 0, st>>>(d_pairs, d_frames, d_pout, L->hist.as<int>(), nullptr, kinds);
+    if (kinds & (LISREG_LOOP_SC | LISREG_LOOP_ISC))
+        k_loop_fold<<<dim3((unsigned)P, (unsigned)sem_chunks), 256, 0, st>>>(d_pairs, d_frames, d_pout, d_fold, kinds);
+    k_loop_finish<<<P, 256, 0, st>>>(d_pairs, d_frames, L->hist.as<int>(), d_fold, nd, L->desc.as<uint8_t>());
+    if (C > 0 && n_score > 0) k_loop_score<<<dim3((unsigned)C, (unsigned)n_score), 256, 0, st>>>(K, d_pairs, sk, nd, L->desc.as<uint8_t>(), d_pout);
+    if (db)
+        k_loop_select<<<(K + 63) / 64, 64, 0, st>>>(d_frames, K, d_pairs, d_pout, kinds, threshold, label_threshold,
+                                                    reinterpret_cast<lisreg_loopdet_result*>(d_out + off_res),
+                                                    reinterpret_cast<lisreg_loopdet_match*>(d_out + off_match), reinterpret_cast<int*>(d_out + off_nmatch));
     HIPCHK(c, hipGetLastError());
     L->h_out.resize(out_bytes);
     if (db) HIPCHK(c, hipMemcpyAsync(L->h_out.data(), L->out.p, out_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     return LISREG_OK;
+}
+
+// one LISREG_LOOP_* bit of a descriptor kind (ISC .. SSC) -> its kind index, or -1
+int desc_kind_index(unsigned kind)
+{
+    for (int k = 0; k < kDescKinds; ++k) if (kind == (1u << k)) return k;
+    return -1;
 }
 
 }  // namespace
@@ -545,7 +818,27 @@ int lisreg_loopdet_reset(lisreg_ctx* c, int db_id)
     LoopDet* L = loopdet_of(c);
     if (!L) return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: out of host memory");
     LoopDb& d = L->db[db_id];
-    d.px.clear(); d.py.clear(); d.travel.clear(); d.yaw.clear(); d.last.clear();     // device arrays are kept for reuse
+    d.px.clear(); d.py.clear(); d.travel.clear(); d.yaw.clear(); d.last.clear();     // device arrays and the kinds are kept
+    d.last_scores.clear(); d.last_match.clear();
+    return LISREG_OK;
+}
+
+int lisreg_loopdet_configure(lisreg_ctx* c, int db_id, unsigned kinds, double label_threshold)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (db_id < 0 || db_id >= LISREG_LOOPDET_MAX_DB) return bad(c, "loopdet_configure: bad db_id");
+    if (kinds == 0 || kinds >= (1u << kKinds)) return bad(c, "loopdet_configure: kinds must be a nonzero mask of LISREG_LOOP_* bits");
+    LoopDet* L = loopdet_of(c);
+    if (!L) return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: out of host memory");
+    LoopDb& d = L->db[db_id];
+    if (d.n() > 0) return bad(c, "loopdet_configure: the database holds frames (lisreg_loopdet_reset first)");
+    if (kinds != d.kinds) {
+        d.proj.release();
+        for (auto& b : d.desc) b.release();
+        d.cap = 0;
+    }
+    d.kinds = kinds;
+    d.label_threshold = label_threshold;
     return LISREG_OK;
 }
 
@@ -566,9 +859,11 @@ int lisreg_loopdet_detect(lisreg_ctx* c, int db_id, const lisreg_loopdet_frame* 
     if (params) prm = *params;
     LoopDet* L = loopdet_of(c);
     if (!L) return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: out of host memory");
+    LoopDb& d = L->db[db_id];
+    if ((d.kinds & LISREG_LOOP_ISC) && fmt == LISREG_FMT_DEVICE)
+        return bad(c, "loopdet_detect: ISC reads the intensity of host structs; device records carry only the label");
     if (n_frames == 0) return LISREG_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    LoopDb& d = L->db[db_id];
     const int n0 = d.n();
     int rc = db_reserve(c, d, n0 + n_frames);
     if (rc) return rc;
@@ -599,10 +894,12 @@ int lisreg_loopdet_detect(lisreg_ctx* c, int db_id, const lisreg_loopdet_frame* 
             memset(&q, 0, sizeof q);
             q.frame = k; q.hist = i; q.kind = 1;
             float angle = yaw_t - d.yaw[(size_t)i];                   // globalICP's wrap (:262-265), float through double
+            q.yaw_diff = angle;
             if (angle >= 2. * M_PI) angle = angle - 2. * M_PI;
             if (angle < 0) angle = angle + 2. * M_PI;
             q.yaw = angle;
             q.tmp_id = (int)std::floor(angle / kStep360);
+            q.pos_distance = pos_distance;
             cands.push_back(q);
         }
         F.n_cand = (int)cands.size() - (F.cand0 - n_frames);
@@ -613,29 +910,45 @@ int lisreg_loopdet_detect(lisreg_ctx* c, int db_id, const lisreg_loopdet_frame* 
         fin[(size_t)k] = FrameIn{ { f.corner, f.surf, f.semantic }, { f.n_corner, f.n_surf, f.n_semantic } };
     }
     pairs.insert(pairs.end(), cands.begin(), cands.end());
-    rc = run_launch(c, L, lf, pairs, fin, stride, fmt, &d, prm.distance_threshold);
+    rc = run_launch(c, L, lf, pairs, fin, stride, fmt, &d, d.kinds, prm.distance_threshold, d.label_threshold);
     if (rc) {
         // roll the database back to what it held before the call
         d.px.resize((size_t)n0); d.py.resize((size_t)n0); d.yaw.resize((size_t)n0); d.travel.resize((size_t)n0);
         return rc;
     }
-    const LoopPairOut* po = reinterpret_cast<const LoopPairOut*>(L->h_out.data());
-    const lisreg_loopdet_result* res = reinterpret_cast<const lisreg_loopdet_result*>(L->h_out.data() + align16(sizeof(LoopPairOut) * pairs.size()));
+    const unsigned char* ho = L->h_out.data();
+    const LoopPairOut* po = reinterpret_cast<const LoopPairOut*>(ho);
+    const size_t off_res = align16(sizeof(LoopPairOut) * pairs.size()), off_match = off_res + align16(sizeof(lisreg_loopdet_result) * n_frames);
+    const lisreg_loopdet_result* res = reinterpret_cast<const lisreg_loopdet_result*>(ho + off_res);
+    const lisreg_loopdet_match* mt = reinterpret_cast<const lisreg_loopdet_match*>(ho + off_match);
+    const int* nm = reinterpret_cast<const int*>(ho + off_match + sizeof(lisreg_loopdet_match) * kKinds * n_frames);
     d.last.assign((size_t)n_frames, {});
+    d.last_scores.assign((size_t)n_frames, {});
+    d.last_match.assign((size_t)n_frames, {});
     for (int k = 0; k < n_frames; ++k) {
         results[k] = res[k];
+        d.last_match[(size_t)k].assign(mt + (size_t)k * kKinds, mt + (size_t)k * kKinds + nm[k]);
         const LoopFrame& F = lf[(size_t)k];
         auto& v = d.last[(size_t)k];
+        auto& vs = d.last_scores[(size_t)k];
         v.resize((size_t)F.n_cand);
+        vs.resize((size_t)F.n_cand);
         for (int j = 0; j < F.n_cand; ++j) {
             const LoopPairOut& o = po[F.cand0 + j];
+            const LoopPair& q = pairs[(size_t)(F.cand0 + j)];
             lisreg_loopdet_candidate& r = v[(size_t)j];
             memset(&r, 0, sizeof r);
-            r.history_id = pairs[(size_t)(F.cand0 + j)].hist;
+            r.history_id = q.hist;
             r.yaw_shift = o.yaw_shift; r.yaw_angle = o.yaw_angle;
             r.icp_state = o.state; r.icp_iters = o.iters; r.icp_n_corr = o.n_corr;
             memcpy(r.transform, o.T, sizeof r.transform);
             r.score_shift = o.score_shift; r.score = o.score;
+            lisreg_loopdet_kind_scores& s = vs[(size_t)j];
+            memset(&s, 0, sizeof s);
+            s.history_id = q.hist;
+            for (int kk = 0; kk < kDescKinds; ++kk)
+                if ((d.kinds >> kk) & 1u) { s.score[kk] = o.kscore[kk]; s.shift[kk] = o.kshift[kk]; }
+            if (d.kinds & LISREG_LOOP_POSE) s.score[kPose] = q.pos_distance;
         }
     }
     return LISREG_OK;
@@ -656,6 +969,36 @@ int lisreg_loopdet_candidates(lisreg_ctx* c, int db_id, int k, lisreg_loopdet_ca
     return LISREG_OK;
 }
 
+int lisreg_loopdet_candidate_scores(lisreg_ctx* c, int db_id, int k, lisreg_loopdet_kind_scores* out, int cap, int* n_out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (db_id < 0 || db_id >= LISREG_LOOPDET_MAX_DB) return bad(c, "loopdet_candidate_scores: bad db_id");
+    if (!n_out || cap < 0 || (cap > 0 && !out)) return bad(c, "loopdet_candidate_scores: NULL output");
+    LoopDet* L = loopdet_of(c);
+    if (!L) return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: out of host memory");
+    const LoopDb& d = L->db[db_id];
+    if (k < 0 || k >= (int)d.last_scores.size()) return bad(c, "loopdet_candidate_scores: k is not a frame of the last detect call");
+    const auto& v = d.last_scores[(size_t)k];
+    *n_out = (int)v.size();
+    for (int j = 0; j < std::min(cap, (int)v.size()); ++j) out[j] = v[(size_t)j];
+    return LISREG_OK;
+}
+
+int lisreg_loopdet_matches(lisreg_ctx* c, int db_id, int k, lisreg_loopdet_match* out, int cap, int* n_out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (db_id < 0 || db_id >= LISREG_LOOPDET_MAX_DB) return bad(c, "loopdet_matches: bad db_id");
+    if (!n_out || cap < 0 || (cap > 0 && !out)) return bad(c, "loopdet_matches: NULL output");
+    LoopDet* L = loopdet_of(c);
+    if (!L) return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: out of host memory");
+    const LoopDb& d = L->db[db_id];
+    if (k < 0 || k >= (int)d.last_match.size()) return bad(c, "loopdet_matches: k is not a frame of the last detect call");
+    const auto& v = d.last_match[(size_t)k];
+    *n_out = (int)v.size();
+    for (int j = 0; j < std::min(cap, (int)v.size()); ++j) out[j] = v[(size_t)j];
+    return LISREG_OK;
+}
+
 int lisreg_loopdet_get(lisreg_ctx* c, int db_id, int frame_id, uint8_t* fepsc, float* projection)
 {
     if (!c) return LISREG_ERR_ARG;
@@ -664,13 +1007,48 @@ int lisreg_loopdet_get(lisreg_ctx* c, int db_id, int frame_id, uint8_t* fepsc, f
     if (!L) return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: out of host memory");
     const LoopDb& d = L->db[db_id];
     if (frame_id < 0 || frame_id >= d.n()) return bad(c, "loopdet_get: frame_id out of range");
+    if (fepsc && !(d.kinds & LISREG_LOOP_FEPSC)) return bad(c, "loopdet_get: FEPSC is not enabled on this database");
     HIPCHK(c, hipSetDevice(c->device));
-    if (fepsc) HIPCHK(c, hipMemcpyAsync(fepsc, d.fepsc.as<uint8_t>() + (size_t)frame_id * kCells, kCells, hipMemcpyDeviceToHost, c->stream));
+    if (fepsc) HIPCHK(c, hipMemcpyAsync(fepsc, d.desc[0].as<uint8_t>() + (size_t)frame_id * kCells, kCells, hipMemcpyDeviceToHost, c->stream));
     if (projection)
         HIPCHK(c, hipMemcpyAsync(projection, d.proj.as<float4>() + (size_t)frame_id * kProj, sizeof(float4) * kProj, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LISREG_OK;
 }
+
+int lisreg_loopdet_get_descriptor(lisreg_ctx* c, int db_id, int frame_id, unsigned kind, uint8_t* out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (db_id < 0 || db_id >= LISREG_LOOPDET_MAX_DB) return bad(c, "loopdet_get_descriptor: bad db_id");
+    if (!out) return bad(c, "loopdet_get_descriptor: NULL output");
+    const int ki = desc_kind_index(kind);
+    if (ki < 0) return bad(c, "loopdet_get_descriptor: kind must be one of LISREG_LOOP_ISC .. LISREG_LOOP_SSC");
+    LoopDet* L = loopdet_of(c);
+    if (!L) return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: out of host memory");
+    const LoopDb& d = L->db[db_id];
+    if (!(d.kinds & kind)) return bad(c, "loopdet_get_descriptor: the kind is not enabled on this database");
+    if (frame_id < 0 || frame_id >= d.n()) return bad(c, "loopdet_get_descriptor: frame_id out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, d.desc[kSlotOf[ki]].as<uint8_t>() + (size_t)frame_id * kCells, kCells, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LISREG_OK;
+}
+
+namespace {
+
+// one frame's descriptors under M (no database): pair 0 of a launch with the given kinds; on success L->desc holds nd slots
+int descriptor_launch(lisreg_ctx* c, LoopDet* L, const void* const* ptr, const int* n, int stride, int fmt, const float* M, unsigned kinds)
+{
+    std::vector<LoopFrame> lf(1);
+    memset(&lf[0], 0, sizeof lf[0]);
+    if (M) { lf[0].has_M = 1; memcpy(lf[0].M, M, sizeof lf[0].M); }
+    std::vector<LoopPair> pairs(1);
+    memset(&pairs[0], 0, sizeof pairs[0]);
+    std::vector<FrameIn> fin(1, FrameIn{ { ptr[0], ptr[1], ptr[2] }, { n[0], n[1], n[2] } });
+    return run_launch(c, L, lf, pairs, fin, stride, fmt, nullptr, kinds, 0.0, 0.0);
+}
+
+}  // namespace
 
 int lisreg_loop_descriptor(lisreg_ctx* c, const void* corner, int n_corner, const void* surf, int n_surf, const void* semantic,
                            int n_semantic, int stride, int fmt, const float* M, uint8_t* fepsc, uint8_t* epsc, uint8_t* sepsc,
@@ -684,19 +1062,36 @@ int lisreg_loop_descriptor(lisreg_ctx* c, const void* corner, int n_corner, cons
     LoopDet* L = loopdet_of(c);
     if (!L) return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: out of host memory");
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<LoopFrame> lf(1);
-    memset(&lf[0], 0, sizeof lf[0]);
-    if (M) { lf[0].has_M = 1; memcpy(lf[0].M, M, sizeof lf[0].M); }
-    std::vector<LoopPair> pairs(1);
-    memset(&pairs[0], 0, sizeof pairs[0]);
-    std::vector<FrameIn> fin(1, FrameIn{ { corner, surf, semantic }, { n_corner, n_surf, n_semantic } });
-    rc = run_launch(c, L, lf, pairs, fin, stride, fmt, nullptr, 0.0);
+    rc = descriptor_launch(c, L, ptr, n, stride, fmt, M, LISREG_LOOP_FEPSC);
     if (rc) return rc;
     const uint8_t* dd = L->desc.as<uint8_t>();
     if (fepsc) HIPCHK(c, hipMemcpyAsync(fepsc, dd, kCells, hipMemcpyDeviceToHost, c->stream));
     if (epsc) HIPCHK(c, hipMemcpyAsync(epsc, dd + kCells, kCells, hipMemcpyDeviceToHost, c->stream));
     if (sepsc) HIPCHK(c, hipMemcpyAsync(sepsc, dd + 2 * kCells, kCells, hipMemcpyDeviceToHost, c->stream));
     if (projection) HIPCHK(c, hipMemcpyAsync(projection, L->proj_tmp.p, sizeof(float4) * kProj, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LISREG_OK;
+}
+
+int lisreg_loop_descriptor_kind(lisreg_ctx* c, unsigned kind, const void* corner, int n_corner, const void* surf, int n_surf,
+                                const void* semantic, int n_semantic, int stride, int fmt, const float* M, uint8_t* out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    const int ki = desc_kind_index(kind);
+    if (ki < 0) return bad(c, "loop_descriptor_kind: kind must be one of LISREG_LOOP_ISC .. LISREG_LOOP_SSC");
+    if (!out) return bad(c, "loop_descriptor_kind: NULL output");
+    const void* ptr[3] = { corner, surf, semantic };
+    const int n[3] = { n_corner, n_surf, n_semantic };
+    int rc = check_clouds(c, ptr, n, stride, fmt, "loop_descriptor_kind");
+    if (rc) return rc;
+    if (kind == LISREG_LOOP_ISC && fmt == LISREG_FMT_DEVICE)
+        return bad(c, "loop_descriptor_kind: ISC reads the intensity of host structs; device records carry only the label");
+    LoopDet* L = loopdet_of(c);
+    if (!L) return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: out of host memory");
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = descriptor_launch(c, L, ptr, n, stride, fmt, M, kind);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, L->desc.as<uint8_t>() + (size_t)kSlotOf[ki] * kCells, kCells, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LISREG_OK;
 }

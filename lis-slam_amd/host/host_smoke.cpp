@@ -195,6 +195,31 @@ int main()
         const bool eok = last_id == 23 && matches >= 6;
         std::printf(eok ? "EPSCGeneration ok\n" : "EPSCGeneration FAILED\n");
         ok = ok && eok;
+        // every selector on: matched lists are in push order, FEPSC's entry is the FEPSC-only generator's match, and Pose matches
+        // whenever a frame is gated
+        EPSCGeneration all(reg.handle(), 2, 127), fe(reg.handle(), 3, LISREG_LOOP_FEPSC);
+        int lists = 0, poses = 0;
+        bool kok = true;
+        for (int lap = 0; lap < 2; ++lap)
+            for (int k = 0; k < 12; ++k) {
+                const float a = 6.2831853f * (float)k / 12.f, px = 10.f * std::cos(a), py = 10.f * std::sin(a);
+                PointCloud<PointXYZI> c, s; PointCloud<PointXYZIL> m;
+                frame_at(px, py, c, s, m);
+                for (size_t i = 0; i < m.size(); ++i) m.points[i].intensity = (float)(i % 13) / 10.f;
+                const float odom[12] = { 1, 0, 0, px, 0, 1, 0, py, 0, 0, 1, 0 };
+                all.loopDetection(c, s, m, odom);
+                fe.loopDetection(c, s, m, odom);
+                for (size_t j = 1; j < all.matched_kind.size(); ++j) kok = kok && all.matched_kind[j - 1] < all.matched_kind[j];
+                int f_id = -1;
+                for (size_t j = 0; j < all.matched_kind.size(); ++j) if (all.matched_kind[j] == LISREG_LOOP_FEPSC) f_id = all.matched_frame_id[j];
+                kok = kok && f_id == (fe.matched_frame_id.empty() ? -1 : fe.matched_frame_id[0]);
+                poses += !all.matched_kind.empty() && all.matched_kind.back() == LISREG_LOOP_POSE;
+                lists += all.matched_frame_id.empty() ? 0 : 1;
+            }
+        std::printf("EPSCGeneration (all kinds): %d matched lists, %d with a Pose entry\n", lists, poses);
+        kok = kok && lists >= 6 && poses >= 6;
+        std::printf(kok ? "EPSCGeneration kinds ok\n" : "EPSCGeneration kinds FAILED\n");
+        ok = ok && kok;
     }
     std::printf(ok ? "host_smoke ok\n" : "host_smoke FAILED\n");
     return ok ? 0 : 1;

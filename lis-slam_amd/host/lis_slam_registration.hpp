@@ -539,14 +539,20 @@ inline std::vector<lisreg_icp_result> alignLoopCandidates(lisreg_ctx* ctx, const
     return res;
 }
 
-// EPSCGeneration (src/include/epscGeneration.h, src/core/epscGeneration.cpp:663-992) with UsingFEPSCFlag: loopDetection per key frame,
+// EPSCGeneration (src/include/epscGeneration.h, src/core/epscGeneration.cpp:663-992): loopDetection per key frame with the selectors of a
+// LISREG_LOOP_* mask (the Using*Flag rosparams; default UsingFEPSCFlag alone),
 // the public current_frame_id / matched_frame_id / matched_frame_transform that loopClosureThread reads (subMapOptmizationNode.cpp:
 // 2328-2362).  odom is the row-major 3 x 4 of pclPointToAffine3f(optimized_pose) (lisreg_pose_to_matrix); matched_frame_transform
 // holds row-major 4 x 4 matrices (the EPSC init pose of detectLoopClosureForSubMap, :2796-2805).  The history lives in database
 // db_id of the context, so several generators may share one context.
 class EPSCGeneration {
 public:
-    explicit EPSCGeneration(lisreg_ctx* ctx, int db_id = 0) : ctx_(ctx), db_(db_id) { check(lisreg_loopdet_reset(ctx_, db_)); }
+    explicit EPSCGeneration(lisreg_ctx* ctx, int db_id = 0, unsigned kinds = LISREG_LOOP_FEPSC,
+                            double label_threshold = LISREG_LOOP_LABEL_THRESHOLD) : ctx_(ctx), db_(db_id)
+    {
+        check(lisreg_loopdet_reset(ctx_, db_));
+        check(lisreg_loopdet_configure(ctx_, db_, kinds, label_threshold));
+    }
     void loopDetection(const PointCloud<PointXYZI>& corner_pc, const PointCloud<PointXYZI>& surf_pc, const PointCloud<PointXYZIL>& semantic_pc,
                        const float odom[12]) {
         lisreg_loopdet_frame f;
@@ -559,17 +565,22 @@ public:
         current_frame_id = r.current_frame_id;
         matched_frame_id.clear();
         matched_frame_transform.clear();
-        if (r.matched_frame_id >= 0) {
-            matched_frame_id.push_back(r.matched_frame_id);
-            std::vector<float> T(r.matched_transform, r.matched_transform + 16);
-            matched_frame_transform.push_back(T);
-            last_score = r.score;
+        matched_kind.clear();
+        lisreg_loopdet_match m[LISREG_LOOP_KINDS];
+        int n = 0;
+        check(lisreg_loopdet_matches(ctx_, db_, 0, m, LISREG_LOOP_KINDS, &n));
+        for (int j = 0; j < n; ++j) {                     // ISC, SC, EPSC, SEPSC, FEPSC, SSC, POSE (:894-990)
+            matched_frame_id.push_back(m[j].history_id);
+            matched_frame_transform.emplace_back(m[j].transform, m[j].transform + 16);
+            matched_kind.push_back((unsigned)m[j].kind);
         }
+        if (r.matched_frame_id >= 0) last_score = r.score;
     }
     int current_frame_id = 0;
     std::vector<int> matched_frame_id;
     std::vector<std::vector<float>> matched_frame_transform;
-    double last_score = 0.0;
+    std::vector<unsigned> matched_kind;                   // the LISREG_LOOP_* selector of each entry
+    double last_score = 0.0;                              // the last FEPSC match's score
 private:
     void check(int rc) { if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_)); }
     lisreg_ctx* ctx_;

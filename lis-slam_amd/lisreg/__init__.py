@@ -40,6 +40,8 @@ ABI_SYMBOLS = [
     "lisreg_icp_default_params", "lisreg_icp_align", "lisreg_icp_align_batch", "lisreg_icp_gn_match",
     "lisreg_loopdet_default_params", "lisreg_loopdet_reset", "lisreg_loopdet_detect", "lisreg_loopdet_candidates",
     "lisreg_loopdet_get", "lisreg_loop_descriptor",
+    "lisreg_loopdet_configure", "lisreg_loopdet_matches", "lisreg_loopdet_candidate_scores", "lisreg_loopdet_get_descriptor",
+    "lisreg_loop_descriptor_kind",
 ]
 
 
@@ -108,6 +110,35 @@ class LoopdetCandidate(C.Structure):
         return dict(history_id=self.history_id, yaw_shift=self.yaw_shift, yaw_angle=self.yaw_angle, icp_state=self.icp_state,
                     icp_iters=self.icp_iters, icp_n_corr=self.icp_n_corr,
                     transform=np.array(list(self.transform), np.float32).reshape(4, 4), score_shift=self.score_shift, score=self.score)
+
+
+# the seven loopDetection selectors (lis_slam/Using{ISC,SC,EPSC,SEPSC,FEPSC,SSC,Pose}Flag), bit = kind index, in push order
+LOOP_ISC, LOOP_SC, LOOP_EPSC, LOOP_SEPSC, LOOP_FEPSC, LOOP_SSC, LOOP_POSE = (1 << k for k in range(7))
+LOOP_KIND_NAMES = ("isc", "sc", "epsc", "sepsc", "fepsc", "ssc", "pose")
+LOOP_KINDS = {n: 1 << k for k, n in enumerate(LOOP_KIND_NAMES)}
+LOOP_LABEL_THRESHOLD = 0.79
+
+
+def loop_kinds(kinds) -> int:
+    """a LISREG_LOOP_* mask from an int or an iterable of names ("isc", ..., "pose")."""
+    if isinstance(kinds, (int, np.integer)):
+        return int(kinds)
+    return sum(LOOP_KINDS[k.lower()] for k in kinds)
+
+
+class LoopdetMatch(C.Structure):
+    _fields_ = [("kind", C.c_int), ("history_id", C.c_int), ("transform", C.c_float * 16), ("score", C.c_double)]
+
+    def as_dict(self):
+        return dict(kind=self.kind, kind_name=LOOP_KIND_NAMES[self.kind.bit_length() - 1], history_id=self.history_id,
+                    transform=np.array(list(self.transform), np.float32).reshape(4, 4), score=self.score)
+
+
+class LoopdetKindScores(C.Structure):
+    _fields_ = [("history_id", C.c_int), ("shift", C.c_int * 7), ("score", C.c_double * 7)]
+
+    def as_dict(self):
+        return dict(history_id=self.history_id, shift=np.array(list(self.shift), np.int32), score=np.array(list(self.score), np.float64))
 
 
 def loopdet_default_params() -> LoopdetParams:
@@ -325,6 +356,11 @@ def lib():
         L.lisreg_loopdet_candidates.argtypes = [vp, C.c_int, C.c_int, C.POINTER(LoopdetCandidate), C.c_int, ip]
         L.lisreg_loopdet_get.argtypes = [vp, C.c_int, C.c_int, u8p, fp]
         L.lisreg_loop_descriptor.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, fp, u8p, u8p, u8p, fp]
+        L.lisreg_loopdet_configure.argtypes = [vp, C.c_int, C.c_uint, C.c_double]
+        L.lisreg_loopdet_matches.argtypes = [vp, C.c_int, C.c_int, C.POINTER(LoopdetMatch), C.c_int, ip]
+        L.lisreg_loopdet_candidate_scores.argtypes = [vp, C.c_int, C.c_int, C.POINTER(LoopdetKindScores), C.c_int, ip]
+        L.lisreg_loopdet_get_descriptor.argtypes = [vp, C.c_int, C.c_int, C.c_uint, u8p]
+        L.lisreg_loop_descriptor_kind.argtypes = [vp, C.c_uint, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, fp, u8p]
         _lib = L
     return _lib
 
@@ -1040,6 +1076,44 @@ class Context:
         self._chk(self._L.lisreg_loop_descriptor(self._h, p0, n0, p1, n1, p2, n2, stride, fmt, None if m is None else m.ctypes.data_as(C.POINTER(C.c_float)),
                                                  u8(out["fepsc"]), u8(out["epsc"]), u8(out["sepsc"]), out["projection"].ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    # ---- the other loopDetection selectors (ISC, SC, EPSC, SEPSC, SSC, Pose) ----
+    def loopdet_configure(self, kinds, db_id: int = 0, label_threshold: float = LOOP_LABEL_THRESHOLD):
+        """lisreg_loopdet_configure: the kinds (a LOOP_* mask or names) of an empty database, and SSC's threshold."""
+        self._chk(self._L.lisreg_loopdet_configure(self._h, db_id, loop_kinds(kinds), label_threshold))
+
+    def loopdet_matches(self, k: int, db_id: int = 0):
+        """lisreg_loopdet_matches: the matched list of frame k of the last detect call (matched_frame_id / _transform), push order."""
+        cnt = C.c_int(0)
+        out = (LoopdetMatch * 7)()
+        self._chk(self._L.lisreg_loopdet_matches(self._h, db_id, k, out, 7, C.byref(cnt)))
+        return [out[j].as_dict() for j in range(cnt.value)]
+
+    def loopdet_candidate_scores(self, k: int, db_id: int = 0):
+        """lisreg_loopdet_candidate_scores: per gated candidate of frame k, the score (and shift) of every kind, by kind index."""
+        cnt = C.c_int(0)
+        self._chk(self._L.lisreg_loopdet_candidate_scores(self._h, db_id, k, None, 0, C.byref(cnt)))
+        out = (LoopdetKindScores * max(cnt.value, 1))()
+        self._chk(self._L.lisreg_loopdet_candidate_scores(self._h, db_id, k, out, cnt.value, C.byref(cnt)))
+        return [out[j].as_dict() for j in range(cnt.value)]
+
+    def loopdet_get_descriptor(self, frame_id: int, kind, db_id: int = 0):
+        """lisreg_loopdet_get_descriptor: the stored uint8 [20, 80] descriptor of one enabled kind of frame_id."""
+        d = np.zeros((20, 80), np.uint8)
+        self._chk(self._L.lisreg_loopdet_get_descriptor(self._h, db_id, frame_id, loop_kinds([kind] if isinstance(kind, str) else kind),
+                                                        d.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return d
+
+    def loop_descriptor_kind(self, kind, corner, surf, semantic, M=None):
+        """lisreg_loop_descriptor_kind: one kind's uint8 [20, 80] descriptor of the clouds moved by M."""
+        clouds = [c if isinstance(c, tuple) else np.ascontiguousarray(c) for c in (corner, surf, semantic)]
+        (p0, p1, p2), (n0, n1, n2), fmt, stride = self._loop_clouds(clouds)
+        m = None if M is None else np.ascontiguousarray(M, np.float32).ravel()
+        d = np.zeros((20, 80), np.uint8)
+        self._chk(self._L.lisreg_loop_descriptor_kind(self._h, loop_kinds([kind] if isinstance(kind, str) else kind), p0, n0, p1, n1, p2, n2,
+                                                      stride, fmt, None if m is None else m.ctypes.data_as(C.POINTER(C.c_float)),
+                                                      d.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return d
 
     def icp_gn_match(self, slot: int, source: np.ndarray, max_iterations: int, max_correspond_distance: float, predict_pose,
                      want_transformed: bool = False):

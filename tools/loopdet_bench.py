@@ -5,7 +5,10 @@ between two places A and B 30 m apart (stored with the gate switched off, so bui
 at B after a frame at A then gates every A frame (query gate inflation 1e-4, so the B frames 30 m away never pass): G candidates, each a yaw search + 2-D ICP + the whole query frame (~1e5 semantic
 points, synth-sized corner / surf) binned under its transform + the 20-shift score.
 
-  python tools/loopdet_bench.py [--G 16 64 256] [--reps 5] [--cpu-G 16]
+  python tools/loopdet_bench.py [--G 16 64 256] [--reps 5] [--cpu-G 16] [--kinds isc sc epsc sepsc fepsc ssc pose]
+
+--kinds configures the database with those selectors (lisreg_loopdet_configure; default: unconfigured, i.e. FEPSC alone, and the
+line is then the FEPSC bench line).  The CPU port always measures FEPSC alone.
 
 device_ms: HIP events on the context's stream around one lisreg_loopdet_detect (upload, the six kernels, read-back and the final
 synchronise); wall_ms: the call on the host clock.  cpu_port_ms: tests/loopdet_ref.py (numpy restatement + the oracle's ICP) on
@@ -34,11 +37,13 @@ def scans(h_big, w_big):
     return out
 
 
-def build_history(ctx, db, sc, G):
+def build_history(ctx, db, sc, G, kinds=None):
     import lisreg
     off = lisreg.loopdet_default_params()
     off.inflation_covariance = -1.0                      # no gate while the history is stored
     ctx.loopdet_reset(db)
+    if kinds is not None:
+        ctx.loopdet_configure(kinds, db_id=db)
     frames = [sc["B"] if k % 2 == 0 else sc["A"] for k in range(2 * G)]       # ... B, A: the last stored frame is at A
     for i in range(0, len(frames), 64):
         ctx.loopdet_detect(frames[i:i + 64], db_id=db, params=off)
@@ -52,11 +57,15 @@ def main():
     ap.add_argument("--cpu-G", type=int, default=16)
     ap.add_argument("--h", type=int, default=64)
     ap.add_argument("--w", type=int, default=1800)
+    ap.add_argument("--kinds", nargs="+", default=None, help="selectors to enable (isc sc epsc sepsc fepsc ssc pose, or all)")
     a = ap.parse_args()
     import torch
     import lisreg
     sc = scans(a.h, a.w)
     q = sc["Q"]
+    kinds = None
+    if a.kinds is not None:
+        kinds = 127 if a.kinds == ["all"] else lisreg.loop_kinds(a.kinds)
     ctx = lisreg.Context(0)
     stream = torch.cuda.current_stream()
     ctx.set_stream(stream.cuda_stream)
@@ -66,7 +75,7 @@ def main():
     for G in a.G:
         dev, wall = [], []
         for r in range(a.reps + 1):
-            build_history(ctx, 0, sc, G)
+            build_history(ctx, 0, sc, G, kinds)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -79,7 +88,7 @@ def main():
                 dev.append(e0.elapsed_time(e1)); wall.append(1e3 * (t1 - t0))
         assert res["n_candidates"] == G, res
         # batch: `batch` query frames in one call (each gates the A frames and, from the second on, the B frames before it)
-        build_history(ctx, 0, sc, G)
+        build_history(ctx, 0, sc, G, kinds)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         out = ctx.loopdet_detect([q] * a.batch, db_id=0, params=qp)
@@ -107,9 +116,13 @@ def main():
         cpu = dict(kind="port", G=a.cpu_G, ms_per_keyframe=round(1e3 * (t1 - t0), 1), threads=1,
                    what="tests/loopdet_ref.py: numpy restatement + oracle ICP")
     ctx.close()
-    print(json.dumps(dict(workload="loopdet_fepsc", semantic_points=int(len(q[2])), corner_points=int(len(q[0])),
-                          surf_points=int(len(q[1])), rows=rows, cpu_baseline=cpu,
-                          stage_split="per kernel: rocprofv3 --kernel-trace --stats, profiles/loopdet_*")))
+    line = dict(workload="loopdet_fepsc", semantic_points=int(len(q[2])), corner_points=int(len(q[0])),
+                surf_points=int(len(q[1])), rows=rows, cpu_baseline=cpu,
+                stage_split="per kernel: rocprofv3 --kernel-trace --stats, profiles/loopdet_*")
+    if kinds is not None:
+        line["workload"] = "loopdet_kinds"
+        line["kinds"] = [n for k, n in enumerate(lisreg.LOOP_KIND_NAMES) if (kinds >> k) & 1]
+    print(json.dumps(line))
 
 
 if __name__ == "__main__":
