@@ -215,7 +215,8 @@ void* lisreg_batch_result_device(const lisreg_ctx* ctx);
  * competing for the fifth place: the first one met wins, and the front-ends meet them in different orders),
  * "sort_sources" (0 caller order, 1 column sort, 2 auto [default]: probe the order when a batch is prepared — one pass over the sources
  * and a 4-byte read-back, skipped for batches of the same shape (items, points) as the one last probed, whose verdict is reused; every 32nd
- * such batch is probed again; the verdict decides speed only, the search is exact on any order),
+ * such batch is probed again; the search is exact on any order — the same neighbours —, but a sorted batch sums the rows of its
+ * workgroups in another order, so its poses may differ from the unsorted ones in the last bits),
  * "index_build" (how "rebuild_targets_each_run" rebuilds the target grids of a batch: 0 bucket sort with one global atomic per
  * point, 1 strip form — LDS histograms, one workgroup per strip of cells; an error if a grid does not fit its LDS tables —,
  * 2 [default] strip form whenever the grids fit; both produce the same index bit for bit), "index_strip_cells" (cells per strip aimed at; 0 [default]: 1024 for a batch of one or two
@@ -255,7 +256,11 @@ void* lisreg_batch_result_device(const lisreg_ctx* ctx);
  * bit for bit.  A run counts such queries; more than one query-iteration in a thousand and the prepared batch's later runs, and the next
  * 32 batches prepared on the context, build all rows.  0: all rows always),
  * "graph_min_ratio", "cell_min_ratio" (auto takes the cell rows from this many query-iterations per target point: 110), "cell_rows_max_mb",
- * "first_pass_mm", "count_searches", "early_stop_chunk". */
+ * "first_pass_mm" (radius of the cell walk's first pass, >= 0: a negative value is refused with LISREG_ERR_ARG), "count_searches",
+ * "early_stop_chunk" (<= -1 auto, 0 never look).  Out-of-range values of the numeric knobs are clamped, not refused: "index_strip_cells"
+ * below 0 is 0 (auto), "index_strip_cap" is kept in [64, 16384], "interleave_min_blocks" below 2 is 2, "cell_anchor_until" and
+ * "trace_cap" below 0 are 0; "xcd_order", "interleave", "index_build" and "search_mode" refuse values they do not name.
+ * Which options may change results, and which must not, is pinned by tests/test_option_state.py. */
 int  lisreg_set_option(lisreg_ctx* ctx, const char* name, int value);
 /* Read back an option, or "front_end" = the search front-end the prepared batch actually runs (auto resolved), or
  * "index_build_now" = 1 if the prepared batch rebuilds its targets in strip form, "xcd_order_now" = 1 if the last run used the

@@ -904,7 +904,8 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
     // (a single odometry frame) skip the probe and its host round trip: a sort could not pay for itself there.
     c->sort_now = c->sort_sources == 1;
     // (the probe costs a pass over the sources and a host round trip — 0.15 ms in front of a pipelined batch: batches of the same shape as
-    // the one last probed reuse its verdict, re-probed every 32nd; the verdict decides speed only, never results)
+    // the one last probed reuse its verdict, re-probed every 32nd; the verdict never changes the neighbours, only the order in which a
+    // workgroup sums its rows — the last bits of the poses)
     if (c->sort_sources == 2 && c->n_elems >= 65536 && c->probe_items == n_items && c->probe_elems == c->n_elems && c->probe_age < 32) {
         ++c->probe_age;
         c->sort_now = c->probe_verdict;
@@ -1063,10 +1064,14 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
             const int nb0 = split_blk ? split_blk : c->n_blocks;
             launch_xcd_order(c->blocks.as<BlockDesc>(), nb0, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(), c->items.as<ItemState>(),
                              c->sort_now ? c->sorted_all.as<float4>() : nullptr, many_targets, c->xcd_tab.as<int>(), c->xcd_tab.as<int>() + c->n_blocks, s_);
-            if (split_blk)
+            if (split_blk) {
                 launch_xcd_order(c->blocks.as<BlockDesc>() + split_blk, c->n_blocks - split_blk, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(),
                                  c->items.as<ItemState>(), c->sort_now ? c->sorted_all.as<float4>() : nullptr, many_targets,
                                  c->xcd_tab.as<int>() + split_blk, c->xcd_tab.as<int>() + c->n_blocks + split_blk, s_);
+                // the half tables have overwritten the batch's table from lisreg_batch_prepare: a later unsplit run of this batch (interleave
+                // switched off, interleave_min_blocks raised) must make its own instead of reading half-relative ids as whole-batch ones
+                c->xcd_cached = false;
+            }
         }
     };
     // (the registrations are reset already — by lisreg_batch_prepare or by the run before, launch_finalize — unless a run ended in an error)
@@ -1323,7 +1328,10 @@ int lisreg_set_option(lisreg_ctx* c, const char* name, int value)
     if (!strcmp(name, "exact_arithmetic")) { c->exact = value != 0; c->prepared = false; return LISREG_OK; }
     if (!strcmp(name, "feeder_copy_engine")) { c->feeder_engine = value; return LISREG_OK; }
     if (!strcmp(name, "canonical_ties")) { c->canonical_ties = value != 0; c->prepared = false; return LISREG_OK; }
-    if (!strcmp(name, "first_pass_mm")) { c->first_pass_r = 1e-3f * (float)value; return LISREG_OK; }
+    if (!strcmp(name, "first_pass_mm")) {          // (a negative radius would square to the positive one: refused rather than taken as that)
+        if (value < 0) return fail(c, LISREG_ERR_ARG, "first_pass_mm: a radius in millimetres, >= 0");
+        c->first_pass_r = 1e-3f * (float)value; return LISREG_OK;
+    }
     if (!strcmp(name, "trace_cap")) { c->trace_cap = std::max(0, value); c->prepared = false; return LISREG_OK; }
     if (!strcmp(name, "feeder_threads")) { c->feeder_threads = std::min(std::max(value, 0), 64); return LISREG_OK; }
     if (!strcmp(name, "feeder_numa")) { c->feeder_numa = value != 0; return LISREG_OK; }       // takes effect when the thread pool is created
