@@ -204,7 +204,7 @@ void* lisreg_batch_result_device(const lisreg_ctx* ctx);
 /* Options outside the reference's parameter surface: "rebuild_targets_each_run" (0/1: re-run the target index
  * build inside every lisreg_batch_run, as the reference rebuilds both kd-trees per registration, :602-603),
  * "trace_cap" (per-item trace records kept on the device for batches; 0 = off), "search_mode" (the exact 5-NN front-end
- * that stands in for pcl::KdTreeFLANN::nearestKSearch: 0 LDS-staged workgroup box, 1 per-lane grid walk,
+ * that stands in for pcl::KdTreeFLANN::nearestKSearch: 1 per-lane grid walk,
  * 3 k-NN graph scan with the walk as its fall-back — costs 1 KB of device memory per target point for the
  * neighbour rows —, 5 cell rows: the same certified list scan, but the list belongs to the grid cell (or the octant of it) the query
  * falls into instead of to last iteration's nearest neighbour, so nothing is carried between Gauss-Newton iterations and the first
@@ -259,7 +259,7 @@ void* lisreg_batch_result_device(const lisreg_ctx* ctx);
  * "first_pass_mm" (radius of the cell walk's first pass, >= 0: a negative value is refused with LISREG_ERR_ARG), "count_searches",
  * "early_stop_chunk" (<= -1 auto, 0 never look).  Out-of-range values of the numeric knobs are clamped, not refused: "index_strip_cells"
  * below 0 is 0 (auto), "index_strip_cap" is kept in [64, 16384], "interleave_min_blocks" below 2 is 2, "cell_anchor_until" and
- * "trace_cap" below 0 are 0; "xcd_order", "interleave", "index_build" and "search_mode" refuse values they do not name.
+ * "trace_cap" below 0 are 0; "xcd_order", "interleave", "index_build" and "search_mode" (0, 2, 6, ...) refuse values they do not name.
  * Which options may change results, and which must not, is pinned by tests/test_option_state.py. */
 int  lisreg_set_option(lisreg_ctx* ctx, const char* name, int value);
 /* Read back an option, or "front_end" = the search front-end the prepared batch actually runs (auto resolved), or

@@ -30,18 +30,24 @@ int ctx_fail(lisreg_ctx* c, int code, const std::string& msg)
     if (c) c->err = msg; else g_static_err = msg;
     return code;
 }
+
+bool ensure_side_stream(lisreg_ctx* c)
+{
+    if (!c->side_stream) {
+        if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess) c->side_stream = nullptr;
+        if (c->side_stream && (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
+                               hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)) {
+            (void)hipStreamDestroy(c->side_stream); c->side_stream = nullptr;
+        }
+    }
+    return c->side_stream != nullptr;
+}
 }  // namespace lisreg
 
 namespace {
 
 
 int fail(lisreg_ctx* c, int code, const std::string& msg) { return lisreg::ctx_fail(c, code, msg); }
-
-float env_float(const char* name, float dflt)
-{
-    const char* s = getenv(name);
-    return s ? (float)atof(s) : dflt;
-}
 
 void pose_to_matrix_host(const float T[6], float M[12])
 {
@@ -128,13 +134,12 @@ void make_grid(const float bb_in[6], int n, GridIndex* g, int* n_cells, int marg
     g->n = n;
     // Cell edge: 0.5 m is the measured optimum for the 200 k-point submap of BASELINE configs[1]; the optimum
     // scales with the point spacing, so denser maps get smaller cells (footprint density as the proxy: lidar maps are
-    // surfaces over a ground plane).  1 M points over the same 80 x 80 m: 0.25 m, +14 % registrations/s.  LISREG_CELL overrides.
+    // surfaces over a ground plane).  1 M points over the same 80 x 80 m: 0.25 m, +14 % registrations/s.
     float cell = 0.5f;
     if (n > 0) {
         const double area = std::max(1.0, (double)(bb[3] - bb[0]) * (double)(bb[4] - bb[1]));
         cell = (float)std::min(0.5, std::max(0.25, 2.8 / std::sqrt((double)n / area)));
     }
-    cell = env_float("LISREG_CELL", cell);
     if (n <= 0) { g->cell = cell; g->inv_cell = 1.f / cell; g->nx = g->ny = g->nz = 0; *n_cells = 1; return; }
     const double max_cells = 1 << 24;
     // registration targets: the grid reaches `margin_cells` cells past the cloud on every side, so that a query a pose error away from
@@ -390,25 +395,6 @@ int lisreg_create(int device, lisreg_ctx** out)
     if (hipHostMalloc((void**)&c->done_host, sizeof(int), hipHostMallocDefault) != hipSuccess) c->done_host = nullptr;
     if (c->done_dev.ensure(sizeof(int)) != hipSuccess) { lisreg_destroy(c); return fail(nullptr, LISREG_ERR_HIP, "lisreg_create: hipMalloc failed"); }
     lisreg_default_params(LISREG_VARIANT_ODOM, &c->params);
-    if (const char* m = getenv("LISREG_SEARCH_MODE")) {            // the same values lisreg_set_option("search_mode") takes
-        const int v = atoi(m);
-        if (v == 0 || v == 1 || v == 3 || v == 4 || v == 5) c->search_mode = v;
-        else fprintf(stderr, "[lisreg] LISREG_SEARCH_MODE=%s ignored (0, 1, 3, 4 or 5)\n", m);
-    }
-    if (const char* m = getenv("LISREG_SORT_SOURCES")) c->sort_sources = atoi(m);
-    if (const char* m = getenv("LISREG_EXACT")) c->exact = atoi(m) != 0;
-    if (const char* m = getenv("LISREG_CANONICAL_TIES")) c->canonical_ties = atoi(m) != 0;
-    if (const char* m = getenv("LISREG_FIRST_PASS_MM")) c->first_pass_r = 1e-3f * (float)atoi(m);
-    if (const char* m = getenv("LISREG_WIDE_UNTIL")) c->wide_until = atoi(m);
-    if (const char* m = getenv("LISREG_GRAPH_WIDE_UNTIL")) c->graph_wide_until = atoi(m);
-    if (const char* m = getenv("LISREG_CROW_WIDE_UNTIL")) c->crow_wide_until = atoi(m);
-    if (const char* m = getenv("LISREG_GRAPH_HOPS")) c->graph_hops = atoi(m);
-    if (const char* m = getenv("LISREG_CELL_ANCHOR_UNTIL")) c->cell_anchor_until = std::max(atoi(m), 0);
-    if (const char* m = getenv("LISREG_XCD_ORDER")) c->xcd_order = atoi(m);
-    if (const char* m = getenv("LISREG_ROW_REACH")) c->row_reach = atoi(m);
-    if (const char* m = getenv("LISREG_GRAPH_MIN_RATIO")) c->graph_min_ratio = atoi(m);
-    if (const char* m = getenv("LISREG_CELL_MIN_RATIO")) c->cell_min_ratio = atoi(m);
-    if (const char* m = getenv("LISREG_WIDE_FROM")) c->wide_from = c->wide_from_small = atoi(m);
     *out = c;
     return LISREG_OK;
 }
@@ -640,12 +626,6 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
     c->prm = make_dev_params(*params);
     c->prm.exact = c->exact ? 1 : 0;
     c->prm.ties = (c->canonical_ties || c->exact) ? 1 : 0;
-#ifdef LISREG_XP_HOOKS      /* timing experiments that change results are compiled in only on request (csrc/Makefile: XP=1), never into the shipped library */
-    c->prm.freeze_pose = getenv("LISREG_XP_FREEZE_POSE") ? 1 : 0;          // tests/ab.sh: see DevParams
-    if (c->prm.freeze_pose) fprintf(stderr, "[lisreg] LISREG_XP_FREEZE_POSE is set: poses are NOT updated (timing experiment)\n");
-#else
-    c->prm.freeze_pose = 0;
-#endif
     c->n_items = n_items;
     c->h_blocks.clear(); c->h_segs.clear(); c->h_items.assign((size_t)n_items, ItemState());
     c->batch_slots.clear();
@@ -666,10 +646,6 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
         }
         if (total_src > 2000000000LL) return fail(c, LISREG_ERR_ARG, "batch_prepare: more than 2e9 source points in one batch");
         c->mode_now = c->search_mode;
-        // the LDS-staged box (front-end 0, the first version of the search, kept for cross-checks) keeps the first point met on equal
-        // distances and has no canonical re-selection: it cannot honour "canonical_ties" / "exact_arithmetic", so it refuses them
-        if (c->search_mode == 0 && (c->canonical_ties || c->exact))
-            return fail(c, LISREG_ERR_ARG, "batch_prepare: search_mode 0 does not implement canonical_ties / exact_arithmetic (use 1, 3 or 4)");
         if (c->search_mode == 4) {
             const double qi = (double)total_src * (double)c->prm.bound;
             c->mode_now = (t_pts > 0 && qi >= (double)c->graph_min_ratio * t_pts) ? 3 : 1;
@@ -708,7 +684,7 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
     // 2-D sort columns of the (optional) source sort: 0.25 m tiles over every item's target footprint.  The bucket count is kept
     // in 64 bits and the tile grows until the whole batch fits 2^26 buckets (km-scale submaps x large batches would otherwise
     // overflow the int32 bucket numbering and ask for gigabytes of histogram).
-    float tile = env_float("LISREG_TILE", 0.25f);
+    float tile = 0.25f;
     for (;;) {
         long long total = 0;
         for (int i = 0; i < n_items; ++i) {
@@ -995,11 +971,20 @@ static int exact_pose_caches(lisreg_ctx* c)
     return LISREG_OK;
 }
 
+// GN iterations kWideFrom..kWideUntil walk centre-first (no seeds, or seeds a pose step off).  Batches searched with eight lanes per query
+// (single frames, sequential use) start at kWideFromSmall: their first guess is usually a frame step off, and the radius-limited first pass of
+// the plain walk then settles iteration 0 in 160-200 us instead of 230-310 (replay of configs[2]); 1 % slower on a single frame with a
+// 2-degree error (configs[0] stand-in).  The graph scan (search_mode 3) runs the centre-first fall-back walk until kGraphWideUntil; the cell
+// rows (search_mode 5) never do (1.4 % of the queries walk at iteration 0: the plain kernel's iteration 0 takes 317 us against 330 with the
+// centre-first variant, iteration 1 201 against 205; same neighbours).
+constexpr int kWideFrom = 0, kWideFromSmall = 1, kWideUntil = 2, kGraphWideUntil = 1;
+constexpr int kGraphHops = 3;              // search_mode 3: neighbour lists scanned per query (anchor, then nearest found, ...) before the walk takes over
+
 // XCD-aware dispatch order for the prepared batch? (see run_impl)
 static bool xcd_order_wanted(const lisreg_ctx* c)
 {
     const bool many_targets = c->batch_slots.size() >= 8 && c->xcd_order == 1;
-    return c->lanes_q != 8 && c->mode_now != 0 &&
+    return c->lanes_q != 8 &&
            (((c->mode_now == 3 || c->mode_now == 5) && (c->xcd_order == 1 || (c->xcd_order == 2 && c->n_blocks >= 2048 && c->n_items >= 32))) ||
             (many_targets && c->xcd_order != 0 && c->n_blocks >= 2048));
 }
@@ -1023,9 +1008,6 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
     const bool many_targets = c->batch_slots.size() >= 8 && c->xcd_order == 1;
     c->xcd_now = xcd_order_wanted(c);
     if (c->xcd_now) HIPCHK(c, c->xcd_tab.ensure(sizeof(int) * 2 * (size_t)c->n_blocks));
-    // per-run reset of the registrations and the dispatch order: both depend on the batch only (items, initial poses, grid geometry), not on
-    // the rebuilt index — with the cell rows they ride on the side stream behind the corner target's rows, underneath the surf target's
-    // (25-30 us of two small launches and a single-workgroup counting sort off the critical path of a configs[1] step)
     // Two halves of the batch on two streams (round 5).  The 6x6 solves are one workgroup per registration and ~13 us of dependent latency
     // between two correspondence launches: the chip idles through ten of them per step.  Registrations are independent, so the batch is cut
     // in two at an item boundary near the middle of the workgroups: the first half iterates on the context's stream, the second on the side
@@ -1034,14 +1016,8 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
     // that do not stop early from the host (fixed iteration counts, lisreg_batch_run) and are big enough to fill the chip twice.
     const bool can_stop = early_stop && c->prm.fixed_iters <= 0 && c->done_host && c->early_stop_chunk != 0;
     int split_item = 0, split_blk = 0;
-    if (c->interleave != 0 && !c->exact && !can_stop && c->lanes_q == 1 && c->mode_now != 0 && c->n_items >= 2 && c->n_blocks >= c->interleave_min_blocks) {
-        if (!c->side_stream) {
-            if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess) c->side_stream = nullptr;
-            if (c->side_stream && (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                                   hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)) {
-                (void)hipStreamDestroy(c->side_stream); c->side_stream = nullptr;
-            }
-        }
+    if (c->interleave != 0 && !c->exact && !can_stop && c->lanes_q == 1 && c->n_items >= 2 && c->n_blocks >= c->interleave_min_blocks) {
+        ensure_side_stream(c);
         if (c->side_stream && !c->ev_ab && (hipEventCreateWithFlags(&c->ev_ab, hipEventDisableTiming) != hipSuccess ||
                                             hipEventCreateWithFlags(&c->ev_ba, hipEventDisableTiming) != hipSuccess)) { c->ev_ab = nullptr; c->ev_ba = nullptr; }
         if (c->side_stream) {
@@ -1056,32 +1032,9 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
     c->reach_now = c->rebuild_targets_each_run && c->mode_now == 5 && c->reach_ready && !c->exact;
     int* const miss_dev = reinterpret_cast<int*>(c->results.as<float>() + (size_t)std::max(c->n_items, 1) * kResultSize);
     c->prm.reach_miss = c->reach_now ? miss_dev : nullptr;
-    bool reset_done = false, order_done = false;
-    auto dispatch_order = [&](hipStream_t s_) {
-        order_done = true;
-        if (c->xcd_now && !(c->xcd_cached && split_blk == 0)) {
-            // (an interleaved run dispatches its halves separately: one table per half, positions and ids relative to the half)
-            const int nb0 = split_blk ? split_blk : c->n_blocks;
-            launch_xcd_order(c->blocks.as<BlockDesc>(), nb0, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(), c->items.as<ItemState>(),
-                             c->sort_now ? c->sorted_all.as<float4>() : nullptr, many_targets, c->xcd_tab.as<int>(), c->xcd_tab.as<int>() + c->n_blocks, s_);
-            if (split_blk) {
-                launch_xcd_order(c->blocks.as<BlockDesc>() + split_blk, c->n_blocks - split_blk, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(),
-                                 c->items.as<ItemState>(), c->sort_now ? c->sorted_all.as<float4>() : nullptr, many_targets,
-                                 c->xcd_tab.as<int>() + split_blk, c->xcd_tab.as<int>() + c->n_blocks + split_blk, s_);
-                // the half tables have overwritten the batch's table from lisreg_batch_prepare: a later unsplit run of this batch (interleave
-                // switched off, interleave_min_blocks raised) must make its own instead of reading half-relative ids as whole-batch ones
-                c->xcd_cached = false;
-            }
-        }
-    };
     // (the registrations are reset already — by lisreg_batch_prepare or by the run before, launch_finalize — unless a run ended in an error)
-    if (c->items_reset) reset_done = true;
+    const bool reset_done = c->items_reset;
     c->items_reset = false;
-    auto reset_and_order = [&](hipStream_t s_) {
-        if (!reset_done) launch_reset_items(c->items.as<ItemState>(), c->n_items, c->prm, c->done_dev.as<int>(), s_);
-        dispatch_order(s_);
-        reset_done = true;
-    };
     if (c->rebuild_targets_each_run) {                 // the reference rebuilds both kd-trees per registration (:602-603)
         prof_mark(c, 2);
         if (c->strip_now) {
@@ -1089,13 +1042,7 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
             sl.cnt = c->strip_tab.as<int>(); sl.fill = sl.cnt + (c->t_strips + 1); sl.start = sl.fill + (c->t_strips + 1);
             sl.scan_tmp = sl.start + (c->t_strips + 2);
             sl.tmp_pts = c->tmp_pts.as<float4>(); sl.slot_idx = c->elem_bucket.as<uint32_t>(); sl.slot_pos = c->elem_sub.as<uint32_t>();
-            if (!c->side_stream) {                    // created once; failure just means the two variants run back to back
-                if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess) c->side_stream = nullptr;
-                if (c->side_stream && (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                                       hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)) {
-                    (void)hipStreamDestroy(c->side_stream); c->side_stream = nullptr;
-                }
-            }
+            ensure_side_stream(c);                    // failure just means the two variants run back to back
             sl.side = c->side_stream; sl.ev_fork = c->ev_fork; sl.ev_join = c->ev_join;
             if (launch_build_targets_strips(c->tchunk_dev.as<BlockDesc>(), (int)c->h_tchunks.size(), c->tseg_dev.as<TargetSeg>(),
                                             (int)c->h_tsegs.size(), c->t_strips, c->t_max_units, c->t_max_ucells, c->strip_cap, sl, st, &c->strip_zero_ints))
@@ -1106,8 +1053,7 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
         if (c->mode_now == 3)
             launch_build_graph(c->tblk_dev.as<BlockDesc>(), (int)c->h_tblocks.size(), c->tseg_dev.as<TargetSeg>(),
                                c->grids_dev.as<GridIndex>(), st);
-        static const bool crow_pair = !(getenv("LISREG_CROW_PAIR") && atoi(getenv("LISREG_CROW_PAIR")) == 0);      // A/B: 0 = rounds 4-5's side stream
-        if (c->mode_now == 5 && crow_pair) {
+        if (c->mode_now == 5) {
             // corner and surf target of a slot in ONE launch sequence on this stream (launch_crow_rows_pair): no side stream, no event hops
             for (int slot : c->batch_slots) {
                 Target& t = c->targets[(size_t)slot];
@@ -1117,30 +1063,6 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
                 int* oz2[2] = { &t.omask_zero[0], &t.omask_zero[1] };
                 launch_crow_rows_pair(g2, nc2, cb2, st, oz2);
             }
-        } else
-        if (c->mode_now == 5) {
-            // (LISREG_CROW_PAIR=0) the rows of the corner targets (a few ten thousand rows: launches that leave most of the chip idle) are built on the side stream,
-            // underneath the surf targets' — separate buffers per target kind, joined before the first correspondence launch
-            if (!c->side_stream) {
-                if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess) c->side_stream = nullptr;
-                if (c->side_stream && (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                                       hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)) {
-                    (void)hipStreamDestroy(c->side_stream); c->side_stream = nullptr;
-                }
-            }
-            const bool fork = c->side_stream && hipEventRecord(c->ev_fork, st) == hipSuccess &&
-                              hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) == hipSuccess;
-            for (int k = 0; k < 2; ++k) {
-                hipStream_t sk = (k == 0 && fork) ? c->side_stream : st;
-                for (int slot : c->batch_slots) {
-                    Target& t = c->targets[(size_t)slot];
-                    if (t.n[k] <= 0) continue;
-                    launch_crow_classify(t.g[k], t.n_cells[k], crow_buffers(t, k, c->reach_now), sk, &t.omask_zero[k]);
-                    launch_crow_build(t.g[k], t.n_cells[k], crow_buffers(t, k, c->reach_now), sk, &t.omask_zero[k]);
-                }
-            }
-            if (fork && !c->sort_now && !c->exact) reset_and_order(c->side_stream);
-            if (fork) { (void)hipEventRecord(c->ev_join, c->side_stream); (void)hipStreamWaitEvent(st, c->ev_join, 0); }
         }
         prof_mark(c, -1);
     }
@@ -1150,7 +1072,20 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
     launch_sort_sources(c->blocks.as<BlockDesc>(), c->n_blocks, c->segs.as<Segment>(), c->n_segs, c->items.as<ItemState>(),
                         c->n_elems, c->sort_now ? c->n_buckets : 0, sort_buffers(c), c->sorted_all.as<float4>(), c->order_all.as<int>(), st);
     prof_mark(c, -1);
-    if (!order_done) dispatch_order(st);                   // (after the source sort: the keys read the sorted records)
+    if (c->xcd_now && !(c->xcd_cached && split_blk == 0)) {      // (after the source sort: the keys read the sorted records)
+        // (an interleaved run dispatches its halves separately: one table per half, positions and ids relative to the half)
+        const int nb0 = split_blk ? split_blk : c->n_blocks;
+        launch_xcd_order(c->blocks.as<BlockDesc>(), nb0, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(), c->items.as<ItemState>(),
+                         c->sort_now ? c->sorted_all.as<float4>() : nullptr, many_targets, c->xcd_tab.as<int>(), c->xcd_tab.as<int>() + c->n_blocks, st);
+        if (split_blk) {
+            launch_xcd_order(c->blocks.as<BlockDesc>() + split_blk, c->n_blocks - split_blk, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(),
+                             c->items.as<ItemState>(), c->sort_now ? c->sorted_all.as<float4>() : nullptr, many_targets,
+                             c->xcd_tab.as<int>() + split_blk, c->xcd_tab.as<int>() + c->n_blocks + split_blk, st);
+            // the half tables have overwritten the batch's table from lisreg_batch_prepare: a later unsplit run of this batch (interleave
+            // switched off, interleave_min_blocks raised) must make its own instead of reading half-relative ids as whole-batch ones
+            c->xcd_cached = false;
+        }
+    }
     // how often the host looks at the "registrations finished" counter: a skipped launch of a big batch still dispatches tens of
     // thousands of workgroups (check every 3 iterations), a skipped launch of a single frame costs ~2 us (check every 6: one
     // round trip for the typical 3-6 iteration registration)
@@ -1168,7 +1103,7 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
                      c->blocks.as<BlockDesc>() + b0, nb, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(),
                      c->items.as<ItemState>(), c->prm, c->sort_now ? c->sorted_all.as<float4>() : nullptr, c->partials.as<double>() + (size_t)b0 * kNumAcc,
                      c->mode_now, c->nn.as<int>(), c->n_elems, c->first_pass_r * c->first_pass_r,
-                     it >= (c->lanes_q == 8 ? c->wide_from_small : c->wide_from) && it <= (c->mode_now == 5 ? c->crow_wide_until : (c->mode_now == 3 ? c->graph_wide_until : c->wide_until)), c->graph_hops,
+                     c->mode_now != 5 && it >= (c->lanes_q == 8 ? kWideFromSmall : kWideFrom) && it <= (c->mode_now == 3 ? kGraphWideUntil : kWideUntil), kGraphHops,
                      c->count_searches ? c->counters.as<unsigned long long>() : nullptr,
                      c->dump_neighbors ? c->dbg_nn.as<int>() : nullptr, c->lanes_q,
                      c->blocks_q.as<BlockDesc>(), (int)c->h_blocks_q.size(), c->coef.as<float4>(), c->coef_ok.as<int>(),
@@ -1295,7 +1230,7 @@ int lisreg_set_option(lisreg_ctx* c, const char* name, int value)
     if (!strcmp(name, "sort_sources")) { c->sort_sources = value; c->probe_items = -1; return LISREG_OK; }
     if (!strcmp(name, "cell_anchor_until")) { c->cell_anchor_until = std::max(value, 0); return LISREG_OK; }
     if (!strcmp(name, "search_mode")) {
-        if (value < 0 || value > 5 || value == 2) return fail(c, LISREG_ERR_ARG, "search_mode: 0 LDS-staged box, 1 cell walk, 3 k-NN graph scan, 4 auto, 5 cell rows");
+        if (value < 1 || value > 5 || value == 2) return fail(c, LISREG_ERR_ARG, "search_mode: 1 cell walk, 3 k-NN graph scan, 4 auto, 5 cell rows");
         c->search_mode = value; c->prepared = false; return LISREG_OK;
     }
     if (!strcmp(name, "graph_min_ratio")) { c->graph_min_ratio = value; c->prepared = false; return LISREG_OK; }

@@ -247,18 +247,11 @@ int lisreg_stage_host_items(lisreg_ctx* c, int n_items, const lisreg_item* items
     // kernels of the batch that is running, the copies ordered after it start when that batch is through, and the upload of batch k + 1
     // no longer hides underneath batch k (measured, round 6: 12.8 k reg/s against 23.7 k for the same loop with the streams on separate
     // queues — profiles/r06_pcie_overlap.md).  The copy engines themselves do not go through that queue.
-    static const bool feed_legacy = getenv("LISREG_FEED_LEGACY") != nullptr;      // A/B only (tests/pcie_prio_ab.sh): rounds 3-5's device-side wait and
-                                                                                  // packing kernels on the copy stream; same results, no overlap when queues alias
-    if (!c->copy_stream) {
-        const char* e = getenv("LISREG_COPY_PRIO");              // experiments: -1 (high) / 1 (low) put the stream into another queue pool
-        if (e) HIPCHK(c, hipStreamCreateWithPriority(&c->copy_stream, hipStreamNonBlocking, atoi(e)));
-        else HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    }
+    if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     if (!c->pack_copied[b]) HIPCHK(c, hipEventCreateWithFlags(&c->pack_copied[b], hipEventDisableTiming));
     if (!c->pack_free[b]) HIPCHK(c, hipEventCreateWithFlags(&c->pack_free[b], hipEventDisableTiming));
-    else if (!feed_legacy) HIPCHK(c, hipEventSynchronize(c->pack_free[b]));      // the batch that last read device buffer b has run (two batches
-                                                                                 // back in a pipelined loop: long done; a HOST wait, for the reason above)
-    else HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->pack_free[b], 0));
+    else HIPCHK(c, hipEventSynchronize(c->pack_free[b]));      // the batch that last read device buffer b has run (two batches
+                                                               // back in a pipelined loop: long done; a HOST wait, for the reason above)
     // the staging buffer's previous contents have left it (its copies are two calls old)
     if (c->pack_cap[b]) HIPCHK(c, hipEventSynchronize(c->pack_copied[b]));
     const size_t bytes = sizeof(lisreg_dpoint) * std::max<size_t>(total, 1);
@@ -346,8 +339,8 @@ int lisreg_stage_host_items(lisreg_ctx* c, int n_items, const lisreg_item* items
                             }
                             // on a stream of their own: the packing kernel is a packet of a hardware queue that may be busy with the running
                             // batch, and the packed chunks' copies must not be ordered behind it
-                            if (!c->pack_stream && !feed_legacy) HIPCHK(c, hipStreamCreateWithFlags(&c->pack_stream, hipStreamNonBlocking));
-                            hipStream_t ps = feed_legacy ? c->copy_stream : c->pack_stream;
+                            if (!c->pack_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->pack_stream, hipStreamNonBlocking));
+                            hipStream_t ps = c->pack_stream;
                             HIPCHK(c, hipMemcpyAsync(raw_dev + raw_off, ck.src, bytes_k, hipMemcpyHostToDevice, ps));
                             launch_pack_cloud(raw_dev + raw_off, (size_t)ck.n, ck.stride, ck.fmt == LISREG_FMT_XYZIL ? 1 : 0,
                                               reinterpret_cast<float4*>(dev + (ck.dst - host)), ps);

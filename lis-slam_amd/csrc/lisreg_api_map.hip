@@ -257,13 +257,7 @@ int lisreg_map_index_set_batch(lisreg_ctx* c, int n_maps, const int* slots, cons
         sl.cnt = c->strip_tab.as<int>(); sl.fill = sl.cnt + (tstrip + 1); sl.start = sl.fill + (tstrip + 1);
         sl.scan_tmp = sl.start + (tstrip + 2);
         sl.tmp_pts = c->tmp_pts.as<float4>(); sl.slot_idx = c->elem_bucket.as<uint32_t>(); sl.slot_pos = c->elem_sub.as<uint32_t>();
-        if (!c->side_stream) {                    // created once; failure just means the two strip variants run back to back
-            if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess) c->side_stream = nullptr;
-            if (c->side_stream && (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                                   hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)) {
-                (void)hipStreamDestroy(c->side_stream); c->side_stream = nullptr;
-            }
-        }
+        ensure_side_stream(c);                    // failure just means the two strip variants run back to back
         sl.side = c->side_stream; sl.ev_fork = c->ev_fork; sl.ev_join = c->ev_join;
         for (int k = 0; k < n_maps; ++k)          // an empty cloud has no strip: its one-cell table is [0, 0]
             if (counts[k] <= 0) HIPCHK(c, hipMemsetAsync(ms[(size_t)k]->cell_start.p, 0, sizeof(int) * ((size_t)ms[(size_t)k]->n_cells + 1), st));

@@ -16,9 +16,7 @@
 //                      candidates are 16-B records read through L1/L2, four loads in flight per lane;
 //       k_assoc_walk<.., kGraph = true>   certified scan of the k-NN graph row of last iteration's nearest neighbour, the cell walk
 //                      only without a certificate (big shared-target batches);
-//       k_assoc_staged (first version, kept for cross-checks) workgroup bounding box + sqrt(tau), covered cell runs
-//                      staged through LDS, all lanes scan via LDS broadcast;
-//     all return the same neighbour SETS (tests require identical correspondence counts);
+//     both return the same neighbour SETS (tests require identical correspondence counts);
 //   * the 5 neighbours are gathered once (5 x 16 B), the 3x3 eigen / 5x3 QR fit, weights and the Jacobian row stay in
 //     registers, and the 28 normal-equation scalars are reduced by a wave-level halving butterfly -> LDS -> one partial row
 //     per workgroup (fixed order, no float atomics: reproducible).
@@ -54,15 +52,9 @@ namespace {
 namespace LISREG_ASSOC_NS {
 
 constexpr bool kExactArith = LISREG_EXACT != 0;
-#ifndef LISREG_KEEP_SRC
-#define LISREG_KEEP_SRC 1        // one-lane-per-query kernels keep the source record in registers across the search (see k_assoc_walk)
-#endif
 // (Round 5 built three variants of this file that measured no gain and were taken out again — the 28 wave sums on the matrix pipe
 // (v_mfma_f32_16x16x4_f32: gfx950's f32 MFMA runs at the f32 vector rate), the heads of the cell rows staged in LDS, the plane fit's pivot
 // swaps as selects: profiles/r05_kernel_experiments.md sections 1, 3, 11; the code is profiles/r05_xp_mfma_stage_select.patch.)
-#ifndef LISREG_MED3_INSERT
-#define LISREG_MED3_INSERT 1
-#endif
 // LDS of the reduction: one private region per wavefront (kRedWaveFloats floats) inside one array of the kernel.
 //   the region starts with the wave's 28 sums (doubles)
 constexpr int kRedWaveFloats = 1024;
@@ -362,12 +354,7 @@ __device__ __forceinline__ void lstsq5x3(const float4 nb[5], float X[3])
 // by decimetres (relative error ~ cond(A) eps ~ 1e-4 for a far patch), the scatter matrix on the differences alone.  Where the five points
 // are close to ONE LINE (second eigenvalue of S under 1e-2 of the first: adj(S) loses its digits, and the reference's answer is whatever
 // the pivoted QR makes of a rank-deficient system) the QR runs as before: `false` is returned.
-#ifndef LISREG_PLANE_CLOSED
-#define LISREG_PLANE_CLOSED 1
-#endif
-#ifndef LISREG_PLANE_LINE_RATIO
-#define LISREG_PLANE_LINE_RATIO 1e-2f
-#endif
+constexpr float kPlaneLineRatio = 1e-2f;
 __device__ __forceinline__ bool plane5_closed(const float4 nb[5], float& pa, float& pb, float& pc, float& pd)
 {
     const float cx = ((nb[0].x + nb[1].x) + (nb[2].x + nb[3].x) + nb[4].x) * 0.2f;
@@ -388,17 +375,14 @@ __device__ __forceinline__ bool plane5_closed(const float4 nb[5], float& pa, flo
     const float iw = __builtin_amdgcn_rsqf(ww);
     pa = -wx * iw; pb = -wy * iw; pc = -wz * iw;
     pd = (det * 0.2f + (cx * wx + cy * wy + cz * wz)) * iw;
-    return tra > LISREG_PLANE_LINE_RATIO * (tr * tr) && ww > 0.f && ww < 3.0e38f;
+    return tra > kPlaneLineRatio * (tr * tr) && ww > 0.f && ww < 3.0e38f;
 }
 
 __device__ __forceinline__ float4 surf_model(const float4 nb[5], const DevParams& P)
 {
     float pa, pb, pc, pd;
     bool closed = false;
-    if (!kExactArith && LISREG_PLANE_CLOSED) closed = plane5_closed(nb, pa, pb, pc, pd);
-#if LISREG_PLANE_CLOSED == 2        /* timing experiment: never the QR */
-    closed = true;
-#endif
+    if (!kExactArith) closed = plane5_closed(nb, pa, pb, pc, pd);
     if (!closed) {
         float X[3];
         lstsq5x3(nb, X);
@@ -539,27 +523,14 @@ __device__ __forceinline__ bool residual_coeffs(bool valid, int i0, int i1, int 
     if (found) {
         float4 nb[5];
         const gptr_f4 gp = (gptr_f4)g.pts;
-#ifdef LISREG_XP_NOGATHER      /* timing experiment (wrong results): five synthetic neighbours on a plane through the query, no memory access */
-        (void)gp;
-        v4f n0, n1, n2, n3, n4;
-        n0.x = qx + 0.11f; n0.y = qy + 0.02f; n0.z = qz; n0.w = 0.f;  n1.x = qx - 0.07f; n1.y = qy + 0.13f; n1.z = qz; n1.w = 0.f;
-        n2.x = qx - 0.12f; n2.y = qy - 0.09f; n2.z = qz; n2.w = 0.f;  n3.x = qx + 0.05f; n3.y = qy - 0.14f; n3.z = qz; n3.w = 0.f;
-        n4.x = qx + 0.01f * (float)(i4 & 7); n4.y = qy + 0.21f; n4.z = qz; n4.w = 0.f;
-#else
         v4f n0, n1, n2, n3, n4;
         n0 = LISREG_LD4(gp, i0); n1 = LISREG_LD4(gp, i1); n2 = LISREG_LD4(gp, i2); n3 = LISREG_LD4(gp, i3); n4 = LISREG_LD4(gp, i4);
-#endif
         nb[0] = make_float4(n0.x, n0.y, n0.z, n0.w); nb[1] = make_float4(n1.x, n1.y, n1.z, n1.w);
         nb[2] = make_float4(n2.x, n2.y, n2.z, n2.w); nb[3] = make_float4(n3.x, n3.y, n3.z, n3.w);
         nb[4] = make_float4(n4.x, n4.y, n4.z, n4.w);
         float w = 1.f;
         if (P.use_label) w = label_weight(P, q4.w);
-#ifdef LISREG_XP_NOFIT          /* timing experiment (wrong results): no line / plane fit, the gathered points stay live */
-        cf[0] = nb[0].x + nb[1].y + w; cf[1] = nb[2].z + nb[3].x; cf[2] = nb[4].y + nb[0].z; cf[3] = (nb[1].x + nb[2].y + nb[3].z + nb[4].x) * 1e-3f;
-        ok = cf[3] < 1.0e30f;
-#else
         ok = (kind == 0) ? corner_coeff(nb, qx, qy, qz, w, P, cf) : surf_coeff(nb, qx, qy, qz, w, P, cf);
-#endif
     }
     return ok;
 }
@@ -579,10 +550,6 @@ __device__ __forceinline__ void row_and_reduce(bool ok, const float cf[4], const
                                                const DevParams& P, float* s_red, double* __restrict__ out)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef LISREG_XP_NOREDUCE       /* timing experiment (wrong results): no Jacobian row, no sums */
-    if (ok && tid < kNumAcc) out[tid] = (double)(cf[0] + cf[1] + cf[2] + cf[3] + q4.x);
-    return;
-#endif
     double (*s_acc)[kRedWaveFloats / 2] = reinterpret_cast<double (*)[kRedWaveFloats / 2]>(s_red);     // s_acc[wave][k]: the wave's region as doubles
     (void)s_acc;
     float row[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }, rb = 0.f, one = 0.f;
@@ -693,144 +660,8 @@ __device__ __forceinline__ void row_and_reduce(bool ok, const float cf[4], const
     }
 }
 
-
-__global__ __launch_bounds__(kBlockQ) void k_assoc_staged(const BlockDesc* __restrict__ blocks,
-                                                   const Segment* __restrict__ segs,
-                                                   const GridIndex* __restrict__ grids,
-                                                   const ItemState* __restrict__ items, const DevParams P,
-                                                   const float4* __restrict__ sorted_all,
-                                                   double* __restrict__ partials)
-{
-    __shared__ float4 s_pts[kStageCap];
-    __shared__ int    s_run_start[kBlockQ];
-    __shared__ int    s_run_off[kBlockQ + 1];
-    __shared__ int    s_wave[4];
-    __shared__ float  s_bb[4][6];
-    __shared__ __attribute__((aligned(16))) float s_red[4 * kRedWaveFloats];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const BlockDesc bd = blocks[blockIdx.x];
-    const ItemState* it = &items[bd.item];
-    if (it->done) return;                       // converged / guarded-out item: solve kernel skips it too
-    const Segment sg = segs[bd.seg];
-    const GridIndex g = grids[sg.target];
-    double* out = partials + (size_t)blockIdx.x * kNumAcc;
-    if (g.n < 5) {                              // nearestKSearch cannot return 5 neighbours: no correspondences
-        if (tid < kNumAcc) out[tid] = 0.0;
-        return;
-    }
-
-    const float* M = it->M;            // trans2Affine3f(T), cached by the solve kernel (uniform -> SGPRs)
-
-    const bool valid = tid < bd.count;
-    float4 q4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (valid) q4 = sorted_all ? sorted_all[sg.flat_base + bd.start + tid] : sg.src[bd.start + tid];
-    // pointAssociateToMap (:243-258)
-    float qx = M[0] * q4.x + M[1] * q4.y + M[2] * q4.z + M[3];
-    float qy = M[4] * q4.x + M[5] * q4.y + M[6] * q4.z + M[7];
-    float qz = M[8] * q4.x + M[9] * q4.y + M[10] * q4.z + M[11];
-
-    // ---- workgroup bounding box of the transformed queries --------------------------------------------------
-    float lo[3] = { valid ? qx : 3.0e38f, valid ? qy : 3.0e38f, valid ? qz : 3.0e38f };
-    float hi[3] = { valid ? qx : -3.0e38f, valid ? qy : -3.0e38f, valid ? qz : -3.0e38f };
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], d));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], d));
-        }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { s_bb[wave][k] = lo[k]; s_bb[wave][3 + k] = hi[k]; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        lo[k] = fminf(fminf(s_bb[0][k], s_bb[1][k]), fminf(s_bb[2][k], s_bb[3][k]));
-        hi[k] = fmaxf(fmaxf(s_bb[0][3 + k], s_bb[1][3 + k]), fmaxf(s_bb[2][3 + k], s_bb[3][3 + k]));
-    }
-    if (!valid) { qx = qy = qz = 3.0e18f; }     // never closer than tau to anything
-
-    // ---- covered cell range: every target point with |p - q|_inf <= margin lies inside ----------------------
-    const float margin = sqrtf(P.tau) * 1.0005f + 1e-3f;
-    int ix0 = grid_coord(lo[0] - margin, g.ox, g.inv_cell), ix1 = grid_coord(hi[0] + margin, g.ox, g.inv_cell);
-    int iy0 = grid_coord(lo[1] - margin, g.oy, g.inv_cell), iy1 = grid_coord(hi[1] + margin, g.oy, g.inv_cell);
-    int iz0 = grid_coord(lo[2] - margin, g.oz, g.inv_cell), iz1 = grid_coord(hi[2] + margin, g.oz, g.inv_cell);
-    ix0 = max(ix0, 0); iy0 = max(iy0, 0); iz0 = max(iz0, 0);
-    ix1 = min(ix1, g.nx - 1); iy1 = min(iy1, g.ny - 1); iz1 = min(iz1, g.nz - 1);
-    const int nrx = ix1 - ix0 + 1, nry = iy1 - iy0 + 1;
-    const int nruns = (nrx > 0 && nry > 0 && iz1 >= iz0) ? nrx * nry : 0;
-
-    // ---- exact fixed-radius 5-NN: sorted top-5 in registers, initialised at tau ------------------------------
-    float b0 = P.tau, b1 = P.tau, b2 = P.tau, b3 = P.tau, b4 = P.tau;
-    int   i0 = -1, i1 = -1, i2 = -1, i3 = -1, i4 = -1;
-
-    for (int rb = 0; rb < nruns; rb += kBlockQ) {
-        const int r = rb + tid;
-        int rs = 0, rl = 0;
-        if (r < nruns) {
-            const int ix = ix0 + r / nry, iy = iy0 + r % nry;
-            const int base = (ix * g.ny + iy) * g.nz;
-            rs = g.cell_start[base + iz0];
-            rl = g.cell_start[base + iz1 + 1] - rs;
-        }
-        // workgroup exclusive scan of run lengths
-        int inc = rl;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d); if (lane >= d) inc += t; }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        int wbase = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { const int s = s_wave[w]; if (w < wave) wbase += s; total += s; }
-        s_run_start[tid] = rs;
-        s_run_off[tid] = wbase + inc - rl;
-        if (tid == 0) s_run_off[kBlockQ] = total;
-        __syncthreads();
-
-        for (int chunk = 0; chunk < total; chunk += kStageCap) {
-            const int cnt = min(kStageCap, total - chunk);
-            // stage: flat candidate id -> (run, offset) by binary search over the run offsets
-            for (int j = tid; j < cnt; j += kBlockQ) {
-                const int gidx = chunk + j;
-                int l = 0, h = kBlockQ - 1;
-                while (l < h) {
-                    const int mid = (l + h + 1) >> 1;
-                    if (s_run_off[mid] <= gidx) l = mid; else h = mid - 1;
-                }
-                const int src = s_run_start[l] + (gidx - s_run_off[l]);
-                float4 v = g.pts[src];
-                v.w = __int_as_float(src);                 // position in the sorted target array
-                s_pts[j] = v;
-            }
-            __syncthreads();
-            // scan: every lane tests every staged point (LDS broadcast read)
-#pragma unroll 4
-            for (int j = 0; j < cnt; ++j) {
-                const float4 c = s_pts[j];
-                const float dx = qx - c.x, dy = qy - c.y, dz = qz - c.z;
-                const float d2 = dx * dx + dy * dy + dz * dz;     // flann::L2_Simple order
-                if (d2 < b4) {
-                    const int id = __float_as_int(c.w);
-                    const bool c3 = d2 < b3, c2 = d2 < b2, c1 = d2 < b1, c0 = d2 < b0;
-                    b4 = c3 ? b3 : d2;               i4 = c3 ? i3 : id;
-                    b3 = c3 ? (c2 ? b2 : d2) : b3;   i3 = c3 ? (c2 ? i2 : id) : i3;
-                    b2 = c2 ? (c1 ? b1 : d2) : b2;   i2 = c2 ? (c1 ? i1 : id) : i2;
-                    b1 = c1 ? (c0 ? b0 : d2) : b1;   i1 = c1 ? (c0 ? i0 : id) : i1;
-                    b0 = c0 ? d2 : b0;               i0 = c0 ? id : i0;
-                }
-            }
-            __syncthreads();
-        }
-    }
-
-    residual_and_reduce(valid, i0, i1, i2, i3, i4, g, q4, qx, qy, qz, it->jk, P, sg.kind, s_red, out);
-}
-
-// sorted top-5 insertion (ascending); `id` must not already be in the list
-#if LISREG_MED3_INSERT
-// the inner distances of the new list are medians of three (the list ascends and d2 < b4 here): three v_med3_f32 instead of six selects,
+// sorted top-5 insertion (ascending); `id` must not already be in the list.
+// The inner distances of the new list are medians of three (the list ascends and d2 < b4 here): three v_med3_f32 instead of six selects,
 // same values (d2 equal to an entry: both forms keep the entry in front)
 #define LISREG_INSERT(d2, id) do { \
         const bool c3_ = (d2) < b3, c2_ = (d2) < b2, c1_ = (d2) < b1, c0_ = (d2) < b0; \
@@ -843,15 +674,6 @@ __global__ __launch_bounds__(kBlockQ) void k_assoc_staged(const BlockDesc* __res
         i1 = c1_ ? (c0_ ? i0 : (id)) : i1; \
         i0 = c0_ ? (id) : i0; \
         b4 = n4_; b3 = n3_; b2 = n2_; b1 = n1_; b0 = n0_; } while (0)
-#else
-#define LISREG_INSERT(d2, id) do { \
-        const bool c3_ = (d2) < b3, c2_ = (d2) < b2, c1_ = (d2) < b1, c0_ = (d2) < b0; \
-        b4 = c3_ ? b3 : (d2);               i4 = c3_ ? i3 : (id); \
-        b3 = c3_ ? (c2_ ? b2 : (d2)) : b3;  i3 = c3_ ? (c2_ ? i2 : (id)) : i3; \
-        b2 = c2_ ? (c1_ ? b1 : (d2)) : b2;  i2 = c2_ ? (c1_ ? i1 : (id)) : i2; \
-        b1 = c1_ ? (c0_ ? b0 : (d2)) : b1;  i1 = c1_ ? (c0_ ? i0 : (id)) : i1; \
-        b0 = c0_ ? (d2) : b0;               i0 = c0_ ? (id) : i0; } while (0)
-#endif
 
 // Per-lane grid walk: every lane visits only the cells that can hold a point closer than its current 5th-best
 // distance (pruned per x-slab, per (x,y) column and per z-range), reading candidates straight from the
@@ -1192,20 +1014,13 @@ __device__ __forceinline__ int cell_anchor(const GridIndex& g, gptr_i32 cells, g
                 const float thr_ = __builtin_amdgcn_sqrtf(b4) * 1.0001f + da_; thr2_ = thr_ * thr_; \
                 if (cnt_ > 0) LISREG_GRAPH_GROUP(r0_, r1_, r2_, r3_, LISREG_TRY_ND); \
             } \
-            _Pragma("unroll 1") for (int g_ = 1; !stop_ && 4 * g_ < cnt_ && LISREG_XP_SCAN_GROUPS(g_); ++g_) { \
+            _Pragma("unroll 1") for (int g_ = 1; !stop_ && 4 * g_ < cnt_; ++g_) { \
                 const v4f e0g_ = R_[4 * g_], e1g_ = R_[4 * g_ + 1], e2g_ = R_[4 * g_ + 2], e3g_ = R_[4 * g_ + 3]; \
                 LISREG_GRAPH_GROUP(e0g_, e1g_, e2g_, e3g_, LISREG_TRY_ND); \
             } \
             if (!stop_) stop_ = rho2_ > thr2_;                 /* list exhausted: the coverage radius decides */ \
-            certified = stop_ || LISREG_XP_ALWAYS_CERTIFIED; } while (0)
+            certified = stop_; } while (0)
 
-#ifdef LISREG_XP_NOSCAN         /* timing experiment (wrong results): two groups of the row, no stop test, never a walk */
-#define LISREG_XP_SCAN_GROUPS(g_) ((g_) < 2)
-#define LISREG_XP_ALWAYS_CERTIFIED true
-#else
-#define LISREG_XP_SCAN_GROUPS(g_) true
-#define LISREG_XP_ALWAYS_CERTIFIED false
-#endif
 #define LISREG_CE5(a, b) do { const bool sw_ = sd[b] < sd[a]; const float ta_ = sd[a]; const int ia_ = sid[a]; \
                               sd[a] = sw_ ? sd[b] : ta_; sd[b] = sw_ ? ta_ : sd[b]; sid[a] = sw_ ? sid[b] : ia_; sid[b] = sw_ ? ia_ : sid[b]; } while (0)
 
@@ -1307,19 +1122,11 @@ __global__ __launch_bounds__(kBlockQ) __attribute__((amdgpu_waves_per_eu(kShare 
     // sources: the tile-sorted copy if the batch was sorted, else the caller's own records (no flattening copy).  Both are
     // addressed with the batch-wide position qflat, so that one register serves the source and the seed arrays.
     const float4* qsrc = sorted_all ? sorted_all : (const float4*)((uintptr_t)sg.src - (uintptr_t)sg.flat_base * sizeof(float4));
-    float qx, qy, qz;
-#if LISREG_KEEP_SRC
     float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
-    {
-#if !LISREG_KEEP_SRC
-        float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
-        if (valid) q0 = qsrc[qflat];
-        qx = M[0] * q0.x + M[1] * q0.y + M[2] * q0.z + M[3];
-        qy = M[4] * q0.x + M[5] * q0.y + M[6] * q0.z + M[7];
-        qz = M[8] * q0.x + M[9] * q0.y + M[10] * q0.z + M[11];
-    }
+    if (valid) q0 = qsrc[qflat];
+    float qx = M[0] * q0.x + M[1] * q0.y + M[2] * q0.z + M[3];
+    float qy = M[4] * q0.x + M[5] * q0.y + M[6] * q0.z + M[7];
+    float qz = M[8] * q0.x + M[9] * q0.y + M[10] * q0.z + M[11];
 
     // the five-best list (ascending).  Not initialised here: the common path (graph scan, first list with >= 4 entries) overwrites all
     // ten registers, and an initialisation up front is executed by every wavefront (the compiler even emitted it twice)
@@ -1518,15 +1325,8 @@ __global__ __launch_bounds__(kBlockQ) __attribute__((amdgpu_waves_per_eu(kShare 
     // 55-57 of 64 with it — and the second read, a dependent load at the end of a wavefront's chain, was 6 us of a 172 us launch);
     // eight lanes per query read it again (the sharing variant is at its register limit)
     float4 q4 = make_float4(0.f, 0.f, 0.f, 0.f);
-#ifdef LISREG_XP_NOSRC2         /* timing experiment (wrong results): no second read of the source record */
-    q4 = make_float4(qx, qy, qz, 0.f);
-#else
-#if LISREG_KEEP_SRC
     if (kQ == 1) q4 = q0;
-    else
-#endif
-    if (valid) { const v4f t = __builtin_nontemporal_load((const v4f*)&qsrc[qflat]); q4 = make_float4(t.x, t.y, t.z, t.w); }
-#endif
+    else if (valid) { const v4f t = __builtin_nontemporal_load((const v4f*)&qsrc[qflat]); q4 = make_float4(t.x, t.y, t.z, t.w); }
     if (kQ == 1) {
         residual_and_reduce(valid, i0, i1, i2, i3, i4, g, q4, qx, qy, qz, it->jk, P, sg.kind, s_red, out,
                                          dbg_nn ? dbg_nn + 5 * (size_t)n_elems + qflat : nullptr);
@@ -1591,7 +1391,7 @@ __global__ __launch_bounds__(64) void k_test_fit_models(int kind, int n, const f
     if (kind == 1) {
         float pa, pb, pc, pd;
         bool closed = false;
-        if (!kExactArith && LISREG_PLANE_CLOSED) closed = plane5_closed(nb, pa, pb, pc, pd);
+        if (!kExactArith) closed = plane5_closed(nb, pa, pb, pc, pd);
         const float4 m = surf_model(nb, P);
         const bool ok = surf_eval(m, qx, qy, qz, 1.f, P, cf);
         o[0] = m.x; o[1] = m.y; o[2] = m.z; o[3] = m.w; o[4] = closed ? 1.f : 0.f;
@@ -1733,9 +1533,7 @@ static void launch_assoc_impl(const BlockDesc* blocks, int n_blocks, const Segme
         k_rows_reduce<<<n_blocks, kBlockQ, 0, st>>>(blocks, segs, grids, items, prm, sorted_all, coef, coef_ok, partials);
         return;
     }
-    if (mode == 0)
-        k_assoc_staged<<<n_blocks, kBlockQ, 0, st>>>(blocks, segs, grids, items, prm, sorted_all, partials);
-    else if (mode == 1) {
+    if (mode == 1) {
         if (wide)
             k_assoc_walk<true, 0, 1, kTies><<<n_blocks, kBlockQ, 0, st>>>(blocks, segs, grids, items, prm, sorted_all, nn, n_elems,
                                                                               first_pass_r2, graph_hops, counters, dbg_nn, coef, coef_ok, partials, xcd_order);
@@ -1743,12 +1541,8 @@ static void launch_assoc_impl(const BlockDesc* blocks, int n_blocks, const Segme
             k_assoc_walk<false, 0, 1, kTies><<<n_blocks, kBlockQ, 0, st>>>(blocks, segs, grids, items, prm, sorted_all, nn, n_elems,
                                                                                first_pass_r2, graph_hops, counters, dbg_nn, coef, coef_ok, partials, xcd_order);
     } else if (mode == 5) {
-        if (wide)
-            k_assoc_walk<true, 2, 1, kTies><<<n_blocks, kBlockQ, 0, st>>>(blocks, segs, grids, items, prm, sorted_all, nn, n_elems,
-                                                                          first_pass_r2, graph_hops, counters, dbg_nn, coef, coef_ok, partials, xcd_order);
-        else
-            k_assoc_walk<false, 2, 1, kTies><<<n_blocks, kBlockQ, 0, st>>>(blocks, segs, grids, items, prm, sorted_all, nn, n_elems,
-                                                                           first_pass_r2, graph_hops, counters, dbg_nn, coef, coef_ok, partials, xcd_order);
+        k_assoc_walk<false, 2, 1, kTies><<<n_blocks, kBlockQ, 0, st>>>(blocks, segs, grids, items, prm, sorted_all, nn, n_elems,
+                                                                       first_pass_r2, graph_hops, counters, dbg_nn, coef, coef_ok, partials, xcd_order);
     } else {
         if (wide)
             k_assoc_walk<true, 1, 1, kTies><<<n_blocks, kBlockQ, 0, st>>>(blocks, segs, grids, items, prm, sorted_all, nn, n_elems,

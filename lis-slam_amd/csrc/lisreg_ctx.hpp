@@ -180,7 +180,7 @@ struct lisreg_ctx {
     int       t_elems = 0, t_buckets = 0;
     bool      count_searches = false;
     bool      dump_neighbors = false;   // tests: keep the five neighbour ids of every query of the last iteration run
-    int       search_mode = 4;           // 0 LDS-staged box, 1 per-lane cell walk, 3 k-NN graph scan, 5 cell rows,
+    int       search_mode = 4;           // 1 per-lane cell walk, 3 k-NN graph scan, 5 cell rows,
                                          // 4 auto: 3 when the prepared batch asks enough queries per target point to pay for the graph, else 1
     int       mode_now = 1;              // front-end of the prepared batch
     int       lanes_q = 1;               // lanes per query of the prepared batch (8 for small walk-mode batches)
@@ -203,10 +203,6 @@ struct lisreg_ctx {
     int       feeder_numa = 1;           // packing threads bound to the CPUs of the device's NUMA node (those this process owns)
     int       feeder_node = -1, feeder_cpus = 0;       // what that found: the node, the CPUs bound to
     int       cell_anchor_until = 1;     // graph front-end: GN iterations 1 .. this also try an anchor out of the query's own grid column
-    int       graph_hops = 3;            // neighbour lists scanned per query (anchor, then nearest found, ...) before the walk takes over
-    int       graph_wide_until = 1;      // search_mode 3: GN iterations 0..this run the centre-first variant of the fall-back walk
-    int       crow_wide_until = -1;      // search_mode 5: the same for the cell rows — never (1.4 % of the queries walk at iteration 0: the plain kernel's
-                                         // iteration 0 takes 317 us against 330 with the centre-first variant, iteration 1 201 against 205; same neighbours)
     bool      canonical_ties = false;    // "canonical_ties" (always on with exact_arithmetic)
     bool      exact = false;             // "exact_arithmetic": the correspondence launches and the pose cache run the reference's arithmetic (lisreg_assoc.hip)
     int       sort_sources = 2;          // 0: keep the caller order, 1: 2-D column sort, 2: auto (probe the order at prepare time)
@@ -214,12 +210,6 @@ struct lisreg_ctx {
     int       probe_items = -1, probe_elems = -1, probe_age = 0; bool probe_verdict = false;   // the batch shape the order was last probed on (auto): batches of a stream are alike
     float     first_pass_r = 0.45f;
     int       last_launches = 0;         // Gauss-Newton iterations the last fetched batch ran (its slowest item): where run_impl looks first
-    int       wide_from = 0;
-    int       wide_from_small = 1;       // the same for batches searched with eight lanes per query (single frames, sequential use): their
-                                         // first guess is usually a frame step off, and the radius-limited first pass of the plain walk
-                                         // then settles iteration 0 in 160-200 us instead of 230-310 (replay of configs[2]); 1 % slower on
-                                         // a single frame with a 2-degree error (configs[0] stand-in)
-    int       wide_until = 2;            // GN iterations wide_from..wide_until walk centre-first (no seeds, or seeds a pose step off)
     std::vector<lisreg::BlockDesc> h_blocks;      // 256-query workgroups: partial rows, sorts, probes
     std::vector<lisreg::BlockDesc> h_blocks_q;    // lanes_q > 1: kBlockQ / lanes_q queries per workgroup of the search kernel
     std::vector<lisreg::Segment>   h_segs;
@@ -253,6 +243,8 @@ namespace lisreg {
 void feeder_destroy(lisreg_ctx* c);
 void loopdet_destroy(lisreg_ctx* c);
 int  ctx_fail(lisreg_ctx* c, int code, const std::string& msg);
+// the side stream and its fork / join events, created on first use; false if they cannot be made (the caller then runs on one stream)
+bool ensure_side_stream(lisreg_ctx* c);
 // pack PCL structs (stride/format of common.h:9,25-35) into 16-B device records
 void pack_cloud(const void* cloud, int n, int stride, int fmt, lisreg_dpoint* out);
 // grid geometry from a bounding box; cell edge grows if the box would need too many cells

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void k_feat_occlude(const int* __restrict__ co
 
 // extractFeatures (:610-713): one wave per ring
 __global__ __launch_bounds__(256) void k_feat_select(const int* __restrict__ pos, int H, int W, lisreg_feature_params P,
-                                                    FeatureBuffers fb, int rows_per_sweep, int xp_stop)
+                                                    FeatureBuffers fb, int rows_per_sweep)
 {
     __shared__ int   s_picked[kMaxRingPts];
     __shared__ float s_curv[kMaxRingPts];
@@ -156,7 +156,6 @@ __global__ __launch_bounds__(256) void k_feat_select(const int* __restrict__ pos
         while (nb < 5 && pair_ok(a - nb)) ++nb;
         s_run[a - lo] = (unsigned char)(nf | (nb << 4));
     }
-    if (xp_stop == 1) return;                                          // timing experiments only (LISREG_XP_FEAT_STOP): wrong results
 
     // std::sort of every sector's curvatures (:620), ascending by (curvature, index) — by RANK COUNTING (round 5): a curvature is a square,
     // so its float bits order like the value, and (bits << 32 | position) is one 64-bit key per point; a point's place in its sector's
@@ -197,7 +196,7 @@ __global__ __launch_bounds__(256) void k_feat_select(const int* __restrict__ pos
         }
     }
     __syncthreads();
-    if (wave != 0 || xp_stop == 2) return;                             // the picking below is one wavefront's work; no barrier follows
+    if (wave != 0) return;                                             // the picking below is one wavefront's work; no barrier follows
 
     for (int j = 0; j < 6; ++j) {
         const int sp = (startRing * (6 - j) + endRing * j) / 6;
@@ -532,13 +531,7 @@ void launch_extract_features(const float4* pts, const uint32_t* rings, int n, li
     k_feat_extract<<<(hw + 16 + 255) / 256, 256, 0, st>>>(pts, fb.owner, fb.pos, H, W, fb);
     k_feat_smooth<<<(hw + 255) / 256, 256, 0, st>>>(fb.counts, fb.range, fb.curv, fb.pos, hw_sweep, n_sweeps);
     k_feat_occlude<<<(hw + 255) / 256, 256, 0, st>>>(fb.counts, fb.range, fb.col, fb.picked, fb.pos, hw_sweep, n_sweeps);
-#ifdef LISREG_XP_HOOKS      /* timing experiment (wrong features), compiled in only on request (csrc/Makefile: XP=1) */
-    static const int xp_stop = getenv("LISREG_XP_FEAT_STOP") ? atoi(getenv("LISREG_XP_FEAT_STOP")) : 0;
-    if (xp_stop) fprintf(stderr, "[lisreg] LISREG_XP_FEAT_STOP is set: feature selection stops early (timing experiment)\n");
-#else
-    const int xp_stop = 0;
-#endif
-    k_feat_select<<<H, 256, 0, st>>>(fb.pos, H, W, P, fb, rows_per_sweep, xp_stop);   // grid = sweeps x rings
+    k_feat_select<<<H, 256, 0, st>>>(fb.pos, H, W, P, fb, rows_per_sweep);   // grid = sweeps x rings
     k_feat_surface_flags<<<(hw + 16 + 255) / 256, 256, 0, st>>>(fb.pos, H, W, fb);
     // the second scan goes to the upper half of `pos`; the lower half (ring boundaries) stays valid
     launch_exclusive_scan(fb.flag, fb.pos + (hw + 17), fb.scan_tmp, hw + 16, st);

@@ -678,13 +678,8 @@ __global__ __launch_bounds__(kLarge ? 1024 : 256) void k_strip_build(const Targe
 // One wavefront per workgroup: the rows are wavefront-level work (no barrier), and a workgroup's slots come free only when its LAST
 // wavefront ends — with four wavefronts of unequal work per workgroup the build ran at 2.4 wavefronts per SIMD in flight (round 5,
 // profiles/r05_kernel_experiments.md section 19: graph build 947 -> 906 us per launch on configs[4] with 8 points per wavefront, row build below)
-#ifndef LISREG_GRAPH_WPB
-#define LISREG_GRAPH_WPB 1           // wavefronts per workgroup of the graph build
-#endif
-#ifndef LISREG_GRAPH_PPW
-#define LISREG_GRAPH_PPW 8
-#endif
-constexpr int kGraphPPW = LISREG_GRAPH_PPW;            // points per wave (sequential)
+constexpr int kGraphWPB = 1;                          // wavefronts per workgroup of the graph build
+constexpr int kGraphPPW = 8;                          // points per wave (sequential)
 
 // value of lane (l ^ M).  The sort below is bound by cross-lane traffic, and ds_bpermute (the LDS crossbar, 4 LDS cycles per
 // wave-instruction) was 40 % of the build's wave time; most masks of the network have a pure-VALU form on gfx950: quad
@@ -702,150 +697,25 @@ template <int M> __device__ __forceinline__ int lane_xor(int v)
     else return __shfl_xor(v, M);
 }
 
-// compare-exchange of 64-bit keys (squared distance bits << 32 | id: positive floats order like unsigned integers, the id breaks
-// ties) with the lane M away; lanes whose bit `LowBit` is clear keep the smaller key.  Every stage of the network below has
-// this one direction, so a stage is two cross-lane moves, one 64-bit compare and two selects.
-template <int M, int LowBit> __device__ __forceinline__ unsigned long long cmpx64(unsigned long long k, int lane)
-{
-    const unsigned lo = (unsigned)lane_xor<M>((int)(unsigned)k), hi = (unsigned)lane_xor<M>((int)(unsigned)(k >> 32));
-    const unsigned long long pk = ((unsigned long long)hi << 32) | lo;
-    const bool take_min = (lane & LowBit) == 0;
-    return ((pk < k) == take_min) ? pk : k;
-}
-
-template <int H> __device__ __forceinline__ unsigned long long half_cleaners(unsigned long long k, int lane)
-{
-    if constexpr (H > 0) { k = cmpx64<H, H>(k, lane); return half_cleaners<(H >> 1)>(k, lane); }
-    else return k;
-}
-// merge sorted blocks of H into sorted blocks of 2H, in the "mirror" form: the first stage pairs lane i with the lane mirrored
-// inside the block, the rest are half-cleaners — the lower lane always keeps the minimum
-template <int H> __device__ __forceinline__ unsigned long long merge_blocks(unsigned long long k, int lane)
-{
-    k = cmpx64<2 * H - 1, H>(k, lane);
-    return half_cleaners<(H >> 1)>(k, lane);
-}
-// ascending sort of one key per lane across the wave
-__attribute__((unused)) __device__ __forceinline__ unsigned long long sort64(unsigned long long k, int lane)
-{
-    k = merge_blocks<1>(k, lane); k = merge_blocks<2>(k, lane); k = merge_blocks<4>(k, lane);
-    k = merge_blocks<8>(k, lane); k = merge_blocks<16>(k, lane); k = merge_blocks<32>(k, lane);
-    return k;
-}
-
-// One row: the kGraphK target points nearest to the location q (home cell hx, hy, hz; `s` = a sorted point to leave out, or -1), ascending,
-// with the coverage radius of the 5 x 5 x 5 block — the k-NN graph's rows are anchored at the points themselves (graph_build_wave), the
-// cell rows of search_mode 5 at cell and octant centres (k_crow_build).
-template <int R>                          // block = (2 R + 1)^3 cells
-__device__ __forceinline__ void row_build_wave(const GridIndex& g, const float4 q, int hx, int hy, int hz, int s,
-                                               float4* __restrict__ row_out, float2* __restrict__ meta_out, int (*s_off)[64], int (*s_js)[64])
-{
-    constexpr int W = 2 * R + 1, NR = W * W;
-    static_assert(NR <= 64, "one lane per z-run");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr float kEps = 1e-3f;
-    const int x0 = max(hx - R, 0), x1 = min(hx + R, g.nx - 1), y0 = max(hy - R, 0), y1 = min(hy + R, g.ny - 1);
-    const int z0 = max(hz - R, 0), z1 = min(hz + R, g.nz - 1);
-    // inscribed radius: faces of the block that coincide with the grid boundary have nothing beyond them
-    float rc = 3.0e18f;
-    if (x0 > 0)        rc = fminf(rc, q.x - (g.ox + (float)x0 * g.cell));
-    if (x1 < g.nx - 1) rc = fminf(rc, (g.ox + (float)(x1 + 1) * g.cell) - q.x);
-    if (y0 > 0)        rc = fminf(rc, q.y - (g.oy + (float)y0 * g.cell));
-    if (y1 < g.ny - 1) rc = fminf(rc, (g.oy + (float)(y1 + 1) * g.cell) - q.y);
-    if (z0 > 0)        rc = fminf(rc, q.z - (g.oz + (float)z0 * g.cell));
-    if (z1 < g.nz - 1) rc = fminf(rc, (g.oz + (float)(z1 + 1) * g.cell) - q.z);
-    rc = fmaxf(rc - kEps, 0.f);
-    // the 25 z-runs of the block, their exclusive prefix
-    int js = 0, len = 0;
-    if (lane < NR) {
-        const int ix = hx + lane / W - R, iy = hy + lane % W - R;
-        if (ix >= x0 && ix <= x1 && iy >= y0 && iy <= y1) {
-            const int base = (ix * g.ny + iy) * g.nz;
-            js = g.cell_start[base + z0];
-            len = g.cell_start[base + z1 + 1] - js;
-        }
-    }
-    int inc = len;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d); if (lane >= d) inc += t; }
-    const int total = __shfl(inc, 63);
-    __builtin_amdgcn_wave_barrier();
-    s_off[wave][lane] = inc - len; s_js[wave][lane] = js;
-    __builtin_amdgcn_wave_barrier();
-
-    constexpr unsigned long long kEmpty = ((unsigned long long)0x7f800000u << 32) | 0xffffffffull;      // (+inf, id -1)
-    unsigned long long top = kEmpty;                        // running kGraphK best in lanes 0..kGraphK-1, ascending
-#pragma unroll 1
-    for (int c0 = 0; c0 < total; c0 += 64) {
-        const int t = c0 + lane;
-        unsigned long long k = kEmpty;
-        if (t < total) {
-            int lo = 0, hi = NR - 1;                        // last run whose offset is <= t
-#pragma unroll
-            for (int it = 0; it < (NR > 32 ? 6 : 5); ++it) { const int mid = (lo + hi + 1) >> 1; if (s_off[wave][mid] <= t) lo = mid; else hi = mid - 1; }
-            const int j = s_js[wave][lo] + (t - s_off[wave][lo]);
-            const float4 c = g.pts[j];
-            const float ex = q.x - c.x, ey = q.y - c.y, ez = q.z - c.z;
-            const float d2 = ex * ex + ey * ey + ez * ez;
-            if (j != s && d2 < 3.0e38f) k = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)j;   // NaN / Inf points are never neighbours
-        }
-        k = sort64(k, lane);
-        if constexpr (kGraphK == 32) {
-            // lanes 32..63 <- the chunk's 32 smallest, reversed; lanes 0..31 keep the running best: one bitonic sequence, merged
-            // by the half-cleaners alone
-            const unsigned rlo = (unsigned)__shfl((int)(unsigned)k, 63 - lane), rhi = (unsigned)__shfl((int)(unsigned)(k >> 32), 63 - lane);
-            unsigned long long m = lane < 32 ? top : (((unsigned long long)rhi << 32) | rlo);
-            top = half_cleaners<32>(m, lane);
-        } else {
-            // running 64 best in all lanes: the lane-wise minimum of the running list and the reversed chunk is the 64 smallest of
-            // both as one bitonic sequence; the half-cleaners sort it
-            const unsigned rlo = (unsigned)__shfl((int)(unsigned)k, 63 - lane), rhi = (unsigned)__shfl((int)(unsigned)(k >> 32), 63 - lane);
-            const unsigned long long r = ((unsigned long long)rhi << 32) | rlo;
-            top = half_cleaners<32>(r < top ? r : top, lane);
-        }
-    }
-    const float tk = __uint_as_float((unsigned)(top >> 32));
-    const int ti = (int)(unsigned)top;
-    const float dK = __shfl(tk, kGraphK - 1);
-    const float rho2 = fminf(rc * rc, dK);
-    const bool keep = lane < kGraphK && ti >= 0 && tk <= rho2;
-    const int cnt = __popcll(__ballot(keep));
-    if (lane < kGraphK) {
-        // the row carries the neighbour's coordinates next to its id (one coalesced 1-KB store per point): the correspondence
-        // kernel then scans a row without an id -> point gather.  Entries that are not kept alias the point itself.
-        float4 e = make_float4(q.x, q.y, q.z, __int_as_float(-1));
-        if (keep) { const float4 c = g.pts[ti]; e = make_float4(c.x, c.y, c.z, __int_as_float(ti)); }
-        row_out[lane] = e;
-    }
-    if (lane == 0) *meta_out = make_float2(rho2, __int_as_float(cnt));
-}
-
 // Round 5: the graph's rows through the sort of the cell rows (32-bit keys: the squared distance's float bits with the low 7 bits replaced by
 // the lane, one min / max per network stage instead of a 64-bit compare and four selects; defined with the cell rows below).  The order of a
 // row is then exact to 2^-16 relative — far inside the millimetre of slack the scan's stop test carries for exactly this (kEps in
-// LISREG_GRAPH_GROUP) — and rho comes from the quantised key of the first point left out, a floor: "closer than rho => listed" holds as before.
-// -DLISREG_GRAPH_KEYS64=1 keeps the 64-bit (distance, id) keys of rounds 2-4.
-#ifndef LISREG_GRAPH_KEYS64
-#define LISREG_GRAPH_KEYS64 0
-#endif
-__attribute__((unused)) __device__ __forceinline__ void graph_row_q32(const GridIndex& g, const float4 q, int hx, int hy, int hz, int s,
+// LISREG_GRAPH_GROUP) — and rho comes from the quantised key of the first point left out, a floor: "closer than rho => listed" holds as
+// with the 64-bit (distance, id) keys of rounds 2-4.
+__device__ __forceinline__ void graph_row_q32(const GridIndex& g, const float4 q, int hx, int hy, int hz, int s,
                                               float4* __restrict__ row_out, float2* __restrict__ meta_out, int (*s_off)[64], int (*s_js)[64]);
 
 __device__ __forceinline__ void graph_build_wave(const GridIndex& g, int s, int (*s_off)[64], int (*s_js)[64])
 {
     const float4 q = g.pts[s];
     const int hx = cell_coord(q.x, g.ox, g.inv_cell, g.nx), hy = cell_coord(q.y, g.oy, g.inv_cell, g.ny), hz = cell_coord(q.z, g.oz, g.inv_cell, g.nz);
-#if LISREG_GRAPH_KEYS64
-    row_build_wave<2>(g, q, hx, hy, hz, s, const_cast<float4*>(g.nbr) + (size_t)s * kGraphK, const_cast<float2*>(g.nbr_meta) + s, s_off, s_js);
-#else
     graph_row_q32(g, q, hx, hy, hz, s, const_cast<float4*>(g.nbr) + (size_t)s * kGraphK, const_cast<float2*>(g.nbr_meta) + s, s_off, s_js);
-#endif
 }
 
-__global__ __launch_bounds__(64 * LISREG_GRAPH_WPB) void k_graph_build_one(GridIndex g)
+__global__ __launch_bounds__(64 * kGraphWPB) void k_graph_build_one(GridIndex g)
 {
-    __shared__ int s_off[LISREG_GRAPH_WPB][64], s_js[LISREG_GRAPH_WPB][64];
-    const int first = (blockIdx.x * LISREG_GRAPH_WPB + (threadIdx.x >> 6)) * kGraphPPW;
+    __shared__ int s_off[kGraphWPB][64], s_js[kGraphWPB][64];
+    const int first = (blockIdx.x * kGraphWPB + (threadIdx.x >> 6)) * kGraphPPW;
 #pragma unroll 1
     for (int i = 0; i < kGraphPPW; ++i) {
         const int s = first + i;
@@ -854,15 +724,15 @@ __global__ __launch_bounds__(64 * LISREG_GRAPH_WPB) void k_graph_build_one(GridI
     }
 }
 
-__global__ __launch_bounds__(64 * LISREG_GRAPH_WPB) void k_graph_build_batched(const BlockDesc* __restrict__ blocks,
+__global__ __launch_bounds__(64 * kGraphWPB) void k_graph_build_batched(const BlockDesc* __restrict__ blocks,
                                                              const TargetSeg* __restrict__ tsegs,
                                                              const GridIndex* __restrict__ grids)
 {
-    __shared__ int s_off[LISREG_GRAPH_WPB][64], s_js[LISREG_GRAPH_WPB][64];
-    constexpr int kSub = kBlockQ / (LISREG_GRAPH_WPB * kGraphPPW);         // workgroups per 256-point block descriptor
-    static_assert(kSub * LISREG_GRAPH_WPB * kGraphPPW == kBlockQ, "whole workgroups per block descriptor");
+    __shared__ int s_off[kGraphWPB][64], s_js[kGraphWPB][64];
+    constexpr int kSub = kBlockQ / (kGraphWPB * kGraphPPW);         // workgroups per 256-point block descriptor
+    static_assert(kSub * kGraphWPB * kGraphPPW == kBlockQ, "whole workgroups per block descriptor");
     const BlockDesc bd = blocks[blockIdx.x / kSub];
-    const int first = ((int)(blockIdx.x % kSub) * LISREG_GRAPH_WPB + (int)(threadIdx.x >> 6)) * kGraphPPW;
+    const int first = ((int)(blockIdx.x % kSub) * kGraphWPB + (int)(threadIdx.x >> 6)) * kGraphPPW;
     const GridIndex g = grids[tsegs[bd.seg].grid_id];
 #pragma unroll 1
     for (int i = 0; i < kGraphPPW; ++i) {
@@ -945,13 +815,8 @@ __device__ __forceinline__ void crow_mark_point_tile(const GridIndex& g, const f
 
 // k_crow_classify: one workgroup per tile of kCtX x kCtY columns over the whole z-range: the cell_start rows of the tile and its
 // two-column rim are staged in LDS once (two global reads per cell instead of fifty), every thread sums its cells' 5 x 5 columns from there.
-#ifndef LISREG_CT_X
-#define LISREG_CT_X 4            // tile of 4 x 8 columns (8 x 8 until round 5: 441 workgroups for a 200 k-point target left most of the chip idle; 17.8 -> 14.6-16.5 us)
-#endif
-#ifndef LISREG_CT_Y
-#define LISREG_CT_Y 8
-#endif
-constexpr int kCtX = LISREG_CT_X, kCtY = LISREG_CT_Y, kCtRim = 2;
+// Tile of 4 x 8 columns (8 x 8 until round 5: 441 workgroups for a 200 k-point target left most of the chip idle; 17.8 -> 14.6-16.5 us).
+constexpr int kCtX = 4, kCtY = 8, kCtRim = 2;
 // (both classification kernels) reach != null: a populated cell that no query of the batch comes within a metre of gets no rows this
 // run — need 0, and bit 30 of its mask tells the build to write -1 ("no row: walk") instead of -2 ("nothing within two cells") into its table entry
 constexpr int kCrowUnreached = 1 << 30;
@@ -1328,26 +1193,20 @@ __device__ __forceinline__ void crow_build_wave(const GridIndex& g, const float4
 // load and store for all of them), then the cells that have rows one after the other, the whole wave on each.
 // crow_tab[cell] = -2: nothing within two cells; -1: no row (its rows did not fit the capacity the buffers were sized for); else
 // (first row << 8) | octant mask, rows = [centre, the octants of the mask in ascending order].
-#ifndef LISREG_CROW_WPB
-#define LISREG_CROW_WPB 1            // wavefronts per workgroup of the row build.  Measured (same box, interleaved): 1 -> 213-236 us per launch, 2 -> 222,
-                                     // 4 (rounds 4-5) -> 248-270, 16 -> 370: most cells of a grid have no row, a few have nine — a workgroup of four
-                                     // wavefronts holds its slots until the slowest of them is through
-#endif
-#ifndef LISREG_CROW_CPW
-#define LISREG_CROW_CPW 8
-#endif
-constexpr int kCrowCPW = LISREG_CROW_CPW;
-#ifndef LISREG_CROW_WAVES
-#define LISREG_CROW_WAVES 6          // waves per SIMD the row build is compiled for (0: the compiler's choice = 86 registers, 5 waves).  The build is a
-                                     // chain of dependent loads per cell: measured (profiles/r05_kernel_experiments.md) 6 waves with 3 spilled registers beat 5
-                                     // without by 2-3 % of a configs[1] step; 7 and 8 waves (10 / 18 spilled) lose it again
-#endif
+constexpr int kCrowWPB = 1;              // wavefronts per workgroup of the row build.  Measured (same box, interleaved): 1 -> 213-236 us per launch, 2 -> 222,
+                                         // 4 (rounds 4-5) -> 248-270, 16 -> 370: most cells of a grid have no row, a few have nine — a workgroup of four
+                                         // wavefronts holds its slots until the slowest of them is through
+constexpr int kCrowCPW = 8;              // cells per wavefront
+constexpr int kCrowWaves = 6;            // waves per SIMD the row build is compiled for (the compiler's own choice: 86 registers, 5 waves).  The build is a
+                                         // chain of dependent loads per cell: measured (profiles/r05_kernel_experiments.md) 6 waves with 3 spilled registers beat 5
+                                         // without by 2-3 % of a configs[1] step; 7 and 8 waves (10 / 18 spilled) lose it again
+static_assert(kGraphWPB <= kListQueueWaves && kCrowWPB <= kListQueueWaves, "crow_list's LDS queue has one region per wavefront of a workgroup");
 __device__ __forceinline__ void crow_build_body(const GridIndex& g, int n_cells, const int* __restrict__ need, int* __restrict__ omask,
-                                                const int* __restrict__ scan, int cap, int use_r3 /* 0: never the 7^3 block (experiments) */,
+                                                const int* __restrict__ scan, int cap,
                                                 int blk_, int (*s_off)[64], int (*s_js)[64])
 {
     const int lane = threadIdx.x & 63;
-    const int first = __builtin_amdgcn_readfirstlane((blk_ * LISREG_CROW_WPB + (int)(threadIdx.x >> 6)) * kCrowCPW);
+    const int first = __builtin_amdgcn_readfirstlane((blk_ * kCrowWPB + (int)(threadIdx.x >> 6)) * kCrowCPW);
     int* tab = const_cast<int*>(g.crow_tab);
     int n_l = 0, b_l = 0, om_l = 0;
     if (lane < kCrowCPW && first + lane < n_cells) {
@@ -1374,21 +1233,16 @@ __device__ __forceinline__ void crow_build_body(const GridIndex& g, int n_cells,
         // a centre row serves queries up to 0.87 cells from the centre wherever they are relative to the surface; one with fewer than five
         // points inside sqrt(tau) is certified by the coverage radius alone, which then has to reach sqrt(tau) + 0.87 cells: where the
         // 5 x 5 x 5 block does not fill the row (2.5 cells of coverage), the 7 x 7 x 7 block is searched (3.5 cells; few candidates there)
-        if (mask != 0u || !use_r3 || (int)(om >> 8) >= kGraphK) crow_build_wave<2>(g, q, hx, hy, hz, mask, row, meta, s_off, s_js);
+        if (mask != 0u || (int)(om >> 8) >= kGraphK) crow_build_wave<2>(g, q, hx, hy, hz, mask, row, meta, s_off, s_js);
         else crow_build_wave<3>(g, q, hx, hy, hz, 0u, row, meta, s_off, s_js);
     }
 }
 
-#if LISREG_CROW_WAVES
-#define LISREG_CROW_BUILD_ATTR __global__ __launch_bounds__(64 * LISREG_CROW_WPB) __attribute__((amdgpu_waves_per_eu(LISREG_CROW_WAVES, LISREG_CROW_WAVES)))
-#else
-#define LISREG_CROW_BUILD_ATTR __global__ __launch_bounds__(64 * LISREG_CROW_WPB)
-#endif
-LISREG_CROW_BUILD_ATTR void k_crow_build(GridIndex g, int n_cells, const int* __restrict__ need, int* __restrict__ omask,
-                                         const int* __restrict__ scan, int cap, int use_r3)
+__global__ __launch_bounds__(64 * kCrowWPB) __attribute__((amdgpu_waves_per_eu(kCrowWaves, kCrowWaves)))
+void k_crow_build(GridIndex g, int n_cells, const int* __restrict__ need, int* __restrict__ omask, const int* __restrict__ scan, int cap)
 {
-    __shared__ int s_off[LISREG_CROW_WPB][64], s_js[LISREG_CROW_WPB][64];
-    crow_build_body(g, n_cells, need, omask, scan, cap, use_r3, blockIdx.x, s_off, s_js);
+    __shared__ int s_off[kCrowWPB][64], s_js[kCrowWPB][64];
+    crow_build_body(g, n_cells, need, omask, scan, cap, blockIdx.x, s_off, s_js);
 }
 
 // Round 6: the corner and the surf target of a slot through the row build in ONE launch sequence (marks, classification, two scan launches,
@@ -1412,12 +1266,12 @@ __global__ __launch_bounds__(256) void k_crow_classify_pair(CrowJobs J, float ma
     if (j.plain) crow_classify_plain_body(j.g, j.n_cells, j.need, j.omask, j.reach, blk);
     else crow_classify_body(j.g, j.tiles_y, j.need, j.omask, j.reach, blk, s_cs, margin_cells * j.g.cell);
 }
-LISREG_CROW_BUILD_ATTR void k_crow_build_pair(CrowJobs J, int use_r3)
+__global__ __launch_bounds__(64 * kCrowWPB) __attribute__((amdgpu_waves_per_eu(kCrowWaves, kCrowWaves))) void k_crow_build_pair(CrowJobs J)
 {
-    __shared__ int s_off[LISREG_CROW_WPB][64], s_js[LISREG_CROW_WPB][64];
+    __shared__ int s_off[kCrowWPB][64], s_js[kCrowWPB][64];
     const int k = (int)blockIdx.x < J.j[0].nb ? 0 : 1;
     const CrowJob& j = J.j[k];
-    crow_build_body(j.g, j.n_cells, j.need, j.omask, j.scan, j.cap, use_r3, (int)blockIdx.x - (k ? J.j[0].nb : 0), s_off, s_js);
+    crow_build_body(j.g, j.n_cells, j.need, j.omask, j.scan, j.cap, (int)blockIdx.x - (k ? J.j[0].nb : 0), s_off, s_js);
 }
 
 // Coherence probe for sort_sources = auto: how many consecutive source points are further apart than `thr`?
@@ -1799,13 +1653,13 @@ void launch_build_graph(const BlockDesc* blocks, int n_blocks, const TargetSeg* 
                         hipStream_t st)
 {
     if (n_blocks <= 0) return;
-    k_graph_build_batched<<<n_blocks * (kBlockQ / (LISREG_GRAPH_WPB * kGraphPPW)), 64 * LISREG_GRAPH_WPB, 0, st>>>(blocks, tsegs, grids);
+    k_graph_build_batched<<<n_blocks * (kBlockQ / (kGraphWPB * kGraphPPW)), 64 * kGraphWPB, 0, st>>>(blocks, tsegs, grids);
 }
 
 void launch_build_graph_one(GridIndex g, hipStream_t st)
 {
     if (g.n <= 0 || !g.nbr) return;
-    k_graph_build_one<<<(g.n + LISREG_GRAPH_WPB * kGraphPPW - 1) / (LISREG_GRAPH_WPB * kGraphPPW), 64 * LISREG_GRAPH_WPB, 0, st>>>(g);
+    k_graph_build_one<<<(g.n + kGraphWPB * kGraphPPW - 1) / (kGraphWPB * kGraphPPW), 64 * kGraphWPB, 0, st>>>(g);
 }
 
 // Query marks: one thread per source point of the batch.  Consecutive points of a sweep fall into the same cell a dozen at a time: a lane
@@ -1885,19 +1739,15 @@ static size_t crow_classify_lds(int nz)
     return sizeof(int) * ((size_t)(kCtX + 2 * kCtRim) * (kCtY + 2 * kCtRim) * (size_t)(nz + 1) + (size_t)kCtX * kCtY * (size_t)nz);
 }
 
-float crow_oct_margin_cells()
-{
-    static const float margin = std::min(0.249f, std::max(0.f, getenv("LISREG_CROW_MARGIN") ? (float)atof(getenv("LISREG_CROW_MARGIN")) : 0.249f));
-    return margin;
-}
+// octant margin in cells: under a quarter cell (half an octant's edge), so that a point is near at most two octants per axis
+constexpr float kCrowOctMargin = 0.249f;
 
 void launch_crow_classify(GridIndex g, int n_cells, CrowBuffers cb, hipStream_t st, int* omask_zero_cells)
 {
     if (g.n <= 0 || n_cells <= 0) return;
     const bool zero_already = omask_zero_cells && *omask_zero_cells >= n_cells;
     if (omask_zero_cells) *omask_zero_cells = 0;              // the marks go in now; launch_crow_build takes them out again
-    // octant margin in cells: under a quarter cell (half an octant's edge), so that a point is near at most two octants per axis
-    const float margin = crow_oct_margin_cells();
+    const float margin = kCrowOctMargin;
     const size_t lds = crow_classify_lds(g.nz);
     if (lds <= 64 * 1024) {                                   // the tiled classification makes the marks itself, in LDS
         const int tiles_x = (g.nx + kCtX - 1) / kCtX, tiles_y = (g.ny + kCtY - 1) / kCtY;
@@ -1914,15 +1764,13 @@ void launch_crow_build(GridIndex g, int n_cells, CrowBuffers cb, hipStream_t st,
 {
     if (g.n <= 0 || n_cells <= 0 || cb.cap_rows <= 0 || !g.crow) return;
     if (omask_zero_cells) *omask_zero_cells = n_cells;        // (k_crow_build zeroes the mask of every cell it is dealt, with or without rows)
-    static const int use_r3 = getenv("LISREG_CROW_R3") ? atoi(getenv("LISREG_CROW_R3")) : 1;
-    k_crow_build<<<(n_cells + LISREG_CROW_WPB * kCrowCPW - 1) / (LISREG_CROW_WPB * kCrowCPW), 64 * LISREG_CROW_WPB, 0, st>>>(g, n_cells, cb.need, cb.omask, cb.scan, cb.cap_rows, use_r3);
+    k_crow_build<<<(n_cells + kCrowWPB * kCrowCPW - 1) / (kCrowWPB * kCrowCPW), 64 * kCrowWPB, 0, st>>>(g, n_cells, cb.need, cb.omask, cb.scan, cb.cap_rows);
 }
 
 // classification + rows of the corner (job 0) and surf (job 1) target of one slot, five launches on ONE stream (see CrowJob)
 void launch_crow_rows_pair(const GridIndex g[2], const int n_cells[2], const CrowBuffers cb[2], hipStream_t st, int* omask_zero_cells[2])
 {
-    const float margin = crow_oct_margin_cells();
-    static const int use_r3 = getenv("LISREG_CROW_R3") ? atoi(getenv("LISREG_CROW_R3")) : 1;
+    const float margin = kCrowOctMargin;
     CrowJobs J = {};
     bool on[2];
     for (int k = 0; k < 2; ++k) {
@@ -1969,9 +1817,9 @@ void launch_crow_rows_pair(const GridIndex g[2], const int n_cells[2], const Cro
     }
     // rows
     {
-        const int per = LISREG_CROW_WPB * kCrowCPW;
+        const int per = kCrowWPB * kCrowCPW;
         const unsigned nb = grid((n_cells[0] + per - 1) / per, (n_cells[1] + per - 1) / per);
-        k_crow_build_pair<<<nb, 64 * LISREG_CROW_WPB, 0, st>>>(J, use_r3);
+        k_crow_build_pair<<<nb, 64 * kCrowWPB, 0, st>>>(J);
     }
 }
 

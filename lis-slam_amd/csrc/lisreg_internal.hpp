@@ -8,7 +8,6 @@
 namespace lisreg {
 
 constexpr int kBlockQ     = 256;   // queries per workgroup in the correspondence kernel (4 waves)
-constexpr int kStageCap   = 1024;  // target points staged in LDS per chunk (16 KiB)
 constexpr int kNumAcc     = 28;    // 21 upper-tri AtA + 6 AtB + 1 count
 constexpr int kResultSize = 12;    // floats per item in the result block
 constexpr int kTraceStride = LISREG_TRACE_STRIDE;
@@ -102,8 +101,6 @@ struct DevParams {
     int   cell_anchor_until;   // graph front-end: GN iterations 1 .. this also try an anchor out of the query's own grid column
     int   n_guard_failed;      // registrations of the batch that fail the feature-count guard (known on the host): the done counter's value after a reset
     int*  reach_miss;          // cell rows built under "row_reach": queries that found their cell without rows (-1) are counted here (null: not counted)
-    int   freeze_pose;         // timing experiments only (env LISREG_XP_FREEZE_POSE): the solve leaves T as it is, so that every launch of a run
-                               // sees the same queries whatever a variant under test writes into the normal equations
 };
 
 // Mutable per-registration state (device resident for the whole GN loop — no host sync per iteration).
@@ -212,7 +209,7 @@ void launch_reset_items(ItemState* items, int n_items, DevParams prm, int* done_
 // (launch_finalize with done_counter != null also leaves every registration reset for the NEXT run of the prepared batch: see run_impl)
 void launch_assoc(const BlockDesc* blocks, int n_blocks, const Segment* segs, const GridIndex* grids,
                   const ItemState* items, DevParams prm, const float4* sorted_all, double* partials,
-                  int mode /* 0 LDS-staged workgroup box, 1 per-lane grid walk, 3 k-NN graph scan (walk without a certificate) */,
+                  int mode /* 1 per-lane grid walk, 3 k-NN graph scan (walk without a certificate), 5 cell rows */,
                   int* nn, int n_elems, float first_pass_r2,
                   bool wide /* centre-first walk for the early iterations whose seeds / anchors are stale */,
                   int graph_hops /* mode 3: neighbour lists scanned per query before the cell walk takes over */,

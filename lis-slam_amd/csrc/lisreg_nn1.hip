@@ -108,10 +108,6 @@ __device__ __forceinline__ int nn1_search(float qx, float qy, float qz, const Gr
 // The seed enters one ulp ABOVE its distance: the walk meets the seed point itself (its cell is inside the final box) and inserts it at
 // its true distance by the strict rule — so a real tie with it is an equality like any other, and meeting it is not.
 constexpr int kNn1Cap = 8;
-#ifndef LISREG_ICP_FLAT
-#define LISREG_ICP_FLAT 1
-#endif
-constexpr bool kIcpFlat = LISREG_ICP_FLAT != 0;
 __device__ __forceinline__ int nn1_search_flat(float qx, float qy, float qz, const GridIndex& g, float max_d2, float* d2_out, int seed,
                                                int2 (*s_runs)[256])
 {
@@ -401,7 +397,7 @@ __global__ __launch_bounds__(256) void k_icp_assoc(const IcpItem* __restrict__ i
         // last iteration's neighbour (position in the sorted target); the first iteration takes a point out of the query's own grid column
         const int seed = stp->iters == 0 ? nn1_cell_seed(px, py, pz, g) : I.nn[i];
         int bi;
-        if (Q == 1 && kIcpFlat) bi = nn1_search_flat(px, py, pz, g, cap2, &d2, seed, s_runs);
+        if (Q == 1) bi = nn1_search_flat(px, py, pz, g, cap2, &d2, seed, s_runs);
         else bi = nn1_search<Q>(px, py, pz, g, cap2, &d2, seed);          // (all Q lanes have read their record before the lead lane writes)
         if (lead) { I.cur[i] = make_float4(px, py, pz, s.w); I.nn[i] = bi; }
         if (bi >= 0 && lead) {
@@ -527,7 +523,7 @@ __global__ __launch_bounds__(256) void k_icp_fitness_b(const IcpItem* __restrict
         float px, py, pz, d2;
         apply4(states[item].F, s.x, s.y, s.z, px, py, pz);
         // seed: the neighbour of the last ICP iteration (every item has run at least one; -1 where nothing was within reach)
-        const int bi = (Q == 1 && kIcpFlat) ? nn1_search_flat(px, py, pz, g, 3.0e38f, &d2, I.nn[i], s_runs) : nn1_search<Q>(px, py, pz, g, 3.0e38f, &d2, I.nn[i]);
+        const int bi = Q == 1 ? nn1_search_flat(px, py, pz, g, 3.0e38f, &d2, I.nn[i], s_runs) : nn1_search<Q>(px, py, pz, g, 3.0e38f, &d2, I.nn[i]);
         if (bi >= 0 && (threadIdx.x & (Q - 1)) == 0) { sum = d2; cnt = 1; }
     }
     sum = wave_sum_up(sum); cnt = wave_sum_up(cnt);

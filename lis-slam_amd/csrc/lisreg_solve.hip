@@ -378,18 +378,14 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve(ItemState* __restrict__
                     s_X[r] = (float)s;
                 }
             }
-            if (!P.freeze_pose) {
 #pragma unroll
-                for (int m = 0; m < 6; ++m) { Tn[m] = it->T[m] + s_X[m]; it->T[m] = Tn[m]; }      // :955-960
-            }
+            for (int m = 0; m < 6; ++m) { Tn[m] = it->T[m] + s_X[m]; it->T[m] = Tn[m]; }      // :955-960
         }
-        if (!P.freeze_pose) {
-            // the pose cache's three sine / cosine pairs (yaw, pitch, roll) on three lanes at once; lane 0 assembles the cache from them
-            const float ang = lane == 0 ? lane_value(Tn[2], 0) : (lane == 1 ? lane_value(Tn[1], 0) : lane_value(Tn[0], 0));
-            const float cs = cosf(ang), sn = sinf(ang);
-            const float trig[6] = { lane_value(cs, 0), lane_value(sn, 0), lane_value(cs, 1), lane_value(sn, 1), lane_value(cs, 2), lane_value(sn, 2) };
-            if (l0) write_pose_cache(it, trig);
-        }
+        // the pose cache's three sine / cosine pairs (yaw, pitch, roll) on three lanes at once; lane 0 assembles the cache from them
+        const float ang = lane == 0 ? lane_value(Tn[2], 0) : (lane == 1 ? lane_value(Tn[1], 0) : lane_value(Tn[0], 0));
+        const float cs = cosf(ang), sn = sinf(ang);
+        const float trig[6] = { lane_value(cs, 0), lane_value(sn, 0), lane_value(cs, 1), lane_value(sn, 1), lane_value(cs, 2), lane_value(sn, 2) };
+        if (l0) write_pose_cache(it, trig);
         if (l0) {
             const double r0 = (double)(s_X[0] * 57.29578f), r1 = (double)(s_X[1] * 57.29578f), r2 = (double)(s_X[2] * 57.29578f);
             const double t0 = (double)(s_X[3] * 100.f), t1 = (double)(s_X[4] * 100.f), t2 = (double)(s_X[5] * 100.f);

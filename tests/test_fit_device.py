@@ -134,7 +134,7 @@ def test_device_plane_fit_matches_oracle_far_from_origin(gpu_ctx, oracle, dist, 
 
 @pytest.mark.gpu
 def test_device_plane_fit_hand_over_to_qr(gpu_ctx, oracle):
-    """Near-collinear neighbourhoods around LISREG_PLANE_LINE_RATIO (second eigenvalue of the scatter matrix / first = 1e-2): at half the
+    """Near-collinear neighbourhoods around kPlaneLineRatio (second eigenvalue of the scatter matrix / first = 1e-2): at half the
     ratio the QR runs (flag 0), at twice the ratio the closed form does; either way the coefficients stay with the oracle's.  A plane
     THROUGH the map origin (n . p = -1 has no solution: the reference's QR returns a huge |n|, pd ~ 0) and five coincident points are
     handed over too or rejected consistently."""

@@ -93,9 +93,9 @@ def test_device_resident_batch_and_rerun_is_idempotent(gpu_ctx):
     assert all(s["iters"] == 6 for s in s1)
 
 
-@pytest.mark.parametrize("mode,sort", [(0, 0), (0, 1), (1, 0), (1, 1), (3, 0), (3, 1), (5, 0), (5, 1)])
+@pytest.mark.parametrize("mode,sort", [(1, 0), (1, 1), (3, 0), (3, 1), (5, 0), (5, 1)])
 def test_search_front_ends_agree(oracle, gpu_ctx, mode, sort):
-    """LDS-staged workgroup box search and per-lane grid walk are both exact: same correspondence counts."""
+    """Per-lane grid walk, k-NN graph scan and cell rows are all exact: the oracle's correspondence counts."""
     import lisreg
     from lisreg import synth
     case = synth.make_case(h=16, w=450, m_points=20000, scan_seed=1234)

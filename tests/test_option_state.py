@@ -45,9 +45,10 @@ OPTIONS = {
     "graph_min_ratio": (TIES, True, "auto front-end choice: graph scan or cell walk"),
     "cell_min_ratio": (TIES, True, "auto front-end choice: cell rows"),
     "cell_rows_max_mb": (TIES, True, "caps the cell rows (cells past the cap walk) or makes auto decline them for the graph scan"),
+    "search_mode": (TIES, True, "the front-end itself: 1, 3 and 5 give the same bits under canonical ties "
+                                "(test_neighbors.test_equal_distances_resolve_by_original_index_in_every_front_end, test_round4_edges)"),
     # (class (b) without canonical ties — within the oracle bar — is what test_gpu_batch.test_search_front_ends_agree and
-    #  test_round4_edges check for the front-ends these three lead to)
-    "search_mode": (DESIGN, True, "0, the staged box, cannot honour canonical ties; 1, 3, 5 behave as class (b)"),
+    #  test_round4_edges check for the front-ends these four lead to)
     "sort_sources": (DESIGN, True, "same neighbours, but a sorted batch sums its workgroups' rows in another order (last bits); "
                                    "auto equals the choice it makes (test_sort_sources_*)"),
     "exact_arithmetic": (DESIGN, True, "the reference's arithmetic"),
@@ -388,7 +389,7 @@ def test_out_of_range_values():
     c = lisreg.Context(0)
     try:
         for name, value in (("first_pass_mm", -450), ("xcd_order", 3), ("xcd_order", -1), ("interleave", 3), ("interleave", -1),
-                            ("index_build", 3), ("search_mode", 2), ("search_mode", 6)):
+                            ("index_build", 3), ("search_mode", 0), ("search_mode", 2), ("search_mode", 6)):
             with pytest.raises(lisreg.LisregError) as e:
                 c.set_option(name, value)
             assert e.value.code == lisreg.ERR_ARG, (name, value)

@@ -1,6 +1,6 @@
 """Round-4 edge cases: in-place voxel grids (lisreg_localmap_extract grids a class cloud onto itself; the single-cloud
-fallback of lisreg_voxel_downsample_multi wrote the output over records other threads were still reading), the search_mode
-environment override, and front-end 0 refusing the tie / exact options it does not implement."""
+fallback of lisreg_voxel_downsample_multi wrote the output over records other threads were still reading), and cell rows
+(search_mode 5) whose buffers are under-sized, that exceed their memory bound, or that sit on a tall grid."""
 import ctypes as C
 import os
 import subprocess
@@ -88,48 +88,6 @@ def test_localmap_extract_with_a_single_class_over_100k_points(oracle, gpu_ctx):
     assert np.array_equal(gpu_ctx.localmap_get(7, 6).view(np.uint32), rec(ts).view(np.uint32))
     for c in range(5):
         assert np.array_equal(gpu_ctx.localmap_get(7, c).view(np.uint32), rec(lm.cls[c]).view(np.uint32)), c
-
-
-def test_front_end_0_refuses_canonical_ties_and_exact(gpu_ctx):
-    import lisreg
-    from lisreg import synth
-    case = synth.make_case(h=16, w=450, m_points=20000, scan_seed=4400)
-    gpu_ctx.set_target(case["tgt_corner"], case["tgt_surf"])
-    p = lisreg.default_params(1)
-    try:
-        gpu_ctx.set_option("search_mode", 0)
-        T, st, _ = gpu_ctx.align(case["src_corner"], case["src_surf"], case["T_init"], p)      # plain: fine
-        assert st["status"] == 0
-        for opt in ("canonical_ties", "exact_arithmetic"):
-            gpu_ctx.set_option(opt, 1)
-            with pytest.raises(lisreg.LisregError):
-                gpu_ctx.align(case["src_corner"], case["src_surf"], case["T_init"], p)
-            gpu_ctx.set_option(opt, 0)
-    finally:
-        gpu_ctx.set_option("canonical_ties", 0); gpu_ctx.set_option("exact_arithmetic", 0); gpu_ctx.set_option("search_mode", 4)
-
-
-def test_search_mode_environment_override_is_validated():
-    """LISREG_SEARCH_MODE outside {0, 1, 3, 4, 5} is ignored with a message (it used to select the graph kernel without a graph)."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = f"""
-import sys
-sys.path.insert(0, {os.path.join(root, 'lis-slam_amd')!r})
-import lisreg
-from lisreg import synth
-case = synth.make_case(h=16, w=450, m_points=20000, scan_seed=4500)
-ctx = lisreg.Context(0)
-assert ctx.get_option("search_mode") == 4
-ctx.set_target(case["tgt_corner"], case["tgt_surf"])
-T, st, _ = ctx.align(case["src_corner"], case["src_surf"], case["T_init"], lisreg.default_params(1))
-assert st["status"] == 0
-ctx.close()
-print("OK")
-"""
-    env = dict(os.environ, LISREG_SEARCH_MODE="2")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0 and "OK" in r.stdout, r.stderr
-    assert "LISREG_SEARCH_MODE=2 ignored" in r.stderr
 
 
 @pytest.mark.gpu

@@ -1,6 +1,5 @@
 """Round 6: behaviour the round-5 review asked to pin."""
 import ctypes as C
-import os
 import time
 
 import numpy as np
@@ -95,8 +94,7 @@ def test_upload_hides_under_kernels_with_other_contexts_alive():
     for cx in extra: cx.close()
     for t in keep: t.free()
     for sh in pool: hip.hipStreamDestroy(sh)
-    if not os.environ.get("LISREG_FEED_LEGACY"):
-        assert best <= 1.25 * max(t_stage, t_run) + 1.0e-4, (best, t_stage, t_run)
+    assert best <= 1.25 * max(t_stage, t_run) + 1.0e-4, (best, t_stage, t_run)
 
 
 @pytest.mark.gpu
