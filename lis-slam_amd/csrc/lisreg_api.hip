@@ -33,12 +33,9 @@ int ctx_fail(lisreg_ctx* c, int code, const std::string& msg)
 
 bool ensure_side_stream(lisreg_ctx* c)
 {
-    if (!c->side_stream) {
-        if (hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) != hipSuccess) c->side_stream = nullptr;
-        if (c->side_stream && (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                               hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)) {
-            (void)hipStreamDestroy(c->side_stream); c->side_stream = nullptr;
-        }
+    if (!c->side_stream && (c->side_stream.create(hipStreamNonBlocking) != hipSuccess || c->ev_fork.create(hipEventDisableTiming) != hipSuccess ||
+                            c->ev_join.create(hipEventDisableTiming) != hipSuccess)) {
+        c->side_stream.reset(); c->ev_fork.reset(); c->ev_join.reset();
     }
     return c->side_stream != nullptr;
 }
@@ -276,7 +273,7 @@ int ensure_crows(lisreg_ctx* c, Target& t, int k, bool may_decline = false, long
         const hipError_t e2 = e1 == hipSuccess ? t.crow_meta[k].ensure(sizeof(float2) * (size_t)t.crow_cap[k]) : e1;
         if (e2 != hipSuccess) {
             (void)hipGetLastError();
-            t.crow[k].release(); t.crow_meta[k].release();
+            t.crow[k].release(); t.crow_meta[k].release();      // (the half that was granted goes back now: the target lives on without rows)
             if (may_decline) { t.crow_too_big[k] = true; t.g[k].crow_tab = nullptr; return LISREG_OK; }
             return lisreg::ctx_fail(c, LISREG_ERR_HIP, std::string("cell rows: ") + hipGetErrorString(e2));
         }
@@ -305,18 +302,15 @@ int upload_grids(lisreg_ctx* c)
     // through a pinned buffer of the context, guarded by an event: the copy is asynchronous and the host goes on building the batch's
     // tables while the stream still works on the target index it has just been given (a frame loop sets a target per frame: waiting
     // here meant an idle device for the rest of lisreg_batch_prepare)
-    if (bytes > c->grids_host_cap) {
+    if (bytes > c->grids_host.cap) {
         if (c->grids_done) (void)hipEventSynchronize(c->grids_done);
-        if (c->grids_host) (void)hipHostFree(c->grids_host);
-        c->grids_host = nullptr; c->grids_host_cap = 0;
-        if (hipHostMalloc((void**)&c->grids_host, 2 * bytes + 1024, hipHostMallocDefault) == hipSuccess) c->grids_host_cap = 2 * bytes + 1024;
-        else { (void)hipGetLastError(); c->grids_host = nullptr; }
+        if (c->grids_host.ensure(bytes, 2 * bytes + 1024) != hipSuccess) (void)hipGetLastError();
     }
-    if (!c->grids_done && hipEventCreateWithFlags(&c->grids_done, hipEventDisableTiming) != hipSuccess) c->grids_done = nullptr;
-    if (bytes && c->grids_host && c->grids_done) {
+    if (!c->grids_done) (void)c->grids_done.create(hipEventDisableTiming);
+    if (bytes && c->grids_host.p && c->grids_done) {
         HIPCHK(c, hipEventSynchronize(c->grids_done));          // (recorded by the previous upload: long past)
-        memcpy(c->grids_host, h.data(), bytes);
-        HIPCHK(c, hipMemcpyAsync(c->grids_dev.p, c->grids_host, bytes, hipMemcpyHostToDevice, c->stream));
+        memcpy(c->grids_host.p, h.data(), bytes);
+        HIPCHK(c, hipMemcpyAsync(c->grids_dev.p, c->grids_host.p, bytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipEventRecord(c->grids_done, c->stream));
     } else if (bytes) {
         HIPCHK(c, hipMemcpyAsync(c->grids_dev.p, h.data(), bytes, hipMemcpyHostToDevice, c->stream));
@@ -331,10 +325,10 @@ int upload_grids(lisreg_ctx* c)
 void prof_mark(lisreg_ctx* c, int kind_of_next_interval, int sidx = 0)
 {
     if (!c->profiling) return;
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return;
+    Event e;
+    if (e.create(hipEventDefault) != hipSuccess) return;
     (void)hipEventRecord(e, sidx ? c->side_stream : c->stream);
-    c->ev.push_back(e);
+    c->ev.push_back(std::move(e));
     c->ev_kind.push_back(kind_of_next_interval);
     c->ev_sidx.push_back(sidx);
 }
@@ -355,7 +349,6 @@ void prof_collect(lisreg_ctx* c)
             else if (c->ev_kind[i] == 2) c->timing[4] += ms;
         }
     }
-    for (auto e : c->ev) (void)hipEventDestroy(e);
     c->ev.clear(); c->ev_kind.clear(); c->ev_sidx.clear();
 }
 
@@ -386,13 +379,13 @@ int lisreg_create(int device, lisreg_ctx** out)
     lisreg_ctx* c = new (std::nothrow) lisreg_ctx();
     if (!c) return fail(nullptr, LISREG_ERR_NOMEM, "lisreg_create: out of host memory");
     c->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || c->own_stream.create(hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return fail(nullptr, LISREG_ERR_HIP, "lisreg_create: hipSetDevice/hipStreamCreate failed");
     }
     c->stream = c->own_stream;
     c->targets.resize(1);
-    if (hipHostMalloc((void**)&c->done_host, sizeof(int), hipHostMallocDefault) != hipSuccess) c->done_host = nullptr;
+    (void)c->done_host.ensure(sizeof(int), sizeof(int));     // (a failure is tolerated: runs then do not stop early)
     if (c->done_dev.ensure(sizeof(int)) != hipSuccess) { lisreg_destroy(c); return fail(nullptr, LISREG_ERR_HIP, "lisreg_create: hipMalloc failed"); }
     lisreg_default_params(LISREG_VARIANT_ODOM, &c->params);
     *out = c;
@@ -404,37 +397,12 @@ void lisreg_destroy(lisreg_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
+    // everything the context owns goes with `delete c`, in no particular order; what has to be over BEFORE that is said here:
+    // no stream of the context still runs work that reads or writes its buffers, and no packing thread still writes pinned staging
+    if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
+    if (c->grids_done) (void)hipEventSynchronize(c->grids_done);
     lisreg_comm_destroy(c);
-    feeder_destroy(c);
-    loopdet_destroy(c);
-    for (auto& t : c->targets) for (int k = 0; k < 2; ++k) { t.raw[k].release(); t.sorted[k].release(); t.cell_start[k].release(); t.nbr[k].release(); t.nbr_meta[k].release();
-        t.crow[k].release(); t.crow_meta[k].release(); t.crow_tab[k].release(); t.crow_need[k].release(); t.crow_omask[k].release(); t.crow_scan[k].release(); t.crow_scan_tmp[k].release(); t.crow_qmark[k].release(); t.crow_reach[k].release(); }
-    DevBuf* bufs[] = { &c->grids_dev, &c->hist, &c->bucket_start, &c->scan_tmp, &c->elem_bucket, &c->elem_sub,
-                       &c->tmp_bucket, &c->tmp_sub, &c->tmp_idx, &c->tmp_pts, &c->bbox_dev, &c->bbox_scratch, &c->blocks, &c->segs,
-                       &c->items, &c->sorted_all, &c->order_all, &c->partials, &c->results, &c->trace, &c->src_upload, &c->raw_upload, &c->dbg_nn, &c->blocks_q, &c->coef, &c->coef_ok, &c->nn, &c->counters, &c->tseg_dev, &c->tblk_dev, &c->tchunk_dev, &c->strip_tab, &c->done_dev, &c->xcd_tab, &c->vox_in, &c->vox_lab, &c->vox_order, &c->vox_sidx,
-                       &c->vox_head, &c->vox_slot, &c->vox_start, &c->vox_out, &c->vox_outlab, &c->vox_M,
-                       &c->ft_owner, &c->ft_flag, &c->ft_pos, &c->ft_scan, &c->ft_col, &c->ft_range, &c->ft_src, &c->ft_curv,
-                       &c->ft_picked, &c->ft_label, &c->ft_rlists, &c->ft_rcounts, &c->ft_lists, &c->ft_counts, &c->ft_rings,
-                       &c->ft_gather, &c->ft_cat, &c->ft_bounds, &c->ft_dsk_tab, &c->ft_dsk_pts, &c->ft_dsk_misc, &c->ft_dsk_time };
-    for (auto b : bufs) b->release();
-    for (auto& kv : c->maps) { auto& m = kv.second; m.raw.release(); m.sorted.release(); m.cell_start.release(); m.g_dev.release(); }
-    for (auto& m : c->localmaps) { for (auto& b : m.cls) b.release(); m.tgt[0].release(); m.tgt[1].release(); }
-    for (auto& r : c->keyrings) { for (auto& f : r.frames) { f.cloud[0].release(); f.cloud[1].release(); } r.cat[0].release(); r.cat[1].release(); r.tgt[0].release(); r.tgt[1].release(); }
-    DevBuf* mbufs[] = { &c->lm_in, &c->lm_tmp, &c->lm_bbox, &c->exact_trig, &c->mp_pts, &c->mp_flag, &c->mp_pos, &c->mp_idx, &c->mp_cnt, &c->mp_d2, &c->mp_out, &c->icp_state, &c->icp_partials, &c->icp_cur, &c->icp_items, &c->map_tab, &c->map_tsegs, &c->map_tblocks, &c->map_stage };
-    for (auto b : mbufs) b->release();
-    for (auto e : c->ev) (void)hipEventDestroy(e);
-    if (c->done_host) (void)hipHostFree(c->done_host);
-    if (c->stage_host) (void)hipHostFree(c->stage_host);
-    if (c->fetch_host) (void)hipHostFree(c->fetch_host);
-    if (c->stage_done) (void)hipEventDestroy(c->stage_done);
-    if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
-    if (c->grids_done) { (void)hipEventSynchronize(c->grids_done); (void)hipEventDestroy(c->grids_done); }
-    if (c->grids_host) (void)hipHostFree(c->grids_host);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->ev_ab) (void)hipEventDestroy(c->ev_ab);
-    if (c->ev_ba) (void)hipEventDestroy(c->ev_ba);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    feeder_stop(c);
     delete c;
 }
 
@@ -858,18 +826,14 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
         size_t total = 0;
         for (const Part& pt : parts) total += (pt.bytes + 63) & ~(size_t)63;
         if (c->stage_done) HIPCHK(c, hipEventSynchronize(c->stage_done));      // the previous batch's copies have left the buffer
-        else HIPCHK(c, hipEventCreateWithFlags(&c->stage_done, hipEventDisableTiming));
-        if (total > c->stage_cap) {
-            if (c->stage_host) (void)hipHostFree(c->stage_host);
-            c->stage_host = nullptr; c->stage_cap = 0;
-            HIPCHK(c, hipHostMalloc((void**)&c->stage_host, total + total / 2 + 4096, hipHostMallocDefault));
-            c->stage_cap = total + total / 2 + 4096;
-        }
+        else HIPCHK(c, c->stage_done.create(hipEventDisableTiming));
+        HIPCHK(c, c->stage_host.ensure(total, total + total / 2 + 4096));
+        unsigned char* stage = c->stage_host.as<unsigned char>();
         size_t off = 0;
         for (const Part& pt : parts) {
             if (pt.bytes) {
-                memcpy(c->stage_host + off, pt.src, pt.bytes);
-                HIPCHK(c, hipMemcpyAsync(pt.dst, c->stage_host + off, pt.bytes, hipMemcpyHostToDevice, c->stream));
+                memcpy(stage + off, pt.src, pt.bytes);
+                HIPCHK(c, hipMemcpyAsync(pt.dst, stage + off, pt.bytes, hipMemcpyHostToDevice, c->stream));
             }
             off += (pt.bytes + 63) & ~(size_t)63;
         }
@@ -889,7 +853,7 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
     if (c->sort_sources == 2 && c->n_elems >= 65536) {
         launch_count_jumps(c->blocks.as<BlockDesc>(), c->n_blocks, c->segs.as<Segment>(), 1.5f, c->done_dev.as<int>(), c->stream);
         int jumps_stack = 0;
-        int* jumps = c->done_host ? c->done_host : &jumps_stack;       // lisreg_create tolerates a failed pinned allocation
+        int* jumps = c->done_host.p ? c->done_host.as<int>() : &jumps_stack;       // lisreg_create tolerates a failed pinned allocation
         HIPCHK(c, hipMemcpyAsync(jumps, c->done_dev.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->sort_now = (double)*jumps > 0.25 * (double)c->n_elems;
@@ -1014,12 +978,12 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
     // stream, and each half's solve (and launch gaps, and the thinning tail of its correspondence launch) runs underneath the other half's
     // correspondence launch.  Same kernels on the same data in the same order per registration: same results to the bit.  Only for runs
     // that do not stop early from the host (fixed iteration counts, lisreg_batch_run) and are big enough to fill the chip twice.
-    const bool can_stop = early_stop && c->prm.fixed_iters <= 0 && c->done_host && c->early_stop_chunk != 0;
+    const bool can_stop = early_stop && c->prm.fixed_iters <= 0 && c->done_host.p && c->early_stop_chunk != 0;
     int split_item = 0, split_blk = 0;
     if (c->interleave != 0 && !c->exact && !can_stop && c->lanes_q == 1 && c->n_items >= 2 && c->n_blocks >= c->interleave_min_blocks) {
         ensure_side_stream(c);
-        if (c->side_stream && !c->ev_ab && (hipEventCreateWithFlags(&c->ev_ab, hipEventDisableTiming) != hipSuccess ||
-                                            hipEventCreateWithFlags(&c->ev_ba, hipEventDisableTiming) != hipSuccess)) { c->ev_ab = nullptr; c->ev_ba = nullptr; }
+        if (c->side_stream && !c->ev_ab && (c->ev_ab.create(hipEventDisableTiming) != hipSuccess ||
+                                            c->ev_ba.create(hipEventDisableTiming) != hipSuccess)) { c->ev_ab.reset(); c->ev_ba.reset(); }
         if (c->side_stream) {
             for (int i = 1; i < c->n_items; ++i)
                 if (c->h_items[(size_t)i].blk_begin * 2 >= c->n_blocks) { split_item = i; split_blk = c->h_items[(size_t)i].blk_begin; break; }
@@ -1147,9 +1111,9 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
         iteration(it, 0, c->n_items, 0, c->n_blocks, st, 0, nullptr);
         if (c->exact && it + 1 < c->prm.bound) { int rc = exact_pose_caches(c); if (rc) return rc; }
         if (can_stop && it + 1 == next_check && it + 1 < c->prm.bound) {
-            HIPCHK(c, hipMemcpyAsync(c->done_host, c->done_dev.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemcpyAsync(c->done_host.p, c->done_dev.p, sizeof(int), hipMemcpyDeviceToHost, st));
             HIPCHK(c, hipStreamSynchronize(st));
-            if (*c->done_host >= c->n_items) break;
+            if (*c->done_host.as<int>() >= c->n_items) break;
             next_check += c->early_stop_chunk > 0 ? chunk : std::min(chunk, 3);
         }
     }
@@ -1175,24 +1139,20 @@ int lisreg_batch_fetch(lisreg_ctx* c, float* T, lisreg_stats* stats)
     // results (and, for lisreg_align, the trace) land in pinned memory: asynchronous copies, ONE synchronisation
     const size_t res_floats = ((size_t)std::max(c->n_items, 1) + 1) * kResultSize;
     const size_t trace_floats = c->fetch_trace_records > 0 ? (size_t)kTraceStride * (size_t)c->fetch_trace_records : 0;
-    if ((res_floats + trace_floats) * sizeof(float) > c->fetch_cap) {
-        if (c->fetch_host) (void)hipHostFree(c->fetch_host);
-        c->fetch_host = nullptr; c->fetch_cap = 0;
-        const size_t want = (res_floats + trace_floats) * sizeof(float) * 2 + 4096;
-        HIPCHK(c, hipHostMalloc((void**)&c->fetch_host, want, hipHostMallocDefault));
-        c->fetch_cap = want;
-    }
+    const size_t fetch_bytes = (res_floats + trace_floats) * sizeof(float);
+    HIPCHK(c, c->fetch_host.ensure(fetch_bytes, fetch_bytes * 2 + 4096));
+    float* fetched = c->fetch_host.as<float>();
     const bool with_miss = c->n_items > 0 && c->reach_now;
-    if (c->n_items) HIPCHK(c, hipMemcpyAsync(c->fetch_host, c->results.p, sizeof(float) * kResultSize * ((size_t)c->n_items + (with_miss ? 1 : 0)), hipMemcpyDeviceToHost, c->stream));
-    if (trace_floats && c->trace.p) HIPCHK(c, hipMemcpyAsync(c->fetch_host + res_floats, c->trace.p, sizeof(float) * trace_floats, hipMemcpyDeviceToHost, c->stream));
+    if (c->n_items) HIPCHK(c, hipMemcpyAsync(fetched, c->results.p, sizeof(float) * kResultSize * ((size_t)c->n_items + (with_miss ? 1 : 0)), hipMemcpyDeviceToHost, c->stream));
+    if (trace_floats && c->trace.p) HIPCHK(c, hipMemcpyAsync(fetched + res_floats, c->trace.p, sizeof(float) * trace_floats, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->h_results.assign(c->fetch_host, c->fetch_host + res_floats);
+    c->h_results.assign(fetched, fetched + res_floats);
     if (with_miss) {
         // "row_reach" watches itself: the marks are the queries' cells under their INITIAL poses grown by a metre; a batch whose first steps move
         // its points farther than that sends queries into cells without rows, where they walk (exact, but slow: configs[4] with a 0.5 m
         // dilation ran 30 % longer).  More than one query-iteration in a thousand there: the prepared batch's later runs, and the next 32
         // batches prepared on this context, build all rows.
-        int cum; memcpy(&cum, c->fetch_host + (size_t)c->n_items * kResultSize, sizeof cum);      // (cumulative since the batch was prepared)
+        int cum; memcpy(&cum, fetched + (size_t)c->n_items * kResultSize, sizeof cum);      // (cumulative since the batch was prepared)
         const int miss = cum - c->reach_miss_seen;
         c->reach_miss_seen = cum;
         c->reach_miss_last = miss;
@@ -1454,8 +1414,8 @@ int lisreg_align(lisreg_ctx* c, const void* src_corner, int n_corner, const void
         c->last_trace_n = std::min(bound, st.iters + 1);
         if (st.status == LISREG_NOT_ENOUGH_FEATURES) c->last_trace_n = 0;
         c->last_trace.assign((size_t)kTraceStride * (size_t)std::max(c->last_trace_n, 1), 0.f);
-        if (c->last_trace_n > 0 && c->fetch_host)
-            memcpy(c->last_trace.data(), c->fetch_host + 2 * (size_t)kResultSize, sizeof(float) * kTraceStride * (size_t)c->last_trace_n);      // (one item + the "row_reach" record in front: lisreg_batch_fetch)
+        if (c->last_trace_n > 0 && c->fetch_host.p)
+            memcpy(c->last_trace.data(), c->fetch_host.as<float>() + 2 * (size_t)kResultSize, sizeof(float) * kTraceStride * (size_t)c->last_trace_n);      // (one item + the "row_reach" record in front: lisreg_batch_fetch)
         if (stats) *stats = st;
         rc = st.status;
     }
@@ -1590,7 +1550,6 @@ int lisreg_test_fit_models(lisreg_ctx* c, int kind, int n, const float* neighbou
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, o.p, sizeof(float) * 10 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    nb.release(); q.release(); o.release();
     return LISREG_OK;
 }
 

@@ -26,7 +26,7 @@
 namespace lisreg {
 
 // The host side of the feeder is memory-bound (two passes over the batch), and the pool's hosts are multi-socket: the same binary staged a
-// batch in 2.7 ms on one box and 5.9 ms on another.  The staging buffers come from hipHostMalloc, which places them on the
+// batch in 2.7 ms on one box and 5.9 ms on another.  The staging buffers are pinned by HIP (PinnedBuf), which places them on the
 // NUMA node nearest the device; the packing threads are bound to the CPUs of that node that this process may run on (option
 // "feeder_numa", default 1; nothing happens when sysfs says nothing or the process owns no CPU there).
 static int feeder_numa_cpus(int device, std::vector<int>& cpus)
@@ -191,29 +191,15 @@ struct PackPool {
     }
 };
 
-void feeder_destroy(lisreg_ctx* c)
+void PackPoolDelete::operator()(PackPool* p) const { delete p; }
+
+void feeder_stop(lisreg_ctx* c)
 {
     // order: the copy stream drains first (its copies read the pinned staging buffers and write the device buffers), then the threads
-    // are joined (nothing packs into a buffer that is about to go), then events, pinned and device memory
+    // are joined (nothing packs into a buffer that is about to go); only after that may events, pinned and device memory go
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->pack_stream) (void)hipStreamSynchronize(c->pack_stream);
-    delete c->pack_pool; c->pack_pool = nullptr;
-    for (int b = 0; b < 2; ++b) {
-        if (c->pack_copied[b]) (void)hipEventDestroy(c->pack_copied[b]);
-        if (c->pack_free[b]) (void)hipEventDestroy(c->pack_free[b]);
-        c->pack_copied[b] = c->pack_free[b] = nullptr;
-        if (c->pack_host[b]) (void)hipHostFree(c->pack_host[b]);
-        c->pack_host[b] = nullptr; c->pack_cap[b] = 0;
-        c->pack_dev[b].release(); c->pack_raw[b].release();
-    }
-    if (c->pack_raw_done) (void)hipEventDestroy(c->pack_raw_done);
-    c->pack_raw_done = nullptr; c->pack_pending = nullptr;
-    if (c->up_host) (void)hipHostFree(c->up_host);
-    c->up_host = nullptr; c->up_cap = 0;
-    if (c->pack_kernels_done) (void)hipEventDestroy(c->pack_kernels_done);
-    c->pack_kernels_done = nullptr;
-    if (c->pack_stream) { (void)hipStreamDestroy(c->pack_stream); c->pack_stream = nullptr; }
-    if (c->copy_stream) { (void)hipStreamDestroy(c->copy_stream); c->copy_stream = nullptr; }
+    c->pack_pool.reset();
 }
 
 }  // namespace lisreg
@@ -247,22 +233,17 @@ int lisreg_stage_host_items(lisreg_ctx* c, int n_items, const lisreg_item* items
     // kernels of the batch that is running, the copies ordered after it start when that batch is through, and the upload of batch k + 1
     // no longer hides underneath batch k (measured, round 6: 12.8 k reg/s against 23.7 k for the same loop with the streams on separate
     // queues — profiles/r06_pcie_overlap.md).  The copy engines themselves do not go through that queue.
-    if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    if (!c->pack_copied[b]) HIPCHK(c, hipEventCreateWithFlags(&c->pack_copied[b], hipEventDisableTiming));
-    if (!c->pack_free[b]) HIPCHK(c, hipEventCreateWithFlags(&c->pack_free[b], hipEventDisableTiming));
+    if (!c->copy_stream) HIPCHK(c, c->copy_stream.create(hipStreamNonBlocking));
+    if (!c->pack_copied[b]) HIPCHK(c, c->pack_copied[b].create(hipEventDisableTiming));
+    if (!c->pack_free[b]) HIPCHK(c, c->pack_free[b].create(hipEventDisableTiming));
     else HIPCHK(c, hipEventSynchronize(c->pack_free[b]));      // the batch that last read device buffer b has run (two batches
                                                                // back in a pipelined loop: long done; a HOST wait, for the reason above)
     // the staging buffer's previous contents have left it (its copies are two calls old)
-    if (c->pack_cap[b]) HIPCHK(c, hipEventSynchronize(c->pack_copied[b]));
+    if (c->pack_host[b].cap) HIPCHK(c, hipEventSynchronize(c->pack_copied[b]));
     const size_t bytes = sizeof(lisreg_dpoint) * std::max<size_t>(total, 1);
-    if (bytes > c->pack_cap[b]) {
-        if (c->pack_host[b]) (void)hipHostFree(c->pack_host[b]);
-        c->pack_host[b] = nullptr; c->pack_cap[b] = 0;
-        HIPCHK(c, hipHostMalloc((void**)&c->pack_host[b], bytes + bytes / 8 + 4096, hipHostMallocDefault));
-        c->pack_cap[b] = bytes + bytes / 8 + 4096;
-    }
+    HIPCHK(c, c->pack_host[b].ensure(bytes, bytes + bytes / 8 + 4096));
     HIPCHK(c, c->pack_dev[b].ensure(bytes));
-    lisreg_dpoint* host = reinterpret_cast<lisreg_dpoint*>(c->pack_host[b]);
+    lisreg_dpoint* host = c->pack_host[b].as<lisreg_dpoint>();
     lisreg_dpoint* dev = c->pack_dev[b].as<lisreg_dpoint>();
     // chunks of <= 64 k points, in staging order
     constexpr int kChunk = 65536;
@@ -303,12 +284,12 @@ int lisreg_stage_host_items(lisreg_ctx* c, int n_items, const lisreg_item* items
         const int want = total >= 262144 ? std::max(1, std::min(c->feeder_threads, (int)std::thread::hardware_concurrency() - 1)) : 0;
         std::shared_ptr<PackPool::Job> job;
         if (want > 0) {
-            if (!c->pack_pool) { c->pack_pool = new PackPool(); if (c->feeder_numa) c->feeder_node = feeder_numa_cpus(c->device, c->pack_pool->cpus); c->feeder_cpus = (int)c->pack_pool->cpus.size(); }
+            if (!c->pack_pool) { c->pack_pool.reset(new PackPool()); if (c->feeder_numa) c->feeder_node = feeder_numa_cpus(c->device, c->pack_pool->cpus); c->feeder_cpus = (int)c->pack_pool->cpus.size(); }
             c->pack_pool->start(want);
             job = c->pack_pool->run(chunks.data(), n_chunks, c->pack_done.data());
         }
         // every way out of this block — the HIPCHK returns too — first takes the job away from the threads and waits for them
-        PackPool::JobGuard guard{ want > 0 ? c->pack_pool : nullptr, job };
+        PackPool::JobGuard guard{ want > 0 ? c->pack_pool.get() : nullptr, job };
         // Copies follow the packing chunk by chunk, several chunks per copy (per-copy overhead is ~10 us; 4 MB copies run at link rate).
         // While the next packed chunk is not ready and the copy engine has nothing left to do, this thread hands the engine the LAST free
         // chunk as it is — 32-byte structs over the link, packed by a kernel on the copy stream — so the two ends of the batch are worked
@@ -339,13 +320,13 @@ int lisreg_stage_host_items(lisreg_ctx* c, int n_items, const lisreg_item* items
                             }
                             // on a stream of their own: the packing kernel is a packet of a hardware queue that may be busy with the running
                             // batch, and the packed chunks' copies must not be ordered behind it
-                            if (!c->pack_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->pack_stream, hipStreamNonBlocking));
+                            if (!c->pack_stream) HIPCHK(c, c->pack_stream.create(hipStreamNonBlocking));
                             hipStream_t ps = c->pack_stream;
                             HIPCHK(c, hipMemcpyAsync(raw_dev + raw_off, ck.src, bytes_k, hipMemcpyHostToDevice, ps));
                             launch_pack_cloud(raw_dev + raw_off, (size_t)ck.n, ck.stride, ck.fmt == LISREG_FMT_XYZIL ? 1 : 0,
                                               reinterpret_cast<float4*>(dev + (ck.dst - host)), ps);
                             raw_off += (bytes_k + 63) & ~(size_t)63;
-                            if (!c->pack_raw_done) HIPCHK(c, hipEventCreateWithFlags(&c->pack_raw_done, hipEventDisableTiming));
+                            if (!c->pack_raw_done) HIPCHK(c, c->pack_raw_done.create(hipEventDisableTiming));
                             HIPCHK(c, hipEventRecord(c->pack_raw_done, ps));      // the engine has read the caller's memory up to here
                             lowest_stolen = k;
                             stole = true;
@@ -378,7 +359,7 @@ int lisreg_stage_host_items(lisreg_ctx* c, int n_items, const lisreg_item* items
         if (c->pack_stolen > 0 && c->pack_raw_done) HIPCHK(c, hipEventSynchronize(c->pack_raw_done));
     }
     if (c->pack_stolen > 0 && c->pack_stream) {   // the packing kernels' output belongs to the batch: the one wait the copy stream ever gets, at its very end
-        if (!c->pack_kernels_done) HIPCHK(c, hipEventCreateWithFlags(&c->pack_kernels_done, hipEventDisableTiming));
+        if (!c->pack_kernels_done) HIPCHK(c, c->pack_kernels_done.create(hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(c->pack_kernels_done, c->pack_stream));
         HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->pack_kernels_done, 0));
     }
@@ -401,16 +382,11 @@ int lisreg_upload_cloud(lisreg_ctx* c, const void* cloud, int n, int stride_byte
     if (n == 0) return LISREG_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = sizeof(lisreg_dpoint) * (size_t)n;
-    if (bytes > c->up_cap) {
+    if (bytes > c->up_host.cap) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        const size_t old_cap = c->up_cap;
-        if (c->up_host) (void)hipHostFree(c->up_host);
-        c->up_host = nullptr; c->up_cap = 0;
-        const size_t want = std::max(std::max(bytes + bytes / 4 + 4096, 2 * old_cap), (size_t)8 << 20);     // sweeps vary by a few per cent: no re-pinning per frame
-        HIPCHK(c, hipHostMalloc((void**)&c->up_host, want, hipHostMallocDefault));
-        c->up_cap = want;
+        HIPCHK(c, c->up_host.ensure(bytes, std::max(std::max(bytes + bytes / 4 + 4096, 2 * c->up_host.cap), (size_t)8 << 20)));     // sweeps vary by a few per cent: no re-pinning per frame
     }
-    lisreg_dpoint* host = reinterpret_cast<lisreg_dpoint*>(c->up_host);
+    lisreg_dpoint* host = c->up_host.as<lisreg_dpoint>();
     constexpr int kChunk = 16384;
     std::vector<PackChunk> chunks;
     for (int s = 0; s < n; s += kChunk)
@@ -420,10 +396,10 @@ int lisreg_upload_cloud(lisreg_ctx* c, const void* cloud, int n, int stride_byte
     if (want > 0) {
         if ((int)c->pack_done.size() < n_chunks) c->pack_done = std::vector<std::atomic<int>>((size_t)n_chunks);
         for (int i = 0; i < n_chunks; ++i) c->pack_done[(size_t)i].store(0, std::memory_order_relaxed);
-        if (!c->pack_pool) { c->pack_pool = new PackPool(); if (c->feeder_numa) c->feeder_node = feeder_numa_cpus(c->device, c->pack_pool->cpus); c->feeder_cpus = (int)c->pack_pool->cpus.size(); }
+        if (!c->pack_pool) { c->pack_pool.reset(new PackPool()); if (c->feeder_numa) c->feeder_node = feeder_numa_cpus(c->device, c->pack_pool->cpus); c->feeder_cpus = (int)c->pack_pool->cpus.size(); }
         c->pack_pool->start(want);
         // `chunks` is a local: the guard ends the job (and waits for the threads) before the table goes out of scope, on every path
-        PackPool::JobGuard guard{ c->pack_pool, c->pack_pool->run(chunks.data(), n_chunks, c->pack_done.data()) };
+        PackPool::JobGuard guard{ c->pack_pool.get(), c->pack_pool->run(chunks.data(), n_chunks, c->pack_done.data()) };
         c->pack_pool->drain();                                   // the caller packs too
         for (int i = 0; i < n_chunks; ++i) while (!c->pack_done[(size_t)i].load(std::memory_order_acquire)) std::this_thread::yield();
     } else {

@@ -42,8 +42,7 @@ int grow_keep(lisreg_ctx* c, DevBuf& b, size_t bytes, size_t keep)
     }
     if (keep > 0 && b.p) HIPCHK(c, hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.release();
-    b = nb;
+    b = std::move(nb);
     return LISREG_OK;
 }
 
@@ -504,7 +503,6 @@ int lisreg_keyframes_reset(lisreg_ctx* c, int ring_id)
     if ((size_t)ring_id >= c->keyrings.size()) c->keyrings.resize((size_t)ring_id + 1);
     KeyframeRing& r = c->keyrings[(size_t)ring_id];
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (auto& f : r.frames) { f.cloud[0].release(); f.cloud[1].release(); }
     r.frames.clear();
     r.built = false;
     r.n_tgt[0] = r.n_tgt[1] = 0;
@@ -546,14 +544,13 @@ int lisreg_keyframes_push(lisreg_ctx* c, int ring_id, const void* corner, int n_
             src = c->lm_in.as<float4>();
         }
         int rc = lisreg_transform_cloud(c, src, n[k], 16, LISREG_FMT_DEVICE, pose, f.cloud[k].p);      // transformPointCloud(.., &thisPose6D)
-        if (rc) { f.cloud[0].release(); f.cloud[1].release(); return rc; }
+        if (rc) return rc;
     }
-    r.frames.push_back(f);
+    r.frames.push_back(std::move(f));
     r.built = false;
     r.payload_is_label = fmt == LISREG_FMT_DEVICE || fmt == LISREG_FMT_XYZIL;       // what the ring's voxel grids do with the fourth channel
     while ((int)r.frames.size() > max_keep) {         // while (size() >= 20) erase(begin())  with max_keep = 19
         HIPCHK(c, hipStreamSynchronize(st));
-        r.frames.front().cloud[0].release(); r.frames.front().cloud[1].release();
         r.frames.erase(r.frames.begin());
     }
     if (info) { info->n_keyframes = (int)r.frames.size(); info->n_target_corner = r.n_tgt[0]; info->n_target_surf = r.n_tgt[1]; }

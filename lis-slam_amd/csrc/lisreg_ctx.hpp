@@ -5,14 +5,30 @@
 
 #include <atomic>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 namespace lisreg {
 
-struct DevBuf {
+// Owners of the context's GPU resources.  Each gives back what it holds in its destructor and can be moved but not copied, so a buffer,
+// event or stream that is a member (of the context, a Target, a map, a ring frame, ...) or a local goes away with its owner, on error
+// paths too.  A moved-from owner is empty; move-assignment first gives back what the target held.
+template <hipError_t (*Free)(void*)>
+struct OwnedMem {
     void*  p = nullptr;
     size_t cap = 0;
+    OwnedMem() = default;
+    OwnedMem(const OwnedMem&) = delete;
+    OwnedMem& operator=(const OwnedMem&) = delete;
+    OwnedMem(OwnedMem&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    OwnedMem& operator=(OwnedMem&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~OwnedMem() { release(); }
+    void release() { if (p) (void)Free(p); p = nullptr; cap = 0; }      // for memory that goes back early, on purpose: teardown is the destructor's
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+struct DevBuf : OwnedMem<hipFree> {
     hipError_t ensure(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
@@ -29,8 +45,38 @@ struct DevBuf {
         if (e == hipSuccess) cap = want; else p = nullptr;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// pinned host memory; the caller chooses the head-room: `want` bytes are allocated when `bytes` no longer fit
+struct PinnedBuf : OwnedMem<hipHostFree> {
+    hipError_t ensure(size_t bytes, size_t want)
+    {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) cap = want; else p = nullptr;
+        return e;
+    }
+};
+
+// an event / a stream of the context's own: made on first use by create(), converts to the raw handle
+template <class H, hipError_t (*Destroy)(H)>
+struct OwnedHandle {
+    H h = nullptr;
+    OwnedHandle() = default;
+    OwnedHandle(const OwnedHandle&) = delete;
+    OwnedHandle& operator=(const OwnedHandle&) = delete;
+    OwnedHandle(OwnedHandle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    OwnedHandle& operator=(OwnedHandle&& o) noexcept { if (this != &o) { reset(); h = o.h; o.h = nullptr; } return *this; }
+    ~OwnedHandle() { reset(); }
+    void reset() { if (h) (void)Destroy(h); h = nullptr; }
+    operator H() const { return h; }
+};
+struct Event : OwnedHandle<hipEvent_t, hipEventDestroy> {
+    hipError_t create(unsigned flags) { reset(); const hipError_t e = hipEventCreateWithFlags(&h, flags); if (e != hipSuccess) h = nullptr; return e; }
+};
+struct Stream : OwnedHandle<hipStream_t, hipStreamDestroy> {
+    hipError_t create(unsigned flags) { reset(); const hipError_t e = hipStreamCreateWithFlags(&h, flags); if (e != hipSuccess) h = nullptr; return e; }
 };
 
 struct Target {
@@ -93,6 +139,9 @@ struct KeyframeRing {
 
 struct PackPool;           // host feeder threads (lisreg_api_feed.hip)
 struct LoopDet;            // loop-closure candidate databases and their scratch (lisreg_loop.hip)
+// (both are incomplete here: their deleters are defined next to the types)
+struct PackPoolDelete { void operator()(PackPool* p) const; };
+struct LoopDetDelete { void operator()(LoopDet* p) const; };
 struct PackChunk { const unsigned char* src; lisreg_dpoint* dst; int n, stride, fmt; int pinned; };      // <= 64 k points of one host cloud; pinned: the DMA engine may read src
 
 struct RcclApi {
@@ -107,15 +156,15 @@ struct RcclApi {
 
 struct lisreg_ctx {
     int          device = 0;
-    hipStream_t  own_stream = nullptr, stream = nullptr;
+    lisreg::Stream own_stream;
+    hipStream_t  stream = nullptr;           // own_stream, or the caller's (lisreg_set_stream): not owned
     std::string  err;
     std::vector<lisreg::Target> targets;
     unsigned long long   target_gen = 0;
     lisreg::DevBuf       grids_dev;
     bool         grids_dirty = true;
-    unsigned char* grids_host = nullptr;    // pinned staging of the GridIndex table (upload_grids does not wait for the stream)
-    size_t       grids_host_cap = 0;
-    hipEvent_t   grids_done = nullptr;      // the last upload has left the staging buffer
+    lisreg::PinnedBuf grids_host;           // pinned staging of the GridIndex table (upload_grids does not wait for the stream)
+    lisreg::Event grids_done;               // the last upload has left the staging buffer
     // sort scratch (shared by target build and source sort; stream-ordered so reuse is safe)
     lisreg::DevBuf hist, bucket_start, scan_tmp, elem_bucket, elem_sub, tmp_bucket, tmp_sub, tmp_idx, tmp_pts, bbox_dev, bbox_scratch;
     // batch
@@ -124,24 +173,22 @@ struct lisreg_ctx {
            ft_owner, ft_flag, ft_pos, ft_scan, ft_col, ft_range, ft_src, ft_curv, ft_picked, ft_label, ft_rlists, ft_rcounts,
            ft_lists, ft_counts, ft_rings, ft_gather, ft_cat, ft_bounds, ft_dsk_tab, ft_dsk_pts, ft_dsk_misc, ft_dsk_time;
     // host feeder (lisreg_api_feed.hip): clouds packed to 16-byte records by a few threads into pinned staging, uploaded on a copy stream
-    lisreg::PackPool* pack_pool = nullptr;
+    std::unique_ptr<lisreg::PackPool, lisreg::PackPoolDelete> pack_pool;
     int          feeder_threads = 8;
-    unsigned char* pack_host[2] = { nullptr, nullptr };
-    size_t       pack_cap[2] = { 0, 0 };
+    lisreg::PinnedBuf pack_host[2];
     lisreg::DevBuf pack_dev[2];
     int            feeder_engine = 1;                    // 0: the copy engine takes no chunks; 1: when idle (default); 2: whenever a packed chunk is not ready; 3: the same and one chunk up front, ready or not (tests)
     int            pack_stolen = 0, pack_chunks_n = 0;   // last lisreg_stage_host_items: chunks the copy engine took / all chunks
     lisreg::DevBuf pack_raw[2];                // structs that crossed the link as they are (chunks the copy engine took over), packed on the device
-    unsigned char* up_host = nullptr;          // pinned staging of lisreg_upload_cloud
-    size_t         up_cap = 0;
-    hipEvent_t   pack_copied[2] = { nullptr, nullptr };   // the uploads into device buffer b are done (recorded on copy_stream)
-    hipEvent_t   pack_free[2] = { nullptr, nullptr };     // the batch reading device buffer b has run (recorded on stream)
-    hipEvent_t   pack_pending = nullptr;                  // uploads the next prepared batch has to wait for
-    hipEvent_t   pack_raw_done = nullptr;                 // the copy engine's last read of the CALLER's pinned memory (chunks it took over)
+    lisreg::PinnedBuf up_host;                 // pinned staging of lisreg_upload_cloud
+    lisreg::Event pack_copied[2];                         // the uploads into device buffer b are done (recorded on copy_stream)
+    lisreg::Event pack_free[2];                           // the batch reading device buffer b has run (recorded on stream)
+    hipEvent_t   pack_pending = nullptr;                  // uploads the next prepared batch has to wait for (one of pack_copied: not owned)
+    lisreg::Event pack_raw_done;                          // the copy engine's last read of the CALLER's pinned memory (chunks it took over)
     int          pack_flip = 0, pack_last = -1, pack_in_use = -1;
-    hipStream_t  copy_stream = nullptr;
-    hipStream_t  pack_stream = nullptr;                   // chunks the copy engine takes as they are: raw copy + k_pack_cloud (never on copy_stream: see lisreg_stage_host_items)
-    hipEvent_t   pack_kernels_done = nullptr;             // recorded on pack_stream behind the last k_pack_cloud of a staging call
+    lisreg::Stream copy_stream;
+    lisreg::Stream pack_stream;                           // chunks the copy engine takes as they are: raw copy + k_pack_cloud (never on copy_stream: see lisreg_stage_host_items)
+    lisreg::Event pack_kernels_done;                      // recorded on pack_stream behind the last k_pack_cloud of a staging call
     std::vector<lisreg::PackChunk> pack_chunks;
     std::vector<std::atomic<int>> pack_done;
     std::map<int, lisreg::MapIndex> maps;             // by slot (sparse: the local maps keep theirs at 60000 + id)
@@ -150,12 +197,10 @@ struct lisreg_ctx {
     lisreg::DevBuf lm_in, lm_tmp, lm_bbox, exact_trig;
     lisreg::DevBuf map_stage;                          // lisreg_map_index_set_batch: host clouds of a batch, packed, in one upload
     lisreg::DevBuf mp_pts, mp_flag, mp_pos, mp_idx, mp_cnt, mp_d2, mp_out, icp_state, icp_partials, icp_cur, icp_items, map_tab, map_tsegs, map_tblocks;
-    int*      done_host = nullptr;          // pinned
-    unsigned char* stage_host = nullptr;    // pinned staging of the per-batch tables
-    size_t    stage_cap = 0;
-    hipEvent_t stage_done = nullptr;
-    float*    fetch_host = nullptr;         // pinned landing area of results (+ trace)
-    size_t    fetch_cap = 0;
+    lisreg::PinnedBuf done_host;            // one int
+    lisreg::PinnedBuf stage_host;           // pinned staging of the per-batch tables
+    lisreg::Event stage_done;
+    lisreg::PinnedBuf fetch_host;           // pinned landing area of results (+ trace)
     int       early_stop_chunk = -1;        // iterations between host looks at the finished-counter; -1 auto, 0 never
     int       fetch_trace_records = 0;      // lisreg_align: trace records copied out together with the results
     std::vector<lisreg::TargetSeg> h_tsegs;
@@ -174,9 +219,9 @@ struct lisreg_ctx {
     int         reach_miss_seen = 0, runs_since_fetch = 0;
     int         reach_miss_last = 0;                    // query-iterations of the last fetched run that found their cell without rows
     bool        reach_now = false;                      // the last run built its rows that way
-    hipStream_t side_stream = nullptr;                  // strip build: the big-strip kernel runs here, forked from / joined to `stream`
-    hipEvent_t  ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t  ev_ab = nullptr, ev_ba = nullptr;       // interleaved runs: "half A's / half B's correspondence launch is through"
+    lisreg::Stream side_stream;                         // strip build: the big-strip kernel runs here, forked from / joined to `stream`
+    lisreg::Event ev_fork, ev_join;
+    lisreg::Event ev_ab, ev_ba;                         // interleaved runs: "half A's / half B's correspondence launch is through"
     int       t_elems = 0, t_buckets = 0;
     bool      count_searches = false;
     bool      dump_neighbors = false;   // tests: keep the five neighbour ids of every query of the last iteration run
@@ -224,7 +269,7 @@ struct lisreg_ctx {
     int       degenerate = 0;               // isDegenerate member (odomEstimationNode.cpp:67)
     // profiling
     bool      profiling = false;
-    std::vector<hipEvent_t> ev;
+    std::vector<lisreg::Event> ev;
     std::vector<int>        ev_kind;        // kind of the interval STARTING at event i: 0 assoc, 1 solve, 2 index, -1 none
     std::vector<int>        ev_sidx;        // stream the event was recorded on: 0 the context's, 1 the side stream (interleaved runs)
     double    timing[5] = { 0, 0, 0, 0, 0 };
@@ -235,13 +280,12 @@ struct lisreg_ctx {
     lisreg::RcclApi   rccl;
     void*     comm = nullptr;
     int       comm_nranks = 0;
-    // FEPSC loop-closure candidate detection (lisreg_loop.hip): created on first use, released by loopdet_destroy
-    lisreg::LoopDet* loopdet = nullptr;
+    // FEPSC loop-closure candidate detection (lisreg_loop.hip): created on first use
+    std::unique_ptr<lisreg::LoopDet, lisreg::LoopDetDelete> loopdet;
 };
 
 namespace lisreg {
-void feeder_destroy(lisreg_ctx* c);
-void loopdet_destroy(lisreg_ctx* c);
+void feeder_stop(lisreg_ctx* c);       // drains the copy and pack streams and joins the packing threads (lisreg_destroy, before the staging goes)
 int  ctx_fail(lisreg_ctx* c, int code, const std::string& msg);
 // the side stream and its fork / join events, created on first use; false if they cannot be made (the caller then runs on one stream)
 bool ensure_side_stream(lisreg_ctx* c);

@@ -625,22 +625,14 @@ struct LoopDet {
     std::vector<unsigned char> h_in, h_out;
 };
 
-void loopdet_destroy(lisreg_ctx* c)
-{
-    if (!c->loopdet) return;
-    for (auto& d : c->loopdet->db) { d.proj.release(); for (auto& b : d.desc) b.release(); }
-    c->loopdet->in.release(); c->loopdet->hist.release(); c->loopdet->desc.release(); c->loopdet->out.release(); c->loopdet->proj_tmp.release();
-    c->loopdet->fold.release();
-    delete c->loopdet;
-    c->loopdet = nullptr;
-}
+void LoopDetDelete::operator()(LoopDet* p) const { delete p; }
 
 namespace {
 
 LoopDet* loopdet_of(lisreg_ctx* c)
 {
-    if (!c->loopdet) c->loopdet = new (std::nothrow) LoopDet();
-    return c->loopdet;
+    if (!c->loopdet) c->loopdet.reset(new (std::nothrow) LoopDet());
+    return c->loopdet.get();
 }
 
 // grow a database's device arrays to hold `need` frames, keeping the frames stored so far
@@ -649,11 +641,10 @@ int db_reserve(lisreg_ctx* c, LoopDb& d, int need)
     if (need <= d.cap) return LISREG_OK;
     const int cap = std::max(need, std::max(64, 2 * d.cap));
     DevBuf np, nd[kDescKinds];
-    auto drop = [&]() { np.release(); for (auto& b : nd) b.release(); };
     bool ok = np.ensure(sizeof(float4) * kProj * (size_t)cap) == hipSuccess;
     for (int s = 0; s < kDescKinds && ok; ++s)
         if (d.stores(s)) ok = nd[s].ensure((size_t)kCells * cap) == hipSuccess;
-    if (!ok) { drop(); return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: device allocation failed"); }
+    if (!ok) return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: device allocation failed");
     const int n = d.n();
     hipError_t e = hipSuccess;
     if (n > 0) {
@@ -662,10 +653,9 @@ int db_reserve(lisreg_ctx* c, LoopDb& d, int need)
             if (d.stores(s)) e = hipMemcpyAsync(nd[s].p, d.desc[s].p, (size_t)kCells * n, hipMemcpyDeviceToDevice, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { drop(); return ctx_fail(c, LISREG_ERR_HIP, std::string("loopdet: ") + hipGetErrorString(e)); }
-    d.proj.release();
-    d.proj = np;
-    for (int s = 0; s < kDescKinds; ++s) { d.desc[s].release(); d.desc[s] = nd[s]; }
+    if (e != hipSuccess) return ctx_fail(c, LISREG_ERR_HIP, std::string("loopdet: ") + hipGetErrorString(e));
+    d.proj = std::move(np);
+    for (int s = 0; s < kDescKinds; ++s) d.desc[s] = std::move(nd[s]);
     d.cap = cap;
     return LISREG_OK;
 }
@@ -832,7 +822,7 @@ int lisreg_loopdet_configure(lisreg_ctx* c, int db_id, unsigned kinds, double la
     if (!L) return ctx_fail(c, LISREG_ERR_NOMEM, "loopdet: out of host memory");
     LoopDb& d = L->db[db_id];
     if (d.n() > 0) return bad(c, "loopdet_configure: the database holds frames (lisreg_loopdet_reset first)");
-    if (kinds != d.kinds) {
+    if (kinds != d.kinds) {       // other descriptors: the arrays of the old ones go back now, the next add sizes new ones
         d.proj.release();
         for (auto& b : d.desc) b.release();
         d.cap = 0;

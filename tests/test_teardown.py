@@ -148,6 +148,109 @@ print("CASE_DONE")
 """))
 
 
+# free(1) - free(N) of the case below on the commit before the owners (bytes), and the smallest non-zero step hipMemGetInfo took there
+# (around one 64-byte lisreg.DeviceArray, grown until the reading moved): both measured on an MI355X, see the docstring
+PARENT_DROP_BYTES = 16777216
+MEMINFO_STEP_BYTES = 2097152
+
+
+@pytest.mark.gpu
+def test_destroy_gives_device_memory_back():
+    """6 cycles of create -> every subsystem that owns device memory -> destroy in one process: registrations on cell rows (search_mode 5)
+    and on the graph (3), a staged host batch (feeder), lisreg_upload_cloud, the voxel grid single and multi, feature extraction with
+    de-skew, the semantic split, a local map, a key-frame ring pushed past 19 frames, a map index with one ICP alignment, a loop database
+    grown past 64 frames.  Free device memory (hipMemGetInfo) is read after the destroy of cycle 1 and of cycle 6: a resource that a
+    context does not give back costs five times its size between the two readings.
+    Measured on the commit before the owners: drop = free(1) - free(6) = 16777216 bytes (all of it between cycles 1 and 2: the five
+    readings after that are equal, so it is the runtime settling, not something a context keeps), smallest non-zero step of
+    hipMemGetInfo = 2097152 bytes; the bar is their sum.  With the owners: the same six readings, drop 16777216."""
+    r = run_case(SMALL_BATCH + """
+from lisreg import replay
+hip = lisreg.hip_runtime()
+def free_bytes():
+    fr, tot = C.c_size_t(), C.c_size_t()
+    assert hip.hipMemGetInfo(C.byref(fr), C.byref(tot)) == 0
+    return fr.value
+case = synth.make_case(h=16, w=450, m_points=20000, scan_seed=1500)
+labelled = next(iter(replay.synthetic_drive(1, h=32, w=900, car=False)))[0]
+raw = synth.make_raw_scan(16, 450, 7400)
+t_imu = 100.0 - 0.01 + np.arange(70) / 500.0
+rot = np.zeros((70, 3)); rot[:, 2] = 0.6 * (t_imu - t_imu[0])         # integrated IMU rotation: a steady yaw rate
+drive = synth.make_loop_drive(22, 3, h=16, w=361)
+assert len(drive) > 64
+# the test's own device arrays live across all cycles: they are in both readings
+rec = lisreg.pack_device_records(labelled)
+vin = [lisreg.DeviceArray(rec), lisreg.DeviceArray(rec[: len(rec) // 2])]
+vout = [lisreg.DeviceArray(np.zeros_like(rec)), lisreg.DeviceArray(np.zeros_like(rec))]
+up = lisreg.DeviceArray(np.zeros((len(labelled), 4), np.float32))
+def cycle():
+    ctx = lisreg.Context(0)
+    p1 = lisreg.default_params(1)
+    ctx.set_option("search_mode", 5)
+    ctx.set_target(case["tgt_corner"], case["tgt_surf"])
+    ctx.align(case["src_corner"], case["src_surf"], case["T_init"], p1)
+    assert ctx.front_end() == 5
+    ctx.set_option("search_mode", 3)
+    ctx.align(case["src_corner"], case["src_surf"], case["T_init"], p1)
+    assert ctx.front_end() == 3
+    ctx.set_option("search_mode", 4)
+    ctx.set_target(cases[0]["tgt_corner"], cases[0]["tgt_surf"])
+    arr, keep = items()
+    staged = (lisreg.Item * n)()
+    assert ctx._L.lisreg_stage_host_items(ctx._h, n, arr, staged) == 0
+    assert ctx._L.lisreg_batch_prepare(ctx._h, n, staged, C.byref(p), T0.ctypes.data_as(C.POINTER(C.c_float))) == 0
+    assert ctx._L.lisreg_batch_run(ctx._h) == 0
+    ctx._n_items = n
+    T, st = ctx.batch_fetch()
+    assert all(s["status"] == 0 for s in st)
+    assert ctx.upload_cloud(labelled, up.ptr) == len(labelled)
+    rc, vox = ctx.voxel_downsample(case["tgt_surf"], 0.4)
+    assert rc == 0 and 0 < len(vox) < len(case["tgt_surf"])
+    nd = ctx.voxel_downsample_multi_device([a.ptr for a in vin], [len(rec), len(rec) // 2], [0.4, 0.2], [o.ptr for o in vout], [len(rec)] * 2)
+    assert all(k > 0 for k in nd)
+    feat = ctx.extract_features(raw, lisreg.FeatureParams(16, 450, 1, 0.0, 70.0, 1.0, 0.1),
+                                lisreg.make_deskew(t_imu, rot[:, 0], rot[:, 1], rot[:, 2], 100.0))
+    assert len(feat["deskewed"]) > 1000
+    parts = ctx.semantic_split(labelled)                     # dynamic, ground, building, pole, outlier
+    assert sum(len(q) for q in parts) == len(labelled)
+    lm = lisreg.localmap_default_params()
+    pose = np.array([0, 0, 0.01, 0.2, -0.1, 0.0], np.float32)
+    ctx.localmap_reset(0)
+    ctx.localmap_insert(0, [parts[0], parts[3], parts[1], parts[2], parts[4]], pose, lm)      # map order: dynamic, pole, ground, building, outlier
+    assert ctx.localmap_extract(0, pose, lm, target_slot=3)["n_target_surf"] > 1000
+    for k in range(22):
+        kf = ctx.keyframes_push(0, case["src_corner"], case["src_surf"], np.array([0, 0, 0.01 * k, 0.1 * k, 0, 0], np.float32))
+    assert kf["n_keyframes"] == 19
+    assert ctx.keyframes_target(0, 0.2, 0.4, target_slot=1)["n_target_surf"] > 0
+    ctx.map_index_set(0, case["tgt_surf"])
+    ctx.icp_align(0, case["src_surf"], lisreg.icp_default_params(0))
+    ctx.loopdet_reset(0)
+    assert len(ctx.loopdet_detect([(f["corner"], f["surf"], f["semantic"], f["odom"]) for f in drive], db_id=0)) == len(drive)
+    ctx.close()
+N = 6
+# the smallest non-zero step of hipMemGetInfo: a small allocation, grown until the reading moves
+step, probes, size = 0, [], 64
+while step == 0 and size <= 2 ** 28:
+    f0 = free_bytes()
+    probes.append(lisreg.DeviceArray(np.zeros(size, np.uint8)))
+    step = f0 - free_bytes()
+    size *= 4
+for a in probes: a.free()
+free_after = []
+for i in range(N):
+    cycle()
+    free_after.append(free_bytes())
+print("FREE_AFTER", free_after)
+print("MEMINFO_STEP", step)
+print("DROP", free_after[0] - free_after[-1])
+print("CASE_DONE")
+""", timeout=900)
+    print(r.stdout[-2000:])
+    check(r)
+    drop = int(r.stdout.split("DROP")[1].split()[0])
+    assert drop <= PARENT_DROP_BYTES + MEMINFO_STEP_BYTES, (drop, r.stdout[-2000:])
+
+
 def _have_torch():
     try:
         import importlib.util
