@@ -411,6 +411,44 @@ int  lisreg_extract_features_deskew(lisreg_ctx* ctx, const void* cloud, int n, i
 int  lisreg_extract_features_batch(lisreg_ctx* ctx, int n_sweeps, const void* const* sweeps, const int* n,
                                    const lisreg_feature_params* params, lisreg_feature_out* outs);
 
+/* ---- laser pretreatment: ring and per-point time of a raw sweep ------------------------------------------------- */
+/* Replaces LaserPretreatment::Pretreatment (src/core/laserPretreatment.cpp:4-81, :84-161; inline in src/node/laserPretreatmentNode.cpp:
+ * 60-219; removeClosedPointCloud, src/include/laserPretreatment.h:25-54): non-finite and out-of-range points are dropped, the ring comes
+ * from the elevation angle through the beam table of N_SCAN 16 / 32 / 64 (points outside the table are dropped), the time from the
+ * azimuth with the halfPassed seam logic; input order is kept and x, y, z, intensity are copied bit for bit.  The arithmetic is the
+ * reference's, operation for operation (float / double steps listed at the top of lis-slam_amd/csrc/lisreg_pretreat.hip; a float libm
+ * function is the correctly rounded value, as for lisreg_extract_features).  Its outputs are what lisreg_extract_features* (ring) and
+ * lisreg_deskew.time_device (time) take. */
+#define LISREG_FMT_XYZI_PACKED 5   /* host: floats x@0 y@4 z@8 intensity@12, 16-byte stride (KITTI velodyne .bin files, PointCloud2 point_step 16) */
+typedef struct lisreg_pretreat_params {
+    int    n_scan;        /* N_SCAN: 16, 32 or 64 — anything else LISREG_ERR_ARG (the reference: ROS_BREAK)      */
+    float  min_range;     /* lidarMinRange (config/params.yaml:73)                                               */
+    float  max_range;     /* lidarMaxRange (:74)                                                                 */
+    double scan_period;   /* scanPeriod = 0.1, a double constant (laserPretreatment.h:12)                        */
+} lisreg_pretreat_params;
+typedef struct lisreg_pretreat_out {
+    void*  cloud;         /* host input: PointXYZIRT structs (32 B: x y z, intensity@16, uint16 ring@20, float time@24);
+                             device input: lisreg_dpoint, ring in the low 16 bits of the payload                   */
+    int    capacity;      /* points; n (input count) is always enough                                             */
+    int    n;             /* written back: points kept                                                            */
+    float* time_device;   /* device input only: per-point time [capacity] — what lisreg_deskew.time_device takes  */
+    float* intensity_device; /* device input only, may be NULL: per-point intensity [capacity]                    */
+    float  start_ori, end_ori;   /* written back: the sweep's startOri / endOri after the 2 pi adjustment (0 when no point is finite and in range) */
+    int    half_index;    /* written back: output index of the point at which halfPassed became true, -1 if never */
+} lisreg_pretreat_out;
+int  lisreg_default_pretreat_params(lisreg_pretreat_params* p);          /* 64, 0.0, 70.0, 0.1 */
+/* One sweep.  fmt: LISREG_FMT_XYZI (PCL PointXYZI / the reference's PointIn: intensity at byte 16) or LISREG_FMT_XYZI_PACKED — host in,
+ * host PointXYZIRT out; LISREG_FMT_DEVICE_XYZI (device records, payload = float intensity) — device in, device out, only the 16-byte
+ * result header crosses the link.  More points kept than `capacity`: nothing is written, out->n receives the count, LISREG_ERR_ARG.
+ * n_scan not 16 / 32 / 64, n < 0, or an output that overlaps the input: LISREG_ERR_ARG.  n == 0 or nothing kept: LISREG_OK, out->n = 0,
+ * half_index = -1 (the reference reads points[0] of an empty cloud there). */
+int  lisreg_pretreat(lisreg_ctx* ctx, const void* cloud, int n, int stride_bytes, int fmt,
+                     const lisreg_pretreat_params* params, lisreg_pretreat_out* out);
+/* n_sweeps (<= 256) sweeps of device records (LISREG_FMT_DEVICE_XYZI) in ONE launch sequence — the same launches as a single call; every
+ * outs[s] is identical to what a single call on sweeps[s] gives and feeds lisreg_extract_features_batch directly. */
+int  lisreg_pretreat_batch(lisreg_ctx* ctx, int n_sweeps, const void* const* sweeps, const int* n,
+                           const lisreg_pretreat_params* params, lisreg_pretreat_out* outs);
+
 /* The "semantic mask": SemanticFusionNode::categoryMapping (src/node/semanticFusionNode.cpp:173-189) splits the labelled
  * cloud, preserving order, by UsingLableMap[label] (config/label.yaml:177-196): 10 -> dynamic, 40 -> ground, 50 -> building,
  * 81 -> pole, anything else (label 0 has no entry) -> outlier.  These five clouds are what semantic_info carries and what

@@ -103,6 +103,12 @@ struct PackPool {
         const unsigned char* s = k.src;
         lisreg_dpoint* o = k.dst;
         const bool lab = k.fmt == LISREG_FMT_XYZIL;
+        if (k.fmt == LISREG_FMT_XYZI_PACKED || k.fmt == kPackIntensity) {      // raw sweeps: the payload is the float intensity, bit for bit
+            const int at = k.fmt == kPackIntensity ? 16 : 12;
+            if (at == 12 && k.stride == 16) { memcpy(o, s, (size_t)k.n * 16); return; }
+            for (int i = 0; i < k.n; ++i, s += k.stride, ++o) { memcpy(o, s, 12); memcpy(&o->payload, s + at, 4); }
+            return;
+        }
         for (int i = 0; i < k.n; ++i, s += k.stride, ++o) {
             memcpy(o, s, 12);
             uint16_t l = 0;
@@ -377,8 +383,15 @@ int lisreg_upload_cloud(lisreg_ctx* c, const void* cloud, int n, int stride_byte
 {
     if (!c) return LISREG_ERR_ARG;
     if (n < 0 || (n > 0 && (!cloud || !dev_out))) return ctx_fail(c, LISREG_ERR_ARG, "upload_cloud: bad arguments");
-    if (fmt != LISREG_FMT_XYZIL && fmt != LISREG_FMT_XYZI) return ctx_fail(c, LISREG_ERR_ARG, "upload_cloud: host clouds only (LISREG_FMT_XYZI / _XYZIL)");
-    if (stride_bytes < 12 || (fmt == LISREG_FMT_XYZIL && stride_bytes < 22)) return ctx_fail(c, LISREG_ERR_ARG, "upload_cloud: bad stride");
+    if (fmt != LISREG_FMT_XYZIL && fmt != LISREG_FMT_XYZI && fmt != LISREG_FMT_XYZI_PACKED)
+        return ctx_fail(c, LISREG_ERR_ARG, "upload_cloud: host clouds only (LISREG_FMT_XYZI / _XYZIL / _XYZI_PACKED)");
+    if (stride_bytes < 12 || (fmt == LISREG_FMT_XYZIL && stride_bytes < 22) || (fmt == LISREG_FMT_XYZI_PACKED && stride_bytes < 16))
+        return ctx_fail(c, LISREG_ERR_ARG, "upload_cloud: bad stride");
+    return upload_records(c, cloud, n, stride_bytes, fmt, dev_out);
+}
+
+int lisreg::upload_records(lisreg_ctx* c, const void* cloud, int n, int stride_bytes, int fmt, void* dev_out)
+{
     if (n == 0) return LISREG_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = sizeof(lisreg_dpoint) * (size_t)n;

@@ -172,6 +172,10 @@ struct lisreg_ctx {
            vox_in, vox_lab, vox_order, vox_sidx, vox_head, vox_slot, vox_start, vox_out, vox_outlab, vox_M,
            ft_owner, ft_flag, ft_pos, ft_scan, ft_col, ft_range, ft_src, ft_curv, ft_picked, ft_label, ft_rlists, ft_rcounts,
            ft_lists, ft_counts, ft_rings, ft_gather, ft_cat, ft_bounds, ft_dsk_tab, ft_dsk_pts, ft_dsk_misc, ft_dsk_time;
+    // laser pretreatment (lisreg_pretreat.hip): startOri / endOri per sweep, per-point ring / ori, per-workgroup partials, result headers, the
+    // sweep table of a batch; staging of a host sweep and of its results
+    lisreg::DevBuf pt_ends, pt_ring, pt_ori, pt_blk, pt_hdr, pt_tab, pt_in, pt_out, pt_time;
+    lisreg::PinnedBuf pt_hdr_host;
     // host feeder (lisreg_api_feed.hip): clouds packed to 16-byte records by a few threads into pinned staging, uploaded on a copy stream
     std::unique_ptr<lisreg::PackPool, lisreg::PackPoolDelete> pack_pool;
     int          feeder_threads = 8;
@@ -291,6 +295,10 @@ int  ctx_fail(lisreg_ctx* c, int code, const std::string& msg);
 bool ensure_side_stream(lisreg_ctx* c);
 // pack PCL structs (stride/format of common.h:9,25-35) into 16-B device records
 void pack_cloud(const void* cloud, int n, int stride, int fmt, lisreg_dpoint* out);
+// lisreg_upload_cloud's body: fmt is LISREG_FMT_XYZI (payload 0), _XYZIL (uint16 at byte 20), _XYZI_PACKED (the float at byte 12) or
+// kPackIntensity (PCL PointXYZI with the float intensity at byte 16 as the payload)
+constexpr int kPackIntensity = 0x100;
+int  upload_records(lisreg_ctx* c, const void* cloud, int n, int stride_bytes, int fmt, void* dev_out);
 // grid geometry from a bounding box; cell edge grows if the box would need too many cells
 void make_grid(const float bb[6], int n, GridIndex* g, int* n_cells, int margin_cells = 0);
 SortBuffers sort_buffers(lisreg_ctx* c);

@@ -221,6 +221,26 @@ int main()
         std::printf(kok ? "EPSCGeneration kinds ok\n" : "EPSCGeneration kinds FAILED\n");
         ok = ok && kok;
     }
+    {   // LaserPretreatment: one turn of a 16-beam sweep, clockwise as the sensor spins; rings 0..15 in order, time 0 -> scanPeriod
+        LaserPretreatment pre(reg.handle());
+        pre.params.n_scan = 16;
+        PointCloud<PointIn> rawSweep;
+        const int W = 360;
+        for (int c = 0; c < W; ++c)
+            for (int b = 0; b < 16; ++b) {
+                const float az = -6.2831853f * (float)c / (float)W, el = (-15.f + 2.f * (float)b) * 0.01745329252f, r = 10.f + 0.01f * (float)b;
+                PointIn p{}; p.x = r * std::cos(el) * std::cos(az); p.y = r * std::cos(el) * std::sin(az); p.z = r * std::sin(el); p.intensity = (float)b;
+                rawSweep.push_back(p);
+            }
+        PointIn nanp{}; nanp.x = std::nanf(""); rawSweep.points[5] = nanp;
+        PointCloud<PointXYZIRT> sweep = pre.Pretreatment(rawSweep);
+        bool pok = sweep.size() == rawSweep.size() - 1 && pre.halfIndex > 0;
+        for (size_t i = 0; i < sweep.size() && pok; ++i)
+            pok = sweep.points[i].ring == (uint16_t)sweep.points[i].intensity && sweep.points[i].time > -1e-4f && sweep.points[i].time < 0.1001f;
+        pok = pok && sweep.points.back().time > 0.099f && sweep.points.front().time < 0.001f;
+        std::printf(pok ? "LaserPretreatment ok (%zu of %zu points)\n" : "LaserPretreatment FAILED (%zu of %zu points)\n", sweep.size(), rawSweep.size());
+        ok = ok && pok;
+    }
     std::printf(ok ? "host_smoke ok\n" : "host_smoke FAILED\n");
     return ok ? 0 : 1;
 }

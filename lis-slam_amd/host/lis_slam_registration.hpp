@@ -253,6 +253,38 @@ private:
     lisreg_ctx* ctx_;
 };
 
+// ---- laser pretreatment: the node in front of LaserProcessing -------------------------------------------------------------
+// LaserPretreatment (src/include/laserPretreatment.h:57-69, src/core/laserPretreatment.cpp:4-161): a raw sweep (PointIn: x y z + float i
+// at byte 16, the layout of pcl::PointXYZI) becomes PointXYZIRT — non-finite and out-of-range points dropped, ring from the elevation
+// angle with the N_SCAN 16 / 32 / 64 table, time from the azimuth.  N_SCAN, lidarMinRange and lidarMaxRange are ParamServer members in
+// the reference; here they are `params`.
+using PointIn = PointXYZI;
+class LaserPretreatment {
+public:
+    lisreg_pretreat_params params;
+    float startOri = 0.f, endOri = 0.f;     // of the last sweep
+    int   halfIndex = -1;                   // output index of the point at which halfPassed became true, -1 if never
+    explicit LaserPretreatment(lisreg_ctx* ctx) : ctx_(ctx) { lisreg_default_pretreat_params(&params); }
+    PointCloud<PointXYZIRT> Pretreatment(const PointCloud<PointIn>& cloudIn) {
+        return run(cloudIn.points.data(), (int)cloudIn.size(), (int)sizeof(PointIn), LISREG_FMT_XYZI);
+    }
+    // the same for a packed buffer of x y z intensity floats (a KITTI velodyne file, a PointCloud2 with point_step 16)
+    PointCloud<PointXYZIRT> Pretreatment(const float* xyzi, int n) { return run(xyzi, n, 16, LISREG_FMT_XYZI_PACKED); }
+private:
+    PointCloud<PointXYZIRT> run(const void* cloud, int n, int stride, int fmt) {
+        PointCloud<PointXYZIRT> out;
+        out.points.resize((size_t)n);
+        lisreg_pretreat_out o{};
+        o.cloud = out.points.data(); o.capacity = n;
+        const int rc = lisreg_pretreat(ctx_, cloud, n, stride, fmt, &params, &o);
+        if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_));
+        out.points.resize((size_t)o.n);
+        startOri = o.start_ori; endOri = o.end_ori; halfIndex = o.half_index;
+        return out;
+    }
+    lisreg_ctx* ctx_;
+};
+
 // ---- the compute steps of SubMapManager (src/include/subMap.h) ---------------------------------------------
 struct bounds_t { double min_x, min_y, min_z, max_x, max_y, max_z; };     // src/include/subMap.h:32-39
 struct centerpoint_t { double x, y, z; };                                  // src/include/subMap.h:11-16

@@ -19,7 +19,7 @@ CSRC = os.path.join(_PKG, "csrc")
 
 OK, NOT_ENOUGH_FEATURES, TOO_FEW_CORRESPONDENCES, LEAF_TOO_SMALL = 0, 1, 2, 3
 ERR_ARG, ERR_HIP, ERR_NO_TARGET, ERR_NOMEM, ERR_COMM = -1, -2, -3, -4, -5
-FMT_XYZI, FMT_XYZIL, FMT_DEVICE, FMT_XYZIRT, FMT_DEVICE_XYZI = 0, 1, 2, 3, 4
+FMT_XYZI, FMT_XYZIL, FMT_DEVICE, FMT_XYZIRT, FMT_DEVICE_XYZI, FMT_XYZI_PACKED = 0, 1, 2, 3, 4, 5
 VARIANT_ODOM, VARIANT_KEYFRAME, VARIANT_SUBMAP = 1, 2, 3
 TRACE_STRIDE = 56
 RESULT_SIZE = 12
@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "lisreg_loopdet_get", "lisreg_loop_descriptor",
     "lisreg_loopdet_configure", "lisreg_loopdet_matches", "lisreg_loopdet_candidate_scores", "lisreg_loopdet_get_descriptor",
     "lisreg_loop_descriptor_kind",
+    "lisreg_default_pretreat_params", "lisreg_pretreat", "lisreg_pretreat_batch",
 ]
 
 
@@ -233,6 +234,18 @@ class FeatureOut(C.Structure):
                 for f, t in ((name, C.c_void_p), ("cap_" + name, C.c_int), ("n_" + name, C.c_int))]
 
 
+class PretreatParams(C.Structure):
+    _fields_ = [("n_scan", C.c_int), ("min_range", C.c_float), ("max_range", C.c_float), ("scan_period", C.c_double)]
+
+
+class PretreatOut(C.Structure):
+    _fields_ = [("cloud", C.c_void_p), ("capacity", C.c_int), ("n", C.c_int), ("time_device", C.c_void_p),
+                ("intensity_device", C.c_void_p), ("start_ori", C.c_float), ("end_ori", C.c_float), ("half_index", C.c_int)]
+
+    def as_dict(self):
+        return dict(n=self.n, start_ori=np.float32(self.start_ori), end_ori=np.float32(self.end_ori), half_index=self.half_index)
+
+
 class SemanticOut(C.Structure):
     _fields_ = [("cloud", C.c_void_p * 5), ("cap", C.c_int * 5), ("n", C.c_int * 5)]
 
@@ -315,6 +328,10 @@ def lib():
                                                     C.POINTER(FeatureOut)]
         L.lisreg_extract_features_deskew.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FeatureParams), C.POINTER(Deskew),
                                                      C.POINTER(FeatureOut)]
+        L.lisreg_default_pretreat_params.argtypes = [C.POINTER(PretreatParams)]
+        L.lisreg_pretreat.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PretreatParams), C.POINTER(PretreatOut)]
+        L.lisreg_pretreat_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(PretreatParams),
+                                            C.POINTER(PretreatOut)]
         L.lisreg_semantic_split.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(SemanticOut)]
         ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
         L.lisreg_map_index_set.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
@@ -739,6 +756,51 @@ class Context:
         self._chk(self._L.lisreg_extract_features_batch(self._h, S, ptrs, ns, C.byref(params), fos))
         return [{k: getattr(fos[s], "n_" + k) for k in ("deskewed", "corner", "surface", "corner_sharp", "surface_sharp")} for s in range(S)]
 
+    # -- laser pretreatment: ring and time of a raw sweep ---------------------------------------------------
+    def pretreat(self, raw: np.ndarray, params: "PretreatParams", capacity: int | None = None, info: dict | None = None) -> np.ndarray:
+        """LaserPretreatment::Pretreatment on a host sweep: an (n, 4) float32 array (x y z intensity, the packed 16-byte layout of KITTI's
+        velodyne files) or a PCL struct array with the intensity at byte 16.  Returns the kept points as PointXYZIRT structs; `info`, when
+        given, receives n, start_ori, end_ori and half_index."""
+        from .synth import XYZIRT_DTYPE
+        raw = np.ascontiguousarray(raw)
+        if raw.dtype.names:
+            fmt, n, stride = FMT_XYZI, len(raw), raw.dtype.itemsize
+        else:
+            raw = np.ascontiguousarray(raw, np.float32).reshape(-1, 4)
+            fmt, n, stride = FMT_XYZI_PACKED, len(raw), 16
+        cap = n if capacity is None else capacity
+        out = np.zeros(max(cap, 1), XYZIRT_DTYPE)
+        po = PretreatOut()
+        po.cloud, po.capacity = out.ctypes.data_as(C.c_void_p), cap
+        rc = self._L.lisreg_pretreat(self._h, _vp(raw) if n else None, n, stride, fmt, C.byref(params), C.byref(po))
+        if info is not None:
+            info.update(po.as_dict())
+        self._chk(rc)
+        return out[: po.n]
+
+    def pretreat_device(self, in_ptr: int, n: int, params: "PretreatParams", out_ptr: int, time_ptr: int, cap: int,
+                        intensity_ptr: int | None = None) -> dict:
+        """lisreg_pretreat on device records whose payload is the float intensity (a KITTI sweep copied to HBM as it is): ring records to
+        out_ptr, times to time_ptr, intensities to intensity_ptr when given (`cap` points each).  Returns n, start_ori, end_ori, half_index."""
+        po = PretreatOut()
+        po.cloud, po.capacity, po.time_device = C.c_void_p(out_ptr), cap, C.c_void_p(time_ptr)
+        po.intensity_device = C.c_void_p(intensity_ptr) if intensity_ptr else None
+        self._chk(self._L.lisreg_pretreat(self._h, C.c_void_p(in_ptr), n, 16, FMT_DEVICE_XYZI, C.byref(params), C.byref(po)))
+        return po.as_dict()
+
+    def pretreat_batch_device(self, in_ptrs, counts, params: "PretreatParams", out_ptrs, time_ptrs, cap: int, intensity_ptrs=None) -> list:
+        """lisreg_pretreat_batch: per sweep a device input, a record buffer and a time buffer (optionally an intensity buffer) of `cap`
+        points.  Returns the per-sweep result dicts."""
+        S = len(in_ptrs)
+        ptrs = (C.c_void_p * S)(*[C.c_void_p(int(p)) if n else None for p, n in zip(in_ptrs, counts)])
+        ns = (C.c_int * S)(*[int(x) for x in counts])
+        pos = (PretreatOut * S)()
+        for s in range(S):
+            pos[s].cloud, pos[s].capacity, pos[s].time_device = C.c_void_p(int(out_ptrs[s])), cap, C.c_void_p(int(time_ptrs[s]))
+            pos[s].intensity_device = C.c_void_p(int(intensity_ptrs[s])) if intensity_ptrs else None
+        self._chk(self._L.lisreg_pretreat_batch(self._h, S, ptrs, ns, C.byref(params), pos))
+        return [pos[s].as_dict() for s in range(S)]
+
     def concat_device(self, in_ptrs, counts, out_ptr: int) -> int:
         """lisreg_concat_device: K device clouds end to end into out_ptr (stream-ordered, no wait).  Returns the total count."""
         k = len(in_ptrs)
@@ -752,6 +814,10 @@ class Context:
         """lisreg_upload_cloud: a host PCL struct array (x, y, z at 0 / 4 / 8; the uint16 at byte 20 — label or ring — becomes the
         payload when the dtype has one) into a device buffer of len(cloud) 16-byte records.  Returns the count."""
         cloud = np.ascontiguousarray(cloud)
+        if not cloud.dtype.names:                                    # a raw sweep: (n, 4) float32 x y z intensity, the records as they are
+            cloud = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4)
+            self._chk(self._L.lisreg_upload_cloud(self._h, cloud.ctypes.data_as(C.c_void_p), len(cloud), 16, FMT_XYZI_PACKED, C.c_void_p(dev_ptr)))
+            return len(cloud)
         names = cloud.dtype.names or ()
         has16 = any(cloud.dtype.fields[k][1] == 20 and cloud.dtype.fields[k][0].itemsize == 2 for k in names)
         self._chk(self._L.lisreg_upload_cloud(self._h, cloud.ctypes.data_as(C.c_void_p), len(cloud), cloud.dtype.itemsize,
@@ -1291,6 +1357,16 @@ def device_to_host(ptr: int, shape, dtype=np.float32) -> np.ndarray:
     if hip.hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_size_t(out.nbytes), 2) != 0:
         raise RuntimeError("hipMemcpy D2H failed")
     return out
+
+
+def default_pretreat_params(n_scan: int | None = None) -> PretreatParams:
+    p = PretreatParams()
+    rc = lib().lisreg_default_pretreat_params(C.byref(p))
+    if rc:
+        raise LisregError(rc, "lisreg_default_pretreat_params")
+    if n_scan is not None:
+        p.n_scan = n_scan
+    return p
 
 
 def default_feature_params() -> FeatureParams:

@@ -126,14 +126,16 @@ def kitti_rings(raw: np.ndarray, n_scan: int = 64, min_range: float = 0.0, max_r
     return out
 
 
-def kitti_raw_sequence(root: str, seq: str, max_frames: int | None = None):
-    """Yields the pretreated sweeps (PointXYZIRT) of <root>/sequences/<seq>/velodyne in order."""
+def kitti_raw_sequence(root: str, seq: str, max_frames: int | None = None, pretreated: bool = True):
+    """Yields the sweeps of <root>/sequences/<seq>/velodyne in order: pretreated on the host (PointXYZIRT, kitti_rings), or — pretreated=False —
+    the raw (n, 4) float32 arrays as they are in the files, for RawOdomReplayer."""
     d = os.path.join(root, "sequences", seq, "velodyne")
     names = sorted(f for f in os.listdir(d) if f.endswith(".bin"))
     for i, nm in enumerate(names):
         if max_frames is not None and i >= max_frames:
             return
-        yield kitti_rings(np.fromfile(os.path.join(d, nm), np.float32).reshape(-1, 4)), None
+        raw = np.fromfile(os.path.join(d, nm), np.float32).reshape(-1, 4)
+        yield (kitti_rings(raw) if pretreated else raw), None
 
 
 def synthetic_raw_drive(n_frames: int, h: int = 64, w: int = 1800, step: float = 0.45, seed: int = 11):
@@ -257,12 +259,16 @@ class DeviceOdomReplayer(OdomReplayer):
         self.T_pri = self.T.copy()
         self.key_id += 1
 
-    def step(self, sweep) -> dict:
-        t0 = time.perf_counter()
+    def _front(self, sweep) -> dict:
+        """the sweep into HBM and through the feature extraction: the counts of the five clouds"""
         n = len(sweep)
         assert n <= 2 * self.cap
         self.ctx.upload_cloud(sweep, self.raw.ptr)                   # (x, y, z, ring) records
-        cnt = self.ctx.extract_features_device(self.raw.ptr, n, self.fp, {k: v.ptr for k, v in self.feat.items()}, self.cap)
+        return self.ctx.extract_features_device(self.raw.ptr, n, self.fp, {k: v.ptr for k, v in self.feat.items()}, self.cap)
+
+    def step(self, sweep) -> dict:
+        t0 = time.perf_counter()
+        cnt = self._front(sweep)
         n_c, n_s = cnt["corner"], cnt["surface"]
         self._guess()
         rec = dict(frame=self.k, n_corner=n_c, n_surf=n_s, guess=self.T.copy(), stats=None, keyframe=False)
@@ -287,8 +293,36 @@ class DeviceOdomReplayer(OdomReplayer):
         return rec
 
 
-def replay_odom(ctx, sweeps, feature_params=None, on_frame=None, device_resident: bool = False):
-    r = DeviceOdomReplayer(ctx, feature_params) if device_resident else OdomReplayer(ctx, feature_params)
+class RawOdomReplayer(DeviceOdomReplayer):
+    """DeviceOdomReplayer fed with RAW sweeps — (n, 4) float32 arrays x y z intensity, a KITTI velodyne file as it is: the 16-byte records
+    go to HBM untouched, lisreg_pretreat derives ring and time there (laserPretreatmentNode), and the ring records (with the times, when
+    `deskew_of` returns a Deskew for the frame) go to the feature extraction.  No host pass over the sweep."""
+
+    def __init__(self, ctx, feature_params=None, target_slot: int = 0, ring_id: int = 0, pretreat_params=None, deskew_of=None):
+        super().__init__(ctx, feature_params, target_slot, ring_id)
+        import lisreg
+        self.pp = pretreat_params or lisreg.default_pretreat_params(self.fp.n_scan)
+        self.raw_in = lisreg.DeviceArray(np.zeros((2 * self.cap, 4), np.float32))
+        self.time = lisreg.DeviceArray(np.zeros(2 * self.cap, np.float32))
+        self.deskew_of = deskew_of                                   # frame number -> lisreg.Deskew (time_device is filled in here) or None
+        self.pretreat = None                                         # the last frame's pretreatment result
+
+    def _front(self, sweep) -> dict:
+        import ctypes as C
+        sweep = np.ascontiguousarray(sweep, np.float32).reshape(-1, 4)
+        n = len(sweep)
+        assert n <= 2 * self.cap
+        self.ctx.upload_cloud(sweep, self.raw_in.ptr)                # the records as they are
+        self.pretreat = self.ctx.pretreat_device(self.raw_in.ptr, n, self.pp, self.raw.ptr, self.time.ptr, 2 * self.cap)
+        dk = self.deskew_of(self.k) if self.deskew_of else None
+        if dk is not None:
+            dk.time_device = C.cast(C.c_void_p(self.time.ptr), C.POINTER(C.c_float))
+        return self.ctx.extract_features_device(self.raw.ptr, self.pretreat["n"], self.fp, {k: v.ptr for k, v in self.feat.items()}, self.cap,
+                                                deskew=dk)
+
+
+def replay_odom(ctx, sweeps, feature_params=None, on_frame=None, device_resident: bool = False, raw_input: bool = False):
+    r = RawOdomReplayer(ctx, feature_params) if raw_input else DeviceOdomReplayer(ctx, feature_params) if device_resident else OdomReplayer(ctx, feature_params)
     out = []
     for sw in sweeps:
         rec = r.step(sw)

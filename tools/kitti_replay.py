@@ -40,6 +40,9 @@ def main(argv=None):
     ap.add_argument("--variant", type=int, default=2, help="parameter set: 2 = subMapOptimization (default), 3 = loop-closure copy")
     ap.add_argument("--mode", choices=("submap", "odom"), default="submap",
                     help="submap: labelled sweeps through the sliding local map (copy #2); odom: raw sweeps, keyframe odometry (copy #1)")
+    ap.add_argument("--device-pretreat", action="store_true",
+                    help="--mode odom: the velodyne records go to HBM as they are and lisreg_pretreat derives ring and time there "
+                         "(default: the host stand-in replay.kitti_rings in front of the upload)")
     ap.add_argument("--check-oracle", type=int, default=0, metavar="N", help="also run the CPU restatement on the first N frames")
     ap.add_argument("--exact", action="store_true",
                     help="register with the exact-arithmetic build (the reference's arithmetic operation for operation, ~0.5x the speed): "
@@ -53,12 +56,21 @@ def main(argv=None):
     import lisreg
     from lisreg import replay
     odom = args.mode == "odom"
-    frames = (replay.kitti_raw_sequence if odom else replay.kitti_sequence)(args.root, args.seq, args.frames or None)
+    if args.device_pretreat and (not odom or args.check_oracle):
+        print("kitti_replay: --device-pretreat goes with --mode odom and without --check-oracle (the restatement takes pretreated sweeps)", file=sys.stderr)
+        return 2
+    if odom:
+        frames = replay.kitti_raw_sequence(args.root, args.seq, args.frames or None, pretreated=not args.device_pretreat)
+    else:
+        frames = replay.kitti_sequence(args.root, args.seq, args.frames or None)
     ctx = lisreg.Context(args.device)
     if args.exact:
         ctx.set_option("exact_arithmetic", 1)
     # the device-resident drivers: the sweep goes up once, every cloud of the frame stays in HBM (bit-identical to the host-cloud drivers)
-    r = replay.DeviceOdomReplayer(ctx) if odom else replay.DeviceReplayer(ctx, args.variant)
+    if odom:
+        r = replay.RawOdomReplayer(ctx) if args.device_pretreat else replay.DeviceOdomReplayer(ctx)
+    else:
+        r = replay.DeviceReplayer(ctx, args.variant)
     recs, kept = [], []
     t0 = time.perf_counter()
     for cloud, _ in frames:
