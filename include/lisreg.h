@@ -449,6 +449,54 @@ int  lisreg_pretreat(lisreg_ctx* ctx, const void* cloud, int n, int stride_bytes
 int  lisreg_pretreat_batch(lisreg_ctx* ctx, int n_sweeps, const void* const* sweeps, const int* n,
                            const lisreg_pretreat_params* params, lisreg_pretreat_out* outs);
 
+/* ---- RangeNet++ around the network: range-image projection and point labelling --------------------------------- */
+/* The host code the reference wraps around its segmentation network, without the network (the model is the
+ * caller's).  lisreg_rangenet_project replaces NetTensorRT::doProjection and the input half of NetTensorRT::infer (src/segnet/
+ * netTensorRT.cpp:143-300, :333-354): spherical projection of the sweep into an img_h x img_w image in which the nearest point wins a
+ * pixel, the invalid-pixel test, normalisation into the 5 x H x W input tensor (range, x, y, z, intensity; channel-major).
+ * lisreg_rangenet_label replaces the output half (:403-428) and RangenetAPI::infer's argmax (src/core/rangenetAPI.cpp:50-73, :103-110):
+ * invalid pixels masked, one logit vector per point through its pixel, argmax, labelled records — what lisreg_semantic_split takes.
+ * The arithmetic is the reference's, operation for operation (float / double steps listed at the top of lis-slam_amd/csrc/
+ * lisreg_rangenet.hip; a float libm function is the correctly rounded value).  Defined where the reference is not: among points of
+ * exactly equal range in one pixel the one of highest input index wins; a point with a non-finite x, y, z or intensity takes no part
+ * (pixel index -1, label 0); img_h * img_w <= 2^24; n_classes <= 32. */
+typedef struct lisreg_rangenet_params {
+    int    img_h, img_w;          /* the network's input height and width                                          */
+    double fov_up, fov_down;      /* degrees, doubles as in the reference (net.hpp:103)                           */
+    float  means[5], stds[5];     /* per channel (range, x, y, z, intensity).  The real ones belong to the caller's model — its
+                                     arch_cfg.yaml, which is not part of the reference tree: the defaults are 0 and 1 */
+    int    n_classes;             /* planes of the logits, 1 .. 32                                                 */
+} lisreg_rangenet_params;
+typedef struct lisreg_rangenet_out {   /* caller-owned DEVICE buffers                                              */
+    float*         tensor;        /* [5][img_h][img_w]; may be a torch tensor's data_ptr()                         */
+    unsigned char* invalid_mask;  /* [img_h * img_w]: 1 where the pixel is invalid (empty, or all five values truncate to 0) */
+    int*           pixel_index;   /* [n]: y * img_w + x of every point, -1 for a non-finite one                    */
+    int            n_valid;       /* written back: valid pixels (the one read-back of the call)                    */
+} lisreg_rangenet_out;
+int  lisreg_default_rangenet_params(lisreg_rangenet_params* p);   /* 64, 2048, 3.0, -25.0 (netTensorRT.cpp:144-145), means 0, stds 1, 20 */
+/* One sweep.  fmt: LISREG_FMT_XYZI or LISREG_FMT_XYZI_PACKED (host sweep, uploaded first) or LISREG_FMT_DEVICE_XYZI (device records,
+ * payload = float intensity; stride ignored).  The outputs are complete when the call returns.  img_h / img_w / n_classes out of range,
+ * n < 0, a NULL buffer, or an output that overlaps the input or another output: LISREG_ERR_ARG.  n == 0: an all-invalid image, an
+ * all-zero tensor, LISREG_OK. */
+int  lisreg_rangenet_project(lisreg_ctx* ctx, const void* cloud, int n, int stride_bytes, int fmt,
+                             const lisreg_rangenet_params* params, lisreg_rangenet_out* out);
+/* n_sweeps (<= 256) sweeps of device records (LISREG_FMT_DEVICE_XYZI) in ONE launch sequence; outs[s].tensor = base + s * 5 * H * W
+ * gives the n_sweeps x 5 x H x W tensor of a batched network.  Every outs[s] is bit for bit what a single call on sweeps[s] gives. */
+int  lisreg_rangenet_project_batch(lisreg_ctx* ctx, int n_sweeps, const void* const* sweeps, const int* n,
+                                   const lisreg_rangenet_params* params, lisreg_rangenet_out* outs);
+/* Labels from the network's logits (DEVICE float [n_classes][img_h][img_w]).  cloud: the sweep that was projected (device records,
+ * LISREG_FMT_DEVICE_XYZI or LISREG_FMT_DEVICE; the payload is not read); pixel_index / invalid_mask: what lisreg_rangenet_project wrote.
+ * labelled_out: n LISREG_FMT_DEVICE records, x y z bit for bit, the label in the payload.  label_image_out: the img_h x img_w label
+ * image (one byte per pixel), or NULL.  The outputs are complete when the call returns. */
+int  lisreg_rangenet_label(lisreg_ctx* ctx, const void* cloud, int n, int fmt, const int* pixel_index,
+                           const unsigned char* invalid_mask, const float* logits, const lisreg_rangenet_params* params,
+                           void* labelled_out, unsigned char* label_image_out);
+/* The same for n_sweeps (<= 256) sweeps in one launch sequence; label_image_out may be NULL, and so may any of its entries. */
+int  lisreg_rangenet_label_batch(lisreg_ctx* ctx, int n_sweeps, const void* const* sweeps, const int* n,
+                                 const int* const* pixel_index, const unsigned char* const* invalid_mask,
+                                 const float* const* logits, const lisreg_rangenet_params* params,
+                                 void* const* labelled_out, unsigned char* const* label_image_out);
+
 /* The "semantic mask": SemanticFusionNode::categoryMapping (src/node/semanticFusionNode.cpp:173-189) splits the labelled
  * cloud, preserving order, by UsingLableMap[label] (config/label.yaml:177-196): 10 -> dynamic, 40 -> ground, 50 -> building,
  * 81 -> pole, anything else (label 0 has no entry) -> outlier.  These five clouds are what semantic_info carries and what

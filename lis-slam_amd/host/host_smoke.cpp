@@ -14,8 +14,18 @@ using namespace lis_slam;
 
 static void add(PointCloud<PointType>& c, float x, float y, float z) { PointType p{}; p.x = x; p.y = y; p.z = z; c.push_back(p); }
 
+// RangenetAPI mirror: this program has no HIP runtime to allocate device memory with, so the labeller is only instantiated here (the
+// node that owns the model owns device memory too); tests/test_rangenet.py runs the same two calls on the GPU.
+static const void* rangenet_mirror_instantiates(lisreg_ctx* ctx, const RangenetWorkspace& ws, const void* sweep_device, int n)
+{
+    RangenetAPI api(ctx, ws);
+    api.params.img_w = 1800;
+    return api.infer(sweep_device, n, [](const float* /* tensor */, float* /* logits */) { /* the caller's model runs here */ });
+}
+
 int main()
 {
+    (void)&rangenet_mirror_instantiates;
     if (lisreg_device_count() == 0) {
         try { Scan2SubMapRegistration<> reg(Variant::Odom); }
         catch (const RegistrationError& e) { std::printf("no HIP device: constructor failed loudly as designed (%d: %s)\n", e.code, e.what()); return 0; }

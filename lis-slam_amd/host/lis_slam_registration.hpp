@@ -285,6 +285,53 @@ private:
     lisreg_ctx* ctx_;
 };
 
+// ---- RangeNet++ around the network: the semantic labeller --------------------------------------------------------------------
+// RangenetAPI (src/include/rangenetAPI.h:16-68, src/core/rangenetAPI.cpp) without the network: infer() projects the sweep into the
+// network's 5 x H x W input tensor, hands tensor and logits to the caller's model as DEVICE pointers, and labels the points from the
+// logits — nothing crosses the link but the valid-pixel count.  The model is a callable `void(const float* tensor, float* logits)` that
+// has finished writing `logits` (n_classes x H x W floats) when it returns.  This header has no HIP dependency, so the node — which
+// owns a HIP runtime for its model anyway — provides the device memory: the sweep as lisreg_dpoint records with the float intensity in
+// the payload (lisreg_upload_cloud with LISREG_FMT_XYZI_PACKED, or the output of lisreg_extract_features*), and the workspace below.
+// The RGB clouds of the reference's class are not mirrored.
+struct RangenetWorkspace {              // caller-owned device memory for sweeps of up to max_points points
+    float*         tensor = nullptr;    // 5 * H * W floats
+    float*         logits = nullptr;    // n_classes * H * W floats
+    unsigned char* invalid_mask = nullptr;   // H * W bytes
+    unsigned char* label_image = nullptr;    // H * W bytes, or NULL
+    int*           pixel_index = nullptr;    // max_points ints
+    void*          labelled = nullptr;       // max_points lisreg_dpoint records: getLabelPointCloud() on the device
+    int            max_points = 0;
+};
+class RangenetAPI {
+public:
+    lisreg_rangenet_params params;
+    int validPixels = 0;                // of the last sweep
+    RangenetAPI(lisreg_ctx* ctx, const RangenetWorkspace& ws) : ctx_(ctx), ws_(ws) { lisreg_default_rangenet_params(&params); }
+    // infer (rangenetAPI.cpp:16-125): returns the labelled device records (ws.labelled; x y z bit for bit, label in the payload) —
+    // what lisreg_semantic_split takes with LISREG_FMT_DEVICE
+    template <class Network>
+    const void* infer(const void* currentCloudInDevice, int num_points, Network&& network) {
+        if (num_points > ws_.max_points) throw RegistrationError(LISREG_ERR_ARG, "RangenetAPI::infer: the workspace is too small");
+        lisreg_rangenet_out o{};
+        o.tensor = ws_.tensor; o.invalid_mask = ws_.invalid_mask; o.pixel_index = ws_.pixel_index;
+        int rc = lisreg_rangenet_project(ctx_, currentCloudInDevice, num_points, 16, LISREG_FMT_DEVICE_XYZI, &params, &o);
+        if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_));
+        validPixels = o.n_valid;
+        network(static_cast<const float*>(ws_.tensor), ws_.logits);
+        rc = lisreg_rangenet_label(ctx_, currentCloudInDevice, num_points, LISREG_FMT_DEVICE_XYZI, ws_.pixel_index, ws_.invalid_mask, ws_.logits,
+                                   &params, ws_.labelled, ws_.label_image);
+        if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_));
+        num_points_ = num_points;
+        return ws_.labelled;
+    }
+    const void* getLabelPointCloud() const { return ws_.labelled; }
+    int size() const { return num_points_; }
+private:
+    lisreg_ctx* ctx_;
+    RangenetWorkspace ws_;
+    int num_points_ = 0;
+};
+
 // ---- the compute steps of SubMapManager (src/include/subMap.h) ---------------------------------------------
 struct bounds_t { double min_x, min_y, min_z, max_x, max_y, max_z; };     // src/include/subMap.h:32-39
 struct centerpoint_t { double x, y, z; };                                  // src/include/subMap.h:11-16

@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     "lisreg_loopdet_configure", "lisreg_loopdet_matches", "lisreg_loopdet_candidate_scores", "lisreg_loopdet_get_descriptor",
     "lisreg_loop_descriptor_kind",
     "lisreg_default_pretreat_params", "lisreg_pretreat", "lisreg_pretreat_batch",
+    "lisreg_default_rangenet_params", "lisreg_rangenet_project", "lisreg_rangenet_project_batch", "lisreg_rangenet_label",
+    "lisreg_rangenet_label_batch",
 ]
 
 
@@ -246,6 +248,15 @@ class PretreatOut(C.Structure):
         return dict(n=self.n, start_ori=np.float32(self.start_ori), end_ori=np.float32(self.end_ori), half_index=self.half_index)
 
 
+class RangenetParams(C.Structure):
+    _fields_ = [("img_h", C.c_int), ("img_w", C.c_int), ("fov_up", C.c_double), ("fov_down", C.c_double), ("means", C.c_float * 5),
+                ("stds", C.c_float * 5), ("n_classes", C.c_int)]
+
+
+class RangenetOut(C.Structure):
+    _fields_ = [("tensor", C.c_void_p), ("invalid_mask", C.c_void_p), ("pixel_index", C.c_void_p), ("n_valid", C.c_int)]
+
+
 class SemanticOut(C.Structure):
     _fields_ = [("cloud", C.c_void_p * 5), ("cap", C.c_int * 5), ("n", C.c_int * 5)]
 
@@ -332,6 +343,14 @@ def lib():
         L.lisreg_pretreat.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PretreatParams), C.POINTER(PretreatOut)]
         L.lisreg_pretreat_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(PretreatParams),
                                             C.POINTER(PretreatOut)]
+        L.lisreg_default_rangenet_params.argtypes = [C.POINTER(RangenetParams)]
+        L.lisreg_rangenet_project.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(RangenetParams), C.POINTER(RangenetOut)]
+        L.lisreg_rangenet_project_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(RangenetParams),
+                                                    C.POINTER(RangenetOut)]
+        L.lisreg_rangenet_label.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(RangenetParams), vp, vp]
+        L.lisreg_rangenet_label_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(RangenetParams),
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.lisreg_semantic_split.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(SemanticOut)]
         ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
         L.lisreg_map_index_set.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
@@ -800,6 +819,59 @@ class Context:
             pos[s].intensity_device = C.c_void_p(int(intensity_ptrs[s])) if intensity_ptrs else None
         self._chk(self._L.lisreg_pretreat_batch(self._h, S, ptrs, ns, C.byref(params), pos))
         return [pos[s].as_dict() for s in range(S)]
+
+    # -- RangeNet++ around the network: range-image projection and point labelling ---------------------------
+    def rangenet_project(self, raw: np.ndarray, params: "RangenetParams", tensor_ptr: int, mask_ptr: int, pixel_ptr: int) -> int:
+        """lisreg_rangenet_project on a host sweep: an (n, 4) float32 array (x y z intensity, packed 16-byte records) or a PCL struct
+        array with the intensity at byte 16.  The outputs are the caller's device buffers.  Returns the number of valid pixels."""
+        raw = np.ascontiguousarray(raw)
+        if raw.dtype.names:
+            fmt, n, stride = FMT_XYZI, len(raw), raw.dtype.itemsize
+        else:
+            raw = np.ascontiguousarray(raw, np.float32).reshape(-1, 4)
+            fmt, n, stride = FMT_XYZI_PACKED, len(raw), 16
+        ro = RangenetOut(C.c_void_p(tensor_ptr), C.c_void_p(mask_ptr), C.c_void_p(pixel_ptr), 0)
+        self._chk(self._L.lisreg_rangenet_project(self._h, _vp(raw) if n else None, n, stride, fmt, C.byref(params), C.byref(ro)))
+        return ro.n_valid
+
+    def rangenet_project_device(self, in_ptr: int, n: int, params: "RangenetParams", tensor_ptr: int, mask_ptr: int, pixel_ptr: int) -> int:
+        """lisreg_rangenet_project on device records whose payload is the float intensity: the 5 x H x W float tensor to tensor_ptr (a
+        torch tensor's data_ptr() will do), the H x W invalid mask (bytes) to mask_ptr, the per-point int32 pixel index to pixel_ptr;
+        all complete when the call returns.  Returns the number of valid pixels."""
+        ro = RangenetOut(C.c_void_p(tensor_ptr), C.c_void_p(mask_ptr), C.c_void_p(pixel_ptr), 0)
+        self._chk(self._L.lisreg_rangenet_project(self._h, C.c_void_p(in_ptr) if n else None, n, 16, FMT_DEVICE_XYZI, C.byref(params), C.byref(ro)))
+        return ro.n_valid
+
+    def rangenet_project_batch_device(self, in_ptrs, counts, params: "RangenetParams", tensor_ptr: int, mask_ptrs, pixel_ptrs) -> list:
+        """lisreg_rangenet_project_batch: sweep s writes plane block s of the (S, 5, H, W) float tensor at tensor_ptr, its own mask and
+        its own pixel index.  Returns the per-sweep valid-pixel counts."""
+        S = len(in_ptrs)
+        ptrs = (C.c_void_p * S)(*[C.c_void_p(int(p)) if n else None for p, n in zip(in_ptrs, counts)])
+        ns = (C.c_int * S)(*[int(x) for x in counts])
+        ros = (RangenetOut * S)()
+        plane = 5 * params.img_h * params.img_w * 4
+        for s in range(S):
+            ros[s].tensor, ros[s].invalid_mask, ros[s].pixel_index = C.c_void_p(int(tensor_ptr) + s * plane), C.c_void_p(int(mask_ptrs[s])), C.c_void_p(int(pixel_ptrs[s]))
+        self._chk(self._L.lisreg_rangenet_project_batch(self._h, S, ptrs, ns, C.byref(params), ros))
+        return [int(ros[s].n_valid) for s in range(S)]
+
+    def rangenet_label_device(self, in_ptr: int, n: int, pixel_ptr: int, mask_ptr: int, logits_ptr: int, params: "RangenetParams",
+                              out_ptr: int, image_ptr: int | None = None):
+        """lisreg_rangenet_label: logits_ptr is the network's n_classes x H x W float output in HBM; out_ptr receives n device records
+        (x y z bit for bit, label in the payload — what semantic_split_device takes), image_ptr the H x W label image when given."""
+        self._chk(self._L.lisreg_rangenet_label(self._h, C.c_void_p(in_ptr) if n else None, n, FMT_DEVICE_XYZI, C.c_void_p(pixel_ptr) if n else None,
+                                                C.c_void_p(mask_ptr), C.c_void_p(logits_ptr), C.byref(params), C.c_void_p(out_ptr) if n else None,
+                                                C.c_void_p(image_ptr) if image_ptr else None))
+
+    def rangenet_label_batch_device(self, in_ptrs, counts, pixel_ptrs, mask_ptrs, logits_ptrs, params: "RangenetParams", out_ptrs, image_ptrs=None):
+        """lisreg_rangenet_label_batch: the per-sweep buffers of rangenet_label_device, one launch sequence."""
+        S = len(in_ptrs)
+
+        def arr(ps, gate=None):
+            return (C.c_void_p * S)(*[C.c_void_p(int(p)) if (p and (gate is None or gate[k])) else None for k, p in enumerate(ps)])
+        ns = (C.c_int * S)(*[int(x) for x in counts])
+        self._chk(self._L.lisreg_rangenet_label_batch(self._h, S, arr(in_ptrs, counts), ns, arr(pixel_ptrs, counts), arr(mask_ptrs), arr(logits_ptrs),
+                                                      C.byref(params), arr(out_ptrs, counts), arr(image_ptrs) if image_ptrs else None))
 
     def concat_device(self, in_ptrs, counts, out_ptr: int) -> int:
         """lisreg_concat_device: K device clouds end to end into out_ptr (stream-ordered, no wait).  Returns the total count."""
@@ -1366,6 +1438,19 @@ def default_pretreat_params(n_scan: int | None = None) -> PretreatParams:
         raise LisregError(rc, "lisreg_default_pretreat_params")
     if n_scan is not None:
         p.n_scan = n_scan
+    return p
+
+
+def default_rangenet_params(img_h: int | None = None, img_w: int | None = None) -> RangenetParams:
+    """lisreg_default_rangenet_params: 64 x 2048, fov 3 / -25 degrees, means 0, stds 1 (the real ones are the model's), 20 classes"""
+    p = RangenetParams()
+    rc = lib().lisreg_default_rangenet_params(C.byref(p))
+    if rc != OK:
+        raise LisregError(rc, "lisreg_default_rangenet_params")
+    if img_h is not None:
+        p.img_h = img_h
+    if img_w is not None:
+        p.img_w = img_w
     return p
 
 

@@ -334,11 +334,18 @@ def replay_odom(ctx, sweeps, feature_params=None, on_frame=None, device_resident
 
 # ---- the frame loop -------------------------------------------------------------------------------------------------
 class Replayer:
-    """makeSubMapThread's state: transformTobeSubMapped, the previous pose, the local map (device object `map_id` of `ctx`)."""
+    """makeSubMapThread's state: transformTobeSubMapped, the previous pose, the local map (device object `map_id` of `ctx`).
 
-    def __init__(self, ctx, variant: int = 2, map_id: int = 0, target_slot: int = 0):
+    labeller: optional callable `logits_ptr = labeller(tensor_ptr)` — the caller's segmentation model on device pointers (the 5 x H x W
+    float input tensor in, the n_classes x H x W float logits out, written when it returns).  With it, step() takes an UNLABELLED sweep
+    ((n, 4) float32 x y z intensity, or PCL structs) and labels it on the device through Context.rangenet_project_device /
+    rangenet_label_device (`rangenet_params`, default lisreg.default_rangenet_params()) in place of labels from a file.  Without it
+    nothing changes."""
+
+    def __init__(self, ctx, variant: int = 2, map_id: int = 0, target_slot: int = 0, labeller=None, rangenet_params=None):
         import lisreg
         self.ctx, self.map_id, self.slot = ctx, map_id, target_slot
+        self.labeller, self.rn_params, self._rn = labeller, rangenet_params, None
         self.params = lisreg.default_params(variant)
         self.lm_params = lisreg.localmap_default_params()
         self.T = np.zeros(6, np.float32)
@@ -347,7 +354,39 @@ class Replayer:
         self.guess_obj = None
         ctx.localmap_reset(map_id)
 
+    def _label_on_device(self, cloud, raw_ptr=None, capacity=None):
+        """project -> labeller -> label: returns (device pointer of the labelled records, n).  `raw_ptr`: a device buffer of `capacity`
+        records to upload the sweep into (one of our own otherwise)."""
+        import lisreg
+        cloud = np.ascontiguousarray(cloud)
+        if cloud.dtype.names:                                          # PCL structs: x y z + intensity at byte 16 -> packed records
+            cloud = np.stack([cloud["x"], cloud["y"], cloud["z"], cloud["intensity"]], 1)
+        cloud = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4)
+        n = len(cloud)
+        if self.rn_params is None:
+            self.rn_params = lisreg.default_rangenet_params()
+        P = self.rn_params
+        hw = P.img_h * P.img_w
+        if self._rn is None or self._rn["cap"] < n or self._rn["hw"] != hw:
+            cap = max(n, capacity or 0, 1)
+            self._rn = dict(cap=cap, hw=hw, tensor=lisreg.DeviceArray(np.zeros(5 * hw, np.float32)), mask=lisreg.DeviceArray(np.zeros(hw, np.uint8)),
+                            pix=lisreg.DeviceArray(np.zeros(cap, np.int32)), lab=lisreg.DeviceArray(np.zeros((cap, 4), np.float32)),
+                            raw=None if raw_ptr else lisreg.DeviceArray(np.zeros((cap, 4), np.float32)))
+        b = self._rn
+        src = raw_ptr if raw_ptr else b["raw"].ptr
+        if n:
+            self.ctx.upload_cloud(cloud, src)
+        self.n_valid_pixels = self.ctx.rangenet_project_device(src, n, P, b["tensor"].ptr, b["mask"].ptr, b["pix"].ptr)
+        logits_ptr = int(self.labeller(b["tensor"].ptr))
+        self.ctx.rangenet_label_device(src, n, b["pix"].ptr, b["mask"].ptr, logits_ptr, P, b["lab"].ptr)
+        return b["lab"].ptr, n, cloud
+
     def _split_and_downsample(self, cloud):
+        if self.labeller is not None:                                  # labels from the model instead of from a file
+            import lisreg
+            ptr, n, raw = self._label_on_device(cloud)
+            rec = lisreg.device_to_host(ptr, (max(n, 1), 4), np.float32)[:n]
+            cloud = synth.to_pcl(raw[:, :3], rec[:, 3].view(np.uint32).astype(np.uint16), raw[:, 3])
         parts = self.ctx.semantic_split(cloud)                      # dynamic, ground, building, pole, outlier
         full = dict(dynamic=parts[0], ground=parts[1], building=parts[2], pole=parts[3], outlier=parts[4])
         down = {k: (self.ctx.voxel_downsample(c, FRAME_LEAF[k])[1] if len(c) else c) for k, c in full.items()}
@@ -400,8 +439,9 @@ class DeviceReplayer(Replayer):
     all take device pointers.  Only counts and the pose come back.  Same kernels in the same order as Replayer: the poses are
     bit-identical (tests/test_replay.py)."""
 
-    def __init__(self, ctx, variant: int = 2, map_id: int = 0, target_slot: int = 0, capacity: int = 1 << 18):
-        super().__init__(ctx, variant, map_id, target_slot)
+    def __init__(self, ctx, variant: int = 2, map_id: int = 0, target_slot: int = 0, capacity: int = 1 << 18, labeller=None,
+                 rangenet_params=None):
+        super().__init__(ctx, variant, map_id, target_slot, labeller, rangenet_params)
         import lisreg
         z = np.zeros((capacity, 4), np.float32)
         self.cap = capacity
@@ -415,8 +455,12 @@ class DeviceReplayer(Replayer):
         t0 = time.perf_counter()
         n = len(cloud)
         assert n <= self.cap
-        self.ctx.upload_cloud(cloud, self.raw.ptr)
-        nf = self.ctx.semantic_split_device(self.raw.ptr, n, [b.ptr for b in self.full], self.cap)
+        if self.labeller is not None:                                  # the sweep goes up unlabelled; the labelled records stay in HBM
+            labelled_ptr, n, _ = self._label_on_device(cloud, self.raw.ptr, self.cap)
+        else:
+            self.ctx.upload_cloud(cloud, self.raw.ptr)
+            labelled_ptr = self.raw.ptr
+        nf = self.ctx.semantic_split_device(labelled_ptr, n, [b.ptr for b in self.full], self.cap)
         order = ("dynamic", "ground", "building", "pole", "outlier")
         leaf = [FRAME_LEAF[k] for k in order]
         nd = self.ctx.voxel_downsample_multi_device([self.full[k].ptr for k in range(5)], nf, leaf, [self.down[k].ptr for k in range(5)], [self.cap] * 5)
