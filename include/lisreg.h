@@ -626,6 +626,45 @@ int  lisreg_submap_extract(lisreg_ctx* ctx, int pre_id, int cur_id, const float 
 void lisreg_submap_crop_boxes(const double pre_local_bound[6], const float pre_pose[6], const double cur_local_bound[6],
                               const float cur_pose[6], float pad, double isect[6], double isect_local[6]);
 
+/* The global map (visualizeGlobalMapThread: publishGlobalMap, src/node/subMapOptmizationNode.cpp:3553-3574, and the PCD export,
+ * :3502-3514) and every other "these classes of these submaps under these poses" cloud of the reference (the loop-verification target
+ * :2787-2790, the corrected current submap :2906-2912, laserCloudFromPre :1151-1154) as ONE gather over the resident store:
+ *   segment 5 * i + k of the output = class k of map_ids[i] (0 dynamic, 1 pole, 2 ground, 3 building, 4 outlier) moved by poses[i]
+ *   ({roll,pitch,yaw,x,y,z} -> lisreg_pose_to_matrix, the arithmetic of lisreg_transform_cloud bit for bit); segments lie end to end in
+ *   that order (:3560-3571); a class that is masked out or empty is an empty segment.  map_ids may name a map twice; local maps and
+ *   submaps share the id space; which submaps go in (the reference leaves the newest out unless FINISHMAP, :3561-3562) is the caller's list.
+ *   poses == NULL: no arithmetic at all, the records are copied bit for bit (an identity matrix would turn -0.0f into +0.0f).
+ *   The payload word (the label) is copied as bits.  The store is read, never changed.
+ * out_fmt LISREG_FMT_DEVICE: 16-byte lisreg_dpoint records.  LISREG_FMT_XYZIL: 32-byte PointXYZIL structs — x, y, z, the label's low 16
+ *   bits as uint16 at byte 20, zeros everywhere else: the store keeps 16-byte records, so the intensity is not available and reads 0.0f.
+ * out may be DEVICE memory (capacity_points records / structs): the table upload and one kernel launch go on the context's stream
+ *   whatever n_maps is, the call does not wait for the GPU, and later calls of the context are ordered behind it (like
+ *   lisreg_concat_device).  Or HOST memory (anything the runtime does not know as device memory): the cloud is produced chunk_points
+ *   points at a time into two buffers of the context, the copy of one chunk under the kernel of the next, and the call returns when the
+ *   data is in out.  All offsets are 64-bit: a map of a few hundred submaps passes 2^32 bytes.
+ * _gather_count: *n_total = points the gather would write; seg_offsets[n_maps * 5 + 1] (or NULL) = where every segment starts, the last
+ *   entry = *n_total.  _gather: *n_out and seg_offsets the same.
+ * Errors: an id that names no map (never reset, never inserted into) LISREG_ERR_NO_TARGET — a map that was only reset is an empty map; capacity_points too small LISREG_ERR_ARG with *n_out = the need — in both
+ *   cases nothing is written to out; n_maps < 0, NULL params, class_mask bits above 31, an out_fmt other than the two: LISREG_ERR_ARG.
+ *   n_maps == 0 or class_mask == 0: LISREG_OK, 0 points. */
+#define LISREG_CLS_DYNAMIC 1u   /* bit k = class k of the store: 0 dynamic, 1 pole, 2 ground, 3 building, 4 outlier */
+#define LISREG_CLS_POLE 2u
+#define LISREG_CLS_GROUND 4u
+#define LISREG_CLS_BUILDING 8u
+#define LISREG_CLS_OUTLIER 16u
+#define LISREG_CLS_ALL 31u
+typedef struct lisreg_gather_params {
+    unsigned class_mask;    /* LISREG_CLS_ALL = publishGlobalMap; 15 = the verification target of :2787-2790 */
+    int      out_fmt;       /* LISREG_FMT_DEVICE: 16-byte records; LISREG_FMT_XYZIL: 32-byte PointXYZIL structs */
+    int      chunk_points;  /* host destinations only: points per staged chunk, 0 = the library's default */
+} lisreg_gather_params;
+int  lisreg_default_gather_params(lisreg_gather_params* p);      /* 31, LISREG_FMT_DEVICE, 0 */
+int  lisreg_submap_gather_count(lisreg_ctx* ctx, int n_maps, const int* map_ids, unsigned class_mask,
+                                long long* n_total, long long* seg_offsets /* n_maps*5 + 1, or NULL */);
+int  lisreg_submap_gather(lisreg_ctx* ctx, int n_maps, const int* map_ids, const float* poses /* n_maps x 6, or NULL */,
+                          const lisreg_gather_params* params, void* out, long long capacity_points,
+                          long long* n_out, long long* seg_offsets /* or NULL */);
+
 /* The odometry node's target (odomEstimationNode.cpp, USING_MULTI_FRAME_TARGET), device-resident:
  *   _push   = saveKeyFrames (:421-468): the frame's FULL corner / surf feature clouds (host PCL structs or LISREG_FMT_DEVICE records,
  *             sensor frame) are transformPointCloud'ed by `pose` into the map frame and kept; the oldest frames are dropped until at

@@ -204,6 +204,13 @@ struct lisreg_ctx {
     std::vector<lisreg::LocalMap> localmaps;
     std::vector<lisreg::KeyframeRing> keyrings;
     lisreg::DevBuf lm_in, lm_tmp, lm_bbox, exact_trig;
+    // submap gather (lisreg_globalmap.hip): the segment table + matrices of a call, staged in one of two pinned slots (a call does not wait
+    // for the GPU, so the slot of the call before may still be read by its upload: gm_up[s] = the upload out of slot s is through);
+    // host destinations: two chunk buffers, "the kernel into buffer b has run" (on stream), "buffer b has been copied out" (on copy_stream)
+    lisreg::DevBuf    gm_tab, gm_chunk[2];
+    lisreg::PinnedBuf gm_host[2];
+    lisreg::Event     gm_up[2], gm_kernel[2], gm_copied[2];
+    int               gm_flip = 0;
     lisreg::DevBuf map_stage;                          // lisreg_map_index_set_batch: host clouds of a batch, packed, in one upload
     lisreg::DevBuf mp_pts, mp_flag, mp_pos, mp_idx, mp_cnt, mp_d2, mp_out, icp_state, icp_partials, icp_cur, icp_items, map_tab, map_tsegs, map_tblocks;
     lisreg::PinnedBuf done_host;            // one int

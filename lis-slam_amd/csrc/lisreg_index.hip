@@ -1548,17 +1548,7 @@ __device__ __forceinline__ void transform_cloud_point(const float4* __restrict__
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float4 p = in[i];
-    // ((m0 x + m1 y) + m2 z) + m3 with every product and sum rounded on its own, like the reference's x86 build (no FMA
-    // contraction): the transformed clouds feed voxel grids and box crops whose parity bar is exact.  HBM-bound either way.
-    auto row = [&](int r) {
-#pragma clang fp contract(off)
-        const float a = M12[4 * r] * p.x, b = M12[4 * r + 1] * p.y, cc = M12[4 * r + 2] * p.z;
-        const float s1 = a + b;
-        const float s2 = s1 + cc;
-        return s2 + M12[4 * r + 3];
-    };
-    out[i] = make_float4(row(0), row(1), row(2), p.w);
+    out[i] = transform_record(in[i], M12);
 }
 __global__ __launch_bounds__(256) void k_transform_cloud(const float4* __restrict__ in, int n, const float* __restrict__ M12,
                                                          float4* __restrict__ out) { transform_cloud_point(in, n, M12, out); }

@@ -260,6 +260,21 @@ void launch_voxel_centroids(int n, int n_vox, const float4* pts, const uint32_t*
 void launch_pack_cloud(const void* raw_dev, size_t n, int stride, int has_label, float4* out, hipStream_t st);
 void launch_transform_cloud(const float4* in, int n, const float* M12_dev, float4* out, hipStream_t st);
 struct Mat12 { float m[12]; };
+// transformPointCloud of ONE record (src/core/common.cpp:112-173): p' = R p + t, the fourth channel is copied.  Every coordinate is
+// ((m0 x + m1 y) + m2 z) + m3 with every product and sum rounded on its own, like the reference's x86 build (no FMA contraction): the
+// transformed clouds feed voxel grids and box crops whose parity bar is exact.  Shared by k_transform_cloud* (lisreg_index.hip) and the
+// submap gather (lisreg_globalmap.hip), so the per-class path and the one-launch map cannot drift apart.
+__device__ __forceinline__ float4 transform_record(const float4 p, const float* __restrict__ M12)
+{
+    auto row = [&](int r) {
+#pragma clang fp contract(off)
+        const float a = M12[4 * r] * p.x, b = M12[4 * r + 1] * p.y, cc = M12[4 * r + 2] * p.z;
+        const float s1 = a + b;
+        const float s2 = s1 + cc;
+        return s2 + M12[4 * r + 3];
+    };
+    return make_float4(row(0), row(1), row(2), p.w);
+}
 void launch_transform_cloud_m(const float4* in, int n, const float M12_host[12], float4* out, hipStream_t st);   // matrix by value
 // number of consecutive source points further apart than thr (coherence probe for sort_sources = auto)
 void launch_count_jumps(const BlockDesc* blocks, int n_blocks, const Segment* segs, float thr, int* jumps, hipStream_t st);

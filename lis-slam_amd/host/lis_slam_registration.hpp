@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -531,6 +532,21 @@ public:
         if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx));
         return out;
     }
+    // The chosen class clouds of this submap end to end (dynamic, pole, ground, building, outlier: LISREG_CLS_*), transformPointCloud'ed by
+    // `pose` (nullptr: as they are, in the submap's own frame), as one host cloud out of one launch: the loop-verification target
+    // (subMapOptmizationNode.cpp:2787-2790 = merged(15, nullptr, ..)), laserCloudFromPre (:1151-1154 = merged(LISREG_CLS_POLE,
+    // submap_pose_6D_optimized, ..)).  The store keeps no intensity: it reads 0.
+    void merged(unsigned class_mask, const float* pose, PointCloud<PointXYZIL>& out) const {
+        lisreg_gather_params gp;
+        lisreg_default_gather_params(&gp);
+        gp.class_mask = class_mask; gp.out_fmt = LISREG_FMT_XYZIL;
+        long long n = 0;
+        int rc = lisreg_submap_gather_count(ctx_, 1, &id_, class_mask, &n, nullptr);
+        if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_));
+        out.points.resize((size_t)n);
+        rc = lisreg_submap_gather(ctx_, 1, &id_, pose, &gp, out.points.data(), n, &n, nullptr);
+        if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_));
+    }
 private:
     void insert(const PointCloud<PointT> down[5], const float* rel) {
         const void* ptr[5]; int n[5];
@@ -542,6 +558,30 @@ private:
     lisreg_ctx* ctx_;
     int id_;
 };
+
+// publishGlobalMap() (subMapOptmizationNode.cpp:3553-3574) and, with finishMap = true, the map of the PCD export (:3502-3514): every submap
+// of subMapInfo in id order — all but the newest unless finishMap (FINISHMAP, :3561-3562) — its five class clouds under its
+// submap_pose_6D_optimized, concatenated.  One gather over the resident submaps, whatever their number; after a loop closure has moved
+// the poses the same call rebuilds the whole map.
+inline void publishGlobalMap(lisreg_ctx* ctx, const std::map<int, SubMap<>*>& subMapInfo, bool finishMap, PointCloud<PointXYZIL>& globalMapCloud) {
+    std::vector<int> ids;
+    std::vector<float> poses;
+    for (auto it = subMapInfo.begin(); it != subMapInfo.end(); ++it) {
+        auto itEnd = subMapInfo.end(); --itEnd;
+        if (!finishMap && it == itEnd) continue;
+        ids.push_back(it->second->id());
+        poses.insert(poses.end(), it->second->submap_pose_6D_optimized, it->second->submap_pose_6D_optimized + 6);
+    }
+    lisreg_gather_params gp;
+    lisreg_default_gather_params(&gp);
+    gp.out_fmt = LISREG_FMT_XYZIL;
+    long long n = 0;
+    int rc = lisreg_submap_gather_count(ctx, (int)ids.size(), ids.data(), gp.class_mask, &n, nullptr);
+    if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx));
+    globalMapCloud.points.resize((size_t)n);
+    rc = lisreg_submap_gather(ctx, (int)ids.size(), ids.data(), poses.data(), &gp, globalMapCloud.points.data(), n, &n, nullptr);
+    if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx));
+}
 
 // The odometry node's multi-frame target (odomEstimationNode.cpp, USING_MULTI_FRAME_TARGET), device-resident: replaces
 // laserCloud{Corner,Surf}Vec + the concatenation loop + the two VoxelGrid filters of laserCloudInfoHandler (:185-207) and the

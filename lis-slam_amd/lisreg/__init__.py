@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "lisreg_map_index_set", "lisreg_map_index_set_batch", "lisreg_nearest", "lisreg_dynamic_filter", "lisreg_bbx_filter", "lisreg_cloud_bounds",
     "lisreg_localmap_default_params", "lisreg_localmap_reset", "lisreg_localmap_insert", "lisreg_localmap_extract",
     "lisreg_localmap_get", "lisreg_predict_pose", "lisreg_guess_state_init", "lisreg_update_initial_guess", "lisreg_submap_insert", "lisreg_submap_extract", "lisreg_submap_crop_boxes",
+    "lisreg_default_gather_params", "lisreg_submap_gather_count", "lisreg_submap_gather",
     "lisreg_icp_default_params", "lisreg_icp_align", "lisreg_icp_align_batch", "lisreg_icp_gn_match",
     "lisreg_loopdet_default_params", "lisreg_loopdet_reset", "lisreg_loopdet_detect", "lisreg_loopdet_candidates",
     "lisreg_loopdet_get", "lisreg_loop_descriptor",
@@ -224,6 +225,11 @@ class SubmapExtractOut(C.Structure):
 
 
 LOCALMAP_CLASSES = ("dynamic", "pole", "ground", "building", "outlier")      # class order of localMap_t (subMap.h:742-753)
+CLS_DYNAMIC, CLS_POLE, CLS_GROUND, CLS_BUILDING, CLS_OUTLIER, CLS_ALL = 1, 2, 4, 8, 16, 31      # bit k = class k (lisreg_submap_gather)
+
+
+class GatherParams(C.Structure):
+    _fields_ = [("class_mask", C.c_uint), ("out_fmt", C.c_int), ("chunk_points", C.c_int)]
 
 
 class FeatureParams(C.Structure):
@@ -374,6 +380,10 @@ def lib():
         L.lisreg_submap_extract.argtypes = [vp, C.c_int, C.c_int, fp, fp, C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(SubmapExtractOut)]
         L.lisreg_submap_crop_boxes.argtypes = [C.POINTER(C.c_double), fp, C.POINTER(C.c_double), fp, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.lisreg_submap_crop_boxes.restype = None
+        llp = C.POINTER(C.c_longlong)
+        L.lisreg_default_gather_params.argtypes = [C.POINTER(GatherParams)]
+        L.lisreg_submap_gather_count.argtypes = [vp, C.c_int, ip, C.c_uint, llp, llp]
+        L.lisreg_submap_gather.argtypes = [vp, C.c_int, ip, fp, C.POINTER(GatherParams), vp, C.c_longlong, llp, llp]
         L.lisreg_predict_pose.argtypes = [fp, fp, fp]
         L.lisreg_predict_pose.restype = None
         L.lisreg_guess_state_init.argtypes = [C.POINTER(GuessState)]
@@ -1013,6 +1023,65 @@ class Context:
         return dict(isect=np.array(out.isect[:], np.float64), isect_local=np.array(out.isect_local[:], np.float64),
                     n_target_corner=out.n_target_corner, n_target_surf=out.n_target_surf,
                     src_corner_ptr=out.src_corner or 0, n_src_corner=out.n_src_corner, src_surf_ptr=out.src_surf or 0, n_src_surf=out.n_src_surf)
+
+    def submap_insert_device(self, map_id: int, ptrs, counts, relative_pose, submap_pose, params: LocalMapParams) -> dict:
+        """submap_insert for five clouds of device records (payload = label bits); relative_pose None = fisrt_submap."""
+        p = (C.c_void_p * 5)(*[C.c_void_p(int(x)) if c else None for x, c in zip(ptrs, counts)])
+        cnt = (C.c_int * 5)(*[int(x) for x in counts])
+        Tr = None if relative_pose is None else np.ascontiguousarray(relative_pose, np.float32)
+        Ts = np.ascontiguousarray(submap_pose, np.float32)
+        info = SubmapInfo()
+        fp = C.POINTER(C.c_float)
+        self._chk(self._L.lisreg_submap_insert(self._h, map_id, p, cnt, 16, FMT_DEVICE, Tr.ctypes.data_as(fp) if Tr is not None else None,
+                                               Ts.ctypes.data_as(fp), C.byref(params), C.byref(info)))
+        return dict(n=list(info.n), feature_point_num=info.feature_point_num, local_bound=np.array(info.local_bound[:], np.float64),
+                    bound=np.array(info.bound[:], np.float64))
+
+    # -- the global map: chosen classes of a list of resident submaps, each under its own pose, as one cloud ------------------------
+    @staticmethod
+    def _gather_list(map_ids, poses):
+        ids = np.ascontiguousarray(map_ids, np.int32).ravel()
+        T = None
+        if poses is not None:
+            T = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+            if len(T) != len(ids):
+                raise ValueError("submap_gather: one pose per listed map")
+        return ids, T
+
+    def submap_gather_count(self, map_ids, class_mask: int = CLS_ALL):
+        """(points the gather would write, int64 segment starts [len(map_ids) * 5 + 1]); segment 5 * i + k = class k of map_ids[i]."""
+        ids, _ = self._gather_list(map_ids, None)
+        n = C.c_longlong(0)
+        off = np.zeros(len(ids) * 5 + 1, np.int64)
+        self._chk(self._L.lisreg_submap_gather_count(self._h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int)), class_mask, C.byref(n),
+                                                     off.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return n.value, off
+
+    def submap_gather_device(self, map_ids, poses, out_ptr: int, capacity_points: int, class_mask: int = CLS_ALL, out_fmt: int = FMT_DEVICE,
+                             chunk_points: int = 0):
+        """The gather into caller memory (a device pointer: one launch on the context's stream, not waited for; a host address: chunked,
+        complete on return).  poses: [len(map_ids), 6] or None (records copied bit for bit).  Returns (points written, segment starts)."""
+        ids, T = self._gather_list(map_ids, poses)
+        prm = GatherParams(class_mask, out_fmt, chunk_points)
+        n = C.c_longlong(0)
+        off = np.zeros(len(ids) * 5 + 1, np.int64)
+        self._chk(self._L.lisreg_submap_gather(self._h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int)),
+                                               T.ctypes.data_as(C.POINTER(C.c_float)) if T is not None else None, C.byref(prm),
+                                               C.c_void_p(int(out_ptr)) if out_ptr else None, capacity_points, C.byref(n),
+                                               off.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return n.value, off
+
+    def submap_gather(self, map_ids, poses=None, class_mask: int = CLS_ALL, out_fmt: int = FMT_DEVICE, chunk_points: int = 0):
+        """The gather into a new host array: [n, 4] float32 records (x, y, z, label bits) for FMT_DEVICE, 32-byte PointXYZIL structs
+        (intensity 0) for FMT_XYZIL.  Returns (cloud, segment starts)."""
+        n, _ = self.submap_gather_count(map_ids, class_mask)
+        if out_fmt == FMT_XYZIL:
+            from .synth import PCL_DTYPE
+            out = np.zeros(max(n, 1), PCL_DTYPE)
+        else:
+            out = np.zeros((max(n, 1), 4), np.float32)
+        m, off = self.submap_gather_device(map_ids, poses, out.ctypes.data, n, class_mask, out_fmt, chunk_points)
+        return out[:m], off
 
     def localmap_get(self, map_id: int, cls: int) -> np.ndarray:
         """[n, 4] float32 records (x, y, z, label bits) of class cls (0-4) or of the corner / surf target (5 / 6)."""
