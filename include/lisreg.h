@@ -124,7 +124,24 @@ int  lisreg_device_count(void);                                   /* number of v
 int  lisreg_create(int device, lisreg_ctx** out);                 /* one context per caller thread (§8b Callers) */
 void lisreg_destroy(lisreg_ctx* ctx);
 const char* lisreg_last_error(const lisreg_ctx* ctx);             /* never NULL                                 */
-/* Use an existing HIP stream (e.g. the caller's); NULL restores the context's own stream. */
+/* Use an existing HIP stream (e.g. the caller's); NULL restores the context's own stream.  The switch drains the stream in use
+ * before: a call on the new stream sees what was queued on the old one.  A caller's stream may be destroyed once it is no longer set.
+ * Streams (pinned by tests/test_caller_stream.py, on a stream that is still busy producing the input when the call is made):
+ *   - Every entry point reads its device inputs and writes its device outputs in the order of the context's stream, side streams of
+ *     the library (interleaved halves, the strip build, the feeder's uploads) forking from and joining it: an input another
+ *     operation of that stream is still producing needs no host synchronisation in front of the call, an output is ready for the next
+ *     operation queued on that stream behind it.  Work the caller puts on ANY other stream is not ordered against the library.
+ *   - Without waiting for the GPU return lisreg_batch_run, lisreg_concat_device, lisreg_submap_gather into device memory and
+ *     lisreg_set_option("count_searches") (its zeroing goes behind a run still queued: counters belong to whole runs).
+ *     lisreg_batch_prepare and lisreg_stage_host_items may wait (for a staging buffer of theirs whose copy is still queued); several
+ *     prepare / run pairs, gathers or sweep batches queued behind one another each keep their own tables.  Every other entry point
+ *     returns with its outputs complete (it hands counts or poses back to the host).
+ *   - The library orders by itself what it owns: its device copy of a HOST target (lisreg_set_target* from host memory lands behind a
+ *     run still queued against that slot — that run registers against the old cloud, also when it rebuilds its targets), the submap
+ *     store (lisreg_submap_insert lands behind a gather still queued) and the search counters.
+ *   - The caller's duty: device records the library only REFERENCES — a LISREG_FMT_DEVICE target or map index, the device sources of
+ *     a prepared batch — must not be overwritten (other than in the order of the context's stream) or freed while a run that reads
+ *     them is queued; with "rebuild_targets_each_run" every run re-reads the target's records. */
 int  lisreg_set_stream(lisreg_ctx* ctx, void* hip_stream);
 void* lisreg_get_stream(const lisreg_ctx* ctx);
 

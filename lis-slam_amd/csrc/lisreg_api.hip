@@ -517,7 +517,12 @@ static int set_target_impl(lisreg_ctx* c, int slot, const void* clouds[2], const
                 for (int d = 0; d < 3; ++d) { bb[d] = std::min(bb[d], v[d]); bb[3 + d] = std::max(bb[3 + d], v[d]); }
             }
             HIPCHK(c, t.raw[k].ensure(sizeof(float4) * (size_t)std::max(n, 1)));
-            if (n > 0) HIPCHK(c, hipMemcpy(t.raw[k].p, h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice));
+            // on the context's stream: a run still queued there against this slot (it may re-read the raw records) reads the old
+            // cloud; the null stream would order nothing against it
+            if (n > 0) {
+                HIPCHK(c, hipMemcpyAsync(t.raw[k].p, h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));     // h is a local
+            }
             t.raw_external[k] = false;
             t.raw_ptr[k] = t.raw[k].as<float4>();
         }
@@ -1215,7 +1220,7 @@ int lisreg_set_option(lisreg_ctx* c, const char* name, int value)
     if (!strcmp(name, "index_strip_cap")) { c->strip_cap = std::min(std::max(value, 64), 16384); c->prepared = false; return LISREG_OK; }
     if (!strcmp(name, "count_searches")) {
         c->count_searches = value != 0;
-        if (c->count_searches) { HIPCHK(c, c->counters.ensure(128 * 8)); HIPCHK(c, hipMemset(c->counters.p, 0, 128 * 8)); }
+        if (c->count_searches) { HIPCHK(c, c->counters.ensure(128 * 8)); HIPCHK(c, hipMemsetAsync(c->counters.p, 0, 128 * 8, c->stream)); }   // behind a counting run still queued
         return LISREG_OK;
     }
     if (!strcmp(name, "lanes_per_query")) { c->lanes_per_query_auto = value != 1; c->prepared = false; return LISREG_OK; }   // 1 forces one lane per query, anything else = auto

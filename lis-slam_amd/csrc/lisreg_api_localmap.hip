@@ -484,7 +484,10 @@ int lisreg_localmap_get(lisreg_ctx* c, int map_id, int cls, void* out, int capac
     if (n > capacity) return bad(c, "localmap_get: capacity too small (see *n_out)");
     if (n > 0 && !out) return bad(c, "localmap_get: NULL out");
     HIPCHK(c, hipSetDevice(c->device));
-    if (n > 0) HIPCHK(c, hipMemcpy(out, src, sizeof(float4) * (size_t)n, hipMemcpyDefault));      // host or device destination
+    if (n > 0) {                                     // host or device destination; behind whatever the stream still writes into the store
+        HIPCHK(c, hipMemcpyAsync(out, src, sizeof(float4) * (size_t)n, hipMemcpyDefault, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     return LISREG_OK;
 }
 

@@ -104,7 +104,10 @@ int lisreg_map_index_set(lisreg_ctx* c, int slot, const void* cloud, int n, int 
         std::vector<lisreg_dpoint> h((size_t)std::max(n, 1));
         pack_cloud(cloud, n, stride, fmt, h.data());
         HIPCHK(c, m.raw.ensure(sizeof(float4) * (size_t)std::max(n, 1)));
-        if (n > 0) HIPCHK(c, hipMemcpy(m.raw.p, h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice));
+        if (n > 0) {                                  // behind whatever still searches this slot on the context's stream
+            HIPCHK(c, hipMemcpyAsync(m.raw.p, h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipStreamSynchronize(st));      // h is a local
+        }
         m.raw_ptr = m.raw.as<float4>();
     }
     if (n > 0) {
@@ -162,7 +165,10 @@ int lisreg_map_index_set_batch(lisreg_ctx* c, int n_maps, const int* slots, cons
         long long off = 0;
         for (int k = 0; k < n_maps; ++k) { pack_cloud(clouds[k], counts[k], stride, fmt, h.data() + off); off += counts[k]; }
         HIPCHK(c, c->map_stage.ensure(sizeof(float4) * (size_t)std::max<long long>(total, 1)));
-        if (total > 0) HIPCHK(c, hipMemcpy(c->map_stage.p, h.data(), sizeof(float4) * (size_t)total, hipMemcpyHostToDevice));
+        if (total > 0) {
+            HIPCHK(c, hipMemcpyAsync(c->map_stage.p, h.data(), sizeof(float4) * (size_t)total, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipStreamSynchronize(st));      // h is a local
+        }
         off = 0;
         for (int k = 0; k < n_maps; ++k) { src[(size_t)k] = c->map_stage.as<float4>() + off; off += counts[k]; }
     }
