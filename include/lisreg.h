@@ -35,7 +35,7 @@ extern "C" {
 /* ---- status codes (error conventions: SURVEY.md §8b "Error conventions") -------------------------------- */
 #define LISREG_OK                        0
 #define LISREG_NOT_ENOUGH_FEATURES       1   /* guard at odomEstimationNode.cpp:598,623-625 failed: T untouched */
-#define LISREG_TOO_FEW_CORRESPONDENCES   2   /* every iteration hit the `< 50` early return (:870-872): T untouched */
+#define LISREG_TOO_FEW_CORRESPONDENCES   2   /* every iteration hit the `< 50` early return (:870-872): no step, but transformUpdate (:622) still ran on T */
 #define LISREG_LEAF_TOO_SMALL            3   /* VoxelGrid: dx*dy*dz overflows int32 — PCL warns and copies the input  */
 #define LISREG_ERR_ARG                  -1
 #define LISREG_ERR_HIP                  -2
@@ -313,6 +313,26 @@ int  lisreg_get_neighbors(lisreg_ctx* ctx, int* out, int n_elems);
  * direction (NaN = lambda-ratio test failed), coeff x, y, z, intensity (:729-732), accepted (:734). */
 int  lisreg_test_fit_models(lisreg_ctx* ctx, int kind, int n, const float* neighbours, const float* queries,
                             const lisreg_params* params, int exact, float* out);
+
+/* Test hook: the production Gauss-Newton step kernels (the fixed-order fp64 row sum, cv::solve, the iteration-0 degeneracy analysis,
+ * the projection, the convergence test; then transformUpdate) on caller-given normal equations — n_items independent registrations
+ * of one workgroup each, in buffers of the call's own (a prepared batch of the context is untouched): the registrations are reset, the
+ * solve kernel runs n_steps (1 .. 64) times, then the finalize kernel, all on the context's stream; returns with the outputs complete.
+ *   n_rows[n_items]          partial rows of every item; the items' rows lie back to back in item order (R = their sum)
+ *   rows[n_steps][R][28]     per step, the 28 doubles of every row: 21 upper-triangle AtA (row-major), 6 AtB, 1 count
+ *   T_init[n_items][6], degenerate_in[n_items] (NULL: 0), n_sc / n_ss[n_items] (source sizes for the feature-count guard; NULL:
+ *   the guard passes), imu[n_items] (NULL: none available), params as for lisreg_batch_prepare
+ *   trace_out[n_items][n_steps][LISREG_TRACE_STRIDE]   the trace records (zeros where an item was finished already)
+ *   state_out[n_items][n_steps][LISREG_SOLVE_STATE_STRIDE]   (indexed like trace_out) the registration in device memory after that step:
+ *       [0..35] matP  [36..47] the 3 x 4 pose matrix of the next correspondence launch  [48] isDegenerate  [49] deltaR  [50] deltaT
+ *       [51] n_corr  [52] 1 if finished  [53] iterCount to report  [54] 1 if any step solved  [55] steps started
+ *   results_out[n_items][12] the result block after finalize: T[6], iters, deltaR, deltaT, degenerate, n_corr_last, status
+ * Any output may be NULL. */
+#define LISREG_SOLVE_STATE_STRIDE 56
+int  lisreg_test_solve_steps(lisreg_ctx* ctx, int n_items, int n_steps, const int* n_rows, const double* rows,
+                             const float* T_init, const int* degenerate_in, const int* n_sc, const int* n_ss,
+                             const lisreg_imu* imu, const lisreg_params* params,
+                             float* trace_out, float* state_out, float* results_out);
 
 /* Diagnostics (tests): the search index of target `slot`, kind 0 = corner / 1 = surf, as it stands in HBM after the work queued on
  * the context's stream: dims = {n, nx, ny, nz, n_cells}, geom = {ox, oy, oz, cell edge}, the cell-sorted records

@@ -1558,6 +1558,73 @@ int lisreg_test_fit_models(lisreg_ctx* c, int kind, int n, const float* neighbou
     return LISREG_OK;
 }
 
+int lisreg_test_solve_steps(lisreg_ctx* c, int n_items, int n_steps, const int* n_rows, const double* rows, const float* T_init,
+                            const int* degenerate_in, const int* n_sc, const int* n_ss, const lisreg_imu* imu,
+                            const lisreg_params* params, float* trace_out, float* state_out, float* results_out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (n_items < 0 || n_steps < 1 || n_steps > 64 || !params || (n_items > 0 && (!n_rows || !T_init)))
+        return fail(c, LISREG_ERR_ARG, "test_solve_steps: bad arguments");
+    if (n_items == 0) return LISREG_OK;
+    size_t total_rows = 0;
+    for (int i = 0; i < n_items; ++i) {
+        if (n_rows[i] < 0) return fail(c, LISREG_ERR_ARG, "test_solve_steps: negative row count");
+        total_rows += (size_t)n_rows[i];
+    }
+    if (total_rows > 0x7fffffffu || (total_rows > 0 && !rows)) return fail(c, LISREG_ERR_ARG, "test_solve_steps: bad rows");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_items;
+    DevParams prm = make_dev_params(*params);
+    std::vector<ItemState> h_items(n);
+    memset(h_items.data(), 0, sizeof(ItemState) * n);
+    int blk = 0;
+    prm.n_guard_failed = 0;
+    for (size_t i = 0; i < n; ++i) {
+        ItemState& it = h_items[i];
+        for (int k = 0; k < 6; ++k) it.T_init[k] = T_init[6 * i + k];
+        it.degenerate_in = degenerate_in ? degenerate_in[i] : 0;
+        it.blk_begin = blk; it.blk_count = n_rows[i]; blk += n_rows[i];
+        it.n_sc = n_sc ? n_sc[i] : prm.edge_min + 1;
+        it.n_ss = n_ss ? n_ss[i] : prm.surf_min + 1;
+        if (imu) it.imu = imu[i];
+        if (!(it.n_sc > prm.edge_min && it.n_ss > prm.surf_min)) ++prm.n_guard_failed;
+    }
+    const size_t step_doubles = total_rows * kNumAcc, trace_floats = n * (size_t)n_steps * kTraceStride;
+    DevBuf d_items, d_rows, d_trace, d_results, d_done;
+    HIPCHK(c, d_items.ensure(sizeof(ItemState) * n));
+    HIPCHK(c, d_rows.ensure(sizeof(double) * std::max<size_t>(step_doubles * (size_t)n_steps, 1)));
+    HIPCHK(c, d_trace.ensure(sizeof(float) * trace_floats));
+    HIPCHK(c, d_results.ensure(sizeof(float) * kResultSize * n));
+    HIPCHK(c, d_done.ensure(sizeof(int)));
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_items.p, h_items.data(), sizeof(ItemState) * n, hipMemcpyHostToDevice, st));
+    if (step_doubles) HIPCHK(c, hipMemcpyAsync(d_rows.p, rows, sizeof(double) * step_doubles * (size_t)n_steps, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(d_trace.p, 0, sizeof(float) * trace_floats, st));
+    launch_reset_items(d_items.as<ItemState>(), n_items, prm, d_done.as<int>(), st);
+    for (int s = 0; s < n_steps; ++s) {
+        launch_solve(d_items.as<ItemState>(), n_items, prm, d_rows.as<double>() + step_doubles * (size_t)s, d_trace.as<float>(), n_steps,
+                     d_done.as<int>(), st);
+        HIPCHK(c, hipGetLastError());
+        if (!state_out) continue;
+        HIPCHK(c, hipMemcpyAsync(h_items.data(), d_items.p, sizeof(ItemState) * n, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        for (size_t i = 0; i < n; ++i) {
+            const ItemState& it = h_items[i];
+            float* o = state_out + (i * (size_t)n_steps + (size_t)s) * LISREG_SOLVE_STATE_STRIDE;
+            for (int k = 0; k < 36; ++k) o[k] = it.P[k];
+            for (int k = 0; k < 12; ++k) o[36 + k] = it.M[k];
+            o[48] = (float)it.degenerate; o[49] = it.deltaR; o[50] = it.deltaT; o[51] = (float)it.n_corr;
+            o[52] = (float)it.done; o[53] = (float)it.iters_out; o[54] = (float)it.any_solved; o[55] = (float)it.iter;
+        }
+    }
+    launch_finalize(d_items.as<ItemState>(), n_items, prm, d_results.as<float>(), st);
+    HIPCHK(c, hipGetLastError());
+    if (trace_out) HIPCHK(c, hipMemcpyAsync(trace_out, d_trace.p, sizeof(float) * trace_floats, hipMemcpyDeviceToHost, st));
+    if (results_out) HIPCHK(c, hipMemcpyAsync(results_out, d_results.p, sizeof(float) * kResultSize * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return LISREG_OK;
+}
+
 int lisreg_set_profiling(lisreg_ctx* c, int enable)
 {
     if (!c) return LISREG_ERR_ARG;

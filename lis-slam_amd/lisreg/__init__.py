@@ -23,13 +23,14 @@ FMT_XYZI, FMT_XYZIL, FMT_DEVICE, FMT_XYZIRT, FMT_DEVICE_XYZI, FMT_XYZI_PACKED = 
 VARIANT_ODOM, VARIANT_KEYFRAME, VARIANT_SUBMAP = 1, 2, 3
 TRACE_STRIDE = 56
 RESULT_SIZE = 12
+SOLVE_STATE_STRIDE = 56
 
 # every symbol include/lisreg.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "lisreg_device_count", "lisreg_create", "lisreg_destroy", "lisreg_last_error", "lisreg_set_stream",
     "lisreg_get_stream", "lisreg_default_params", "lisreg_set_target", "lisreg_set_target_slot",
     "lisreg_target_from_classes", "lisreg_align", "lisreg_align_batch", "lisreg_batch_prepare", "lisreg_batch_run",
-    "lisreg_batch_fetch", "lisreg_stage_host_items", "lisreg_upload_cloud", "lisreg_concat_device", "lisreg_batch_result_device", "lisreg_set_option", "lisreg_get_option", "lisreg_get_counters", "lisreg_get_neighbors", "lisreg_test_fit_models", "lisreg_get_target_index", "lisreg_get_target_graph", "lisreg_get_target_cell_rows", "lisreg_keyframes_reset", "lisreg_keyframes_push", "lisreg_keyframes_target", "lisreg_get_trace",
+    "lisreg_batch_fetch", "lisreg_stage_host_items", "lisreg_upload_cloud", "lisreg_concat_device", "lisreg_batch_result_device", "lisreg_set_option", "lisreg_get_option", "lisreg_get_counters", "lisreg_get_neighbors", "lisreg_test_fit_models", "lisreg_test_solve_steps", "lisreg_get_target_index", "lisreg_get_target_graph", "lisreg_get_target_cell_rows", "lisreg_keyframes_reset", "lisreg_keyframes_push", "lisreg_keyframes_target", "lisreg_get_trace",
     "lisreg_set_profiling", "lisreg_get_timing", "lisreg_pose_to_matrix", "lisreg_transform_update",
     "lisreg_comm_unique_id", "lisreg_comm_init", "lisreg_gather_results", "lisreg_comm_destroy",
     "lisreg_voxel_downsample", "lisreg_voxel_downsample_multi", "lisreg_transform_cloud",
@@ -318,6 +319,7 @@ def lib():
         L.lisreg_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int)]
         L.lisreg_get_neighbors.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
         if hasattr(L, "lisreg_test_fit_models"): L.lisreg_test_fit_models.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Params), C.c_int, C.POINTER(C.c_float)]
+        if hasattr(L, "lisreg_test_solve_steps"): L.lisreg_test_solve_steps.argtypes = [vp, C.c_int, C.c_int, ip, C.POINTER(C.c_double), fp, ip, ip, ip, C.POINTER(Imu), C.POINTER(Params), fp, fp, fp]
         L.lisreg_get_target_index.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.lisreg_get_target_graph.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]
         L.lisreg_get_target_cell_rows.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
@@ -556,6 +558,34 @@ class Context:
         self._chk(self._L.lisreg_test_fit_models(self._h, int(kind), nb.shape[0], nb.ctypes.data_as(fp), q.ctypes.data_as(fp), C.byref(params),
                                                  1 if exact else 0, out.ctypes.data_as(fp)))
         return out
+
+    def test_solve_steps(self, n_rows, rows, T_init, params, degenerate_in=None, n_sc=None, n_ss=None, imu=None) -> dict:
+        """Test hook (lisreg_test_solve_steps): the production solve / finalize kernels on caller-given normal equations.  n_rows[n]:
+        partial rows per item (back to back); rows[n_steps, sum(n_rows), 28] float64; T_init[n, 6]; imu: a list of Imu (or None per
+        item).  Returns dict(trace[n, n_steps, 56], state[n, n_steps, 56], results[n, 12]) as include/lisreg.h describes."""
+        n_rows = np.ascontiguousarray(n_rows, np.int32).ravel()
+        n = len(n_rows); total = int(n_rows.sum())
+        rows = np.ascontiguousarray(rows, np.float64)
+        assert rows.ndim == 3 and rows.shape[1:] == (total, 28), rows.shape
+        n_steps = rows.shape[0]
+        T0 = np.ascontiguousarray(T_init, np.float32).reshape(n, 6)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        opt = lambda a: None if a is None else np.ascontiguousarray(a, np.int32).reshape(n)
+        deg, sc, ss = opt(degenerate_in), opt(n_sc), opt(n_ss)
+        iptr = lambda a: None if a is None else a.ctypes.data_as(ip)
+        imu_arr = None
+        if imu is not None:
+            imu_arr = (Imu * max(n, 1))()
+            for i, m in enumerate(imu):
+                if m is not None:
+                    imu_arr[i] = m
+        trace = np.zeros((n, n_steps, TRACE_STRIDE), np.float32)
+        state = np.zeros((n, n_steps, SOLVE_STATE_STRIDE), np.float32)
+        results = np.zeros((n, RESULT_SIZE), np.float32)
+        self._chk(self._L.lisreg_test_solve_steps(self._h, n, n_steps, n_rows.ctypes.data_as(ip), rows.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  T0.ctypes.data_as(fp), iptr(deg), iptr(sc), iptr(ss), imu_arr, C.byref(params),
+                                                  trace.ctypes.data_as(fp), state.ctypes.data_as(fp), results.ctypes.data_as(fp)))
+        return dict(trace=trace, state=state, results=results)
 
     def front_end(self) -> int:
         """search front-end of the prepared batch (1 cell walk, 3 k-NN graph scan, ...)."""

@@ -212,6 +212,37 @@ def make_plane_case(n_tgt=6000, n_src=1500, seed=5, half=8.0, trans=0.2, rot_deg
                 T_init=T0, T_true=T_true.astype(np.float32))
 
 
+def make_corridor_case(angle=0.6, length=15.0, floor=True, tilt=(0.0, 0.0), n_tgt=8000, n_src=2000, seed=11, trans=0.2, rot_deg=1.0):
+    """Degenerate scene whose unobservable direction is OBLIQUE to the coordinate axes: a corridor — two parallel walls 4 m apart and
+    3 m high, `length` metres to either side of the origin, optionally a floor, 1 cm of noise — rotated about z by `angle`, so that the
+    slide along it mixes x and y (make_plane_case's null space is exactly x, y, yaw).  Without the floor z is unobservable too.
+    tilt = (roll, pitch) of the sensor: T_true = (roll, pitch, 0.7, 0.3, -0.2, 1.2).  Sources are world points moved into the
+    sensor frame, as in make_plane_case; all points are planar features."""
+    rng = np.random.default_rng(seed)
+
+    def surfaces(n, half_len):
+        a_wall, a_floor = 2 * half_len * 3.0, (2 * half_len * 4.0 if floor else 0.0)
+        which = rng.choice(3, n, p=np.array([a_wall, a_wall, a_floor]) / (2 * a_wall + a_floor))
+        u = rng.uniform(-half_len, half_len, n)
+        y = np.where(which == 0, 2.0, np.where(which == 1, -2.0, rng.uniform(-2.0, 2.0, n)))
+        z = np.where(which == 2, 0.0, rng.uniform(0.0, 3.0, n))
+        nrm = np.where((which == 2)[:, None], [0.0, 0.0, 1.0], [0.0, 1.0, 0.0])
+        p = np.stack([u, y, z], 1) + rng.normal(0, 0.01, n)[:, None] * nrm
+        ca, sa = np.cos(angle), np.sin(angle)
+        return p @ np.array([[ca, sa, 0.0], [-sa, ca, 0.0], [0.0, 0.0, 1.0]])          # rows rotated about z by `angle`
+
+    tgt = surfaces(n_tgt, length)
+    world = surfaces(n_src, length - 2.0)
+    T_true = np.array([tilt[0], tilt[1], 0.7, 0.3, -0.2, 1.2])
+    M = pose_matrix(T_true)
+    src = (world - M[:3, 3]) @ M[:3, :3]            # sensor frame: R^T (p - t)
+    T0 = perturb_pose(T_true, rng, trans, rot_deg)
+    empty = to_pcl(np.zeros((0, 3), np.float32), np.zeros(0, np.uint16))
+    return dict(tgt_corner=empty, tgt_surf=to_pcl(tgt.astype(np.float32), np.zeros(n_tgt, np.uint16)),
+                src_corner=empty, src_surf=to_pcl(src.astype(np.float32), np.zeros(n_src, np.uint16)),
+                T_init=T0, T_true=T_true.astype(np.float32))
+
+
 # PointXYZIRT (src/include/common.h:12-23): x y z pad intensity, uint16 ring @20, float time @24; 32 bytes
 XYZIRT_DTYPE = np.dtype({"names": ["x", "y", "z", "intensity", "ring", "time"],
                          "formats": ["<f4", "<f4", "<f4", "<f4", "<u2", "<f4"],

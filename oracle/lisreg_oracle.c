@@ -668,6 +668,49 @@ void orc_stage_coeffs(int kind, const void* tgt, int n_t, const void* src, int n
 /* ------------------------------------------------------------------------------------------------------- */
 /* scan2SubMapOptimization (odomEstimationNode.cpp:596-626) and LMOptimization (:852-974)                    */
 /* ------------------------------------------------------------------------------------------------------- */
+/* LMOptimization from the normal equations on (:870-872, :921-973): the `< 50` no-op, cv::solve, the iteration-0
+ * degeneracy analysis, the projection (incl. the local-matP shadowing quirk), the pose update and the step norms. */
+int orc_lm_step(const float AtA[36], const float AtB[6], int n_sel, int iter, const lisreg_params* p,
+                float T[6], float P[36], int* isDegenerate, float X[6], float* deltaR, float* deltaT, int* conv)
+{
+    if (n_sel < p->min_corr) return 0;                         /* :870-872 return false, pose untouched */
+    int isDeg = *isDegenerate;
+    orc_solve6(AtA, AtB, X);                                   /* :921 */
+    if (iter == 0) {                                           /* :923-946 */
+        float E[6], V[36], V2[36], Vi[36];
+        orc_eigen_sym(AtA, 6, E, V);
+        memcpy(V2, V, sizeof V2);
+        isDeg = 0;
+        for (int i = 5; i >= 0; --i) {
+            if (E[i] < p->eig_thresh) { for (int j = 0; j < 6; ++j) V2[6 * i + j] = 0; isDeg = 1; }
+            else break;
+        }
+        orc_inv6(V, Vi);
+        for (int r = 0; r < 6; ++r) for (int c = 0; c < 6; ++c) {
+            double s = 0; for (int k = 0; k < 6; ++k) s += (double)Vi[6 * r + k] * (double)V2[6 * k + c];
+            P[6 * r + c] = (float)s;
+        }
+    } else if (p->emulate_matp_shadow) {
+        memset(P, 0, sizeof(float) * 36);                      /* local cv::Mat matP zero-initialised :880 */
+    }
+    if (isDeg) {                                               /* :948-953 */
+        float X2[6]; memcpy(X2, X, sizeof X2);
+        for (int r = 0; r < 6; ++r) {
+            double s = 0; for (int k = 0; k < 6; ++k) s += (double)P[6 * r + k] * (double)X2[k];
+            X[r] = (float)s;
+        }
+    }
+    for (int k = 0; k < 6; ++k) T[k] += X[k];                  /* :955-960 */
+    /* :962-967 — pcl::rad2deg(float) is float; pow(float,int) and the sum are double */
+    double r0 = (double)(X[0] * 57.29578f), r1 = (double)(X[1] * 57.29578f), r2 = (double)(X[2] * 57.29578f);
+    double t0 = (double)(X[3] * 100), t1 = (double)(X[4] * 100), t2 = (double)(X[5] * 100);
+    *deltaR = (float)sqrt(r0 * r0 + r1 * r1 + r2 * r2);
+    *deltaT = (float)sqrt(t0 * t0 + t1 * t1 + t2 * t2);
+    *conv = (*deltaR < p->conv_deg && *deltaT < p->conv_cm);   /* :969-972 */
+    *isDegenerate = isDeg;
+    return 1;
+}
+
 int orc_align(const void* tgt_corner, int n_tc, const void* tgt_surf, int n_ts,
               const void* src_corner, int n_sc, const void* src_surf, int n_ss,
               int stride, int fmt, const lisreg_params* p, const lisreg_imu* imu,
@@ -738,38 +781,8 @@ int orc_align(const void* tgt_corner, int n_tc, const void* tgt_surf, int n_ts,
             double s = 0; for (int i = 0; i < n_sel; ++i) s += (double)A[6 * i + r] * (double)B[i];
             AtB[r] = (float)s;
         }
-        orc_solve6(AtA, AtB, X);                               /* :921 */
-        if (iter == 0) {                                       /* :923-946 */
-            float E[6], V[36], V2[36], Vi[36];
-            orc_eigen_sym(AtA, 6, E, V);
-            memcpy(V2, V, sizeof V2);
-            isDeg = 0;
-            for (int i = 5; i >= 0; --i) {
-                if (E[i] < p->eig_thresh) { for (int j = 0; j < 6; ++j) V2[6 * i + j] = 0; isDeg = 1; }
-                else break;
-            }
-            orc_inv6(V, Vi);
-            for (int r = 0; r < 6; ++r) for (int c = 0; c < 6; ++c) {
-                double s = 0; for (int k = 0; k < 6; ++k) s += (double)Vi[6 * r + k] * (double)V2[6 * k + c];
-                P[6 * r + c] = (float)s;
-            }
-        } else if (p->emulate_matp_shadow) {
-            memset(P, 0, sizeof P);                            /* local cv::Mat matP zero-initialised :880 */
-        }
-        if (isDeg) {                                           /* :948-953 */
-            float X2[6]; memcpy(X2, X, sizeof X2);
-            for (int r = 0; r < 6; ++r) {
-                double s = 0; for (int k = 0; k < 6; ++k) s += (double)P[6 * r + k] * (double)X2[k];
-                X[r] = (float)s;
-            }
-        }
-        for (int k = 0; k < 6; ++k) T[k] += X[k];              /* :955-960 */
-        /* :962-967 — pcl::rad2deg(float) is float; pow(float,int) and the sum are double */
-        double r0 = (double)(X[0] * 57.29578f), r1 = (double)(X[1] * 57.29578f), r2 = (double)(X[2] * 57.29578f);
-        double t0 = (double)(X[3] * 100), t1 = (double)(X[4] * 100), t2 = (double)(X[5] * 100);
-        st.deltaR = (float)sqrt(r0 * r0 + r1 * r1 + r2 * r2);
-        st.deltaT = (float)sqrt(t0 * t0 + t1 * t1 + t2 * t2);
-        int conv = (st.deltaR < p->conv_deg && st.deltaT < p->conv_cm);
+        int conv = 0;
+        orc_lm_step(AtA, AtB, n_sel, iter, p, T, P, &isDeg, X, &st.deltaR, &st.deltaT, &conv);   /* :921-973 */
         if (tr) {
             memcpy(&tr[1], AtA, sizeof AtA); memcpy(&tr[37], AtB, sizeof AtB); memcpy(&tr[43], X, sizeof X);
             memcpy(&tr[49], T, 24); tr[55] = 1.f;

@@ -65,6 +65,13 @@ void orc_jacobian_row(const float T[6], const float ori[3], const float coeff[4]
 /* transformUpdate (odomEstimationNode.cpp:976-1006) */
 void orc_transform_update(const lisreg_params* p, const lisreg_imu* imu, float T[6]);
 
+/* LMOptimization from the normal equations on (odomEstimationNode.cpp:870-872, :921-973) — what orc_align does with the AtA / AtB
+ * of one iteration: returns 0 and touches nothing when n_sel < min_corr; else 1 with X (after the projection), T += X, deltaR /
+ * deltaT (deg, cm), conv = both below their bounds.  iter == 0 runs the degeneracy analysis and writes P and *isDegenerate; a later
+ * iteration zeroes P when emulate_matp_shadow is set and projects by P while *isDegenerate is set. */
+int  orc_lm_step(const float AtA[36], const float AtB[6], int n_sel, int iter, const lisreg_params* p,
+                 float T[6], float P[36], int* isDegenerate, float X[6], float* deltaR, float* deltaT, int* conv);
+
 /* Whole scan2SubMapOptimization().  Clouds use the ABI's host layouts (LISREG_FMT_XYZI / _XYZIL).
  * degenerate: in/out isDegenerate member.  trace: NULL or max_trace*LISREG_TRACE_STRIDE floats.
  * n_threads: OpenMP threads for the three hot loops (1 = the reference as built).

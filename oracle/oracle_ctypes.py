@@ -126,6 +126,7 @@ def lib():
         L.orc_surf_coeff.argtypes = [fp, fp, C.c_float, C.POINTER(Params), fp]
         L.orc_jacobian_row.argtypes = [fp, fp, fp, fp, fp]
         L.orc_transform_update.argtypes = [C.POINTER(Params), C.POINTER(Imu), fp]
+        L.orc_lm_step.argtypes = [fp, fp, C.c_int, C.c_int, C.POINTER(Params), fp, fp, ip, fp, fp, fp, ip]
         L.orc_align.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                 C.POINTER(Params), C.POINTER(Imu), fp, ip, C.POINTER(Stats), fp, C.c_int,
                                 C.c_int, C.c_int]
@@ -184,6 +185,21 @@ def align(tgt_corner, tgt_surf, src_corner, src_surf, T_init, params: Params, im
     stats = dict(iters=st.iters, deltaR=st.deltaR, deltaT=st.deltaT, degenerate=st.degenerate,
                  n_corr_last=st.n_corr_last, status=st.status)
     return T, stats, trace[:n_rec]
+
+
+def lm_step(AtA, AtB, n_sel: int, it: int, params: Params, T, P, degenerate: int):
+    """orc_lm_step on copies of T[6] / P[36].  Returns dict(solved, X, T, P, degenerate, deltaR, deltaT, conv); an unsolved step
+    (n_sel < min_corr) returns its inputs, X = 0 and deltaR = deltaT = None."""
+    L = lib()
+    A = np.ascontiguousarray(AtA, np.float32).reshape(36); b = np.ascontiguousarray(AtB, np.float32).reshape(6)
+    T = np.array(T, np.float32).reshape(6).copy(); P = np.array(P, np.float32).reshape(36).copy()
+    X = np.zeros(6, np.float32)
+    dR, dT = C.c_float(0), C.c_float(0)
+    deg, conv = C.c_int(int(degenerate)), C.c_int(0)
+    solved = L.orc_lm_step(_fp(A), _fp(b), int(n_sel), int(it), C.byref(params), _fp(T), _fp(P), C.byref(deg), _fp(X),
+                           C.byref(dR), C.byref(dT), C.byref(conv))
+    return dict(solved=int(solved), X=X, T=T, P=P, degenerate=deg.value, deltaR=np.float32(dR.value) if solved else None,
+                deltaT=np.float32(dT.value) if solved else None, conv=conv.value)
 
 
 def stage_coeffs(kind, tgt, src, T, params: Params, fmt: int = 1):
