@@ -533,6 +533,39 @@ int  lisreg_rangenet_label_batch(lisreg_ctx* ctx, int n_sweeps, const void* cons
                                  const int* const* pixel_index, const unsigned char* const* invalid_mask,
                                  const float* const* logits, const lisreg_rangenet_params* params,
                                  void* const* labelled_out, unsigned char* const* label_image_out);
+/* The kNN label clean-up of RangeNet++ (the "++"): lisreg_rangenet_label gives a point the argmax of its pixel, whoever won that pixel, so
+ * a point that lost its pixel to a nearer surface inherits that surface's class.  lisreg_rangenet_label_knn votes instead, per point,
+ * among the knn cells of a search x search window of the range image that are nearest to the point IN RANGE (Gaussian-weighted by their
+ * distance in the window).  The reference tree has no text for this step; it is DEFINED, after the authors' published post-processing,
+ * at the kNN section of lis-slam_amd/csrc/lisreg_rangenet.hip and in tests/rangenet_knn_ref.py: the range image holds the smallest
+ * sqrtf((x*x + y*y) + z*z) of each pixel's points (+inf: empty); cells outside the image are zero padding (range 0, label 0; no wrap at
+ * the azimuth seam); the centre cell takes the point's own range; d_j = fabsf(range_j - r) * w_j; the knn smallest in (d_j, then j) are
+ * selected; a selected cell with cutoff > 0 && d_j > cutoff votes for nobody; the class 1 .. n_classes - 1 with the most votes wins, the
+ * lowest id on a tie, and class 0 never; a point without any such vote gets no_vote_label; a point with pixel index -1 gets 0; a point
+ * whose own range overflows keeps its pixel's label. */
+typedef struct lisreg_rangenet_knn_params {
+    int   knn;                    /* voters per point, 1 .. min(search * search, 16)                                 */
+    int   search;                 /* window side: 1, 3, 5 or 7                                                      */
+    float sigma;                  /* of the Gaussian over window offsets, finite and > 0                             */
+    float cutoff;                 /* weighted range distance beyond which a selected cell does not vote; <= 0: none   */
+    int   no_vote_label;          /* 0 .. n_classes - 1.  1 is the authors' behaviour (argmax + 1 of all-zero counts); 0, the default,
+                                     sends such points to the outlier class of lisreg_semantic_split                 */
+} lisreg_rangenet_knn_params;
+int  lisreg_default_rangenet_knn_params(lisreg_rangenet_knn_params* p);   /* 5, 5, 1.0, 1.0, 0 — the model's own are the `post: KNN: params:` block of its arch_cfg.yaml */
+/* Host only: the search * search window weights w_j = (float)(1.0 - g_j / sum g), g_j = exp(-(dx*dx + dy*dy) / (2 sigma^2)) in double.
+ * Writes nothing when search or sigma is out of range. */
+void lisreg_rangenet_knn_weights(const lisreg_rangenet_knn_params* knn_params, float* out /* [search * search] */);
+/* lisreg_rangenet_label with the clean-up: the same arguments, argument rules and stream behaviour; label_image_out (or NULL) receives
+ * the per-pixel argmax image, as in the plain call.  n_classes must be 2 .. 32; kNN parameters outside their limits: LISREG_ERR_ARG. */
+int  lisreg_rangenet_label_knn(lisreg_ctx* ctx, const void* cloud, int n, int fmt, const int* pixel_index,
+                               const unsigned char* invalid_mask, const float* logits, const lisreg_rangenet_params* params,
+                               const lisreg_rangenet_knn_params* knn_params, void* labelled_out, unsigned char* label_image_out);
+/* The same for n_sweeps (<= 256) sweeps in one launch sequence; every sweep gets bit for bit what a single call gives. */
+int  lisreg_rangenet_label_knn_batch(lisreg_ctx* ctx, int n_sweeps, const void* const* sweeps, const int* n,
+                                     const int* const* pixel_index, const unsigned char* const* invalid_mask,
+                                     const float* const* logits, const lisreg_rangenet_params* params,
+                                     const lisreg_rangenet_knn_params* knn_params, void* const* labelled_out,
+                                     unsigned char* const* label_image_out);
 
 /* The "semantic mask": SemanticFusionNode::categoryMapping (src/node/semanticFusionNode.cpp:173-189) splits the labelled
  * cloud, preserving order, by UsingLableMap[label] (config/label.yaml:177-196): 10 -> dynamic, 40 -> ground, 50 -> building,

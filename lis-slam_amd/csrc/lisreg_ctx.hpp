@@ -177,8 +177,9 @@ struct lisreg_ctx {
     lisreg::DevBuf pt_ends, pt_ring, pt_ori, pt_blk, pt_hdr, pt_tab, pt_in, pt_out, pt_time;
     lisreg::PinnedBuf pt_hdr_host;
     // RangeNet++ projection and labelling (lisreg_rangenet.hip): the pixel keys (all empty between calls: rn_keys_clean), per-workgroup
-    // valid-pixel counts, per-sweep counts, the sweep table of a batch, staging of a host sweep, the label image when the caller wants none
-    lisreg::DevBuf rn_keys, rn_blk, rn_hdr, rn_tab, rn_in, rn_img;
+    // valid-pixel counts, per-sweep counts, the sweep table of a batch, staging of a host sweep, the label image when the caller wants none,
+    // the per-pixel range image of the kNN clean-up (written in full by every call that reads it: no state between calls)
+    lisreg::DevBuf rn_keys, rn_blk, rn_hdr, rn_tab, rn_in, rn_img, rn_rng;
     lisreg::PinnedBuf rn_hdr_host;
     bool         rn_keys_clean = false;
     // host feeder (lisreg_api_feed.hip): clouds packed to 16-byte records by a few threads into pinned staging, uploaded on a copy stream

@@ -41,9 +41,12 @@
 //   k_rn_count     one workgroup per sweep: the sum of its workgroups' counts (no atomics, nothing to clear)
 //   k_rn_argmax    one thread per pixel: step 8-9 over coalesced plane reads, one label byte
 //   k_rn_gather    one thread per point: one byte gathered through the pixel index, one 16-byte record written
+// The kNN label clean-up of RangeNet++ (lisreg_rangenet_label_knn: k_rn_argmax_range, k_rn_range_min, k_rn_knn) is defined and mapped
+// in its own section below.
 // Plain C++ and vector stores only.
 #include "lisreg_ctx.hpp"
 
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -190,6 +193,128 @@ __global__ __launch_bounds__(256) void k_rn_gather(RnLabelSweep one, const RnLab
     sw.out[i] = make_float4(p.x, p.y, p.z, __uint_as_float(label));
 }
 
+// ---- the kNN label clean-up (lisreg_rangenet_label_knn) ------------------------------------------------------------------------
+// The post-processing step of RangeNet++ (the "++"): a k-nearest-neighbour vote in range over a small window of the range image, per
+// point, after the network.  The reference tree has no text for it (its vendored wrapper never reads the `post: KNN: params:` block of
+// the model's arch_cfg.yaml), so it is DEFINED here, after the authors' published post-processing, restated from knowledge.  With
+// S = search, C = n_classes, window cell j = 0 .. S*S - 1 at row offset j / S - (S - 1) / 2 and column offset j % S - (S - 1) / 2:
+//   1. Label image: steps 8-9 above (k_rn_argmax); invalid pixels are 0.
+//   2. Range image: per pixel the smallest range = sqrtf((x*x + y*y) + z*z) (the float expression of step 2, no contraction: the
+//      projection winner's range bit for bit) over the points with that pixel_index; points with pixel_index -1 take no part; a pixel no
+//      point fell into has range +inf.  The invalid mask plays no part in the range image.
+//   3. Weights: g_j = exp(-(dx*dx + dy*dy) / (2 sigma^2)) in double through the C library's exp, summed in the order of j;
+//      w_j = (float)(1.0 - g_j / sum g), rounded once.  Computed on the host (lisreg_rangenet_knn_weights), handed to the kernel.
+//   4. Per point with pixel_index >= 0 and a finite own range r: every window cell takes range and label of its pixel; a cell outside
+//      the image takes range 0 and label 0 (the authors' zero padding, rows and columns, no wrap at the azimuth seam); the centre cell's
+//      range is replaced by r, its label stays the pixel's.  d_j = fabsf(range_j - r) * w_j in float: +inf for an empty pixel, never NaN.
+//   5. Selection: the knn cells smallest in (d_j, then j) — a tie in d goes to the lower window position.
+//   6. Vote: a selected cell with cutoff > 0 && d_j > cutoff votes for nobody; every other selected cell votes for its label.
+//   7. Result: the class in 1 .. C - 1 with the most votes, lowest class id on a tie; class 0 never wins; a point with no vote for any
+//      class 1 .. C - 1 gets no_vote_label (1: the authors' argmax + 1 of all-zero counts; 0, the default: the outlier class).
+//   8. A point with pixel_index -1 gets 0; a point whose own range is not finite keeps its pixel's label of step 1.
+//   9. x, y, z bit for bit, the label in the payload.
+// Limits: search in {1, 3, 5, 7}; 1 <= knn <= min(search^2, 16); sigma finite and > 0; 0 <= no_vote_label < C; C >= 2.
+//
+// gfx950 mapping (the same sequence for one sweep and for 256):
+//   k_rn_argmax_range  one thread per pixel: k_rn_argmax, and the pixel's range set to +inf (nothing is cleared by a memset launch)
+//   k_rn_range_min     one thread per point: step 2 as a 32-bit atomicMin on the range bits (non-negative floats order like their bits)
+//   k_rn_knn<S>        one thread per point: the S*S distances in registers (every index a compile-time constant after unrolling), knn
+//                      rounds of "smallest (d, j) above the last one taken" over them, the selected labels packed a byte each into two
+//                      64-bit words, the vote as knn^2 byte compares — no per-thread array is indexed at run time, no LDS, no scratch
+struct RnKnnSweep {                                 // one sweep of a kNN labelling call (64 bytes)
+    const float4* in; const int* pix; const unsigned char* mask; const float* logits;
+    float4* out; unsigned char* image; unsigned* range;   // image: the caller's, or the context's scratch; range: the context's scratch
+    int n, blk0;
+};
+struct RnKnn { int h, w, knn, no_vote; float cutoff; float wgt[49]; };
+constexpr unsigned kInfBits = 0x7f800000u;
+
+// grid: n_sweeps x bpi workgroups
+__global__ __launch_bounds__(256) void k_rn_argmax_range(RnKnnSweep one, const RnKnnSweep* __restrict__ tab, int bpi, int hw, int n_classes)
+{
+    const int s = blockIdx.x / bpi;
+    const RnKnnSweep& sw = tab ? tab[s] : one;
+    const int pix = (blockIdx.x - s * bpi) * 256 + threadIdx.x;
+    if (pix >= hw) return;
+    int label = 0;
+    if (!sw.mask[pix]) {
+        float prob = 0.f;
+        for (int j = 0; j < n_classes; ++j) {
+            const float v = sw.logits[(size_t)j * (size_t)hw + (size_t)pix];
+            if (prob <= v) { label = j; prob = v; }
+        }
+    }
+    sw.image[pix] = (unsigned char)label;
+    sw.range[pix] = kInfBits;
+}
+
+__global__ __launch_bounds__(256) void k_rn_range_min(RnKnnSweep one, const RnKnnSweep* __restrict__ tab, int n_sweeps, int hw)
+{
+    const RnKnnSweep& sw = sweep_of(one, tab, n_sweeps, blockIdx.x);
+    const int i = (blockIdx.x - sw.blk0) * 256 + threadIdx.x;
+    if (i >= sw.n) return;
+    const int pix = sw.pix[i];
+    if ((unsigned)pix >= (unsigned)hw) return;                          // -1 (or anything outside the image)
+    const float4 p = sw.in[i];
+    const float range = sqrtf((p.x * p.x + p.y * p.y) + p.z * p.z);     // >= 0 or +inf for the finite coordinates of such a point
+    atomicMin(&sw.range[pix], __float_as_uint(range));
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void k_rn_knn(RnKnnSweep one, const RnKnnSweep* __restrict__ tab, int n_sweeps, RnKnn K)
+{
+    const RnKnnSweep& sw = sweep_of(one, tab, n_sweeps, blockIdx.x);
+    const int i = (blockIdx.x - sw.blk0) * 256 + threadIdx.x;
+    if (i >= sw.n) return;
+    const float4 p = sw.in[i];
+    const int pix = sw.pix[i];
+    unsigned label = 0;
+    if ((unsigned)pix < (unsigned)(K.h * K.w)) {
+        label = sw.image[pix];
+        const float r = sqrtf((p.x * p.x + p.y * p.y) + p.z * p.z);
+        if (finite_f(r)) {
+            const int row = pix / K.w, y0 = row - (S - 1) / 2, x0 = pix - row * K.w - (S - 1) / 2;
+            float d[S * S];
+#pragma unroll
+            for (int j = 0; j < S * S; ++j) {
+                const int y = y0 + j / S, x = x0 + j % S;
+                float rj = 0.f;                                         // outside the image: zero padding
+                if ((unsigned)y < (unsigned)K.h && (unsigned)x < (unsigned)K.w) rj = __uint_as_float(sw.range[y * K.w + x]);
+                if (j == (S * S) / 2) rj = r;
+                d[j] = fabsf(rj - r) * K.wgt[j];
+            }
+            // d >= 0 and never NaN: (bits of d, j + 1) orders like (d, j), and 0 is below every key
+            unsigned long long last = 0, lo = 0, hi = 0;
+            for (int a = 0; a < K.knn; ++a) {
+                unsigned long long best = ~0ull;
+#pragma unroll
+                for (int j = 0; j < S * S; ++j) {
+                    const unsigned long long key = ((unsigned long long)__float_as_uint(d[j]) << 32) | (unsigned long long)(j + 1);
+                    if (key > last && key < best) best = key;
+                }
+                last = best;
+                const int j = (int)(best & 0xffull) - 1;
+                const float dj = __uint_as_float((unsigned)(best >> 32));
+                const int y = y0 + j / S, x = x0 + j % S;
+                unsigned long long vote = 0;                            // 0: nobody (class 0 never wins, so its votes need no count)
+                if (!(K.cutoff > 0.f && dj > K.cutoff) && (unsigned)y < (unsigned)K.h && (unsigned)x < (unsigned)K.w)
+                    vote = sw.image[y * K.w + x];
+                if (a < 8) lo |= vote << (8 * a); else hi |= vote << (8 * (a - 8));
+            }
+            int best_n = 0;
+            label = (unsigned)K.no_vote;
+            for (int a = 0; a < K.knn; ++a) {
+                const unsigned la = (unsigned)(((a < 8 ? lo : hi) >> (8 * (a & 7))) & 0xffull);
+                if (la == 0) continue;
+                int cnt = 0;
+                for (int b = 0; b < K.knn; ++b) cnt += (unsigned)(((b < 8 ? lo : hi) >> (8 * (b & 7))) & 0xffull) == la;
+                if (cnt > best_n || (cnt == best_n && la < label)) { best_n = cnt; label = la; }
+            }
+        }
+    }
+    sw.out[i] = make_float4(p.x, p.y, p.z, __uint_as_float(label));
+}
+
 struct Span { const void* p; size_t bytes; };
 bool spans_overlap(const Span& a, const Span& b)
 {
@@ -292,6 +417,73 @@ int label_device(lisreg_ctx* c, int n_sweeps, std::vector<RnLabelSweep>& sw, con
     }
     k_rn_argmax<<<n_sweeps * bpi, 256, 0, st>>>(sw[0], tab, bpi, hw, P.n_classes);
     if (blocks > 0) k_rn_gather<<<blocks, 256, 0, st>>>(sw[0], tab, n_sweeps, hw);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(st));                               // `sw` is the caller's local; the records are complete
+    return LISREG_OK;
+}
+
+int check_knn_params(lisreg_ctx* c, const lisreg_rangenet_params* P, const lisreg_rangenet_knn_params* K, const char* who)
+{
+    if (!K) return ctx_fail(c, LISREG_ERR_ARG, std::string(who) + ": no kNN parameters");
+    if (P->n_classes < 2) return ctx_fail(c, LISREG_ERR_ARG, std::string(who) + ": n_classes must be 2 .. 32");
+    if (K->search != 1 && K->search != 3 && K->search != 5 && K->search != 7)
+        return ctx_fail(c, LISREG_ERR_ARG, std::string(who) + ": search must be 1, 3, 5 or 7");
+    if (K->knn < 1 || K->knn > K->search * K->search || K->knn > 16)
+        return ctx_fail(c, LISREG_ERR_ARG, std::string(who) + ": knn must be 1 .. min(search^2, 16)");
+    if (!(K->sigma > 0.f) || !(K->sigma <= kFltMax)) return ctx_fail(c, LISREG_ERR_ARG, std::string(who) + ": sigma must be finite and > 0");
+    if (K->no_vote_label < 0 || K->no_vote_label >= P->n_classes)
+        return ctx_fail(c, LISREG_ERR_ARG, std::string(who) + ": no_vote_label must be 0 .. n_classes - 1");
+    return LISREG_OK;
+}
+
+// step 3; the parameters have been checked
+void knn_weights(const lisreg_rangenet_knn_params& K, float* out)
+{
+    const int S = K.search, half = (S - 1) / 2;
+    const double s = (double)K.sigma;
+    double g[49], sum = 0.0;
+    for (int j = 0; j < S * S; ++j) {
+        const int dy = j / S - half, dx = j % S - half;
+        g[j] = exp(-(double)(dx * dx + dy * dy) / (2.0 * s * s));
+        sum += g[j];
+    }
+    for (int j = 0; j < S * S; ++j) out[j] = (float)(1.0 - g[j] / sum);
+}
+
+int label_knn_device(lisreg_ctx* c, int n_sweeps, std::vector<RnKnnSweep>& sw, const lisreg_rangenet_params& P, const lisreg_rangenet_knn_params& Kp)
+{
+    hipStream_t st = c->stream;
+    const int hw = P.img_h * P.img_w, bpi = (hw + 255) / 256;
+    int blocks = 0, scratch = 0;
+    for (auto& s : sw) { s.blk0 = blocks; blocks += (s.n + 255) / 256; if (!s.image) ++scratch; }
+    HIPCHK(c, c->rn_rng.ensure(sizeof(unsigned) * (size_t)n_sweeps * (size_t)hw));
+    if (scratch) HIPCHK(c, c->rn_img.ensure((size_t)scratch * (size_t)hw));
+    unsigned* rp = c->rn_rng.as<unsigned>();
+    unsigned char* ip = c->rn_img.as<unsigned char>();
+    for (auto& s : sw) {
+        s.range = rp; rp += hw;
+        if (!s.image) { s.image = ip; ip += hw; }
+    }
+    const RnKnnSweep* tab = nullptr;
+    if (n_sweeps > 1) {
+        HIPCHK(c, c->rn_tab.ensure(sizeof(RnKnnSweep) * (size_t)n_sweeps));
+        HIPCHK(c, hipMemcpyAsync(c->rn_tab.p, sw.data(), sizeof(RnKnnSweep) * (size_t)n_sweeps, hipMemcpyHostToDevice, st));
+        tab = c->rn_tab.as<RnKnnSweep>();
+    }
+    RnKnn K;
+    K.h = P.img_h; K.w = P.img_w; K.knn = Kp.knn; K.no_vote = Kp.no_vote_label; K.cutoff = Kp.cutoff;
+    for (float& w : K.wgt) w = 0.f;
+    knn_weights(Kp, K.wgt);
+    k_rn_argmax_range<<<n_sweeps * bpi, 256, 0, st>>>(sw[0], tab, bpi, hw, P.n_classes);
+    if (blocks > 0) {
+        k_rn_range_min<<<blocks, 256, 0, st>>>(sw[0], tab, n_sweeps, hw);
+        switch (Kp.search) {
+        case 1:  k_rn_knn<1><<<blocks, 256, 0, st>>>(sw[0], tab, n_sweeps, K); break;
+        case 3:  k_rn_knn<3><<<blocks, 256, 0, st>>>(sw[0], tab, n_sweeps, K); break;
+        case 5:  k_rn_knn<5><<<blocks, 256, 0, st>>>(sw[0], tab, n_sweeps, K); break;
+        default: k_rn_knn<7><<<blocks, 256, 0, st>>>(sw[0], tab, n_sweeps, K); break;
+        }
+    }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(st));                               // `sw` is the caller's local; the records are complete
     return LISREG_OK;
@@ -416,4 +608,68 @@ int lisreg_rangenet_label_batch(lisreg_ctx* c, int n_sweeps, const void* const* 
     if (any_overlap(in, out)) return ctx_fail(c, LISREG_ERR_ARG, "rangenet_label_batch: an output overlaps an input or another output");
     HIPCHK(c, hipSetDevice(c->device));
     return label_device(c, n_sweeps, sw, *P);
+}
+
+int lisreg_default_rangenet_knn_params(lisreg_rangenet_knn_params* p)
+{
+    if (!p) return LISREG_ERR_ARG;
+    p->knn = 5; p->search = 5; p->sigma = 1.0f; p->cutoff = 1.0f;      // the `post: KNN: params:` block of the authors' arch_cfg.yaml
+    p->no_vote_label = 0;
+    return LISREG_OK;
+}
+
+void lisreg_rangenet_knn_weights(const lisreg_rangenet_knn_params* K, float* out)
+{
+    if (!K || !out || (K->search != 1 && K->search != 3 && K->search != 5 && K->search != 7) || !(K->sigma > 0.f) || !(K->sigma <= kFltMax)) return;
+    knn_weights(*K, out);
+}
+
+int lisreg_rangenet_label_knn(lisreg_ctx* c, const void* cloud, int n, int fmt, const int* pixel_index, const unsigned char* invalid_mask,
+                              const float* logits, const lisreg_rangenet_params* P, const lisreg_rangenet_knn_params* K, void* labelled_out,
+                              unsigned char* label_image_out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (n < 0 || (n > 0 && (!cloud || !pixel_index || !labelled_out)) || !invalid_mask || !logits)
+        return ctx_fail(c, LISREG_ERR_ARG, "rangenet_label_knn: bad arguments");
+    if (const int rc = check_params(c, P, "rangenet_label_knn")) return rc;
+    if (const int rc = check_knn_params(c, P, K, "rangenet_label_knn")) return rc;
+    if (fmt != LISREG_FMT_DEVICE_XYZI && fmt != LISREG_FMT_DEVICE) return ctx_fail(c, LISREG_ERR_ARG, "rangenet_label_knn: fmt must be DEVICE_XYZI or DEVICE");
+    const size_t hw = (size_t)P->img_h * (size_t)P->img_w;
+    const std::vector<Span> in = { { cloud, (size_t)n * 16 }, { pixel_index, (size_t)n * 4 }, { invalid_mask, hw }, { logits, hw * 4 * (size_t)P->n_classes } };
+    const std::vector<Span> out = { { labelled_out, (size_t)n * 16 }, { label_image_out, label_image_out ? hw : 0 } };
+    if (any_overlap(in, out)) return ctx_fail(c, LISREG_ERR_ARG, "rangenet_label_knn: an output overlaps an input or the other output");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<RnKnnSweep> sw(1);
+    sw[0] = RnKnnSweep{ static_cast<const float4*>(cloud), pixel_index, invalid_mask, logits, static_cast<float4*>(labelled_out), label_image_out, nullptr, n, 0 };
+    return label_knn_device(c, 1, sw, *P, *K);
+}
+
+int lisreg_rangenet_label_knn_batch(lisreg_ctx* c, int n_sweeps, const void* const* sweeps, const int* n, const int* const* pixel_index,
+                                    const unsigned char* const* invalid_mask, const float* const* logits, const lisreg_rangenet_params* P,
+                                    const lisreg_rangenet_knn_params* K, void* const* labelled_out, unsigned char* const* label_image_out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (n_sweeps < 0 || n_sweeps > 256 || (n_sweeps > 0 && (!sweeps || !n || !pixel_index || !invalid_mask || !logits || !labelled_out)))
+        return ctx_fail(c, LISREG_ERR_ARG, "rangenet_label_knn_batch: bad arguments (at most 256 sweeps)");
+    if (const int rc = check_params(c, P, "rangenet_label_knn_batch")) return rc;
+    if (const int rc = check_knn_params(c, P, K, "rangenet_label_knn_batch")) return rc;
+    if (n_sweeps == 0) return LISREG_OK;
+    const size_t hw = (size_t)P->img_h * (size_t)P->img_w;
+    std::vector<RnKnnSweep> sw((size_t)n_sweeps);
+    std::vector<Span> in, out;
+    long long total = 0;
+    for (int s = 0; s < n_sweeps; ++s) {
+        if (n[s] < 0 || (n[s] > 0 && (!sweeps[s] || !pixel_index[s] || !labelled_out[s])) || !invalid_mask[s] || !logits[s])
+            return ctx_fail(c, LISREG_ERR_ARG, "rangenet_label_knn_batch: NULL buffer");
+        if ((total += n[s]) > 1000000000LL) return ctx_fail(c, LISREG_ERR_ARG, "rangenet_label_knn_batch: too many points");
+        unsigned char* img = label_image_out ? label_image_out[s] : nullptr;
+        sw[(size_t)s] = RnKnnSweep{ static_cast<const float4*>(sweeps[s]), pixel_index[s], invalid_mask[s], logits[s],
+                                    static_cast<float4*>(labelled_out[s]), img, nullptr, n[s], 0 };
+        in.push_back({ sweeps[s], (size_t)n[s] * 16 }); in.push_back({ pixel_index[s], (size_t)n[s] * 4 });
+        in.push_back({ invalid_mask[s], hw }); in.push_back({ logits[s], hw * 4 * (size_t)P->n_classes });
+        out.push_back({ labelled_out[s], (size_t)n[s] * 16 }); out.push_back({ img, img ? hw : 0 });
+    }
+    if (any_overlap(in, out)) return ctx_fail(c, LISREG_ERR_ARG, "rangenet_label_knn_batch: an output overlaps an input or another output");
+    HIPCHK(c, hipSetDevice(c->device));
+    return label_knn_device(c, n_sweeps, sw, *P, *K);
 }

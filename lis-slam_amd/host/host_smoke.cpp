@@ -16,10 +16,11 @@ static void add(PointCloud<PointType>& c, float x, float y, float z) { PointType
 
 // RangenetAPI mirror: this program has no HIP runtime to allocate device memory with, so the labeller is only instantiated here (the
 // node that owns the model owns device memory too); tests/test_rangenet.py runs the same two calls on the GPU.
-static const void* rangenet_mirror_instantiates(lisreg_ctx* ctx, const RangenetWorkspace& ws, const void* sweep_device, int n)
+static const void* rangenet_mirror_instantiates(lisreg_ctx* ctx, const RangenetWorkspace& ws, const void* sweep_device, int n, bool knn)
 {
     RangenetAPI api(ctx, ws);
     api.params.img_w = 1800;
+    api.use_knn = knn;                      // the kNN clean-up: tests/test_rangenet_knn.py runs that call on the GPU
     return api.infer(sweep_device, n, [](const float* /* tensor */, float* /* logits */) { /* the caller's model runs here */ });
 }
 
@@ -250,6 +251,14 @@ int main()
         pok = pok && sweep.points.back().time > 0.099f && sweep.points.front().time < 0.001f;
         std::printf(pok ? "LaserPretreatment ok (%zu of %zu points)\n" : "LaserPretreatment FAILED (%zu of %zu points)\n", sweep.size(), rawSweep.size());
         ok = ok && pok;
+    }
+    {   // the kNN window weights of RangeNet++ (host only): symmetric, the centre the smallest, the corners the largest
+        lisreg_rangenet_knn_params kp; lisreg_default_rangenet_knn_params(&kp);
+        float w[25];
+        lisreg_rangenet_knn_weights(&kp, w);
+        const bool wok = kp.knn == 5 && kp.search == 5 && w[12] < w[7] && w[7] < w[6] && w[6] < w[0] && w[0] == w[24] && w[7] == w[17] && w[0] < 1.f && w[12] > 0.f;
+        std::printf(wok ? "rangenet kNN weights ok (centre %g, corner %g)\n" : "rangenet kNN weights FAILED (centre %g, corner %g)\n", w[12], w[0]);
+        ok = ok && wok;
     }
     std::printf(ok ? "host_smoke ok\n" : "host_smoke FAILED\n");
     return ok ? 0 : 1;

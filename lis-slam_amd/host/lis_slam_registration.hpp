@@ -293,7 +293,8 @@ private:
 // has finished writing `logits` (n_classes x H x W floats) when it returns.  This header has no HIP dependency, so the node — which
 // owns a HIP runtime for its model anyway — provides the device memory: the sweep as lisreg_dpoint records with the float intensity in
 // the payload (lisreg_upload_cloud with LISREG_FMT_XYZI_PACKED, or the output of lisreg_extract_features*), and the workspace below.
-// The RGB clouds of the reference's class are not mirrored.
+// The RGB clouds of the reference's class are not mirrored.  With use_knn set, the labels come from lisreg_rangenet_label_knn — the kNN
+// clean-up of RangeNet++, with `knn` taken from the `post: KNN: params:` block of the model's arch_cfg.yaml — instead of the plain argmax.
 struct RangenetWorkspace {              // caller-owned device memory for sweeps of up to max_points points
     float*         tensor = nullptr;    // 5 * H * W floats
     float*         logits = nullptr;    // n_classes * H * W floats
@@ -306,8 +307,13 @@ struct RangenetWorkspace {              // caller-owned device memory for sweeps
 class RangenetAPI {
 public:
     lisreg_rangenet_params params;
+    lisreg_rangenet_knn_params knn;     // read only when use_knn is set
+    bool use_knn = false;
     int validPixels = 0;                // of the last sweep
-    RangenetAPI(lisreg_ctx* ctx, const RangenetWorkspace& ws) : ctx_(ctx), ws_(ws) { lisreg_default_rangenet_params(&params); }
+    RangenetAPI(lisreg_ctx* ctx, const RangenetWorkspace& ws) : ctx_(ctx), ws_(ws) {
+        lisreg_default_rangenet_params(&params);
+        lisreg_default_rangenet_knn_params(&knn);
+    }
     // infer (rangenetAPI.cpp:16-125): returns the labelled device records (ws.labelled; x y z bit for bit, label in the payload) —
     // what lisreg_semantic_split takes with LISREG_FMT_DEVICE
     template <class Network>
@@ -319,8 +325,10 @@ public:
         if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_));
         validPixels = o.n_valid;
         network(static_cast<const float*>(ws_.tensor), ws_.logits);
-        rc = lisreg_rangenet_label(ctx_, currentCloudInDevice, num_points, LISREG_FMT_DEVICE_XYZI, ws_.pixel_index, ws_.invalid_mask, ws_.logits,
-                                   &params, ws_.labelled, ws_.label_image);
+        rc = use_knn ? lisreg_rangenet_label_knn(ctx_, currentCloudInDevice, num_points, LISREG_FMT_DEVICE_XYZI, ws_.pixel_index, ws_.invalid_mask,
+                                                 ws_.logits, &params, &knn, ws_.labelled, ws_.label_image)
+                     : lisreg_rangenet_label(ctx_, currentCloudInDevice, num_points, LISREG_FMT_DEVICE_XYZI, ws_.pixel_index, ws_.invalid_mask,
+                                             ws_.logits, &params, ws_.labelled, ws_.label_image);
         if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_));
         num_points_ = num_points;
         return ws_.labelled;

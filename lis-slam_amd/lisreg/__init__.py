@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "lisreg_default_pretreat_params", "lisreg_pretreat", "lisreg_pretreat_batch",
     "lisreg_default_rangenet_params", "lisreg_rangenet_project", "lisreg_rangenet_project_batch", "lisreg_rangenet_label",
     "lisreg_rangenet_label_batch",
+    "lisreg_default_rangenet_knn_params", "lisreg_rangenet_knn_weights", "lisreg_rangenet_label_knn", "lisreg_rangenet_label_knn_batch",
 ]
 
 
@@ -264,6 +265,10 @@ class RangenetOut(C.Structure):
     _fields_ = [("tensor", C.c_void_p), ("invalid_mask", C.c_void_p), ("pixel_index", C.c_void_p), ("n_valid", C.c_int)]
 
 
+class RangenetKnnParams(C.Structure):
+    _fields_ = [("knn", C.c_int), ("search", C.c_int), ("sigma", C.c_float), ("cutoff", C.c_float), ("no_vote_label", C.c_int)]
+
+
 class SemanticOut(C.Structure):
     _fields_ = [("cloud", C.c_void_p * 5), ("cap", C.c_int * 5), ("n", C.c_int * 5)]
 
@@ -359,6 +364,13 @@ def lib():
         L.lisreg_rangenet_label_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(RangenetParams),
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.lisreg_default_rangenet_knn_params.argtypes = [C.POINTER(RangenetKnnParams)]
+        L.lisreg_rangenet_knn_weights.argtypes = [C.POINTER(RangenetKnnParams), fp]
+        L.lisreg_rangenet_knn_weights.restype = None
+        L.lisreg_rangenet_label_knn.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(RangenetParams), C.POINTER(RangenetKnnParams), vp, vp]
+        L.lisreg_rangenet_label_knn_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(RangenetParams),
+                                                      C.POINTER(RangenetKnnParams), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.lisreg_semantic_split.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(SemanticOut)]
         ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
         L.lisreg_map_index_set.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
@@ -912,6 +924,26 @@ class Context:
         ns = (C.c_int * S)(*[int(x) for x in counts])
         self._chk(self._L.lisreg_rangenet_label_batch(self._h, S, arr(in_ptrs, counts), ns, arr(pixel_ptrs, counts), arr(mask_ptrs), arr(logits_ptrs),
                                                       C.byref(params), arr(out_ptrs, counts), arr(image_ptrs) if image_ptrs else None))
+
+    def rangenet_label_knn_device(self, in_ptr: int, n: int, pixel_ptr: int, mask_ptr: int, logits_ptr: int, params: "RangenetParams",
+                                  knn_params: "RangenetKnnParams", out_ptr: int, image_ptr: int | None = None, fmt: int = FMT_DEVICE_XYZI):
+        """lisreg_rangenet_label_knn: rangenet_label_device followed by the kNN clean-up of RangeNet++ (a vote among the knn cells of a
+        search x search window nearest in range); image_ptr receives the per-pixel argmax image, as in the plain call."""
+        self._chk(self._L.lisreg_rangenet_label_knn(self._h, C.c_void_p(in_ptr) if n else None, n, fmt, C.c_void_p(pixel_ptr) if n else None,
+                                                    C.c_void_p(mask_ptr), C.c_void_p(logits_ptr), C.byref(params), C.byref(knn_params),
+                                                    C.c_void_p(out_ptr) if n else None, C.c_void_p(image_ptr) if image_ptr else None))
+
+    def rangenet_label_knn_batch_device(self, in_ptrs, counts, pixel_ptrs, mask_ptrs, logits_ptrs, params: "RangenetParams",
+                                        knn_params: "RangenetKnnParams", out_ptrs, image_ptrs=None):
+        """lisreg_rangenet_label_knn_batch: the per-sweep buffers of rangenet_label_knn_device, one launch sequence."""
+        S = len(in_ptrs)
+
+        def arr(ps, gate=None):
+            return (C.c_void_p * S)(*[C.c_void_p(int(p)) if (p and (gate is None or gate[k])) else None for k, p in enumerate(ps)])
+        ns = (C.c_int * S)(*[int(x) for x in counts])
+        self._chk(self._L.lisreg_rangenet_label_knn_batch(self._h, S, arr(in_ptrs, counts), ns, arr(pixel_ptrs, counts), arr(mask_ptrs),
+                                                          arr(logits_ptrs), C.byref(params), C.byref(knn_params), arr(out_ptrs, counts),
+                                                          arr(image_ptrs) if image_ptrs else None))
 
     def concat_device(self, in_ptrs, counts, out_ptr: int) -> int:
         """lisreg_concat_device: K device clouds end to end into out_ptr (stream-ordered, no wait).  Returns the total count."""
@@ -1551,6 +1583,25 @@ def default_rangenet_params(img_h: int | None = None, img_w: int | None = None) 
     if img_w is not None:
         p.img_w = img_w
     return p
+
+
+def default_rangenet_knn_params() -> RangenetKnnParams:
+    """lisreg_default_rangenet_knn_params: knn 5, search 5, sigma 1, cutoff 1 (the model's own are the `post: KNN: params:` block of its
+    arch_cfg.yaml), no_vote_label 0"""
+    p = RangenetKnnParams()
+    rc = lib().lisreg_default_rangenet_knn_params(C.byref(p))
+    if rc != OK:
+        raise LisregError(rc, "lisreg_default_rangenet_knn_params")
+    return p
+
+
+def rangenet_knn_weights(knn_params: RangenetKnnParams) -> np.ndarray:
+    """lisreg_rangenet_knn_weights: the search * search float32 window weights (host only, no device needed)"""
+    if knn_params.search not in (1, 3, 5, 7) or not (0.0 < knn_params.sigma < float("inf")):
+        raise LisregError(ERR_ARG, "rangenet_knn_weights: search must be 1, 3, 5 or 7 and sigma finite and > 0")
+    out = np.zeros(knn_params.search ** 2, np.float32)
+    lib().lisreg_rangenet_knn_weights(C.byref(knn_params), out.ctypes.data_as(C.POINTER(C.c_float)))
+    return out
 
 
 def default_feature_params() -> FeatureParams:

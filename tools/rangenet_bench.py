@@ -16,7 +16,13 @@ Medians and inter-quartile ranges over --reps calls.  Criterion (stated before t
 transfers' median by more than the larger of the two IQRs.  Per-kernel times come from a separate run under
 `rocprofv3 --kernel-trace --stats -- python tools/rangenet_bench.py --reps 50 --no-host` (no counters in that run).
 
-  python tools/rangenet_bench.py [--reps 200] [--batch 16] [--h 64] [--w 1800] [--img-h 64] [--img-w 2048] [--out profiles/rangenet_bench.json]"""
+With --knn the run measures the kNN label clean-up instead (lisreg_rangenet_label_knn, default parameters unless --knn-params): per
+repetition and alternating in the same run, Context.rangenet_label_device and Context.rangenet_label_knn_device on the same projected
+sweep (host clock, every call ends in a synchronise), then the two batch calls over --batch sweeps per sweep; medians, IQRs and the
+ratios kNN / plain.  No criterion: nobody has fixed a target for this step.
+
+  python tools/rangenet_bench.py [--reps 200] [--batch 16] [--h 64] [--w 1800] [--img-h 64] [--img-w 2048] [--out profiles/rangenet_bench.json]
+  python tools/rangenet_bench.py --knn [--knn-params 5,5,1.0,1.0] [--out profiles/rangenet_knn_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -35,6 +41,83 @@ def med_iqr(v):
     return round(float(q[1]), 4), round(float(q[2] - q[0]), 4)
 
 
+def knn_bench(a):
+    """--knn: lisreg_rangenet_label_knn next to lisreg_rangenet_label, single and batched"""
+    import lisreg
+    from lisreg import replay
+    raws = []
+    for sw, _ in replay.synthetic_raw_drive(a.sweeps, a.h, a.w):
+        raws.append(np.ascontiguousarray(np.stack([sw["x"], sw["y"], sw["z"], sw["intensity"]], 1), np.float32))
+    cap = max(len(r) for r in raws)
+    H, W, NC = a.img_h, a.img_w, a.classes
+    hw = H * W
+    ctx = lisreg.Context(0)
+    P = lisreg.default_rangenet_params(H, W)
+    P.n_classes = NC
+    K = lisreg.default_rangenet_knn_params()
+    knn, search, sigma, cutoff = a.knn_params.split(",")
+    K.knn, K.search, K.sigma, K.cutoff = int(knn), int(search), float(sigma), float(cutoff)
+    rng = np.random.default_rng(3)
+    S = max(a.batch, len(raws))
+    ins = [lisreg.DeviceArray(raws[s % len(raws)]) for s in range(S)]
+    ns = [len(raws[s % len(raws)]) for s in range(S)]
+    tensor = lisreg.DeviceArray(np.zeros((S, 5 * hw), np.float32))
+    masks = [lisreg.DeviceArray(np.zeros(hw, np.uint8)) for _ in range(S)]
+    pixs = [lisreg.DeviceArray(np.zeros(cap, np.int32)) for _ in range(S)]
+    labs = [lisreg.DeviceArray(np.zeros((cap, 4), np.float32)) for _ in range(S)]
+    labs_knn = [lisreg.DeviceArray(np.zeros((cap, 4), np.float32)) for _ in range(S)]
+    # logits that look like a network's: smooth in the image (a class per patch of 16 x 64 pixels) plus noise, so neighbours often agree
+    patch = rng.integers(0, NC, ((H + 15) // 16, (W + 63) // 64))
+    base = np.kron(patch, np.ones((16, 64), np.int64))[:H, :W]
+    logits_host = rng.normal(0, 1, (NC, H, W)).astype(np.float32)
+    logits_host[base.ravel(), np.arange(hw) // W, np.arange(hw) % W] += 2.0
+    d_logits = lisreg.DeviceArray(logits_host)
+    lg_ptrs = [d_logits.ptr] * S
+    n_valid = ctx.rangenet_project_batch_device([b.ptr for b in ins], ns, P, tensor.ptr, [m.ptr for m in masks], [p.ptr for p in pixs])
+    t_plain, t_knn = [], []
+    for r in range(a.warmup + a.reps):
+        k = r % len(raws)
+        t0 = time.perf_counter()
+        ctx.rangenet_label_device(ins[k].ptr, ns[k], pixs[k].ptr, masks[k].ptr, d_logits.ptr, P, labs[k].ptr)
+        t1 = time.perf_counter()
+        ctx.rangenet_label_knn_device(ins[k].ptr, ns[k], pixs[k].ptr, masks[k].ptr, d_logits.ptr, P, K, labs_knn[k].ptr)
+        t2 = time.perf_counter()
+        if r >= a.warmup:
+            t_plain.append(1e3 * (t1 - t0)); t_knn.append(1e3 * (t2 - t1))
+    a0 = lisreg.device_to_host(labs[0].ptr, (cap, 4), np.float32)[: ns[0], 3].view(np.uint32)
+    a1 = lisreg.device_to_host(labs_knn[0].ptr, (cap, 4), np.float32)[: ns[0], 3].view(np.uint32)
+    t_bplain, t_bknn = [], []
+    reps_b = max(a.reps // 8, 5)
+    B = a.batch
+    for r in range(2 + reps_b):
+        t0 = time.perf_counter()
+        ctx.rangenet_label_batch_device([b.ptr for b in ins[:B]], ns[:B], [p.ptr for p in pixs[:B]], [m.ptr for m in masks[:B]], lg_ptrs[:B], P,
+                                        [o.ptr for o in labs[:B]])
+        t1 = time.perf_counter()
+        ctx.rangenet_label_knn_batch_device([b.ptr for b in ins[:B]], ns[:B], [p.ptr for p in pixs[:B]], [m.ptr for m in masks[:B]], lg_ptrs[:B], P, K,
+                                            [o.ptr for o in labs_knn[:B]])
+        t2 = time.perf_counter()
+        if r >= 2:
+            t_bplain.append(1e3 * (t1 - t0) / B); t_bknn.append(1e3 * (t2 - t1) / B)
+    ctx.close()
+    pm, pi = med_iqr(t_plain)
+    km, ki = med_iqr(t_knn)
+    bpm, bpi = med_iqr(t_bplain)
+    bkm, bki = med_iqr(t_bknn)
+    line = dict(workload="rangenet_knn", sweep_shape=[a.h, a.w], image=[H, W], n_classes=NC, points=int(ns[0]), valid_pixels=int(n_valid[0]),
+                reps=a.reps, knn_params=[K.knn, K.search, K.sigma, K.cutoff, K.no_vote_label], labels_changed=int((a0 != a1).sum()),
+                plain_label_ms=pm, plain_label_iqr_ms=pi, knn_label_ms=km, knn_label_iqr_ms=ki, knn_over_plain=round(km / pm, 3),
+                batch_sweeps=B, batch_plain_label_ms_per_sweep=bpm, batch_plain_label_iqr_ms=bpi, batch_knn_label_ms_per_sweep=bkm,
+                batch_knn_label_iqr_ms=bki, batch_knn_over_plain=round(bkm / bpm, 3),
+                what="plain: rangenet_label_device (2 launches); knn: rangenet_label_knn_device (3 launches); alternating in one run, host clock "
+                     "around calls that end in a synchronise, medians and inter-quartile ranges; batch: the two batch calls, per sweep")
+    text = json.dumps(line)
+    print(text)
+    out = a.out or os.path.join(ROOT, "profiles", "rangenet_knn_bench.json")
+    with open(out, "w") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
@@ -48,7 +131,11 @@ def main():
     ap.add_argument("--sweeps", type=int, default=4, help="different sweeps the calls cycle through")
     ap.add_argument("--no-host", action="store_true", help="skip the numpy stand-in of the host path")
     ap.add_argument("--out", default="")
+    ap.add_argument("--knn", action="store_true", help="measure lisreg_rangenet_label_knn next to lisreg_rangenet_label instead")
+    ap.add_argument("--knn-params", default="5,5,1.0,1.0", help="knn,search,sigma,cutoff")
     a = ap.parse_args()
+    if a.knn:
+        return knn_bench(a)
     import lisreg
     from lisreg import replay
     raws = []
