@@ -857,6 +857,75 @@ int  lisreg_icp_gn_match(lisreg_ctx* ctx, int slot, const void* source, int n, i
                          unsigned max_iterations, float max_correspond_distance, const float predict_pose[16],
                          lisreg_icpgn_result* result, void* transformed_out);
 
+/* ---- §7j: Normal Distributions Transform registration (loop-closure verification) ------------------------------------
+ * select_registration_method("NDT") (src/core/registration.cpp:147-155) returns a pcl::NormalDistributionsTransform with
+ * epsilon 0.01, step size 0.1, resolution 1.0 and 35 iterations; detectLoopClosureForSubMap carries the same four settings as its
+ * first choice of verifier (src/node/subMapOptmizationNode.cpp:2756-2760).  The method: the target is cut into voxels of edge
+ * `resolution`, every voxel with enough points becomes a Gaussian (mean, inflated covariance), and Newton steps with a
+ * More-Thuente line search maximise the sum of the Gaussians' responses to the transformed source points (Magnusson 2009, eq.
+ * 6.8-6.21, algorithm 2).  The DEFINITION is tests/ndt_ref.py (PCL's source is not available to this project); it departs from
+ * what PCL is believed to do in four places:
+ *   - the transform: source points are transformed in double from their float coordinates (PCL transforms the cloud in float);
+ *   - the covariance normalisation: sum d d^T / (n - 1) around the double mean, two passes (PCL's is believed to differ by a
+ *     factor of the order (n - 1) / n);
+ *   - the angle chart: p = (tx, ty, tz, a, b, c), x' = Rx(a) Ry(b) Rz(c) x + t, a = atan2(-R12, R22), b = asin(R02),
+ *     c = atan2(-R01, R00) for a guess matrix; Eigen's [0, pi] eulerAngles convention is not reproduced (the output is the transform);
+ *   - the line-search flag: line_search = 1 runs More-Thuente with the interval starting NOT converged (strong Wolfe conditions,
+ *     at most 10 trials, the next trial selected before the interval is updated, a trial that coincides with an end point ends the
+ *     search); line_search = 0 is the behaviour of PCL releases remembered to start with the flag set, so that the loop never
+ *     runs: one evaluation at clamp(|delta|, transformation_epsilon / 2, step_size).
+ * The GPU evaluates score, gradient and Hessian (one lane per source point, fp64, fixed-order sums: two evaluations of the same
+ * input give the same bits); the 6 x 6 solve and the line search run on the host in double. */
+typedef struct lisreg_ndt_params {
+    double resolution;                  /* setResolution: voxel edge */
+    double step_size;                   /* setStepSize: the longest Newton step */
+    double transformation_epsilon;      /* setTransformationEpsilon */
+    double outlier_ratio;               /* 0.55 */
+    double min_covar_eigvalue_mult;     /* 0.01: the two smaller eigenvalues are raised to this fraction of the largest */
+    int    max_iters;                   /* setMaximumIterations */
+    int    min_points_per_voxel;        /* 6 */
+    int    line_search;                 /* 1 More-Thuente, 0 a single clamped step (see above) */
+    int    reserved;
+} lisreg_ndt_params;
+typedef struct lisreg_ndt_info {
+    int dims[3];                        /* voxel grid of the target */
+    int n_voxels;                       /* voxels holding at least one finite point */
+    int n_valid;                        /* voxels that became a Gaussian */
+    int reserved;
+} lisreg_ndt_info;
+typedef struct lisreg_ndt_result {
+    float  final_transform[16];         /* getFinalTransformation(), row-major 4x4 */
+    double p[6];                        /* tx, ty, tz, a, b, c of it */
+    int    converged;                   /* hasConverged() */
+    int    iters;
+    int    n_evals;                     /* evaluations of the score (with or without the Hessian) */
+    int    reserved;
+    long long n_pairs_last;             /* (source point, voxel) pairs of the last evaluation */
+    double score;                       /* of the last evaluation */
+    double trans_probability;           /* getTransformationProbability(): score / n */
+} lisreg_ndt_result;
+/* kind 0: {1.0, 0.1, 0.01, 0.55, 0.01, 35, 6, 1} */
+int  lisreg_ndt_default_params(int kind, lisreg_ndt_params* p);
+/* setInputTarget + setResolution: the Gaussians of `cloud` into NDT slot `slot` (0 .. 65535; NDT slots are apart from the map-index
+ * slots).  Uses resolution, min_points_per_voxel and min_covar_eigvalue_mult of `params`.  NaN points belong to no voxel.  Refused
+ * (LISREG_ERR_ARG): n <= 0, resolution <= 0, an infinite coordinate, a grid of more than 2^26 cells (the cell table is dense),
+ * a target without a valid voxel.  info may be NULL. */
+int  lisreg_ndt_set_target(lisreg_ctx* ctx, int slot, const void* cloud, int n, int stride_bytes, int fmt,
+                           const lisreg_ndt_params* params, lisreg_ndt_info* info);
+/* align(): guess = row-major 4x4 or NULL for identity; aligned_out: NULL, or room for n points of the input layout.  Host PCL
+ * structs or LISREG_FMT_DEVICE records.  params->resolution must be the slot's.  A source without a pair at the guess returns
+ * converged = 1, iters = 0 and the guess. */
+int  lisreg_ndt_align(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
+                      const lisreg_ndt_params* params, const float* guess, lisreg_ndt_result* result, void* aligned_out);
+/* test hooks: the valid voxels of a slot in ascending cell order (cell id = i + j * dims[0] + k * dims[0] * dims[1]; means [3],
+ * icov6 = xx, xy, xz, yy, yz, zz of the inverse covariance; *n_out = their number, copied only if it fits `capacity`), and one
+ * evaluation at p: out[28] = score, gradient [6], upper triangle of the Hessian row by row [21] (zeros without with_hessian) */
+int  lisreg_ndt_get_voxels(lisreg_ctx* ctx, int slot, int* cell_ids, int* counts, double* means, double* icov6, int capacity,
+                           int* n_out);
+int  lisreg_ndt_derivatives(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
+                            const lisreg_ndt_params* params, const double p[6], int with_hessian, double out[28],
+                            long long* n_pairs);
+
 /* ---- loop-closure candidate detection: FEPSC (src/core/epscGeneration.cpp) -------------------------------------------
  * EPSCGeneration::loopDetection (:663-992) with UsingFEPSCFlag (config/params.yaml:22-28), as loopClosureThread calls it for every
  * key frame (subMapOptmizationNode.cpp:2328-2362): its matched_frame_id / matched_frame_transform become loopKeyPre and the EPSC

@@ -110,6 +110,17 @@ struct MapIndex {
     const float4* raw_ptr = nullptr;
 };
 
+// the Gaussians of one NDT target (lisreg_ndt.hip: lisreg_ndt_set_target)
+struct NdtTarget {
+    bool      valid = false;
+    int       n_voxels = 0, n_occupied = 0, n_valid = 0;
+    int       dims[3] = { 1, 1, 1 }, min_b[3] = { 0, 0, 0 };
+    double    resolution = 0;
+    DevBuf    stats;               // [n_voxels][10] doubles: mean, upper triangle of the inverse covariance, finite points
+    DevBuf    vflag, cell;         // [n_voxels] ints: became a Gaussian / cell id
+    DevBuf    table;               // [dims product] ints: cell -> voxel with a Gaussian, -1 none
+};
+
 // device-resident sliding local map (lisreg_api_localmap.hip)
 struct LocalMap {
     bool   valid = false;
@@ -214,6 +225,11 @@ struct lisreg_ctx {
     int               gm_flip = 0;
     lisreg::DevBuf map_stage;                          // lisreg_map_index_set_batch: host clouds of a batch, packed, in one upload
     lisreg::DevBuf mp_pts, mp_flag, mp_pos, mp_idx, mp_cnt, mp_d2, mp_out, icp_state, icp_partials, icp_cur, icp_items, map_tab, map_tsegs, map_tblocks;
+    // NDT registration (lisreg_ndt.hip): targets by slot (apart from the map-index slots), the cleaned target cloud and the staged source,
+    // per-workgroup partial sums and their total, the voxel counters; pinned landing area of one evaluation
+    std::map<int, lisreg::NdtTarget> ndt;
+    lisreg::DevBuf ndt_pts, ndt_src, ndt_part, ndt_out, ndt_cnt;
+    lisreg::PinnedBuf ndt_host;
     lisreg::PinnedBuf done_host;            // one int
     lisreg::PinnedBuf stage_host;           // pinned staging of the per-batch tables
     lisreg::Event stage_done;

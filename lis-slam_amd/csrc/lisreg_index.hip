@@ -1857,6 +1857,11 @@ void launch_voxel_sort_multi(const float4* pts, int n, const VoxelMulti& m, int 
     exclusive_scan(head, slot, sb.scan_tmp, n, st);
 }
 
+void launch_voxel_starts(int n, const int* head, const int* slot, int* vstart, hipStream_t st)
+{
+    k_voxel_starts<<<(n + 255) / 256, 256, 0, st>>>(n, head, slot, vstart);
+}
+
 void launch_voxel_centroids(int n, int n_vox, const float4* pts, const uint32_t* labels, int w_mode, const int* order,
                             const int* head, const int* slot, int* vstart, float4* out_pts, uint32_t* out_labels,
                             hipStream_t st)

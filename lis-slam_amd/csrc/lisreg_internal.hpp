@@ -242,6 +242,8 @@ void launch_finalize(ItemState* items, int n_items, DevParams prm, float* result
 // §8 f-1 (lisreg_index.hip)
 void launch_voxel_sort(const float4* pts, int n, VoxelDesc d, int n_buckets, SortBuffers sb, int* order, uint32_t* sidx,
                        int* head, int* slot /* [n+1], slot[n] = number of voxels */, hipStream_t st);
+// vstart[v] = first sorted position of voxel v, vstart[n_vox] = n (the start pass of launch_voxel_centroids on its own)
+void launch_voxel_starts(int n, const int* head, const int* slot, int* vstart /* [n_vox+1] */, hipStream_t st);
 struct VoxelHandOut { int k; int vo[kVoxelMultiMax + 1]; float4* out[kVoxelMultiMax]; };
 void launch_bbox_multi(const float4* cat, const VoxelMulti& m, float* bbox_out /* [6 * k] */, float* scratch /* >= 6 * 64 * k floats */, hipStream_t st);
 struct BboxJobs { int k; int n[kVoxelMultiMax]; const float4* pts[kVoxelMultiMax]; };     // n == 0: the empty box (3e38, -3e38)

@@ -1,0 +1,631 @@
+// lisreg_ndt.hip — Normal Distributions Transform registration: the loop-closure verifier the reference names first
+// (pcl::NormalDistributionsTransform, src/core/registration.cpp:147-155, src/node/subMapOptmizationNode.cpp:2756-2760).
+// The definition is tests/ndt_ref.py.  GPU: the target's per-voxel Gaussians (pcl::VoxelGrid keys of lisreg_index.hip, then one lane or
+// one wavefront per voxel, fp64) and one evaluation of score / gradient / Hessian per call (one lane per source point, fp64, sums in a
+// fixed order: no floating-point atomics, the same input gives the same bits).  Host: the 6 x 6 solve and the More-Thuente line search
+// in double, one 29-double read-back per evaluation.  No CPU fallback.
+#include "lisreg_ctx.hpp"
+#include "lisreg_ndt_host.hpp"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+
+using namespace lisreg;
+using namespace lisreg::ndt_host;
+
+namespace {
+
+constexpr int kNdtBig   = 48;          // voxels with more points get a wavefront each (k_ndt_stats_big), the others a lane
+constexpr int kNdtRec   = 10;          // doubles per voxel: mean [3], upper triangle of the inverse covariance [6], finite points
+constexpr int kNdtOut   = 29;          // score, gradient [6], Hessian upper triangle [21], pairs
+constexpr long long kNdtMaxCells = 1LL << 26;
+
+// ---- target: NaN points out of the way ------------------------------------------------------------------------------------------
+// A point with a NaN coordinate belongs to no voxel.  It is moved onto the box's minimum corner and marked in .w, so that the voxel keys
+// of every record are inside the grid whatever a float -> int conversion makes of a NaN; the statistics skip the marked records.
+__global__ __launch_bounds__(256) void k_ndt_clean(const float4* __restrict__ in, int n, float lx, float ly, float lz, float4* __restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = in[i];
+    const bool bad = p.x != p.x || p.y != p.y || p.z != p.z;
+    out[i] = bad ? make_float4(lx, ly, lz, 1.0f) : make_float4(p.x, p.y, p.z, 0.0f);
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// cyclic Jacobi on the symmetric 3 x 3 (a00 .. a22), eigenvectors in the columns of v; every index is a compile-time constant
+#define NDT_ROT(app, aqq, apq, arp, arq, v0p, v0q, v1p, v1q, v2p, v2q)                                  \
+    if (apq != 0.0) {                                                                                     \
+        const double th = (aqq - app) / (2.0 * apq);                                                      \
+        const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));                    \
+        const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;                                           \
+        app -= t * apq; aqq += t * apq; apq = 0.0;                                                        \
+        const double rp = cs * arp - sn * arq, rq = sn * arp + cs * arq; arp = rp; arq = rq;              \
+        double x;                                                                                         \
+        x = cs * v0p - sn * v0q; v0q = sn * v0p + cs * v0q; v0p = x;                                      \
+        x = cs * v1p - sn * v1q; v1q = sn * v1p + cs * v1q; v1p = x;                                      \
+        x = cs * v2p - sn * v2q; v2q = sn * v2p + cs * v2q; v2p = x;                                      \
+    }
+
+// the Gaussian of one voxel from its mean-centred second moments S (already divided by n - 1): eigen-decomposition, the two smaller
+// eigenvalues raised to mult * the largest, inverse = V diag(1 / lambda) V^T.  False: not a valid voxel.
+__device__ bool ndt_gaussian(double a00, double a01, double a02, double a11, double a12, double a22, double mult, double ic[6])
+{
+    double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;
+    for (int sweep = 0; sweep < 40; ++sweep) {
+        const double off = fabs(a01) + fabs(a02) + fabs(a12);
+        if (!(off > 1.0e-22 * (fabs(a00) + fabs(a11) + fabs(a22)))) break;         // also ends on NaN
+        NDT_ROT(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21)
+        NDT_ROT(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22)
+        NDT_ROT(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22)
+    }
+    const double lmax = fmax(a00, fmax(a11, a22));
+    if (a00 < 0.0 || a11 < 0.0 || a22 < 0.0 || !(lmax > 0.0)) return false;
+    const double fl = mult * lmax;
+    const double i0 = 1.0 / fmax(a00, fl), i1 = 1.0 / fmax(a11, fl), i2 = 1.0 / fmax(a22, fl);
+    ic[0] = (i0 * v00 * v00 + i1 * v01 * v01) + i2 * v02 * v02;
+    ic[1] = (i0 * v00 * v10 + i1 * v01 * v11) + i2 * v02 * v12;
+    ic[2] = (i0 * v00 * v20 + i1 * v01 * v21) + i2 * v02 * v22;
+    ic[3] = (i0 * v10 * v10 + i1 * v11 * v11) + i2 * v12 * v12;
+    ic[4] = (i0 * v10 * v20 + i1 * v11 * v21) + i2 * v12 * v22;
+    ic[5] = (i0 * v20 * v20 + i1 * v21 * v21) + i2 * v22 * v22;
+    bool fin = true;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) fin = fin && isfinite(ic[k]);
+    return fin;
+}
+
+struct NdtBuild {
+    const float4*   pts;        // cleaned records
+    const int*      order;      // sorted position -> record
+    const uint32_t* sidx;       // sorted position -> cell id
+    const int*      vstart;     // [n_vox + 1]
+    int             n_vox, min_pts;
+    long long       n_cells;
+    double          mult;
+    double*         stats;      // [n_vox][kNdtRec]
+    int*            vflag;      // [n_vox]
+    int*            cell;       // [n_vox]
+    int*            table;      // [n_cells], -1 on entry
+    int*            counters;   // [0] voxels with a finite point, [1] valid voxels
+};
+
+// WAVE: the 64 lanes of a wavefront share voxel v (every lane ends up with the same sums: the butterfly adds the same pairs everywhere)
+template <bool WAVE>
+__device__ __forceinline__ void ndt_voxel(const NdtBuild& B, int v, int lane)
+{
+    const int a = B.vstart[v], b = B.vstart[v + 1];
+    const int step = WAVE ? 64 : 1;
+    double s0 = 0, s1 = 0, s2 = 0, cnt = 0;
+    for (int k = a + lane; k < b; k += step) {
+        const float4 p = B.pts[B.order[k]];
+        if (p.w != 0.0f) continue;
+        s0 += (double)p.x; s1 += (double)p.y; s2 += (double)p.z; cnt += 1.0;
+    }
+    if (WAVE) { s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); cnt = wave_sum(cnt); }
+    const int n = (int)cnt;
+    const uint32_t cid = B.sidx[a];
+    double rec[kNdtRec];
+#pragma unroll
+    for (int k = 0; k < kNdtRec; ++k) rec[k] = 0.0;
+    rec[9] = cnt;
+    bool ok = n >= B.min_pts && n >= 2;
+    if (ok) {                                                  // uniform across the wavefront: no lane leaves the shuffles below alone
+        const double m0 = s0 / cnt, m1 = s1 / cnt, m2 = s2 / cnt;
+        double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
+        for (int k = a + lane; k < b; k += step) {
+            const float4 p = B.pts[B.order[k]];
+            if (p.w != 0.0f) continue;
+            const double d0 = (double)p.x - m0, d1 = (double)p.y - m1, d2 = (double)p.z - m2;
+            c00 += d0 * d0; c01 += d0 * d1; c02 += d0 * d2; c11 += d1 * d1; c12 += d1 * d2; c22 += d2 * d2;
+        }
+        if (WAVE) { c00 = wave_sum(c00); c01 = wave_sum(c01); c02 = wave_sum(c02); c11 = wave_sum(c11); c12 = wave_sum(c12); c22 = wave_sum(c22); }
+        const double inv = 1.0 / (cnt - 1.0);
+        double ic[6];
+        ok = ndt_gaussian(c00 * inv, c01 * inv, c02 * inv, c11 * inv, c12 * inv, c22 * inv, B.mult, ic);
+        rec[0] = m0; rec[1] = m1; rec[2] = m2;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) rec[3 + k] = ok ? ic[k] : 0.0;
+    }
+    if (lane != 0) return;
+#pragma unroll
+    for (int k = 0; k < kNdtRec; ++k) B.stats[(size_t)v * kNdtRec + k] = rec[k];
+    B.vflag[v] = ok ? 1 : 0;
+    B.cell[v] = (int)cid;
+    if (n > 0) atomicAdd(&B.counters[0], 1);
+    if (ok) {
+        atomicAdd(&B.counters[1], 1);
+        if ((long long)cid < B.n_cells) B.table[cid] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ndt_stats_small(NdtBuild B)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= B.n_vox) return;
+    if (B.vstart[v + 1] - B.vstart[v] > kNdtBig) return;       // k_ndt_stats_big
+    ndt_voxel<false>(B, v, 0);
+}
+
+__global__ __launch_bounds__(64) void k_ndt_stats_big(NdtBuild B)
+{
+    const int v = blockIdx.x;
+    if (v >= B.n_vox) return;
+    if (B.vstart[v + 1] - B.vstart[v] <= kNdtBig) return;      // the whole wavefront leaves together
+    ndt_voxel<true>(B, v, (int)threadIdx.x);
+}
+
+// ---- one evaluation --------------------------------------------------------------------------------------------------------------
+struct NdtGrid {
+    const double* stats;
+    const int*    table;
+    int    d0, d1, d2, m0, m1, m2;
+    double inv_res, r2, g1, g2;                                 // 1 / resolution, resolution^2, the Gaussian constants d1, d2
+};
+
+// one lane per source point, one wavefront per workgroup, one partial record per workgroup
+template <bool HESS>
+__global__ __launch_bounds__(64) void k_ndt_eval(const float4* __restrict__ src, int n, NdtGrid G, NdtPose P, double* __restrict__ part)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    double acc[28];
+#pragma unroll
+    for (int k = 0; k < 28; ++k) acc[k] = 0.0;
+    double pairs = 0.0;
+    bool live = i < n;
+    double x0 = 0, x1 = 0, x2 = 0;
+    if (live) { const float4 s = src[i]; x0 = (double)s.x; x1 = (double)s.y; x2 = (double)s.z; }
+    const double t0 = ((P.R[0] * x0 + P.R[1] * x1) + P.R[2] * x2) + P.t[0];
+    const double t1 = ((P.R[3] * x0 + P.R[4] * x1) + P.R[5] * x2) + P.t[1];
+    const double t2 = ((P.R[6] * x0 + P.R[7] * x1) + P.R[8] * x2) + P.t[2];
+    live = live && t0 == t0 && t1 == t1 && t2 == t2;
+    if (live) {
+        double J[6][3] = { { 1, 0, 0 }, { 0, 1, 0 }, { 0, 0, 1 }, { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
+        double Hv[6][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int r = 0; r < 3; ++r) J[3 + k][r] = (P.dR[9 * k + 3 * r] * x0 + P.dR[9 * k + 3 * r + 1] * x1) + P.dR[9 * k + 3 * r + 2] * x2;
+        if (HESS) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+#pragma unroll
+                for (int r = 0; r < 3; ++r) Hv[k][r] = (P.ddR[9 * k + 3 * r] * x0 + P.ddR[9 * k + 3 * r + 1] * x1) + P.ddR[9 * k + 3 * r + 2] * x2;
+        }
+        const long long c0 = (long long)fmin(fmax(floor(t0 * G.inv_res), -2.0e9), 2.0e9) - G.m0;
+        const long long c1 = (long long)fmin(fmax(floor(t1 * G.inv_res), -2.0e9), 2.0e9) - G.m1;
+        const long long c2 = (long long)fmin(fmax(floor(t2 * G.inv_res), -2.0e9), 2.0e9) - G.m2;
+        for (int dz = -1; dz <= 1; ++dz) {
+            const long long z = c2 + dz;
+            if (z < 0 || z >= G.d2) continue;
+            for (int dy = -1; dy <= 1; ++dy) {
+                const long long y = c1 + dy;
+                if (y < 0 || y >= G.d1) continue;
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const long long x = c0 + dx;
+                    if (x < 0 || x >= G.d0) continue;
+                    const int v = G.table[x + y * G.d0 + z * (long long)G.d0 * G.d1];
+                    if (v < 0) continue;
+                    const double* __restrict__ rec = G.stats + (size_t)v * kNdtRec;
+                    const double q0 = t0 - rec[0], q1 = t1 - rec[1], q2 = t2 - rec[2];
+                    if (!((q0 * q0 + q1 * q1) + q2 * q2 <= G.r2)) continue;
+                    const double C[3][3] = { { rec[3], rec[4], rec[5] }, { rec[4], rec[6], rec[7] }, { rec[5], rec[7], rec[8] } };
+                    double cq[3];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) cq[r] = (C[r][0] * q0 + C[r][1] * q1) + C[r][2] * q2;
+                    const double e = exp(-G.g2 * ((q0 * cq[0] + q1 * cq[1]) + q2 * cq[2]) / 2.0);
+                    pairs += 1.0;
+                    acc[0] += -G.g1 * e;
+                    double w = G.g2 * e;
+                    if (w > 1.0 || w < 0.0 || w != w) continue;
+                    w *= G.g1;
+                    double cJ[6];
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) cJ[a] = (cq[0] * J[a][0] + cq[1] * J[a][1]) + cq[2] * J[a][2];
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) acc[1 + a] += w * cJ[a];
+                    if (HESS) {
+                        double CJ[6][3];
+#pragma unroll
+                        for (int a = 0; a < 6; ++a)
+#pragma unroll
+                            for (int r = 0; r < 3; ++r) CJ[a][r] = (C[r][0] * J[a][0] + C[r][1] * J[a][1]) + C[r][2] * J[a][2];
+#pragma unroll
+                        for (int a = 0; a < 6; ++a)
+#pragma unroll
+                            for (int b = a; b < 6; ++b) {
+                                double t = -G.g2 * cJ[a] * cJ[b] + ((J[b][0] * CJ[a][0] + J[b][1] * CJ[a][1]) + J[b][2] * CJ[a][2]);
+                                if (a >= 3) {
+                                    const int h = a == 3 ? b - 3 : (a == 4 ? b - 1 : 5);          // aa ab ac | bb bc | cc
+                                    t += (cq[0] * Hv[h][0] + cq[1] * Hv[h][1]) + cq[2] * Hv[h][2];
+                                }
+                                acc[7 + a * 6 - a * (a - 1) / 2 + (b - a)] += w * t;
+                            }
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 28; ++k) acc[k] = wave_sum(acc[k]);
+    pairs = wave_sum(pairs);
+    if (threadIdx.x == 0) {
+        double* o = part + (size_t)blockIdx.x * kNdtOut;
+#pragma unroll
+        for (int k = 0; k < 28; ++k) o[k] = acc[k];
+        o[28] = pairs;
+    }
+}
+
+// the partial records added in a fixed order: lane l takes records l, l + 64, ..., then the butterfly
+__global__ __launch_bounds__(64) void k_ndt_total(const double* __restrict__ part, int n_part, double* __restrict__ out)
+{
+    double acc[kNdtOut];
+#pragma unroll
+    for (int k = 0; k < kNdtOut; ++k) acc[k] = 0.0;
+    for (int b = (int)threadIdx.x; b < n_part; b += 64)
+#pragma unroll
+        for (int k = 0; k < kNdtOut; ++k) acc[k] += part[(size_t)b * kNdtOut + k];
+#pragma unroll
+    for (int k = 0; k < kNdtOut; ++k) acc[k] = wave_sum(acc[k]);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < kNdtOut; ++k) out[k] = acc[k];
+}
+
+int bad(lisreg_ctx* c, const std::string& msg) { return ctx_fail(c, LISREG_ERR_ARG, msg); }
+
+struct NdtRun {
+    lisreg_ctx*      c;
+    const NdtTarget* T;
+    const float4*    src;
+    int              n;
+    double           g1, g2;
+    double           out[kNdtOut];
+    int              n_evals = 0;
+};
+
+int evaluate(NdtRun& r, const double p[6], bool hess)
+{
+    lisreg_ctx* c = r.c;
+    hipStream_t st = c->stream;
+    NdtPose P;
+    pose_matrices(p, &P);
+    NdtGrid G;
+    G.stats = r.T->stats.as<double>(); G.table = r.T->table.as<int>();
+    G.d0 = r.T->dims[0]; G.d1 = r.T->dims[1]; G.d2 = r.T->dims[2];
+    G.m0 = r.T->min_b[0]; G.m1 = r.T->min_b[1]; G.m2 = r.T->min_b[2];
+    G.inv_res = 1.0 / r.T->resolution; G.r2 = r.T->resolution * r.T->resolution; G.g1 = r.g1; G.g2 = r.g2;
+    const int nb = (r.n + 63) / 64;
+    HIPCHK(c, c->ndt_part.ensure(sizeof(double) * kNdtOut * (size_t)nb));
+    HIPCHK(c, c->ndt_out.ensure(sizeof(double) * kNdtOut));
+    HIPCHK(c, c->ndt_host.ensure(sizeof(double) * kNdtOut, sizeof(double) * 64));
+    if (hess) k_ndt_eval<true><<<nb, 64, 0, st>>>(r.src, r.n, G, P, c->ndt_part.as<double>());
+    else      k_ndt_eval<false><<<nb, 64, 0, st>>>(r.src, r.n, G, P, c->ndt_part.as<double>());
+    k_ndt_total<<<1, 64, 0, st>>>(c->ndt_part.as<double>(), nb, c->ndt_out.as<double>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->ndt_host.p, c->ndt_out.p, sizeof(double) * kNdtOut, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(r.out, c->ndt_host.p, sizeof(double) * kNdtOut);
+    ++r.n_evals;
+    return LISREG_OK;
+}
+
+// phi(a), phi'(a) along `dir` from `base`
+int eval_along(NdtRun& r, const double base[6], const double dir[6], double a, bool hess, double* phi, double* dphi)
+{
+    double p[6];
+    for (int k = 0; k < 6; ++k) p[k] = base[k] + a * dir[k];
+    const int rc = evaluate(r, p, hess);
+    if (rc) return rc;
+    *phi = -r.out[0];
+    double d = 0;
+    for (int k = 0; k < 6; ++k) d += r.out[1 + k] * dir[k];
+    *dphi = -d;
+    return LISREG_OK;
+}
+
+int check_cloud(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, const char* who)
+{
+    if (n <= 0) return bad(c, std::string(who) + ": n <= 0");
+    if (!cloud) return bad(c, std::string(who) + ": NULL cloud");
+    if (fmt != LISREG_FMT_DEVICE && fmt != LISREG_FMT_XYZI && fmt != LISREG_FMT_XYZIL && fmt != LISREG_FMT_XYZIRT)
+        return bad(c, std::string(who) + ": unknown fmt");
+    if (fmt != LISREG_FMT_DEVICE && stride < 12) return bad(c, std::string(who) + ": stride < 12");
+    if (fmt == LISREG_FMT_XYZIL && stride < 22) return bad(c, std::string(who) + ": XYZIL needs stride >= 22");
+    return LISREG_OK;
+}
+
+// the cloud as 16-byte device records: the caller's memory for LISREG_FMT_DEVICE, else packed and uploaded into `buf`
+int stage(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, DevBuf& buf, const float4** out)
+{
+    if (fmt == LISREG_FMT_DEVICE) { *out = static_cast<const float4*>(cloud); return LISREG_OK; }
+    std::vector<lisreg_dpoint> h((size_t)n);
+    pack_cloud(cloud, n, stride, fmt, h.data());
+    HIPCHK(c, buf.ensure(sizeof(float4) * (size_t)n));
+    HIPCHK(c, hipMemcpyAsync(buf.p, h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // h is a local
+    *out = buf.as<float4>();
+    return LISREG_OK;
+}
+
+int find_target(lisreg_ctx* c, int slot, const lisreg_ndt_params* P, const char* who, NdtTarget** out)
+{
+    auto it = c->ndt.find(slot);
+    if (slot < 0 || it == c->ndt.end() || !it->second.valid)
+        return ctx_fail(c, LISREG_ERR_NO_TARGET, std::string(who) + ": no NDT target in this slot (lisreg_ndt_set_target)");
+    if (P && P->resolution != it->second.resolution) return bad(c, std::string(who) + ": params->resolution differs from the slot's");
+    *out = &it->second;
+    return LISREG_OK;
+}
+
+int check_params(lisreg_ctx* c, const lisreg_ndt_params* P, const char* who)
+{
+    if (!P) return bad(c, std::string(who) + ": NULL params");
+    if (!(P->resolution > 0) || !std::isfinite(P->resolution)) return bad(c, std::string(who) + ": resolution <= 0");
+    if (!(P->outlier_ratio > 0 && P->outlier_ratio < 1)) return bad(c, std::string(who) + ": outlier_ratio outside (0, 1)");
+    if (!(P->step_size > 0) || !(P->transformation_epsilon > 0) || P->max_iters < 0 || !(P->min_covar_eigvalue_mult >= 0))
+        return bad(c, std::string(who) + ": bad step_size / transformation_epsilon / max_iters / min_covar_eigvalue_mult");
+    return LISREG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lisreg_ndt_default_params(int kind, lisreg_ndt_params* p)
+{
+    if (!p || kind != 0) return LISREG_ERR_ARG;
+    *p = lisreg_ndt_params{ 1.0, 0.1, 0.01, 0.55, 0.01, 35, 6, 1, 0 };
+    return LISREG_OK;
+}
+
+int lisreg_ndt_set_target(lisreg_ctx* c, int slot, const void* cloud, int n, int stride, int fmt, const lisreg_ndt_params* P,
+                          lisreg_ndt_info* info)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (slot < 0 || slot > 65535) return bad(c, "ndt_set_target: bad slot");
+    int rc = check_params(c, P, "ndt_set_target");
+    if (rc) return rc;
+    rc = check_cloud(c, cloud, n, stride, fmt, "ndt_set_target");
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    NdtTarget& T = c->ndt[slot];
+    T.valid = false;
+    const float4* raw = nullptr;
+    rc = stage(c, cloud, n, stride, fmt, c->ndt_src, &raw);
+    if (rc) return rc;
+    // ---- bounding box (each coordinate's finite minimum / maximum) and the pcl::VoxelGrid geometry ----------------------------------
+    float bb[6];
+    HIPCHK(c, c->bbox_dev.ensure(sizeof(float) * 8));
+    HIPCHK(c, c->bbox_scratch.ensure(sizeof(float) * 6 * 256));
+    launch_bbox(raw, n, c->bbox_dev.as<float>(), c->bbox_scratch.as<float>(), st);
+    HIPCHK(c, hipMemcpyAsync(bb, c->bbox_dev.p, sizeof bb, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(bb[k])) return bad(c, "ndt_set_target: the cloud has infinite coordinates");
+    if (!(bb[0] <= bb[3] && bb[1] <= bb[4] && bb[2] <= bb[5])) return bad(c, "ndt_set_target: the cloud has no finite point: no valid voxel");
+    const float inv = 1.0f / (float)P->resolution;
+    VoxelDesc d;
+    long long div_b[3];
+    const double lim = 2.0e9;
+    for (int k = 0; k < 3; ++k) {
+        const double lo = floor((double)(bb[k] * inv)), hi = floor((double)(bb[3 + k] * inv));
+        if (!(fabs(lo) < lim && fabs(hi) < lim)) return bad(c, "ndt_set_target: the grid has more than 2^26 cells (resolution too small for this cloud)");
+        T.min_b[k] = (int)floorf(bb[k] * inv);
+        div_b[k] = (long long)floorf(bb[3 + k] * inv) - T.min_b[k] + 1;
+    }
+    if (div_b[0] > kNdtMaxCells || div_b[1] > kNdtMaxCells || div_b[2] > kNdtMaxCells || div_b[0] * div_b[1] > kNdtMaxCells ||
+        div_b[0] * div_b[1] * div_b[2] > kNdtMaxCells)
+        return bad(c, "ndt_set_target: the grid has more than 2^26 cells (the cell table is dense; resolution too small for this cloud)");
+    const long long total = div_b[0] * div_b[1] * div_b[2];
+    for (int k = 0; k < 3; ++k) T.dims[k] = (int)div_b[k];
+    d.inv_leaf = inv; d.min_b0 = T.min_b[0]; d.min_b1 = T.min_b[1]; d.min_b2 = T.min_b[2];
+    d.mul1 = T.dims[0]; d.mul2 = T.dims[0] * T.dims[1];
+    const long long max_buckets = 1LL << 22;
+    d.span = (uint32_t)std::max(1LL, (total + max_buckets - 1) / max_buckets);
+    const int n_buckets = (int)((total + d.span - 1) / d.span);
+    // ---- NaN points aside, sort by voxel, voxel starts (the launches of lisreg_voxel_downsample) -------------------------------------
+    HIPCHK(c, c->ndt_pts.ensure(sizeof(float4) * (size_t)n));
+    k_ndt_clean<<<(n + 255) / 256, 256, 0, st>>>(raw, n, bb[0], bb[1], bb[2], c->ndt_pts.as<float4>());
+    rc = ensure_sort_scratch(c, (size_t)n, (size_t)std::max(n_buckets, n) + 1);
+    if (rc) return rc;
+    HIPCHK(c, c->vox_order.ensure(sizeof(int) * (size_t)n));
+    HIPCHK(c, c->vox_sidx.ensure(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(c, c->vox_head.ensure(sizeof(int) * ((size_t)n + 1)));
+    HIPCHK(c, c->vox_slot.ensure(sizeof(int) * ((size_t)n + 2)));
+    launch_voxel_sort(c->ndt_pts.as<float4>(), n, d, n_buckets, sort_buffers(c), c->vox_order.as<int>(), c->vox_sidx.as<uint32_t>(),
+                      c->vox_head.as<int>(), c->vox_slot.as<int>(), st);
+    int n_vox = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_vox, c->vox_slot.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (n_vox < 1 || n_vox > n) return ctx_fail(c, LISREG_ERR_HIP, "ndt_set_target: the voxel sort returned an impossible voxel count");
+    HIPCHK(c, c->vox_start.ensure(sizeof(int) * ((size_t)n_vox + 2)));
+    launch_voxel_starts(n, c->vox_head.as<int>(), c->vox_slot.as<int>(), c->vox_start.as<int>(), st);
+    // ---- the Gaussians ------------------------------------------------------------------------------------------------------------------
+    HIPCHK(c, T.stats.ensure(sizeof(double) * kNdtRec * (size_t)n_vox));
+    HIPCHK(c, T.vflag.ensure(sizeof(int) * (size_t)n_vox));
+    HIPCHK(c, T.cell.ensure(sizeof(int) * (size_t)n_vox));
+    HIPCHK(c, T.table.ensure(sizeof(int) * (size_t)total));
+    HIPCHK(c, c->ndt_cnt.ensure(sizeof(int) * 4));
+    HIPCHK(c, hipMemsetAsync(T.table.p, 0xFF, sizeof(int) * (size_t)total, st));
+    HIPCHK(c, hipMemsetAsync(c->ndt_cnt.p, 0, sizeof(int) * 4, st));
+    NdtBuild B;
+    B.pts = c->ndt_pts.as<float4>(); B.order = c->vox_order.as<int>(); B.sidx = c->vox_sidx.as<uint32_t>(); B.vstart = c->vox_start.as<int>();
+    B.n_vox = n_vox; B.min_pts = P->min_points_per_voxel; B.n_cells = total; B.mult = P->min_covar_eigvalue_mult;
+    B.stats = T.stats.as<double>(); B.vflag = T.vflag.as<int>(); B.cell = T.cell.as<int>(); B.table = T.table.as<int>();
+    B.counters = c->ndt_cnt.as<int>();
+    k_ndt_stats_small<<<(n_vox + 255) / 256, 256, 0, st>>>(B);
+    k_ndt_stats_big<<<n_vox, 64, 0, st>>>(B);
+    HIPCHK(c, hipGetLastError());
+    int cnt[2] = { 0, 0 };
+    HIPCHK(c, hipMemcpyAsync(cnt, c->ndt_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    T.n_voxels = n_vox; T.n_occupied = cnt[0]; T.n_valid = cnt[1]; T.resolution = P->resolution;
+    if (info) { for (int k = 0; k < 3; ++k) info->dims[k] = T.dims[k]; info->n_voxels = cnt[0]; info->n_valid = cnt[1]; info->reserved = 0; }
+    if (cnt[1] < 1) return bad(c, "ndt_set_target: the target has no valid voxel (min_points_per_voxel points with a positive-definite covariance)");
+    T.valid = true;
+    return LISREG_OK;
+}
+
+int lisreg_ndt_get_voxels(lisreg_ctx* c, int slot, int* cell_ids, int* counts, double* means, double* icov6, int capacity, int* n_out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    NdtTarget* T = nullptr;
+    int rc = find_target(c, slot, nullptr, "ndt_get_voxels", &T);
+    if (rc) return rc;
+    if (!n_out || capacity < 0) return bad(c, "ndt_get_voxels: bad arguments");
+    *n_out = T->n_valid;
+    if (T->n_valid > capacity) return LISREG_OK;
+    if (!cell_ids || !counts || !means || !icov6) return bad(c, "ndt_get_voxels: NULL output");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<double> st((size_t)T->n_voxels * kNdtRec);
+    std::vector<int> fl((size_t)T->n_voxels), ce((size_t)T->n_voxels);
+    HIPCHK(c, hipMemcpyAsync(st.data(), T->stats.p, sizeof(double) * st.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(fl.data(), T->vflag.p, sizeof(int) * fl.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ce.data(), T->cell.p, sizeof(int) * ce.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int m = 0;
+    for (int v = 0; v < T->n_voxels && m < capacity; ++v) {
+        if (!fl[(size_t)v]) continue;
+        const double* r = &st[(size_t)v * kNdtRec];
+        cell_ids[m] = ce[(size_t)v]; counts[m] = (int)r[9];
+        memcpy(means + 3 * (size_t)m, r, sizeof(double) * 3);
+        memcpy(icov6 + 6 * (size_t)m, r + 3, sizeof(double) * 6);
+        ++m;
+    }
+    return LISREG_OK;
+}
+
+int lisreg_ndt_derivatives(lisreg_ctx* c, int slot, const void* source, int n, int stride, int fmt, const lisreg_ndt_params* P,
+                           const double p[6], int with_hessian, double out[28], long long* n_pairs)
+{
+    if (!c) return LISREG_ERR_ARG;
+    int rc = check_params(c, P, "ndt_derivatives");
+    if (rc) return rc;
+    NdtTarget* T = nullptr;
+    rc = find_target(c, slot, P, "ndt_derivatives", &T);
+    if (rc) return rc;
+    rc = check_cloud(c, source, n, stride, fmt, "ndt_derivatives");
+    if (rc) return rc;
+    if (!p || !out) return bad(c, "ndt_derivatives: NULL p / out");
+    HIPCHK(c, hipSetDevice(c->device));
+    NdtRun r; r.c = c; r.T = T; r.n = n;
+    rc = stage(c, source, n, stride, fmt, c->ndt_src, &r.src);
+    if (rc) return rc;
+    gauss_constants(P->outlier_ratio, P->resolution, &r.g1, &r.g2);
+    rc = evaluate(r, p, with_hessian != 0);
+    if (rc) return rc;
+    memcpy(out, r.out, sizeof(double) * 28);
+    if (n_pairs) *n_pairs = (long long)r.out[28];
+    return LISREG_OK;
+}
+
+int lisreg_ndt_align(lisreg_ctx* c, int slot, const void* source, int n, int stride, int fmt, const lisreg_ndt_params* P,
+                     const float* guess, lisreg_ndt_result* res, void* aligned_out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    int rc = check_params(c, P, "ndt_align");
+    if (rc) return rc;
+    NdtTarget* T = nullptr;
+    rc = find_target(c, slot, P, "ndt_align", &T);
+    if (rc) return rc;
+    rc = check_cloud(c, source, n, stride, fmt, "ndt_align");
+    if (rc) return rc;
+    if (!res) return bad(c, "ndt_align: NULL result");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    NdtRun r; r.c = c; r.T = T; r.n = n;
+    rc = stage(c, source, n, stride, fmt, c->ndt_src, &r.src);
+    if (rc) return rc;
+    gauss_constants(P->outlier_ratio, P->resolution, &r.g1, &r.g2);
+    double p[6];
+    p_from_matrix(guess, p);
+    const double eps = P->transformation_epsilon;
+    rc = evaluate(r, p, true);
+    if (rc) return rc;
+    int iters = 0;
+    bool converged = false;
+    while (!converged) {
+        double Hm[36], g[6], delta[6];
+        for (int k = 0; k < 6; ++k) g[k] = r.out[1 + k];
+        for (int i = 0, k = 7; i < 6; ++i)
+            for (int j = i; j < 6; ++j, ++k) Hm[6 * i + j] = Hm[6 * j + i] = r.out[k];
+        solve_step(Hm, g, delta);
+        double nrm = 0;
+        for (int k = 0; k < 6; ++k) nrm += delta[k] * delta[k];
+        nrm = sqrt(nrm);
+        if (nrm == 0 || std::isnan(nrm)) { converged = !std::isnan(nrm); break; }
+        for (int k = 0; k < 6; ++k) delta[k] /= nrm;
+        const double phi_0 = -r.out[0];
+        double d_phi_0 = 0;
+        for (int k = 0; k < 6; ++k) d_phi_0 += g[k] * delta[k];
+        d_phi_0 = -d_phi_0;
+        double a_t = 0.0;
+        if (d_phi_0 != 0) {
+            if (d_phi_0 > 0) { d_phi_0 = -d_phi_0; for (int k = 0; k < 6; ++k) delta[k] = -delta[k]; }
+            double base[6];
+            memcpy(base, p, sizeof base);
+            if (P->line_search) {
+                int trials = 0;
+                rc = line_search_mt([&](double a, bool hess, double* f, double* gd) { return eval_along(r, base, delta, a, hess, f, gd); },
+                                    phi_0, d_phi_0, nrm, P->step_size, eps / 2, &a_t, &trials);
+                if (rc) return rc;
+                if (trials) {                               // one Hessian pass at the accepted step
+                    double f, gd;
+                    rc = eval_along(r, base, delta, a_t, true, &f, &gd);
+                    if (rc) return rc;
+                }
+            } else {
+                a_t = std::min(std::max(nrm, eps / 2), P->step_size);
+                double f, gd;
+                rc = eval_along(r, base, delta, a_t, true, &f, &gd);
+                if (rc) return rc;
+            }
+            for (int k = 0; k < 6; ++k) p[k] = base[k] + a_t * delta[k];
+        }
+        if (iters > P->max_iters || (iters && fabs(a_t) < eps)) converged = true;
+        ++iters;
+    }
+    NdtPose Pm;
+    pose_matrices(p, &Pm);
+    float* F = res->final_transform;
+    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) F[4 * i + j] = (float)Pm.R[3 * i + j]; F[4 * i + 3] = (float)p[i]; }
+    F[12] = F[13] = F[14] = 0.f; F[15] = 1.f;
+    memcpy(res->p, p, sizeof p);
+    res->converged = converged ? 1 : 0; res->iters = iters; res->n_evals = r.n_evals; res->reserved = 0;
+    res->n_pairs_last = (long long)r.out[28];
+    res->score = r.out[0]; res->trans_probability = r.out[0] / (double)n;
+    if (aligned_out) {                                    // `output` of align(): the source under the final transformation
+        HIPCHK(c, c->vox_M.ensure(sizeof(float) * 12));
+        HIPCHK(c, hipMemcpyAsync(c->vox_M.p, F, sizeof(float) * 12, hipMemcpyHostToDevice, st));
+        if (fmt == LISREG_FMT_DEVICE) {
+            launch_transform_cloud(r.src, n, c->vox_M.as<float>(), static_cast<float4*>(aligned_out), st);
+            HIPCHK(c, hipStreamSynchronize(st));
+        } else {
+            HIPCHK(c, c->ndt_pts.ensure(sizeof(float4) * (size_t)n));
+            launch_transform_cloud(r.src, n, c->vox_M.as<float>(), c->ndt_pts.as<float4>(), st);
+            std::vector<float4> hp((size_t)n);
+            HIPCHK(c, hipMemcpyAsync(hp.data(), c->ndt_pts.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            const unsigned char* b = static_cast<const unsigned char*>(source);
+            unsigned char* o = static_cast<unsigned char*>(aligned_out);
+            for (int i = 0; i < n; ++i) {
+                if (o != b) memcpy(o + (size_t)i * (size_t)stride, b + (size_t)i * (size_t)stride, (size_t)stride);
+                memcpy(o + (size_t)i * (size_t)stride, &hp[(size_t)i], 12);
+            }
+        }
+    }
+    return LISREG_OK;
+}
+
+}  // extern "C"

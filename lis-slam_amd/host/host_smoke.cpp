@@ -111,6 +111,18 @@ int main()
     std::printf("ICP: converged=%d iterations=%d fitness=%g t=[%g %g %g] yaw=%g\n", (int)icp.hasConverged(), icp.nr_iterations(),
                 icp.getFitnessScore(), Fm[3], Fm[7], Fm[11], std::atan2(Fm[4], Fm[0]));
     ok = ok && icp.hasConverged() && std::fabs(Fm[3] - tx) < 5e-2f && std::fabs(Fm[7] - ty) < 5e-2f && std::fabs(std::atan2(Fm[4], Fm[0]) - yaw) < 5e-3f;
+    // NDT with the settings of select_registration_method("NDT") (registration.cpp:147-155), from ICP's pose
+    NdtRegistration<PointType> ndt(reg.handle(), 0, 3);
+    ndt.setTransformationEpsilon(0.01); ndt.setStepSize(0.1); ndt.setResolution(1.0f); ndt.setMaximumIterations(35);
+    ndt.setInputTarget(mapSurf);
+    ndt.setInputSource(&surf);
+    PointCloud<PointType> ndtOut;
+    ndt.align(ndtOut, Fm);
+    const float* Nm = ndt.getFinalTransformation();
+    std::printf("NDT: %d of %d voxels valid, converged=%d iterations=%d evaluations=%d probability=%g fitness=%g t=[%g %g %g] yaw=%g\n",
+                ndt.info().n_valid, ndt.info().n_voxels, (int)ndt.hasConverged(), ndt.getFinalNumIteration(), ndt.result().n_evals,
+                ndt.getTransformationProbability(), ndt.getFitnessScore(), Nm[3], Nm[7], Nm[11], std::atan2(Nm[4], Nm[0]));
+    ok = ok && ndt.info().n_valid > 0 && ndtOut.size() == surf.size();      // the pose is held against the definition in tests/test_ndt.py
     // OptimizedICPGN (registration.cpp:19-115) on the same pair
     OptimizedICPGN<PointType> gn(reg.handle(), 2, 15, 4.0f);
     gn.SetTargetCloud(mapSurf);

@@ -447,6 +447,58 @@ private:
     lisreg_icp_result res_{};
 };
 
+// ---- pcl::NormalDistributionsTransform as select_registration_method("NDT") sets it up -------------------------
+// (src/core/registration.cpp:147-155; subMapOptmizationNode.cpp:2756-2760: epsilon 0.01, step size 0.1, resolution 1.0, 35 iterations),
+// with the pcl::Registration surface the loop-closure code uses.  ndt_slot: the NDT target slot; map_slot: a map-index slot of the same
+// target for getFitnessScore (mean squared k = 1 distance of the aligned source, unbounded like PCL's default).
+template <class PointT>
+class NdtRegistration {
+public:
+    NdtRegistration(lisreg_ctx* ctx, int ndt_slot, int map_slot) : tree_(ctx, map_slot), ndt_slot_(ndt_slot) { lisreg_ndt_default_params(0, &prm_); }
+    void setTransformationEpsilon(double e) { prm_.transformation_epsilon = e; }
+    void setStepSize(double s) { prm_.step_size = s; }
+    void setResolution(float r) { prm_.resolution = r; if (target_) setInputTarget(*target_); }
+    void setMaximumIterations(int n) { prm_.max_iters = n; }
+    void setOulierRatio(double o) { prm_.outlier_ratio = o; }          // PCL's spelling
+    void setLineSearch(bool more_thuente) { prm_.line_search = more_thuente ? 1 : 0; }
+    void setInputTarget(const PointCloud<PointT>& cloud) {
+        target_ = &cloud;
+        check(lisreg_ndt_set_target(tree_.ctx(), ndt_slot_, cloud.points.data(), (int)cloud.size(), (int)sizeof(PointT), SearchTree<PointT>::fmt(), &prm_, &info_));
+        tree_.setInputCloud(cloud);
+    }
+    void setInputSource(const PointCloud<PointT>* cloud) { source_ = cloud; }
+    void align(PointCloud<PointT>& output, const float* guess = nullptr) {
+        if (!source_) throw RegistrationError(LISREG_ERR_ARG, "NDT: no input source");
+        output.points.resize(source_->size());
+        check(lisreg_ndt_align(tree_.ctx(), ndt_slot_, source_->points.data(), (int)source_->size(), (int)sizeof(PointT),
+                               SearchTree<PointT>::fmt(), &prm_, guess, &res_, output.points.data()));
+        std::vector<int> idx(output.size());
+        std::vector<float> d2(output.size());
+        check(lisreg_nearest(tree_.ctx(), tree_.slot(), output.points.data(), (int)output.size(), (int)sizeof(PointT), SearchTree<PointT>::fmt(),
+                             1e18f, idx.data(), d2.data()));
+        double sum = 0; size_t nr = 0;
+        for (size_t i = 0; i < d2.size(); ++i) if (idx[i] >= 0) { sum += d2[i]; ++nr; }
+        fitness_ = nr ? sum / (double)nr : 1.7976931348623157e308;
+    }
+    bool hasConverged() const { return res_.converged != 0; }
+    double getFitnessScore() const { return fitness_; }
+    double getTransformationProbability() const { return res_.trans_probability; }
+    const float* getFinalTransformation() const { return res_.final_transform; }     // row-major 4x4
+    int getFinalNumIteration() const { return res_.iters; }
+    const lisreg_ndt_info& info() const { return info_; }
+    const lisreg_ndt_result& result() const { return res_; }
+private:
+    void check(int rc) { if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(tree_.ctx())); }
+    SearchTree<PointT> tree_;
+    int ndt_slot_;
+    const PointCloud<PointT>* target_ = nullptr;
+    const PointCloud<PointT>* source_ = nullptr;
+    lisreg_ndt_params prm_{};
+    lisreg_ndt_info   info_{};
+    lisreg_ndt_result res_{};
+    double fitness_ = 1.7976931348623157e308;
+};
+
 // OptimizedICPGN (src/include/registration.h:44-70, src/core/registration.cpp:8-115): same constructor and calls
 template <class PointT>
 class OptimizedICPGN {

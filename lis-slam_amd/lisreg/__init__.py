@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "lisreg_default_rangenet_params", "lisreg_rangenet_project", "lisreg_rangenet_project_batch", "lisreg_rangenet_label",
     "lisreg_rangenet_label_batch",
     "lisreg_default_rangenet_knn_params", "lisreg_rangenet_knn_weights", "lisreg_rangenet_label_knn", "lisreg_rangenet_label_knn_batch",
+    "lisreg_ndt_default_params", "lisreg_ndt_set_target", "lisreg_ndt_align", "lisreg_ndt_get_voxels", "lisreg_ndt_derivatives",
 ]
 
 
@@ -66,6 +67,27 @@ class IcpResult(C.Structure):
     def as_dict(self):
         return dict(T=np.array(list(self.final_transform), np.float32).reshape(4, 4), converged=bool(self.converged),
                     iters=self.iters, state=self.state, n_corr_last=self.n_corr_last, fitness=self.fitness, prev_mse=self.prev_mse)
+
+
+class NdtParams(C.Structure):
+    _fields_ = [("resolution", C.c_double), ("step_size", C.c_double), ("transformation_epsilon", C.c_double),
+                ("outlier_ratio", C.c_double), ("min_covar_eigvalue_mult", C.c_double), ("max_iters", C.c_int),
+                ("min_points_per_voxel", C.c_int), ("line_search", C.c_int), ("reserved", C.c_int)]
+
+
+class NdtInfo(C.Structure):
+    _fields_ = [("dims", C.c_int * 3), ("n_voxels", C.c_int), ("n_valid", C.c_int), ("reserved", C.c_int)]
+
+
+class NdtResult(C.Structure):
+    _fields_ = [("final_transform", C.c_float * 16), ("p", C.c_double * 6), ("converged", C.c_int), ("iters", C.c_int),
+                ("n_evals", C.c_int), ("reserved", C.c_int), ("n_pairs_last", C.c_longlong), ("score", C.c_double),
+                ("trans_probability", C.c_double)]
+
+    def as_dict(self):
+        return dict(T=np.array(list(self.final_transform), np.float32).reshape(4, 4), p=np.array(list(self.p)),
+                    converged=bool(self.converged), iters=self.iters, n_evals=self.n_evals, n_pairs_last=self.n_pairs_last,
+                    score=self.score, trans_probability=self.trans_probability)
 
 
 class GuessInput(C.Structure):
@@ -421,8 +443,24 @@ def lib():
         L.lisreg_loopdet_candidate_scores.argtypes = [vp, C.c_int, C.c_int, C.POINTER(LoopdetKindScores), C.c_int, ip]
         L.lisreg_loopdet_get_descriptor.argtypes = [vp, C.c_int, C.c_int, C.c_uint, u8p]
         L.lisreg_loop_descriptor_kind.argtypes = [vp, C.c_uint, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, fp, u8p]
+        dbl = C.POINTER(C.c_double)
+        L.lisreg_ndt_default_params.argtypes = [C.c_int, C.POINTER(NdtParams)]
+        L.lisreg_ndt_set_target.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(NdtParams), C.POINTER(NdtInfo)]
+        L.lisreg_ndt_align.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(NdtParams), fp, C.POINTER(NdtResult), vp]
+        L.lisreg_ndt_get_voxels.argtypes = [vp, C.c_int, ip, ip, dbl, dbl, C.c_int, ip]
+        L.lisreg_ndt_derivatives.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(NdtParams), dbl, C.c_int, dbl,
+                                             C.POINTER(C.c_longlong)]
         _lib = L
     return _lib
+
+
+def ndt_default_params(kind: int = 0, **overrides) -> NdtParams:
+    p = NdtParams()
+    if lib().lisreg_ndt_default_params(kind, C.byref(p)):
+        raise LisregError(ERR_ARG, "lisreg_ndt_default_params")
+    for k, v in overrides.items():
+        setattr(p, k, v)
+    return p
 
 
 def localmap_default_params() -> LocalMapParams:
@@ -1406,6 +1444,59 @@ class Context:
         self._chk(self._L.lisreg_icp_align(self._h, slot, C.c_void_p(src_ptr), n, 16, FMT_DEVICE, C.byref(params), g,
                                            C.byref(res), C.c_void_p(out_ptr) if out_ptr else None))
         return res.as_dict()
+
+    # -- §7j: NDT registration ---------------------------------------------------------------------------
+    @staticmethod
+    def _cloud_args(cloud):
+        """(pointer, n, stride, fmt) of a host PCL-struct array or of a (device_ptr, n) tuple of 16-byte records"""
+        if isinstance(cloud, tuple):
+            return C.c_void_p(cloud[0]), int(cloud[1]), 16, FMT_DEVICE, None
+        cloud = np.ascontiguousarray(cloud)
+        return _vp(cloud), len(cloud), cloud.dtype.itemsize, _fmt_of(cloud), cloud
+
+    def ndt_set_target(self, slot: int, cloud, params: "NdtParams") -> dict:
+        """setInputTarget + setResolution; cloud = host PCL-struct array or (device_ptr, n)"""
+        ptr, n, stride, fmt, _keep = self._cloud_args(cloud)
+        info = NdtInfo()
+        self._chk(self._L.lisreg_ndt_set_target(self._h, slot, ptr, n, stride, fmt, C.byref(params), C.byref(info)))
+        return dict(dims=list(info.dims), n_voxels=info.n_voxels, n_valid=info.n_valid)
+
+    def ndt_align(self, slot: int, source, params: "NdtParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
+        """pcl::NormalDistributionsTransform::align against the NDT target in `slot`; returns the result dict (+ 'aligned')."""
+        ptr, n, stride, fmt, keep = self._cloud_args(source)
+        res = NdtResult()
+        g = None if guess is None else np.ascontiguousarray(guess, np.float32).ravel().ctypes.data_as(C.POINTER(C.c_float))
+        out = np.zeros_like(keep) if (want_aligned and keep is not None) else None
+        o = C.c_void_p(out_ptr) if out_ptr else (_vp(out) if out is not None else None)
+        self._chk(self._L.lisreg_ndt_align(self._h, slot, ptr, n, stride, fmt, C.byref(params), g, C.byref(res), o))
+        d = res.as_dict()
+        if out is not None:
+            d["aligned"] = out
+        return d
+
+    def ndt_get_voxels(self, slot: int) -> dict:
+        """the valid voxels of an NDT target in ascending cell order: cell_ids, counts, means [m, 3], icov6 [m, 6]"""
+        m = C.c_int(0)
+        self._chk(self._L.lisreg_ndt_get_voxels(self._h, slot, None, None, None, None, 0, C.byref(m)))
+        cap = max(m.value, 1)
+        ids, cnt = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        means, ic = np.zeros((cap, 3)), np.zeros((cap, 6))
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        self._chk(self._L.lisreg_ndt_get_voxels(self._h, slot, ids.ctypes.data_as(ip), cnt.ctypes.data_as(ip), means.ctypes.data_as(dp),
+                                                ic.ctypes.data_as(dp), cap, C.byref(m)))
+        k = m.value
+        return dict(cell_ids=ids[:k], counts=cnt[:k], means=means[:k], icov6=ic[:k])
+
+    def ndt_derivatives(self, slot: int, source, params: "NdtParams", p, with_hessian: bool = True):
+        """one evaluation at p = (tx, ty, tz, a, b, c): (out [28] = score, gradient, Hessian upper triangle; pairs)"""
+        ptr, n, stride, fmt, _keep = self._cloud_args(source)
+        p = np.ascontiguousarray(p, np.float64)
+        out = np.zeros(28)
+        pairs = C.c_longlong(0)
+        dp = C.POINTER(C.c_double)
+        self._chk(self._L.lisreg_ndt_derivatives(self._h, slot, ptr, n, stride, fmt, C.byref(params), p.ctypes.data_as(dp),
+                                                 1 if with_hessian else 0, out.ctypes.data_as(dp), C.byref(pairs)))
+        return out, pairs.value
 
     def set_profiling(self, on: bool):
         self._chk(self._L.lisreg_set_profiling(self._h, 1 if on else 0))
