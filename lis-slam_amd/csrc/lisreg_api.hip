@@ -1,4 +1,6 @@
-// lisreg_api.hip — C-ABI host layer of liblisreg.so (declared in include/lisreg.h).
+// lisreg_api.hip — C-ABI host layer of liblisreg.so (declared in include/lisreg.h): context lifecycle, registration targets, batch
+// prepare / run / fetch / align, options, diagnostics, test hooks, profiling.  The other subsystems have a unit each
+// (lisreg_api_{cloud,features,feed,map,localmap,comm}.hip); what they all share is in lisreg_api_ctx.hip.
 //
 // Creates the seam the reference lacks: each entry point replaces a piece of
 // scan2SubMapOptimization() — /root/reference/src/node/odomEstimationNode.cpp:596-626 and the copies at
@@ -9,8 +11,6 @@
 // There is deliberately NO CPU fallback: without a HIP device every compute entry point fails with
 // LISREG_ERR_HIP.
 #include "lisreg_ctx.hpp"
-
-#include <dlfcn.h>
 
 #include <algorithm>
 #include <chrono>
@@ -23,54 +23,6 @@
 
 using namespace lisreg;
 
-namespace lisreg {
-thread_local std::string g_static_err;
-int ctx_fail(lisreg_ctx* c, int code, const std::string& msg)
-{
-    if (c) c->err = msg; else g_static_err = msg;
-    return code;
-}
-
-bool ensure_side_stream(lisreg_ctx* c)
-{
-    if (!c->side_stream && (c->side_stream.create(hipStreamNonBlocking) != hipSuccess || c->ev_fork.create(hipEventDisableTiming) != hipSuccess ||
-                            c->ev_join.create(hipEventDisableTiming) != hipSuccess)) {
-        c->side_stream.reset(); c->ev_fork.reset(); c->ev_join.reset();
-    }
-    return c->side_stream != nullptr;
-}
-}  // namespace lisreg
-
-namespace {
-
-
-int fail(lisreg_ctx* c, int code, const std::string& msg) { return lisreg::ctx_fail(c, code, msg); }
-
-void pose_to_matrix_host(const float T[6], float M[12])
-{
-    // pcl::getTransformation via trans2Affine3f (src/core/common.cpp:54-57)
-    float A = cosf(T[2]), B = sinf(T[2]), C = cosf(T[1]), D = sinf(T[1]), E = cosf(T[0]), F = sinf(T[0]);
-    float DE = D * E, DF = D * F;
-    M[0] = A * C;  M[1] = A * DF - B * E;  M[2]  = B * F + A * DE;  M[3]  = T[3];
-    M[4] = B * C;  M[5] = A * E + B * DF;  M[6]  = B * DE - A * F;  M[7]  = T[4];
-    M[8] = -D;     M[9] = C * F;           M[10] = C * E;           M[11] = T[5];
-}
-
-// pack PCL structs (stride/format of common.h:9,25-35) into 16-B device records
-}  // namespace
-namespace lisreg {
-void pack_cloud(const void* cloud, int n, int stride, int fmt, lisreg_dpoint* out)
-{
-    const unsigned char* b = static_cast<const unsigned char*>(cloud);
-    for (int i = 0; i < n; ++i) {
-        const unsigned char* r = b + (size_t)i * (size_t)stride;
-        memcpy(&out[i], r, 12);
-        uint16_t lab = 0;
-        if (fmt == LISREG_FMT_XYZIL) memcpy(&lab, r + 20, 2);
-        out[i].payload = lab;
-    }
-}
-}  // namespace lisreg
 namespace {
 
 DevParams make_dev_params(const lisreg_params& p)
@@ -87,74 +39,6 @@ DevParams make_dev_params(const lisreg_params& p)
     for (int i = 0; i < 32; ++i) d.wtab[i] = (float)(2.0 - (double)p.label_score[i]);   // subMapOptmizationNode.cpp:1671
     return d;
 }
-
-}  // namespace
-namespace lisreg {
-SortBuffers sort_buffers(lisreg_ctx* c)
-{
-    SortBuffers sb;
-    sb.hist = c->hist.as<int>(); sb.bucket_start = c->bucket_start.as<int>(); sb.scan_tmp = c->scan_tmp.as<int>();
-    sb.elem_bucket = c->elem_bucket.as<uint32_t>(); sb.elem_sub = c->elem_sub.as<uint32_t>();
-    sb.tmp_bucket = c->tmp_bucket.as<uint32_t>(); sb.tmp_sub = c->tmp_sub.as<uint32_t>();
-    sb.tmp_idx = c->tmp_idx.as<int>();
-    sb.tmp_pts = c->tmp_pts.as<float4>();
-    return sb;
-}
-}  // namespace lisreg
-namespace {
-
-}  // namespace
-namespace lisreg {
-int ensure_sort_scratch(lisreg_ctx* c, size_t n_elems, size_t n_buckets)
-{
-    HIPCHK(c, c->hist.ensure(sizeof(int) * (n_buckets + 1)));
-    HIPCHK(c, c->bucket_start.ensure(sizeof(int) * (n_buckets + 2)));
-    HIPCHK(c, c->scan_tmp.ensure(sizeof(int) * (n_buckets / 2048 + 4)));
-    HIPCHK(c, c->elem_bucket.ensure(sizeof(uint32_t) * (n_elems + 1)));
-    HIPCHK(c, c->elem_sub.ensure(sizeof(uint32_t) * (n_elems + 1)));
-    HIPCHK(c, c->tmp_bucket.ensure(sizeof(uint32_t) * (n_elems + 1)));
-    HIPCHK(c, c->tmp_sub.ensure(sizeof(uint32_t) * (n_elems + 1)));
-    HIPCHK(c, c->tmp_idx.ensure(sizeof(int) * (n_elems + 1)));
-    HIPCHK(c, c->tmp_pts.ensure(sizeof(float4) * (n_elems + 1)));
-    return LISREG_OK;
-}
-}  // namespace lisreg
-namespace {
-
-// grid geometry from a bounding box; cell edge grows if the box would need too many cells
-}  // namespace
-namespace lisreg {
-void make_grid(const float bb_in[6], int n, GridIndex* g, int* n_cells, int margin_cells)
-{
-    float bb[6] = { bb_in[0], bb_in[1], bb_in[2], bb_in[3], bb_in[4], bb_in[5] };
-    memset(g, 0, sizeof *g);
-    g->n = n;
-    // Cell edge: 0.5 m is the measured optimum for the 200 k-point submap of BASELINE configs[1]; the optimum
-    // scales with the point spacing, so denser maps get smaller cells (footprint density as the proxy: lidar maps are
-    // surfaces over a ground plane).  1 M points over the same 80 x 80 m: 0.25 m, +14 % registrations/s.
-    float cell = 0.5f;
-    if (n > 0) {
-        const double area = std::max(1.0, (double)(bb[3] - bb[0]) * (double)(bb[4] - bb[1]));
-        cell = (float)std::min(0.5, std::max(0.25, 2.8 / std::sqrt((double)n / area)));
-    }
-    if (n <= 0) { g->cell = cell; g->inv_cell = 1.f / cell; g->nx = g->ny = g->nz = 0; *n_cells = 1; return; }
-    const double max_cells = 1 << 24;
-    // registration targets: the grid reaches `margin_cells` cells past the cloud on every side, so that a query a pose error away from
-    // a wall that bounds the cloud still has a cell of its own (cell rows, search_mode 5); empty cells cost four bytes of table each
-    const float bb0[6] = { bb[0], bb[1], bb[2], bb[3], bb[4], bb[5] };
-    for (;;) {
-        for (int d = 0; d < 3; ++d) { bb[d] = bb0[d] - (float)margin_cells * cell; bb[3 + d] = bb0[3 + d] + (float)margin_cells * cell; }
-        double nx = floor((bb[3] - bb[0]) / cell) + 1, ny = floor((bb[4] - bb[1]) / cell) + 1,
-               nz = floor((bb[5] - bb[2]) / cell) + 1;
-        if (nx * ny * nz <= max_cells) { g->nx = (int)nx; g->ny = (int)ny; g->nz = (int)nz; break; }
-        cell *= 1.26f;
-    }
-    g->ox = bb[0]; g->oy = bb[1]; g->oz = bb[2];
-    g->cell = cell; g->inv_cell = 1.f / cell;
-    *n_cells = g->nx * g->ny * g->nz;
-}
-}  // namespace lisreg
-namespace {
 
 constexpr int kCrowGridMargin = 2;
 
@@ -275,7 +159,7 @@ int ensure_crows(lisreg_ctx* c, Target& t, int k, bool may_decline = false, long
             (void)hipGetLastError();
             t.crow[k].release(); t.crow_meta[k].release();      // (the half that was granted goes back now: the target lives on without rows)
             if (may_decline) { t.crow_too_big[k] = true; t.g[k].crow_tab = nullptr; return LISREG_OK; }
-            return lisreg::ctx_fail(c, LISREG_ERR_HIP, std::string("cell rows: ") + hipGetErrorString(e2));
+            return ctx_fail(c, LISREG_ERR_HIP, std::string("cell rows: ") + hipGetErrorString(e2));
         }
     }
     if (rows_left) *rows_left -= t.crow_cap[k];
@@ -353,11 +237,10 @@ void prof_collect(lisreg_ctx* c)
 }
 
 }  // namespace
-namespace lisreg {
+
 // HIP-event marks for the other translation units (lisreg_set_profiling / lisreg_get_timing)
-void ctx_prof_mark(lisreg_ctx* c, int kind_of_next_interval) { prof_mark(c, kind_of_next_interval); }
-void ctx_prof_collect(lisreg_ctx* c) { if (!c->ev.empty()) prof_collect(c); }
-}  // namespace lisreg
+void lisreg::ctx_prof_mark(lisreg_ctx* c, int kind_of_next_interval) { prof_mark(c, kind_of_next_interval); }
+void lisreg::ctx_prof_collect(lisreg_ctx* c) { if (!c->ev.empty()) prof_collect(c); }
 
 // =============================================================================================================
 extern "C" {
@@ -371,22 +254,22 @@ int lisreg_device_count(void)
 
 int lisreg_create(int device, lisreg_ctx** out)
 {
-    if (!out) return fail(nullptr, LISREG_ERR_ARG, "lisreg_create: out is NULL");
+    if (!out) return bad(nullptr, "lisreg_create: out is NULL");
     *out = nullptr;
     int n = lisreg_device_count();
-    if (n <= 0) return fail(nullptr, LISREG_ERR_HIP, "lisreg_create: no HIP device visible (liblisreg has no CPU fallback)");
-    if (device < 0 || device >= n) return fail(nullptr, LISREG_ERR_ARG, "lisreg_create: bad device index");
+    if (n <= 0) return ctx_fail(nullptr, LISREG_ERR_HIP, "lisreg_create: no HIP device visible (liblisreg has no CPU fallback)");
+    if (device < 0 || device >= n) return bad(nullptr, "lisreg_create: bad device index");
     lisreg_ctx* c = new (std::nothrow) lisreg_ctx();
-    if (!c) return fail(nullptr, LISREG_ERR_NOMEM, "lisreg_create: out of host memory");
+    if (!c) return ctx_fail(nullptr, LISREG_ERR_NOMEM, "lisreg_create: out of host memory");
     c->device = device;
     if (hipSetDevice(device) != hipSuccess || c->own_stream.create(hipStreamNonBlocking) != hipSuccess) {
         delete c;
-        return fail(nullptr, LISREG_ERR_HIP, "lisreg_create: hipSetDevice/hipStreamCreate failed");
+        return ctx_fail(nullptr, LISREG_ERR_HIP, "lisreg_create: hipSetDevice/hipStreamCreate failed");
     }
     c->stream = c->own_stream;
     c->targets.resize(1);
     (void)c->done_host.ensure(sizeof(int), sizeof(int));     // (a failure is tolerated: runs then do not stop early)
-    if (c->done_dev.ensure(sizeof(int)) != hipSuccess) { lisreg_destroy(c); return fail(nullptr, LISREG_ERR_HIP, "lisreg_create: hipMalloc failed"); }
+    if (c->done_dev.ensure(sizeof(int)) != hipSuccess) { lisreg_destroy(c); return ctx_fail(nullptr, LISREG_ERR_HIP, "lisreg_create: hipMalloc failed"); }
     lisreg_default_params(LISREG_VARIANT_ODOM, &c->params);
     *out = c;
     return LISREG_OK;
@@ -405,8 +288,6 @@ void lisreg_destroy(lisreg_ctx* c)
     feeder_stop(c);
     delete c;
 }
-
-const char* lisreg_last_error(const lisreg_ctx* c) { return c ? c->err.c_str() : g_static_err.c_str(); }
 
 int lisreg_set_stream(lisreg_ctx* c, void* s)
 {
@@ -439,8 +320,6 @@ int lisreg_default_params(int variant, lisreg_params* p)
     p->imu_rpy_weight = 0.1f; p->rotation_tol = 1000.f; p->z_tol = 1000.f;
     return LISREG_OK;
 }
-
-void lisreg_pose_to_matrix(const float T[6], float M[12]) { pose_to_matrix_host(T, M); }
 
 // transformUpdate, host form (odomEstimationNode.cpp:976-1006): tf's double-precision quaternion slerp of the
 // single-axis roll / pitch rotations, then constraintTransformation (common.cpp:285-291).
@@ -479,13 +358,12 @@ void lisreg_transform_update(const lisreg_params* p, const lisreg_imu* imu, floa
 static int set_target_impl(lisreg_ctx* c, int slot, const void* clouds[2], const int counts[2], int stride, int fmt)
 {
     if (!c) return LISREG_ERR_ARG;
-    if (slot < 0 || slot > 65535) return fail(c, LISREG_ERR_ARG, "set_target: bad slot");
-    for (int k = 0; k < 2; ++k)
-        if (counts[k] < 0 || (counts[k] > 0 && !clouds[k])) return fail(c, LISREG_ERR_ARG, "set_target: NULL cloud with n > 0");
+    if (slot < 0 || slot > 65535) return bad(c, "set_target: bad slot");
+    for (int k = 0; k < 2; ++k)          // (any fmt but DEVICE and XYZIL is read as XYZI structs)
+        if (const int rc = check_cloud(c, "set_target", clouds[k], counts[k], stride, fmt == LISREG_FMT_DEVICE || fmt == LISREG_FMT_XYZIL ? fmt : LISREG_FMT_XYZI,
+                                       fmt_bit(LISREG_FMT_DEVICE) | fmt_bit(LISREG_FMT_XYZI) | fmt_bit(LISREG_FMT_XYZIL), true)) return rc;
     for (int k = 0; k < 2; ++k)          // the kernels address a target's 16-byte records by 32-bit byte offsets from a scalar base
-        if (counts[k] >= (1 << 28)) return fail(c, LISREG_ERR_ARG, "set_target: a cloud of 2^28 points or more");
-    if (fmt != LISREG_FMT_DEVICE && stride < 12) return fail(c, LISREG_ERR_ARG, "set_target: stride < 12");
-    if (fmt == LISREG_FMT_XYZIL && stride < 22) return fail(c, LISREG_ERR_ARG, "set_target: XYZIL needs stride >= 22");
+        if (counts[k] >= (1 << 28)) return bad(c, "set_target: a cloud of 2^28 points or more");
     HIPCHK(c, hipSetDevice(c->device));
     if ((size_t)slot >= c->targets.size()) c->targets.resize((size_t)slot + 1);
     Target& t = c->targets[(size_t)slot];
@@ -516,20 +394,16 @@ static int set_target_impl(lisreg_ctx* c, int slot, const void* clouds[2], const
                 const float v[3] = { h[(size_t)i].x, h[(size_t)i].y, h[(size_t)i].z };
                 for (int d = 0; d < 3; ++d) { bb[d] = std::min(bb[d], v[d]); bb[3 + d] = std::max(bb[3 + d], v[d]); }
             }
-            HIPCHK(c, t.raw[k].ensure(sizeof(float4) * (size_t)std::max(n, 1)));
             // on the context's stream: a run still queued there against this slot (it may re-read the raw records) reads the old
             // cloud; the null stream would order nothing against it
-            if (n > 0) {
-                HIPCHK(c, hipMemcpyAsync(t.raw[k].p, h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));     // h is a local
-            }
+            if (const int rc = upload_packed(c, h.data(), (size_t)n, t.raw[k])) return rc;
             t.raw_external[k] = false;
             t.raw_ptr[k] = t.raw[k].as<float4>();
         }
         for (int d = 0; d < 6; ++d)
-            if (n > 0 && !std::isfinite(bb[d])) return fail(c, LISREG_ERR_ARG, "set_target: the cloud has infinite coordinates (NaN points are ignored, Inf is not indexable)");
+            if (n > 0 && !std::isfinite(bb[d])) return bad(c, "set_target: the cloud has infinite coordinates (NaN points are ignored, Inf is not indexable)");
         if (n > 0 && !(bb[0] <= bb[3] && bb[1] <= bb[4] && bb[2] <= bb[5]))
-            return fail(c, LISREG_ERR_ARG, "set_target: the cloud has no finite point (every coordinate is NaN)");
+            return bad(c, "set_target: the cloud has no finite point (every coordinate is NaN)");
         // the cell rows (search front-end 5) want a grid that reaches two cells past the cloud; when the front-end is left to the batch
         // (auto), a target gets that margin only once a batch has chosen the cell rows for it (ensure_crow_margin)
         // — and keeps it from then on: a slot whose targets went through the cell rows last time (a frame stream re-sets its slot
@@ -571,8 +445,8 @@ int lisreg_target_from_classes(lisreg_ctx* c, int slot, const void* pole, int n_
                                int stride, int fmt)
 {
     if (!c) return LISREG_ERR_ARG;
-    if (fmt == LISREG_FMT_DEVICE) return fail(c, LISREG_ERR_ARG, "target_from_classes: host clouds only");
-    if (stride < 12) return fail(c, LISREG_ERR_ARG, "target_from_classes: stride < 12");
+    if (fmt == LISREG_FMT_DEVICE) return bad(c, "target_from_classes: host clouds only");
+    if (stride < 12) return bad(c, "target_from_classes: stride < 12");      // (the parts are copied by it below; lisreg_set_target_slot checks the rest)
     // surf = ground + building + dynamic, the concat order of extractSlidingCloud (subMapOptmizationNode.cpp:1408-1419)
     const void* parts[3] = { ground, building, dynamic };
     const int cnt[3] = { std::max(n_ground, 0), std::max(n_building, 0), std::max(n_dynamic, 0) };
@@ -592,7 +466,7 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
                          const float* T_init)
 {
     if (!c) return LISREG_ERR_ARG;
-    if (n_items < 0 || (n_items > 0 && (!items || !T_init)) || !params) return fail(c, LISREG_ERR_ARG, "batch_prepare: bad arguments");
+    if (n_items < 0 || (n_items > 0 && (!items || !T_init)) || !params) return bad(c, "batch_prepare: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     c->prepared = false;
     c->params = *params;
@@ -617,7 +491,7 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
                 t_pts += (double)c->targets[(size_t)sl].n[0] + (double)c->targets[(size_t)sl].n[1];
             }
         }
-        if (total_src > 2000000000LL) return fail(c, LISREG_ERR_ARG, "batch_prepare: more than 2e9 source points in one batch");
+        if (total_src > 2000000000LL) return bad(c, "batch_prepare: more than 2e9 source points in one batch");
         c->mode_now = c->search_mode;
         if (c->search_mode == 4) {
             const double qi = (double)total_src * (double)c->prm.bound;
@@ -675,11 +549,11 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
     int flat = 0, bucket = 0;
     for (int i = 0; i < n_items; ++i) {
         const lisreg_item& in = items[i];
-        if (in.fmt != LISREG_FMT_DEVICE) return fail(c, LISREG_ERR_ARG, "batch_prepare: items must be LISREG_FMT_DEVICE (use lisreg_align_batch for host clouds)");
+        if (in.fmt != LISREG_FMT_DEVICE) return bad(c, "batch_prepare: items must be LISREG_FMT_DEVICE (use lisreg_align_batch for host clouds)");
         if (in.n_corner < 0 || in.n_surf < 0 || (in.n_corner > 0 && !in.src_corner) || (in.n_surf > 0 && !in.src_surf))
-            return fail(c, LISREG_ERR_ARG, "batch_prepare: NULL source cloud with n > 0");
+            return bad(c, "batch_prepare: NULL source cloud with n > 0");
         if (in.target < 0 || (size_t)in.target >= c->targets.size() || !c->targets[(size_t)in.target].valid)
-            return fail(c, LISREG_ERR_NO_TARGET, "batch_prepare: item refers to a target slot that was never set");
+            return ctx_fail(c, LISREG_ERR_NO_TARGET, "batch_prepare: item refers to a target slot that was never set");
         if (std::find(c->batch_slots.begin(), c->batch_slots.end(), in.target) == c->batch_slots.end()) c->batch_slots.push_back(in.target);
         const Target& t = c->targets[(size_t)in.target];
         ItemState& st = c->h_items[(size_t)i];
@@ -811,7 +685,7 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
     // (2.2 vs 5.3 ms), and equal for the single shared submap of configs[1]
     c->strip_now = strips_fit && c->index_build != 0;
     if (c->index_build == 1 && !c->strip_now)
-        return fail(c, LISREG_ERR_ARG, "index_build 1: a target grid of this batch does not fit the strip form (strips per target or cells per strip)");
+        return bad(c, "index_build 1: a target grid of this batch does not fit the strip form (strips per target or cells per strip)");
     HIPCHK(c, c->tchunk_dev.ensure(sizeof(BlockDesc) * std::max<size_t>(c->h_tchunks.size(), 1)));
     { const void* before = c->strip_tab.p; HIPCHK(c, c->strip_tab.ensure(sizeof(int) * (3 * ((size_t)tstrip + 4) + (size_t)tstrip / 2048 + 8))); if (c->strip_tab.p != before) c->strip_zero_ints = 0; }
     HIPCHK(c, c->tseg_dev.ensure(sizeof(TargetSeg) * std::max<size_t>(c->h_tsegs.size(), 1)));
@@ -963,7 +837,7 @@ static bool xcd_order_wanted(const lisreg_ctx* c)
 // `break` at :617 — instead of launching no-op kernels up to max_iters.  Results are identical either way.
 static int run_impl(lisreg_ctx* c, bool early_stop)
 {
-    if (!c->prepared) return fail(c, LISREG_ERR_ARG, "batch_run: no prepared batch");
+    if (!c->prepared) return bad(c, "batch_run: no prepared batch");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     // XCD-aware dispatch order (lisreg_assoc.hip, launch_xcd_order): two small launches per run, at the initial poses.  Auto: the graph
@@ -1015,7 +889,7 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
             sl.side = c->side_stream; sl.ev_fork = c->ev_fork; sl.ev_join = c->ev_join;
             if (launch_build_targets_strips(c->tchunk_dev.as<BlockDesc>(), (int)c->h_tchunks.size(), c->tseg_dev.as<TargetSeg>(),
                                             (int)c->h_tsegs.size(), c->t_strips, c->t_max_units, c->t_max_ucells, c->strip_cap, sl, st, &c->strip_zero_ints))
-                return fail(c, LISREG_ERR_HIP, "strip index build: LDS configuration refused");
+                return ctx_fail(c, LISREG_ERR_HIP, "strip index build: LDS configuration refused");
         } else
             launch_build_targets_batched(c->tblk_dev.as<BlockDesc>(), (int)c->h_tblocks.size(), c->tseg_dev.as<TargetSeg>(),
                                          (int)c->h_tsegs.size(), c->t_elems, c->t_buckets, sort_buffers(c), st);
@@ -1109,7 +983,7 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
         if (ie != hipSuccess) {
             (void)hipStreamSynchronize(c->side_stream);
             c->interleaved_now = false;
-            return lisreg::ctx_fail(c, LISREG_ERR_HIP, std::string("interleaved run: ") + hipGetErrorString(ie));
+            return ctx_fail(c, LISREG_ERR_HIP, std::string("interleaved run: ") + hipGetErrorString(ie));
         }
     } else
     for (int it = 0; it < c->prm.bound; ++it) {
@@ -1139,7 +1013,7 @@ int lisreg_batch_run(lisreg_ctx* c)
 int lisreg_batch_fetch(lisreg_ctx* c, float* T, lisreg_stats* stats)
 {
     if (!c) return LISREG_ERR_ARG;
-    if (!c->prepared) return fail(c, LISREG_ERR_ARG, "batch_fetch: no prepared batch");
+    if (!c->prepared) return bad(c, "batch_fetch: no prepared batch");
     HIPCHK(c, hipSetDevice(c->device));
     // results (and, for lisreg_align, the trace) land in pinned memory: asynchronous copies, ONE synchronisation
     const size_t res_floats = ((size_t)std::max(c->n_items, 1) + 1) * kResultSize;
@@ -1195,7 +1069,7 @@ int lisreg_set_option(lisreg_ctx* c, const char* name, int value)
     if (!strcmp(name, "sort_sources")) { c->sort_sources = value; c->probe_items = -1; return LISREG_OK; }
     if (!strcmp(name, "cell_anchor_until")) { c->cell_anchor_until = std::max(value, 0); return LISREG_OK; }
     if (!strcmp(name, "search_mode")) {
-        if (value < 1 || value > 5 || value == 2) return fail(c, LISREG_ERR_ARG, "search_mode: 1 cell walk, 3 k-NN graph scan, 4 auto, 5 cell rows");
+        if (value < 1 || value > 5 || value == 2) return bad(c, "search_mode: 1 cell walk, 3 k-NN graph scan, 4 auto, 5 cell rows");
         c->search_mode = value; c->prepared = false; return LISREG_OK;
     }
     if (!strcmp(name, "graph_min_ratio")) { c->graph_min_ratio = value; c->prepared = false; return LISREG_OK; }
@@ -1210,9 +1084,9 @@ int lisreg_set_option(lisreg_ctx* c, const char* name, int value)
         return LISREG_OK;
     }
     if (!strcmp(name, "early_stop_chunk")) { c->early_stop_chunk = value; return LISREG_OK; }
-    if (!strcmp(name, "xcd_order")) { if (value < 0 || value > 2) return fail(c, LISREG_ERR_ARG, "xcd_order: 0 off, 1 on, 2 auto"); c->xcd_order = value; c->xcd_cached = false; return LISREG_OK; }
+    if (!strcmp(name, "xcd_order")) { if (value < 0 || value > 2) return bad(c, "xcd_order: 0 off, 1 on, 2 auto"); c->xcd_order = value; c->xcd_cached = false; return LISREG_OK; }
     if (!strcmp(name, "index_build")) {
-        if (value < 0 || value > 2) return fail(c, LISREG_ERR_ARG, "index_build: 0 bucket sort, 1 strip form, 2 auto");
+        if (value < 0 || value > 2) return bad(c, "index_build: 0 bucket sort, 1 strip form, 2 auto");
         c->index_build = value; c->prepared = false;
         return LISREG_OK;
     }
@@ -1229,15 +1103,15 @@ int lisreg_set_option(lisreg_ctx* c, const char* name, int value)
     if (!strcmp(name, "feeder_copy_engine")) { c->feeder_engine = value; return LISREG_OK; }
     if (!strcmp(name, "canonical_ties")) { c->canonical_ties = value != 0; c->prepared = false; return LISREG_OK; }
     if (!strcmp(name, "first_pass_mm")) {          // (a negative radius would square to the positive one: refused rather than taken as that)
-        if (value < 0) return fail(c, LISREG_ERR_ARG, "first_pass_mm: a radius in millimetres, >= 0");
+        if (value < 0) return bad(c, "first_pass_mm: a radius in millimetres, >= 0");
         c->first_pass_r = 1e-3f * (float)value; return LISREG_OK;
     }
     if (!strcmp(name, "trace_cap")) { c->trace_cap = std::max(0, value); c->prepared = false; return LISREG_OK; }
     if (!strcmp(name, "feeder_threads")) { c->feeder_threads = std::min(std::max(value, 0), 64); return LISREG_OK; }
     if (!strcmp(name, "feeder_numa")) { c->feeder_numa = value != 0; return LISREG_OK; }       // takes effect when the thread pool is created
     if (!strcmp(name, "interleave_min_blocks")) { c->interleave_min_blocks = std::max(value, 2); return LISREG_OK; }
-    if (!strcmp(name, "interleave")) { if (value < 0 || value > 2) return fail(c, LISREG_ERR_ARG, "interleave: 0 off, 1 alternating halves, 2 free-running halves"); c->interleave = value; return LISREG_OK; }
-    return fail(c, LISREG_ERR_ARG, std::string("set_option: unknown option ") + name);
+    if (!strcmp(name, "interleave")) { if (value < 0 || value > 2) return bad(c, "interleave: 0 off, 1 alternating halves, 2 free-running halves"); c->interleave = value; return LISREG_OK; }
+    return bad(c, std::string("set_option: unknown option ") + name);
 }
 
 int lisreg_get_option(const lisreg_ctx* c, const char* name, int* value)
@@ -1317,17 +1191,17 @@ int lisreg_align_batch(lisreg_ctx* c, int n_items, const lisreg_item* items, con
                        lisreg_stats* stats)
 {
     if (!c) return LISREG_ERR_ARG;
-    if (n_items < 0 || (n_items > 0 && (!items || !T)) || !params) return fail(c, LISREG_ERR_ARG, "align_batch: bad arguments");
+    if (n_items < 0 || (n_items > 0 && (!items || !T)) || !params) return bad(c, "align_batch: bad arguments");
     const auto t_in = std::chrono::steady_clock::now();
     HIPCHK(c, hipSetDevice(c->device));
     // stage host clouds into one device buffer of 16-B records; device items pass through
     size_t total = 0;
     for (int i = 0; i < n_items; ++i) {
         const lisreg_item& in = items[i];
-        if (in.n_corner < 0 || in.n_surf < 0) return fail(c, LISREG_ERR_ARG, "align_batch: negative count");
+        if (in.n_corner < 0 || in.n_surf < 0) return bad(c, "align_batch: negative count");
         if (in.fmt != LISREG_FMT_DEVICE) {
-            if (in.stride_bytes < 12 || (in.fmt == LISREG_FMT_XYZIL && in.stride_bytes < 22)) return fail(c, LISREG_ERR_ARG, "align_batch: bad stride");
-            if ((in.n_corner > 0 && !in.src_corner) || (in.n_surf > 0 && !in.src_surf)) return fail(c, LISREG_ERR_ARG, "align_batch: NULL cloud");
+            if (in.stride_bytes < 12 || (in.fmt == LISREG_FMT_XYZIL && in.stride_bytes < 22)) return bad(c, "align_batch: bad stride");
+            if ((in.n_corner > 0 && !in.src_corner) || (in.n_surf > 0 && !in.src_surf)) return bad(c, "align_batch: NULL cloud");
             total += (size_t)in.n_corner + (size_t)in.n_surf;
         }
     }
@@ -1397,8 +1271,8 @@ int lisreg_align(lisreg_ctx* c, const void* src_corner, int n_corner, const void
                  int fmt, const lisreg_params* params, const lisreg_imu* imu, float T[6], lisreg_stats* stats)
 {
     if (!c) return LISREG_ERR_ARG;
-    if (!params || !T) return fail(c, LISREG_ERR_ARG, "align: params/T NULL");
-    if (c->targets.empty() || !c->targets[0].valid) return fail(c, LISREG_ERR_NO_TARGET, "align: call lisreg_set_target first");
+    if (!params || !T) return bad(c, "align: params/T NULL");
+    if (c->targets.empty() || !c->targets[0].valid) return ctx_fail(c, LISREG_ERR_NO_TARGET, "align: call lisreg_set_target first");
     lisreg_item item;
     memset(&item, 0, sizeof item);
     item.src_corner = src_corner; item.n_corner = n_corner;
@@ -1456,18 +1330,18 @@ int lisreg_get_target_index(lisreg_ctx* c, int slot, int kind, int* dims /* n, n
                             float* sorted_out, int sorted_capacity, int* cell_start_out, int cell_capacity)
 {
     if (!c || slot < 0 || (size_t)slot >= c->targets.size() || kind < 0 || kind > 1 || !c->targets[(size_t)slot].valid)
-        return fail(c, LISREG_ERR_ARG, "get_target_index: no such target");
+        return bad(c, "get_target_index: no such target");
     const Target& t = c->targets[(size_t)slot];
     const GridIndex& g = t.g[kind];
     if (dims) { dims[0] = t.n[kind]; dims[1] = g.nx; dims[2] = g.ny; dims[3] = g.nz; dims[4] = t.n_cells[kind]; }
     if (geom) { geom[0] = g.ox; geom[1] = g.oy; geom[2] = g.oz; geom[3] = g.cell; }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (sorted_out) {
-        if (sorted_capacity < t.n[kind]) return fail(c, LISREG_ERR_ARG, "get_target_index: sorted_capacity too small");
+        if (sorted_capacity < t.n[kind]) return bad(c, "get_target_index: sorted_capacity too small");
         if (t.n[kind] > 0) HIPCHK(c, hipMemcpy(sorted_out, t.sorted[kind].p, sizeof(float4) * (size_t)t.n[kind], hipMemcpyDeviceToHost));
     }
     if (cell_start_out) {
-        if (cell_capacity < t.n_cells[kind] + 1) return fail(c, LISREG_ERR_ARG, "get_target_index: cell_capacity too small");
+        if (cell_capacity < t.n_cells[kind] + 1) return bad(c, "get_target_index: cell_capacity too small");
         HIPCHK(c, hipMemcpy(cell_start_out, t.cell_start[kind].p, sizeof(int) * ((size_t)t.n_cells[kind] + 1), hipMemcpyDeviceToHost));
     }
     return LISREG_OK;
@@ -1476,11 +1350,11 @@ int lisreg_get_target_index(lisreg_ctx* c, int slot, int kind, int* dims /* n, n
 int lisreg_get_target_graph(lisreg_ctx* c, int slot, int kind, int* k_out, float* rows_out, float* meta_out, int capacity_points)
 {
     if (!c || slot < 0 || (size_t)slot >= c->targets.size() || kind < 0 || kind > 1 || !c->targets[(size_t)slot].valid)
-        return fail(c, LISREG_ERR_ARG, "get_target_graph: no such target");
+        return bad(c, "get_target_graph: no such target");
     Target& t = c->targets[(size_t)slot];
     if (k_out) *k_out = kGraphK;
     if (!rows_out && !meta_out) return LISREG_OK;
-    if (capacity_points < t.n[kind]) return fail(c, LISREG_ERR_ARG, "get_target_graph: capacity_points too small");
+    if (capacity_points < t.n[kind]) return bad(c, "get_target_graph: capacity_points too small");
     HIPCHK(c, hipSetDevice(c->device));
     if (!t.graph_valid[kind] || !t.g[kind].nbr) {            // build it now (it is built on demand otherwise)
         int rc = ensure_graph(c, t, kind, true);
@@ -1498,7 +1372,7 @@ int lisreg_get_target_cell_rows(lisreg_ctx* c, int slot, int kind, int* n_rows, 
                                 float* rows_out, float* meta_out, int capacity_rows)
 {
     if (!c || slot < 0 || (size_t)slot >= c->targets.size() || kind < 0 || kind > 1 || !c->targets[(size_t)slot].valid)
-        return fail(c, LISREG_ERR_ARG, "get_target_cell_rows: no such target");
+        return bad(c, "get_target_cell_rows: no such target");
     HIPCHK(c, hipSetDevice(c->device));
     Target& t = c->targets[(size_t)slot];
     if (k_out) *k_out = kGraphK;
@@ -1513,10 +1387,10 @@ int lisreg_get_target_cell_rows(lisreg_ctx* c, int slot, int kind, int* n_rows, 
     rows = std::min(rows, t.crow_cap[kind]);
     if (n_rows) *n_rows = rows;
     if (table_out) {
-        if (capacity_cells < t.n_cells[kind]) return fail(c, LISREG_ERR_ARG, "get_target_cell_rows: capacity_cells too small");
+        if (capacity_cells < t.n_cells[kind]) return bad(c, "get_target_cell_rows: capacity_cells too small");
         HIPCHK(c, hipMemcpy(table_out, t.crow_tab[kind].p, sizeof(int) * (size_t)t.n_cells[kind], hipMemcpyDeviceToHost));
     }
-    if ((rows_out || meta_out) && capacity_rows < rows) return fail(c, LISREG_ERR_ARG, "get_target_cell_rows: capacity_rows too small");
+    if ((rows_out || meta_out) && capacity_rows < rows) return bad(c, "get_target_cell_rows: capacity_rows too small");
     if (rows_out && rows) {
         HIPCHK(c, hipMemcpy(rows_out, t.crow[kind].p, sizeof(float4) * kGraphK * (size_t)rows, hipMemcpyDeviceToHost));
     }
@@ -1528,7 +1402,7 @@ int lisreg_get_neighbors(lisreg_ctx* c, int* out, int n_elems)
 {
     if (!c || !out || n_elems < 0) return LISREG_ERR_ARG;
     if (!c->dump_neighbors || !c->dbg_nn.p || n_elems != c->n_elems || (c->mode_now != 1 && c->mode_now != 3 && c->mode_now != 5))
-        return fail(c, LISREG_ERR_ARG, "get_neighbors: set option dump_neighbors before preparing the batch (search modes 1, 3); n_elems must be the batch's source point count");
+        return bad(c, "get_neighbors: set option dump_neighbors before preparing the batch (search modes 1, 3); n_elems must be the batch's source point count");
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, c->dbg_nn.p, sizeof(int) * 6 * (size_t)n_elems, hipMemcpyDeviceToHost));
     return LISREG_OK;
@@ -1539,7 +1413,7 @@ int lisreg_test_fit_models(lisreg_ctx* c, int kind, int n, const float* neighbou
 {
     if (!c) return LISREG_ERR_ARG;
     if ((kind != 0 && kind != 1) || n < 0 || !params || (n > 0 && (!neighbours || !queries || !out)))
-        return fail(c, LISREG_ERR_ARG, "test_fit_models: bad arguments");
+        return bad(c, "test_fit_models: bad arguments");
     if (n == 0) return LISREG_OK;
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf nb, q, o;
@@ -1564,14 +1438,14 @@ int lisreg_test_solve_steps(lisreg_ctx* c, int n_items, int n_steps, const int* 
 {
     if (!c) return LISREG_ERR_ARG;
     if (n_items < 0 || n_steps < 1 || n_steps > 64 || !params || (n_items > 0 && (!n_rows || !T_init)))
-        return fail(c, LISREG_ERR_ARG, "test_solve_steps: bad arguments");
+        return bad(c, "test_solve_steps: bad arguments");
     if (n_items == 0) return LISREG_OK;
     size_t total_rows = 0;
     for (int i = 0; i < n_items; ++i) {
-        if (n_rows[i] < 0) return fail(c, LISREG_ERR_ARG, "test_solve_steps: negative row count");
+        if (n_rows[i] < 0) return bad(c, "test_solve_steps: negative row count");
         total_rows += (size_t)n_rows[i];
     }
-    if (total_rows > 0x7fffffffu || (total_rows > 0 && !rows)) return fail(c, LISREG_ERR_ARG, "test_solve_steps: bad rows");
+    if (total_rows > 0x7fffffffu || (total_rows > 0 && !rows)) return bad(c, "test_solve_steps: bad rows");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)n_items;
     DevParams prm = make_dev_params(*params);
@@ -1637,674 +1511,6 @@ int lisreg_get_timing(lisreg_ctx* c, double out[5])
     if (!c || !out) return LISREG_ERR_ARG;
     for (int i = 0; i < 5; ++i) out[i] = c->timing[i];
     return LISREG_OK;
-}
-
-// ---- §8 f-1: voxel-grid down-sampling and cloud transform --------------------------------------------------------------
-int lisreg_voxel_downsample(lisreg_ctx* c, const void* in, int n, int stride, int fmt, float leaf, void* out,
-                            int out_capacity, int* n_out)
-{
-    if (!c) return LISREG_ERR_ARG;
-    if (!n_out || n < 0 || !(leaf > 0.f) || (n > 0 && (!in || !out))) return fail(c, LISREG_ERR_ARG, "voxel_downsample: bad arguments");
-    const bool dev = fmt == LISREG_FMT_DEVICE || fmt == LISREG_FMT_DEVICE_XYZI;
-    if (!dev && (stride < 12 || (fmt == LISREG_FMT_XYZIL && stride < 22)))
-        return fail(c, LISREG_ERR_ARG, "voxel_downsample: bad stride");
-    *n_out = 0;
-    if (n == 0) return LISREG_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const bool has_intensity = !dev && stride >= 20;
-    // ---- stage the input as float4 (x,y,z, intensity | payload) [+ labels] ---------------------------------------
-    const float4* pts = nullptr;
-    const uint32_t* labels = nullptr;
-    std::vector<float4> h_pts;
-    std::vector<uint32_t> h_lab;
-    if (dev) pts = static_cast<const float4*>(in);
-    else {
-        h_pts.resize((size_t)n);
-        if (fmt == LISREG_FMT_XYZIL) h_lab.resize((size_t)n);
-        const unsigned char* b = static_cast<const unsigned char*>(in);
-        for (int i = 0; i < n; ++i) {
-            const unsigned char* r = b + (size_t)i * (size_t)stride;
-            float v[3], it = 0.f;
-            memcpy(v, r, 12);
-            if (has_intensity) memcpy(&it, r + 16, 4);
-            h_pts[(size_t)i] = make_float4(v[0], v[1], v[2], it);
-            if (fmt == LISREG_FMT_XYZIL) { uint16_t l; memcpy(&l, r + 20, 2); h_lab[(size_t)i] = l; }
-        }
-        HIPCHK(c, c->vox_in.ensure(sizeof(float4) * (size_t)n));
-        HIPCHK(c, hipMemcpyAsync(c->vox_in.p, h_pts.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, st));
-        pts = c->vox_in.as<float4>();
-        if (fmt == LISREG_FMT_XYZIL) {
-            HIPCHK(c, c->vox_lab.ensure(sizeof(uint32_t) * (size_t)n));
-            HIPCHK(c, hipMemcpyAsync(c->vox_lab.p, h_lab.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-            labels = c->vox_lab.as<uint32_t>();
-        }
-    }
-    // ---- getMinMax3D + grid geometry (voxel_grid.hpp) -------------------------------------------------------------
-    float bb[6];
-    HIPCHK(c, c->bbox_dev.ensure(sizeof(float) * 8));
-    HIPCHK(c, c->bbox_scratch.ensure(sizeof(float) * 6 * 256));
-    launch_bbox(pts, n, c->bbox_dev.as<float>(), c->bbox_scratch.as<float>(), st);
-    HIPCHK(c, hipMemcpyAsync(bb, c->bbox_dev.p, sizeof bb, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    for (int k = 0; k < 6; ++k)       // the reference strips non-finite returns before any filter (pcl::removeNaNFromPointCloud)
-        if (!std::isfinite(bb[k])) return fail(c, LISREG_ERR_ARG, "voxel_downsample: the cloud has infinite coordinates");
-    const float inv = 1.0f / leaf;
-    const long long dx = (long long)((bb[3] - bb[0]) * inv) + 1, dy = (long long)((bb[4] - bb[1]) * inv) + 1,
-                    dz = (long long)((bb[5] - bb[2]) * inv) + 1;
-    if (dx * dy * dz > 2147483647LL) {           // "Leaf size is too small for the input dataset": output = input
-        if (n > out_capacity) { *n_out = n; return fail(c, LISREG_ERR_ARG, "voxel_downsample: out_capacity too small"); }
-        if (dev) { if (out != in) HIPCHK(c, hipMemcpyAsync(out, in, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, st)); }
-        else if (out != in) memmove(out, in, (size_t)n * (size_t)stride);
-        HIPCHK(c, hipStreamSynchronize(st));
-        *n_out = n;
-        return LISREG_LEAF_TOO_SMALL;
-    }
-    VoxelDesc d;
-    int div_b[3];
-    const int min_b[3] = { (int)floorf(bb[0] * inv), (int)floorf(bb[1] * inv), (int)floorf(bb[2] * inv) };
-    const int max_b[3] = { (int)floorf(bb[3] * inv), (int)floorf(bb[4] * inv), (int)floorf(bb[5] * inv) };
-    for (int k = 0; k < 3; ++k) div_b[k] = max_b[k] - min_b[k] + 1;
-    d.inv_leaf = inv; d.min_b0 = min_b[0]; d.min_b1 = min_b[1]; d.min_b2 = min_b[2];
-    d.mul1 = div_b[0]; d.mul2 = div_b[0] * div_b[1];
-    const long long total = (long long)div_b[0] * div_b[1] * div_b[2];
-    const long long max_buckets = 1LL << 22;
-    d.span = (uint32_t)std::max(1LL, (total + max_buckets - 1) / max_buckets);
-    const int n_buckets = (int)((total + d.span - 1) / d.span);
-    // ---- sort by voxel index, count voxels ------------------------------------------------------------------------
-    int rc = ensure_sort_scratch(c, (size_t)n, (size_t)std::max(n_buckets, n) + 1);
-    if (rc) return rc;
-    HIPCHK(c, c->vox_order.ensure(sizeof(int) * (size_t)n));
-    HIPCHK(c, c->vox_sidx.ensure(sizeof(uint32_t) * (size_t)n));
-    HIPCHK(c, c->vox_head.ensure(sizeof(int) * ((size_t)n + 1)));
-    HIPCHK(c, c->vox_slot.ensure(sizeof(int) * ((size_t)n + 2)));
-    launch_voxel_sort(pts, n, d, n_buckets, sort_buffers(c), c->vox_order.as<int>(), c->vox_sidx.as<uint32_t>(),
-                      c->vox_head.as<int>(), c->vox_slot.as<int>(), st);
-    int n_vox = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_vox, c->vox_slot.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    *n_out = n_vox;
-    if (n_vox > out_capacity) return fail(c, LISREG_ERR_ARG, "voxel_downsample: out_capacity too small (see *n_out)");
-    // ---- centroids ---------------------------------------------------------------------------------------------------
-    HIPCHK(c, c->vox_start.ensure(sizeof(int) * ((size_t)n_vox + 2)));
-    // in place (out inside the input records — lisreg_localmap_extract grids a class cloud onto itself): the centroid kernels read
-    // pts[order[..]] while other threads write out[v], so the result is formed in scratch and copied over the input afterwards
-    const bool aliased = dev && (const char*)out < (const char*)in + sizeof(float4) * (size_t)n &&
-                         (const char*)in < (const char*)out + sizeof(float4) * (size_t)std::max(out_capacity, 1);
-    float4* out_pts = dev && !aliased ? static_cast<float4*>(out) : nullptr;
-    if (!out_pts) { HIPCHK(c, c->vox_out.ensure(sizeof(float4) * (size_t)std::max(n_vox, 1))); out_pts = c->vox_out.as<float4>(); }
-    uint32_t* out_lab = nullptr;
-    if (fmt == LISREG_FMT_XYZIL) { HIPCHK(c, c->vox_outlab.ensure(sizeof(uint32_t) * (size_t)n_vox)); out_lab = c->vox_outlab.as<uint32_t>(); }
-    launch_voxel_centroids(n, n_vox, pts, labels, fmt == LISREG_FMT_DEVICE ? 1 : 0 /* label vote on the payload, else .w averaged */, c->vox_order.as<int>(), c->vox_head.as<int>(),
-                           c->vox_slot.as<int>(), c->vox_start.as<int>(), out_pts, out_lab, st);
-    HIPCHK(c, hipGetLastError());
-    if (!dev) {
-        std::vector<float4> r((size_t)n_vox);
-        std::vector<uint32_t> rl(fmt == LISREG_FMT_XYZIL ? (size_t)n_vox : 0);
-        HIPCHK(c, hipMemcpyAsync(r.data(), out_pts, sizeof(float4) * (size_t)n_vox, hipMemcpyDeviceToHost, st));
-        if (out_lab) HIPCHK(c, hipMemcpyAsync(rl.data(), out_lab, sizeof(uint32_t) * (size_t)n_vox, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        unsigned char* o = static_cast<unsigned char*>(out);
-        for (int i = 0; i < n_vox; ++i) {
-            unsigned char* q = o + (size_t)i * (size_t)stride;
-            memset(q, 0, (size_t)stride);
-            memcpy(q, &r[(size_t)i], 12);
-            if (has_intensity) memcpy(q + 16, &r[(size_t)i].w, 4);
-            if (out_lab) { const uint16_t l = (uint16_t)rl[(size_t)i]; memcpy(q + 20, &l, 2); }
-        }
-    } else {
-        if (aliased && n_vox > 0) HIPCHK(c, hipMemcpyAsync(out, out_pts, sizeof(float4) * (size_t)n_vox, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    return LISREG_OK;
-}
-
-// K device clouds through ONE launch sequence (one sort keyed by (cloud, voxel index), one centroid launch) with three host round trips
-// in all — the K bounding boxes, the K voxel counts — instead of ~12 launches and three round trips per cloud: the five class grids of a
-// key frame (subMapOptmizationNode.cpp:806-811) or of extractSlidingCloud (:1385-1389) are launch-bound, not bandwidth-bound.
-// Results are those of K lisreg_voxel_downsample calls, bit for bit (same sort order inside every cloud, same sequential sums).
-int lisreg_voxel_downsample_multi(lisreg_ctx* c, int k, const void* const* in, const int* n, const float* leaf, int fmt,
-                                  void* const* out, const int* out_capacity, int* n_out)
-{
-    if (!c) return LISREG_ERR_ARG;
-    if (k < 0 || (k > 0 && (!in || !n || !leaf || !out || !out_capacity || !n_out))) return fail(c, LISREG_ERR_ARG, "voxel_downsample_multi: bad arguments");
-    if (fmt != LISREG_FMT_DEVICE && fmt != LISREG_FMT_DEVICE_XYZI) return fail(c, LISREG_ERR_ARG, "voxel_downsample_multi: device records only (LISREG_FMT_DEVICE / _DEVICE_XYZI)");
-    for (int s = 0; s < k; ++s) {
-        if (n[s] < 0 || !(leaf[s] > 0.f) || (n[s] > 0 && (!in[s] || !out[s]))) return fail(c, LISREG_ERR_ARG, "voxel_downsample_multi: bad cloud");
-        n_out[s] = 0;
-    }
-    auto one_by_one = [&]() -> int {
-        for (int s = 0; s < k; ++s) {
-            int rc = lisreg_voxel_downsample(c, in[s], n[s], 16, fmt, leaf[s], out[s], out_capacity[s], &n_out[s]);
-            if (rc != LISREG_OK && rc != LISREG_LEAF_TOO_SMALL) return rc;
-        }
-        return LISREG_OK;
-    };
-    long long total_n = 0;
-    int live = 0;
-    for (int s = 0; s < k; ++s) { total_n += n[s]; live += n[s] > 0; }
-    if (live <= 1 || k > kVoxelMultiMax || total_n > 2000000000LL) return one_by_one();
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const int N = (int)total_n;
-    // ---- concatenate, K bounding boxes, one round trip ---------------------------------------------------------------------------
-    HIPCHK(c, c->vox_in.ensure(sizeof(float4) * (size_t)N));
-    HIPCHK(c, c->bbox_dev.ensure(sizeof(float) * 6 * kVoxelMultiMax));
-    HIPCHK(c, c->bbox_scratch.ensure(sizeof(float) * 6 * 256 * kVoxelMultiMax));
-    VoxelMulti m;
-    memset(&m, 0, sizeof m);
-    m.k = k;
-    float4* cat = c->vox_in.as<float4>();
-    for (int s = 0, o = 0; s < k; ++s) {
-        m.off[s] = o;
-        o += n[s];
-        m.off[s + 1] = o;
-    }
-    {
-        BboxJobs jobs;
-        memset(&jobs, 0, sizeof jobs);
-        jobs.k = k;
-        for (int s = 0; s < k; ++s) { jobs.pts[s] = static_cast<const float4*>(in[s]); jobs.n[s] = n[s]; }
-        launch_concat_jobs(jobs, m, cat, st);                  // one launch instead of K copies
-    }
-    launch_bbox_multi(cat, m, c->bbox_dev.as<float>(), c->bbox_scratch.as<float>(), st);
-    float bb[6 * kVoxelMultiMax];
-    HIPCHK(c, hipMemcpyAsync(bb, c->bbox_dev.p, sizeof(float) * 6 * (size_t)k, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    // ---- per-cloud geometry (voxel_grid.hpp), one common bucket span ----------------------------------------------------------
-    long long totals[kVoxelMultiMax] = { 0 }, sum_total = 0;
-    for (int s = 0; s < k; ++s) {
-        if (n[s] == 0) continue;
-        const float* b = bb + 6 * s;
-        for (int q = 0; q < 6; ++q) if (!std::isfinite(b[q])) return fail(c, LISREG_ERR_ARG, "voxel_downsample_multi: a cloud has infinite coordinates");
-        const float inv = 1.0f / leaf[s];
-        const long long dx = (long long)((b[3] - b[0]) * inv) + 1, dy = (long long)((b[4] - b[1]) * inv) + 1, dz = (long long)((b[5] - b[2]) * inv) + 1;
-        if (dx * dy * dz > 2147483647LL) return one_by_one();          // "leaf size too small" for one of them: the single-cloud path knows what to do
-        const int min_b[3] = { (int)floorf(b[0] * inv), (int)floorf(b[1] * inv), (int)floorf(b[2] * inv) };
-        const int max_b[3] = { (int)floorf(b[3] * inv), (int)floorf(b[4] * inv), (int)floorf(b[5] * inv) };
-        int div_b[3];
-        for (int q = 0; q < 3; ++q) div_b[q] = max_b[q] - min_b[q] + 1;
-        VoxelDesc& d = m.d[s];
-        d.inv_leaf = inv; d.min_b0 = min_b[0]; d.min_b1 = min_b[1]; d.min_b2 = min_b[2];
-        d.mul1 = div_b[0]; d.mul2 = div_b[0] * div_b[1];
-        totals[s] = (long long)div_b[0] * div_b[1] * div_b[2];
-        sum_total += totals[s];
-    }
-    if (sum_total >= (1LL << 32)) return one_by_one();                 // the joint voxel index has to fit 32 bits
-    // every cloud its own bucket span (a cloud with a tiny leaf must not coarsen the others' buckets: the rank pass is quadratic inside
-    // a bucket), at most 2^22 buckets in all
-    const long long max_buckets = (1LL << 22) / k;
-    long long nb = 0, ib = 0;
-    for (int s = 0; s < k; ++s) {
-        const uint32_t span = (uint32_t)std::max(1LL, (totals[s] + max_buckets - 1) / max_buckets);
-        m.d[s].span = span;
-        m.bucket_base[s] = (int)nb;
-        m.idx_base[s] = (uint32_t)ib;
-        nb += (totals[s] + span - 1) / span;
-        ib += totals[s];
-    }
-    m.bucket_base[k] = (int)nb;
-    m.idx_base[k] = (uint32_t)ib;
-    const int n_buckets = (int)std::max(nb, 1LL);
-    // ---- one sort, the K voxel counts in one round trip -------------------------------------------------------------------------
-    int rc = ensure_sort_scratch(c, (size_t)N, (size_t)std::max(n_buckets, N) + 1);
-    if (rc) return rc;
-    HIPCHK(c, c->vox_order.ensure(sizeof(int) * (size_t)N));
-    HIPCHK(c, c->vox_sidx.ensure(sizeof(uint32_t) * (size_t)N));
-    HIPCHK(c, c->vox_head.ensure(sizeof(int) * ((size_t)N + 1)));
-    HIPCHK(c, c->vox_slot.ensure(sizeof(int) * ((size_t)N + 2)));
-    launch_voxel_sort_multi(cat, N, m, n_buckets, sort_buffers(c), c->vox_order.as<int>(), c->vox_sidx.as<uint32_t>(),
-                            c->vox_head.as<int>(), c->vox_slot.as<int>(), st);
-    int vo[kVoxelMultiMax + 1];
-    // the sorted sequence is cloud by cloud: cloud s starts at sorted position off[s]; its voxels start at slot[off[s]]
-    HIPCHK(c, c->mp_cnt.ensure(sizeof(int) * (kVoxelMultiMax + 1)));
-    launch_multi_bounds(c->vox_slot.as<int>(), m, c->mp_cnt.as<int>(), st);
-    HIPCHK(c, hipMemcpyAsync(vo, c->mp_cnt.p, sizeof(int) * (size_t)(k + 1), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    const int n_vox = vo[k];
-    for (int s = 0; s < k; ++s) {
-        n_out[s] = vo[s + 1] - vo[s];
-        if (n_out[s] > out_capacity[s]) return fail(c, LISREG_ERR_ARG, "voxel_downsample_multi: out_capacity too small (see n_out)");
-    }
-    // ---- one centroid launch, the slices handed out ------------------------------------------------------------------------------
-    HIPCHK(c, c->vox_start.ensure(sizeof(int) * ((size_t)n_vox + 2)));
-    HIPCHK(c, c->vox_out.ensure(sizeof(float4) * (size_t)std::max(n_vox, 1)));
-    launch_voxel_centroids(N, n_vox, cat, nullptr, fmt == LISREG_FMT_DEVICE ? 1 : 0, c->vox_order.as<int>(), c->vox_head.as<int>(),
-                           c->vox_slot.as<int>(), c->vox_start.as<int>(), c->vox_out.as<float4>(), nullptr, st);
-    HIPCHK(c, hipGetLastError());
-    VoxelHandOut ho;
-    memset(&ho, 0, sizeof ho);
-    ho.k = k;
-    for (int s = 0; s <= k; ++s) ho.vo[s] = vo[s];
-    for (int s = 0; s < k; ++s) ho.out[s] = static_cast<float4*>(out[s]);
-    launch_hand_out(c->vox_out.as<float4>(), ho, st);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(st));           // like the single-cloud call: the outputs are complete on return
-    return LISREG_OK;
-}
-
-// pcl's `*cloud += *other` for device records: K clouds end to end into `out` (one launch on the context's stream, nothing waited for —
-// every later call of this context is ordered behind it).  currentCloudInit's surf source = dynamic + building + ground (:866-889).
-int lisreg_concat_device(lisreg_ctx* c, int k, const void* const* in, const int* n, void* out, int* n_out)
-{
-    if (!c) return LISREG_ERR_ARG;
-    if (k < 0 || k > kVoxelMultiMax || (k > 0 && (!in || !n))) return fail(c, LISREG_ERR_ARG, "concat_device: bad arguments (at most 8 clouds)");
-    VoxelMulti m;
-    BboxJobs jobs;
-    memset(&m, 0, sizeof m); memset(&jobs, 0, sizeof jobs);
-    m.k = jobs.k = k;
-    long long total = 0;
-    for (int s = 0; s < k; ++s) {
-        if (n[s] < 0 || (n[s] > 0 && !in[s])) return fail(c, LISREG_ERR_ARG, "concat_device: NULL cloud with n > 0");
-        m.off[s] = (int)total; jobs.pts[s] = static_cast<const float4*>(in[s]); jobs.n[s] = n[s];
-        total += n[s];
-    }
-    if (total > 2000000000LL || (total > 0 && !out)) return fail(c, LISREG_ERR_ARG, "concat_device: bad output");
-    m.off[k] = (int)total;
-    if (n_out) *n_out = (int)total;
-    HIPCHK(c, hipSetDevice(c->device));
-    launch_concat_jobs(jobs, m, static_cast<float4*>(out), c->stream);
-    HIPCHK(c, hipGetLastError());
-    return LISREG_OK;
-}
-
-int lisreg_transform_cloud(lisreg_ctx* c, const void* in, int n, int stride, int fmt, const float T[6], void* out)
-{
-    if (!c) return LISREG_ERR_ARG;
-    if (n < 0 || !T || (n > 0 && (!in || !out))) return fail(c, LISREG_ERR_ARG, "transform_cloud: bad arguments");
-    if (fmt != LISREG_FMT_DEVICE && stride < 12) return fail(c, LISREG_ERR_ARG, "transform_cloud: bad stride");
-    if (n == 0) return LISREG_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    float M[12];
-    pose_to_matrix_host(T, M);                       // pcl::getTransformation (common.cpp:140-142)
-    if (fmt == LISREG_FMT_DEVICE) {                  // the matrix travels as a kernel argument
-        launch_transform_cloud_m(static_cast<const float4*>(in), n, M, static_cast<float4*>(out), st);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(st));
-        return LISREG_OK;
-    }
-    HIPCHK(c, c->vox_M.ensure(sizeof M));
-    HIPCHK(c, hipMemcpyAsync(c->vox_M.p, M, sizeof M, hipMemcpyHostToDevice, st));
-    std::vector<float4> h((size_t)n);
-    const unsigned char* b = static_cast<const unsigned char*>(in);
-    for (int i = 0; i < n; ++i) { float v[3]; memcpy(v, b + (size_t)i * (size_t)stride, 12); h[(size_t)i] = make_float4(v[0], v[1], v[2], 0.f); }
-    HIPCHK(c, c->vox_in.ensure(sizeof(float4) * (size_t)n));
-    HIPCHK(c, hipMemcpyAsync(c->vox_in.p, h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, st));
-    launch_transform_cloud(c->vox_in.as<float4>(), n, c->vox_M.as<float>(), c->vox_in.as<float4>(), st);
-    HIPCHK(c, hipMemcpyAsync(h.data(), c->vox_in.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    unsigned char* o = static_cast<unsigned char*>(out);
-    for (int i = 0; i < n; ++i) {
-        if (o != b) memcpy(o + (size_t)i * (size_t)stride, b + (size_t)i * (size_t)stride, (size_t)stride);   // other fields copied
-        memcpy(o + (size_t)i * (size_t)stride, &h[(size_t)i], 12);
-    }
-    return LISREG_OK;
-}
-
-// ---- §8 f-2: range-image projection + feature extraction ----------------------------------------------------------------
-int lisreg_default_feature_params(lisreg_feature_params* p)
-{
-    if (!p) return LISREG_ERR_ARG;
-    p->n_scan = 64; p->horizon_scan = 1800; p->downsample_rate = 2;        // config/params.yaml:68-72
-    p->min_range = 0.0f; p->max_range = 70.0f;                            // :73-74
-    p->edge_threshold = 1.0f; p->surf_threshold = 0.1f;                   // :117-118
-    return LISREG_OK;
-}
-
-int lisreg_extract_features(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, const lisreg_feature_params* P,
-                            lisreg_feature_out* out)
-{
-    return lisreg_extract_features_deskew(c, cloud, n, stride, fmt, P, nullptr, out);
-}
-
-int lisreg_extract_features_deskew(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, const lisreg_feature_params* P,
-                                   const lisreg_deskew* dk, lisreg_feature_out* out)
-{
-    if (!c) return LISREG_ERR_ARG;
-    if (!P || !out || n < 0 || (n > 0 && !cloud)) return fail(c, LISREG_ERR_ARG, "extract_features: bad arguments");
-    const bool deskew = dk && dk->enabled && n > 0;
-    if (deskew) {
-        if (dk->imu_pointer_cur < 1 || dk->imu_pointer_cur > (1 << 20) || !dk->imu_time || !dk->imu_rot_x || !dk->imu_rot_y || !dk->imu_rot_z)
-            return fail(c, LISREG_ERR_ARG, "extract_features: de-skew needs IMU tables with imu_pointer_cur >= 1");
-        if (fmt == LISREG_FMT_DEVICE && !dk->time_device) return fail(c, LISREG_ERR_ARG, "extract_features: de-skew of device records needs time_device");
-        if (fmt == LISREG_FMT_XYZIRT && stride < 28) return fail(c, LISREG_ERR_ARG, "extract_features: de-skew needs the time field (stride >= 28)");
-    }
-    if (fmt != LISREG_FMT_XYZIRT && fmt != LISREG_FMT_DEVICE) return fail(c, LISREG_ERR_ARG, "extract_features: fmt must be XYZIRT or DEVICE");
-    if (fmt == LISREG_FMT_XYZIRT && stride < 22) return fail(c, LISREG_ERR_ARG, "extract_features: XYZIRT needs stride >= 22");
-    if (P->n_scan < 1 || P->n_scan > 1024 || P->horizon_scan < 16 || P->horizon_scan > 4096 || P->downsample_rate < 1)
-        return fail(c, LISREG_ERR_ARG, "extract_features: n_scan in [1,1024], horizon_scan in [16,4096], downsample_rate >= 1");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const bool dev = fmt == LISREG_FMT_DEVICE;
-    const int H = P->n_scan, W = P->horizon_scan, hw = H * W;
-    const size_t L = (size_t)hw + 16;
-    HIPCHK(c, c->ft_owner.ensure(sizeof(int) * (size_t)hw));      HIPCHK(c, c->ft_flag.ensure(sizeof(int) * L));
-    HIPCHK(c, c->ft_pos.ensure(sizeof(int) * 2 * (L + 1)));       HIPCHK(c, c->ft_scan.ensure(sizeof(int) * (L / 2048 + 8)));
-    HIPCHK(c, c->ft_col.ensure(sizeof(int) * L));                 HIPCHK(c, c->ft_range.ensure(sizeof(float) * L));
-    HIPCHK(c, c->ft_src.ensure(sizeof(int) * L));                 HIPCHK(c, c->ft_curv.ensure(sizeof(float) * L));
-    HIPCHK(c, c->ft_picked.ensure(sizeof(int) * L));              HIPCHK(c, c->ft_label.ensure(sizeof(int) * L));
-    HIPCHK(c, c->ft_rlists.ensure(sizeof(int) * (size_t)H * 3 * 128));
-    HIPCHK(c, c->ft_rcounts.ensure(sizeof(int) * (size_t)H * 4)); HIPCHK(c, c->ft_lists.ensure(sizeof(int) * 4 * L));
-    HIPCHK(c, c->ft_counts.ensure(sizeof(int) * 8));
-    FeatureBuffers fb;
-    fb.owner = c->ft_owner.as<int>(); fb.flag = c->ft_flag.as<int>(); fb.pos = c->ft_pos.as<int>(); fb.scan_tmp = c->ft_scan.as<int>();
-    fb.col = c->ft_col.as<int>(); fb.range = c->ft_range.as<float>(); fb.src = c->ft_src.as<int>(); fb.curv = c->ft_curv.as<float>();
-    fb.picked = c->ft_picked.as<int>(); fb.label = c->ft_label.as<int>(); fb.ring_lists = c->ft_rlists.as<int>();
-    fb.ring_counts = c->ft_rcounts.as<int>(); fb.lists = c->ft_lists.as<int>(); fb.counts = c->ft_counts.as<int>();
-    // ---- stage the sweep -----------------------------------------------------------------------------------------
-    const float4* pts = nullptr;
-    const uint32_t* rings = nullptr;
-    std::vector<float4> h_pts;
-    std::vector<uint32_t> h_rings;
-    if (dev) pts = static_cast<const float4*>(cloud);
-    else if (n > 0) {
-        h_pts.resize((size_t)n); h_rings.resize((size_t)n);
-        const unsigned char* b = static_cast<const unsigned char*>(cloud);
-        for (int i = 0; i < n; ++i) {
-            const unsigned char* r = b + (size_t)i * (size_t)stride;
-            float v[3], it = 0.f; uint16_t ring;
-            memcpy(v, r, 12); memcpy(&it, r + 16, 4); memcpy(&ring, r + 20, 2);
-            h_pts[(size_t)i] = make_float4(v[0], v[1], v[2], it); h_rings[(size_t)i] = ring;
-        }
-        HIPCHK(c, c->vox_in.ensure(sizeof(float4) * (size_t)n));
-        HIPCHK(c, c->ft_rings.ensure(sizeof(uint32_t) * (size_t)n));
-        HIPCHK(c, hipMemcpyAsync(c->vox_in.p, h_pts.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->ft_rings.p, h_rings.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-        pts = c->vox_in.as<float4>(); rings = c->ft_rings.as<uint32_t>();
-    }
-    launch_extract_features(pts, rings, n, *P, fb, st);
-    HIPCHK(c, hipGetLastError());
-    // ---- IMU de-skew: only the coordinates handed back change (ranges, columns and the selection use the raw points) ----
-    const float4* out_pts = pts;
-    std::vector<float4> h_dsk;
-    if (deskew) {
-        const size_t m = (size_t)dk->imu_pointer_cur + 1;
-        HIPCHK(c, c->ft_dsk_tab.ensure(sizeof(double) * 4 * m + 64));
-        HIPCHK(c, c->ft_dsk_pts.ensure(sizeof(float4) * (size_t)n));
-        HIPCHK(c, c->ft_dsk_misc.ensure(64));
-        double* tab = c->ft_dsk_tab.as<double>();
-        const double* srcs[4] = { dk->imu_time, dk->imu_rot_x, dk->imu_rot_y, dk->imu_rot_z };
-        for (int k = 0; k < 4; ++k) HIPCHK(c, hipMemcpyAsync(tab + (size_t)k * m, srcs[k], sizeof(double) * m, hipMemcpyHostToDevice, st));
-        const float* times_dev = dk->time_device;
-        std::vector<float> h_time;
-        if (!dev) {
-            h_time.resize((size_t)n);
-            const unsigned char* b = static_cast<const unsigned char*>(cloud);
-            for (int i = 0; i < n; ++i) memcpy(&h_time[(size_t)i], b + (size_t)i * (size_t)stride + 24, 4);
-            HIPCHK(c, c->ft_dsk_time.ensure(sizeof(float) * (size_t)n));
-            HIPCHK(c, hipMemcpyAsync(c->ft_dsk_time.p, h_time.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, st));
-            times_dev = c->ft_dsk_time.as<float>();
-        }
-        HIPCHK(c, hipMemcpyAsync(c->ft_dsk_pts.p, pts, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, st));
-        DeskewTables T{ tab, tab + m, tab + 2 * m, tab + 3 * m, dk->imu_pointer_cur, dk->time_scan_cur };
-        launch_deskew(fb.owner, hw, times_dev, T, c->ft_dsk_misc.as<int>(), c->ft_dsk_misc.as<float>() + 4, c->ft_dsk_pts.as<float4>(), st);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(st));               // h_time and the caller's tables are done with
-        out_pts = c->ft_dsk_pts.as<float4>();
-        if (!dev) {
-            h_dsk.resize((size_t)n);
-            HIPCHK(c, hipMemcpyAsync(h_dsk.data(), c->ft_dsk_pts.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
-        }
-    }
-    int counts[8];
-    HIPCHK(c, hipMemcpyAsync(counts, fb.counts, sizeof counts, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    // ---- hand the five clouds back in the caller's layout ------------------------------------------------------------
-    struct Slot { void* buf; int cap; int* n; const int* idx; int cnt; };
-    Slot slots[5] = { { out->deskewed, out->cap_deskewed, &out->n_deskewed, fb.src, counts[0] },
-                      { out->corner, out->cap_corner, &out->n_corner, fb.lists + 0 * L, counts[1] },
-                      { out->surface, out->cap_surface, &out->n_surface, fb.lists + 1 * L, counts[2] },
-                      { out->corner_sharp, out->cap_corner_sharp, &out->n_corner_sharp, fb.lists + 2 * L, counts[3] },
-                      { out->surface_sharp, out->cap_surface_sharp, &out->n_surface_sharp, fb.lists + 3 * L, counts[4] } };
-    for (auto& sl : slots) *sl.n = sl.cnt;
-    for (auto& sl : slots)
-        if (sl.buf && sl.cnt > sl.cap) return fail(c, LISREG_ERR_ARG, "extract_features: an output buffer is too small (counts written back)");
-    std::vector<int> h_idx;
-    for (auto& sl : slots) {
-        if (!sl.buf || sl.cnt == 0) continue;
-        if (dev) launch_gather_points(out_pts, sl.idx, sl.cnt, static_cast<float4*>(sl.buf), st);
-        else {
-            h_idx.resize((size_t)sl.cnt);
-            HIPCHK(c, hipMemcpyAsync(h_idx.data(), sl.idx, sizeof(int) * (size_t)sl.cnt, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            const unsigned char* b = static_cast<const unsigned char*>(cloud);
-            unsigned char* o = static_cast<unsigned char*>(sl.buf);
-            for (int i = 0; i < sl.cnt; ++i) {
-                memcpy(o + (size_t)i * (size_t)stride, b + (size_t)h_idx[(size_t)i] * (size_t)stride, (size_t)stride);
-                if (deskew) memcpy(o + (size_t)i * (size_t)stride, &h_dsk[(size_t)h_idx[(size_t)i]], 12);     // newPoint.x/y/z (:451-456)
-            }
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(st));
-    return LISREG_OK;
-}
-
-// S sweeps in one pass: the sweeps are stacked into ONE range image of S x H rows (grid of the selection kernel = sweeps x
-// rings), every flat pass of the single-sweep pipeline runs once over the stack with per-sweep end guards, and one gather per
-// output list hands every sweep its slice.  Device records in, device records out; the only host round trip is the (S + 1) x 5
-// list boundaries the caller needs anyway.  Results are identical to S single calls (tests/test_features.py).
-int lisreg_extract_features_batch(lisreg_ctx* c, int n_sweeps, const void* const* sweeps, const int* n, const lisreg_feature_params* P,
-                                  lisreg_feature_out* outs)
-{
-    if (!c) return LISREG_ERR_ARG;
-    if (n_sweeps < 0 || (n_sweeps > 0 && (!sweeps || !n || !outs)) || !P) return fail(c, LISREG_ERR_ARG, "extract_features_batch: bad arguments");
-    if (n_sweeps == 0) return LISREG_OK;
-    if (P->n_scan < 1 || P->n_scan > 1024 || P->horizon_scan < 16 || P->horizon_scan > 4096 || P->downsample_rate < 1)
-        return fail(c, LISREG_ERR_ARG, "extract_features_batch: n_scan in [1,1024], horizon_scan in [16,4096], downsample_rate >= 1");
-    if (n_sweeps > 256 || (long long)n_sweeps * P->n_scan > 32768) return fail(c, LISREG_ERR_ARG, "extract_features_batch: at most 256 sweeps and 32768 rows per call");
-    std::vector<int> off((size_t)n_sweeps + 1, 0);
-    for (int s = 0; s < n_sweeps; ++s) {
-        if (n[s] < 0 || (n[s] > 0 && !sweeps[s])) return fail(c, LISREG_ERR_ARG, "extract_features_batch: NULL sweep with n > 0");
-        if ((long long)off[(size_t)s] + n[s] > 2000000000LL) return fail(c, LISREG_ERR_ARG, "extract_features_batch: too many points");
-        off[(size_t)s + 1] = off[(size_t)s] + n[s];
-    }
-    const int N = off[(size_t)n_sweeps];
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const int Hs = P->n_scan, W = P->horizon_scan, H = Hs * n_sweeps, hw = H * W, hw_sweep = Hs * W;
-    const size_t L = (size_t)hw + 16;
-    HIPCHK(c, c->ft_owner.ensure(sizeof(int) * (size_t)hw));      HIPCHK(c, c->ft_flag.ensure(sizeof(int) * L));
-    HIPCHK(c, c->ft_pos.ensure(sizeof(int) * 2 * (L + 1)));       HIPCHK(c, c->ft_scan.ensure(sizeof(int) * (L / 2048 + 8)));
-    HIPCHK(c, c->ft_col.ensure(sizeof(int) * L));                 HIPCHK(c, c->ft_range.ensure(sizeof(float) * L));
-    HIPCHK(c, c->ft_src.ensure(sizeof(int) * L));                 HIPCHK(c, c->ft_curv.ensure(sizeof(float) * L));
-    HIPCHK(c, c->ft_picked.ensure(sizeof(int) * L));              HIPCHK(c, c->ft_label.ensure(sizeof(int) * L));
-    HIPCHK(c, c->ft_rlists.ensure(sizeof(int) * (size_t)H * 3 * 128));
-    HIPCHK(c, c->ft_rcounts.ensure(sizeof(int) * (size_t)H * 4)); HIPCHK(c, c->ft_lists.ensure(sizeof(int) * 4 * L));
-    HIPCHK(c, c->ft_counts.ensure(sizeof(int) * 8));
-    HIPCHK(c, c->ft_cat.ensure(sizeof(float4) * (size_t)std::max(N, 1)));
-    HIPCHK(c, c->ft_rings.ensure(sizeof(uint32_t) * (size_t)std::max(N, 1)));
-    // layout: (S + 1) x 5 list boundaries, then — at the next 16-byte boundary — the 5 x S gather jobs (16 bytes each)
-    const size_t jobs_off = (sizeof(int) * 5 * ((size_t)n_sweeps + 1) + 15) & ~(size_t)15;
-    HIPCHK(c, c->ft_bounds.ensure(jobs_off + 16 * 5 * (size_t)n_sweeps));
-    FeatureBuffers fb;
-    fb.owner = c->ft_owner.as<int>(); fb.flag = c->ft_flag.as<int>(); fb.pos = c->ft_pos.as<int>(); fb.scan_tmp = c->ft_scan.as<int>();
-    fb.col = c->ft_col.as<int>(); fb.range = c->ft_range.as<float>(); fb.src = c->ft_src.as<int>(); fb.curv = c->ft_curv.as<float>();
-    fb.picked = c->ft_picked.as<int>(); fb.label = c->ft_label.as<int>(); fb.ring_lists = c->ft_rlists.as<int>();
-    fb.ring_counts = c->ft_rcounts.as<int>(); fb.lists = c->ft_lists.as<int>(); fb.counts = c->ft_counts.as<int>();
-    float4* cat = c->ft_cat.as<float4>();
-    for (int s = 0; s < n_sweeps; ++s)
-        if (n[s] > 0) HIPCHK(c, hipMemcpyAsync(cat + off[(size_t)s], sweeps[s], sizeof(float4) * (size_t)n[s], hipMemcpyDeviceToDevice, st));
-    launch_feature_batch_rows(cat, N, off.data(), n_sweeps, Hs, P->downsample_rate, c->ft_rings.as<uint32_t>(), st);
-    lisreg_feature_params Pst = *P;
-    Pst.n_scan = H; Pst.downsample_rate = 1;                    // rows are stack rows; the ring filter was applied by k_feat_batch_rows
-    launch_extract_features(cat, c->ft_rings.as<uint32_t>(), N, Pst, fb, st, n_sweeps);
-    int* Bdev = c->ft_bounds.as<int>();
-    launch_feature_batch_bounds(n_sweeps, Hs, hw_sweep, fb, hw, Bdev, st);
-    HIPCHK(c, hipGetLastError());
-    std::vector<int> B(5 * ((size_t)n_sweeps + 1));
-    HIPCHK(c, hipMemcpyAsync(B.data(), Bdev, sizeof(int) * B.size(), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    // ---- per sweep: counts, capacity check, one gather job per list ---------------------------------------------------------
-    struct Job { void* dst; int begin, count; };
-    std::vector<Job> jobs(5 * (size_t)n_sweeps);
-    int max_count[5] = { 0, 0, 0, 0, 0 };
-    for (int s = 0; s < n_sweeps; ++s) {
-        lisreg_feature_out& o = outs[s];
-        // B columns: extracted, corner, corner_sharp, surface_sharp, surface
-        const int cnt[5] = { B[(s + 1) * 5 + 0] - B[s * 5 + 0], B[(s + 1) * 5 + 1] - B[s * 5 + 1], B[(s + 1) * 5 + 4] - B[s * 5 + 4],
-                             B[(s + 1) * 5 + 2] - B[s * 5 + 2], B[(s + 1) * 5 + 3] - B[s * 5 + 3] };      // deskewed, corner, surface, corner_sharp, surface_sharp
-        const int beg[5] = { B[s * 5 + 0], B[s * 5 + 1], B[s * 5 + 4], B[s * 5 + 2], B[s * 5 + 3] };
-        void* bufs[5] = { o.deskewed, o.corner, o.surface, o.corner_sharp, o.surface_sharp };
-        const int caps[5] = { o.cap_deskewed, o.cap_corner, o.cap_surface, o.cap_corner_sharp, o.cap_surface_sharp };
-        o.n_deskewed = cnt[0]; o.n_corner = cnt[1]; o.n_surface = cnt[2]; o.n_corner_sharp = cnt[3]; o.n_surface_sharp = cnt[4];
-        for (int k = 0; k < 5; ++k) {
-            if (bufs[k] && cnt[k] > caps[k]) return fail(c, LISREG_ERR_ARG, "extract_features_batch: an output buffer is too small (counts written back)");
-            jobs[(size_t)k * n_sweeps + s] = Job{ bufs[k], beg[k], bufs[k] ? cnt[k] : 0 };
-            if (bufs[k]) max_count[k] = std::max(max_count[k], cnt[k]);
-        }
-    }
-    static_assert(sizeof(Job) == 16, "gather job = one 16-byte slot");
-    Job* jobs_dev = reinterpret_cast<Job*>(reinterpret_cast<unsigned char*>(Bdev) + jobs_off);     // hipMalloc'ed base is 256-byte aligned
-    HIPCHK(c, hipMemcpyAsync(jobs_dev, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice, st));
-    const int* idx[5] = { fb.src, fb.lists + 0 * L, fb.lists + 1 * L, fb.lists + 2 * L, fb.lists + 3 * L };
-    for (int k = 0; k < 5; ++k)
-        launch_feature_batch_gather(cat, idx[k], jobs_dev + (size_t)k * n_sweeps, n_sweeps, max_count[k], st);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(st));           // `jobs` is a local
-    return LISREG_OK;
-}
-
-int lisreg_semantic_split(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, const uint32_t* using_label,
-                          lisreg_semantic_out* out)
-{
-    if (!c) return LISREG_ERR_ARG;
-    if (!out || n < 0 || (n > 0 && !cloud)) return fail(c, LISREG_ERR_ARG, "semantic_split: bad arguments");
-    if (fmt != LISREG_FMT_XYZIL && fmt != LISREG_FMT_DEVICE) return fail(c, LISREG_ERR_ARG, "semantic_split: fmt must be XYZIL or DEVICE");
-    if (fmt == LISREG_FMT_XYZIL && stride < 22) return fail(c, LISREG_ERR_ARG, "semantic_split: XYZIL needs stride >= 22");
-    static const uint32_t kUsingLabel[32] = { 0, 10, 10, 10, 10, 10, 10, 10, 10, 40, 40, 40, 70, 50, 50, 70, 81, 70, 81, 81 };   // label.yaml:177-196
-    const uint32_t* map = using_label ? using_label : kUsingLabel;
-    for (int k = 0; k < 5; ++k) out->n[k] = 0;
-    if (n == 0) return LISREG_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const bool dev = fmt == LISREG_FMT_DEVICE;
-    const float4* pts = nullptr;
-    const uint32_t* labels = nullptr;
-    std::vector<float4> h_pts;
-    std::vector<uint32_t> h_lab;
-    if (dev) pts = static_cast<const float4*>(cloud);
-    else {
-        h_pts.resize((size_t)n); h_lab.resize((size_t)n);
-        const unsigned char* b = static_cast<const unsigned char*>(cloud);
-        for (int i = 0; i < n; ++i) {
-            const unsigned char* r = b + (size_t)i * (size_t)stride;
-            float v[3]; uint16_t l; memcpy(v, r, 12); memcpy(&l, r + 20, 2);
-            h_pts[(size_t)i] = make_float4(v[0], v[1], v[2], 0.f); h_lab[(size_t)i] = l;
-        }
-        HIPCHK(c, c->vox_in.ensure(sizeof(float4) * (size_t)n));
-        HIPCHK(c, c->vox_lab.ensure(sizeof(uint32_t) * (size_t)n));
-        HIPCHK(c, hipMemcpyAsync(c->vox_in.p, h_pts.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->vox_lab.p, h_lab.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-        pts = c->vox_in.as<float4>(); labels = c->vox_lab.as<uint32_t>();
-    }
-    HIPCHK(c, c->vox_head.ensure(sizeof(int) * (5 * (size_t)n + 1)));
-    HIPCHK(c, c->vox_slot.ensure(sizeof(int) * (5 * (size_t)n + 2)));
-    HIPCHK(c, c->scan_tmp.ensure(sizeof(int) * (5 * (size_t)n / 2048 + 8)));
-    HIPCHK(c, c->ft_lists.ensure(sizeof(int) * 5 * (size_t)n));
-    HIPCHK(c, c->ft_counts.ensure(sizeof(int) * 8));
-    launch_semantic_split(pts, labels, n, map, c->vox_head.as<int>(), c->vox_slot.as<int>(), c->scan_tmp.as<int>(),
-                          c->ft_lists.as<int>(), c->ft_counts.as<int>(), st);
-    HIPCHK(c, hipGetLastError());
-    int counts[5];
-    HIPCHK(c, hipMemcpyAsync(counts, c->ft_counts.p, sizeof counts, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    for (int k = 0; k < 5; ++k) out->n[k] = counts[k];
-    for (int k = 0; k < 5; ++k)
-        if (out->cloud[k] && counts[k] > out->cap[k]) return fail(c, LISREG_ERR_ARG, "semantic_split: an output buffer is too small (counts written back)");
-    std::vector<int> h_idx;
-    if (dev) {
-        SemanticGather sg;
-        for (int k = 0; k < 5; ++k) { sg.out[k] = static_cast<float4*>(out->cloud[k]); sg.count[k] = out->cloud[k] ? counts[k] : 0; }
-        launch_semantic_gather(pts, c->ft_lists.as<int>(), n, sg, st);
-    }
-    for (int k = 0; k < 5; ++k) {
-        if (dev || !out->cloud[k] || counts[k] == 0) continue;
-        const int* idx = c->ft_lists.as<int>() + (size_t)k * n;
-        {
-            h_idx.resize((size_t)counts[k]);
-            HIPCHK(c, hipMemcpyAsync(h_idx.data(), idx, sizeof(int) * (size_t)counts[k], hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            const unsigned char* b = static_cast<const unsigned char*>(cloud);
-            unsigned char* o = static_cast<unsigned char*>(out->cloud[k]);
-            for (int i = 0; i < counts[k]; ++i) memcpy(o + (size_t)i * (size_t)stride, b + (size_t)h_idx[(size_t)i] * (size_t)stride, (size_t)stride);
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(st));
-    return LISREG_OK;
-}
-
-// ---- RCCL pose gather: librccl is loaded lazily so single-GPU users never pay for it ------------
-// ONE RCCL per process, and never in the global symbol scope.  A host process may carry an RCCL of its own already (a PyTorch wheel
-// bundles librccl.so.1 next to ITS librocm_smi64 — soname .so.7, the system's is .so.1, so the loader keeps both): the copy already
-// loaded is reused (RTLD_NOLOAD by soname); only a process without one gets the system's library, RTLD_LOCAL.  Round 3 loaded it
-// RTLD_GLOBAL: the system librocm_smi64's globals then interposed those of the wheel's copy imported later, both static destructors
-// freed the same std::map at exit, and glibc aborted the process ("double free or corruption", exit status 134) after every test had
-// passed.  tests/test_teardown.py runs that sequence in a subprocess.
-static void* rccl_dlopen()
-{
-    void* h = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);
-    if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);
-    if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-    if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-    return h;
-}
-
-static int rccl_load(lisreg_ctx* c)
-{
-    if (c->rccl.handle) return LISREG_OK;
-    void* h = rccl_dlopen();
-    if (!h) return fail(c, LISREG_ERR_COMM, std::string("dlopen(librccl.so): ") + dlerror());
-    c->rccl.handle = h;
-    c->rccl.GetUniqueId = (int (*)(void*))dlsym(h, "ncclGetUniqueId");
-    c->rccl.AllGather = (int (*)(const void*, void*, size_t, int, void*, hipStream_t))dlsym(h, "ncclAllGather");
-    c->rccl.CommDestroy = (int (*)(void*))dlsym(h, "ncclCommDestroy");
-    if (!c->rccl.GetUniqueId || !c->rccl.AllGather || !c->rccl.CommDestroy || !dlsym(h, "ncclCommInitRank"))
-        return fail(c, LISREG_ERR_COMM, "librccl.so lacks the expected nccl* symbols");
-    return LISREG_OK;
-}
-
-int lisreg_comm_unique_id(unsigned char id[128])
-{
-    if (!id) return LISREG_ERR_ARG;
-    void* h = rccl_dlopen();                      // reference-counted by the loader; the library stays for the life of the process
-    if (!h) return fail(nullptr, LISREG_ERR_COMM, "dlopen(librccl.so) failed");
-    auto f = (int (*)(void*))dlsym(h, "ncclGetUniqueId");
-    if (!f || f(id) != 0) return fail(nullptr, LISREG_ERR_COMM, "ncclGetUniqueId failed");
-    return LISREG_OK;
-}
-
-namespace { struct UniqueId128 { char b[128]; }; }
-
-int lisreg_comm_init(lisreg_ctx* c, int rank, int nranks, const unsigned char id[128])
-{
-    if (!c || !id || nranks < 1 || rank < 0 || rank >= nranks) return LISREG_ERR_ARG;
-    int rc = rccl_load(c);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    UniqueId128 uid;
-    memcpy(uid.b, id, 128);
-    auto init = (int (*)(void**, int, UniqueId128, int))dlsym(c->rccl.handle, "ncclCommInitRank");
-    if (init(&c->comm, nranks, uid, rank) != 0) return fail(c, LISREG_ERR_COMM, "ncclCommInitRank failed");
-    c->comm_nranks = nranks;
-    return LISREG_OK;
-}
-
-int lisreg_gather_results(lisreg_ctx* c, const void* local_device, int n_local, void* out_device)
-{
-    if (!c || !local_device || !out_device || n_local < 0) return LISREG_ERR_ARG;
-    if (!c->comm) return fail(c, LISREG_ERR_COMM, "gather_results: call lisreg_comm_init first");
-    const int ncclFloat32 = 7;
-    if (c->rccl.AllGather(local_device, out_device, (size_t)n_local * kResultSize, ncclFloat32, c->comm, c->stream) != 0)
-        return fail(c, LISREG_ERR_COMM, "ncclAllGather failed");
-    return LISREG_OK;
-}
-
-void lisreg_comm_destroy(lisreg_ctx* c)
-{
-    if (!c || !c->comm) return;
-    if (c->rccl.CommDestroy) c->rccl.CommDestroy(c->comm);
-    c->comm = nullptr;
 }
 
 }  // extern "C"

@@ -382,11 +382,9 @@ int lisreg_stage_host_items(lisreg_ctx* c, int n_items, const lisreg_item* items
 int lisreg_upload_cloud(lisreg_ctx* c, const void* cloud, int n, int stride_bytes, int fmt, void* dev_out)
 {
     if (!c) return LISREG_ERR_ARG;
-    if (n < 0 || (n > 0 && (!cloud || !dev_out))) return ctx_fail(c, LISREG_ERR_ARG, "upload_cloud: bad arguments");
-    if (fmt != LISREG_FMT_XYZIL && fmt != LISREG_FMT_XYZI && fmt != LISREG_FMT_XYZI_PACKED)
-        return ctx_fail(c, LISREG_ERR_ARG, "upload_cloud: host clouds only (LISREG_FMT_XYZI / _XYZIL / _XYZI_PACKED)");
-    if (stride_bytes < 12 || (fmt == LISREG_FMT_XYZIL && stride_bytes < 22) || (fmt == LISREG_FMT_XYZI_PACKED && stride_bytes < 16))
-        return ctx_fail(c, LISREG_ERR_ARG, "upload_cloud: bad stride");
+    if (n > 0 && !dev_out) return bad(c, "upload_cloud: NULL dev_out");
+    if (const int rc = check_cloud(c, "upload_cloud", cloud, n, stride_bytes, fmt,      // host clouds only
+                                   fmt_bit(LISREG_FMT_XYZI) | fmt_bit(LISREG_FMT_XYZIL) | fmt_bit(LISREG_FMT_XYZI_PACKED), true)) return rc;
     return upload_records(c, cloud, n, stride_bytes, fmt, dev_out);
 }
 

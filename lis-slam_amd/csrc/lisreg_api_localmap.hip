@@ -2,7 +2,7 @@
 // (/root/reference/src/include/subMap.h:979-1059) and SubMapOptmizationNode::extractSlidingCloud
 // (src/node/subMapOptmizationNode.cpp:1369-1432) as ONE chain over 16-byte device records, ending in the registration
 // target of scan2SubMapOptimization (:1509-1541).  Between frames the five class clouds never leave HBM; per call the host
-// sees only counts and bounding boxes.  Every step is one of the primitives of lisreg_api.hip / lisreg_api_map.hip in
+// sees only counts and bounding boxes.  Every step is one of the primitives of lisreg_api_cloud.hip / lisreg_api_map.hip in
 // LISREG_FMT_DEVICE form, in the reference's order:
 //   insert : transformPointCloud of the frame's dynamic / pole / ground / building clouds (the outlier transform is commented
 //            out in the reference, :1003, so nothing is appended to that class) -> optional map-based dynamic removal of the
@@ -26,7 +26,6 @@ namespace {
 
 constexpr int kMapSlotBase = 60000;      // lisreg_map_index_set slots 60000.. are the local maps' tree_dynamic
 
-int bad(lisreg_ctx* c, const char* msg) { return ctx_fail(c, LISREG_ERR_ARG, msg); }
 
 // grow a device buffer, keeping its first `keep` bytes
 int grow_keep(lisreg_ctx* c, DevBuf& b, size_t bytes, size_t keep)
@@ -238,12 +237,13 @@ static int insert_classes(lisreg_ctx* c, LocalMap* m, int map_id, const void* co
     return update_bound(c, *m);                       // ends with the call's one wait for the stream
 }
 
+// the class clouds of a frame: PCL structs with or without the label, or device records (no LISREG_FMT_XYZIRT here)
+constexpr unsigned kFmtClassClouds = fmt_bit(LISREG_FMT_DEVICE) | fmt_bit(LISREG_FMT_XYZI) | fmt_bit(LISREG_FMT_XYZIL);
 static int check_insert_args(lisreg_ctx* c, const char* who, const void* const clouds[5], const int n[5], int stride, int fmt)
 {
-    if (fmt != LISREG_FMT_DEVICE && fmt != LISREG_FMT_XYZIL && fmt != LISREG_FMT_XYZI) return bad(c, (std::string(who) + ": unknown fmt").c_str());
-    if (fmt != LISREG_FMT_DEVICE && (stride < 12 || (fmt == LISREG_FMT_XYZIL && stride < 22))) return bad(c, (std::string(who) + ": bad stride").c_str());
-    for (int k = 0; k < 5; ++k) if (n[k] < 0 || (n[k] > 0 && !clouds[k])) return bad(c, (std::string(who) + ": NULL cloud with n > 0").c_str());
-    return LISREG_OK;
+    int rc = LISREG_OK;
+    for (int k = 0; k < 5 && !rc; ++k) rc = check_cloud(c, who, clouds[k], n[k], stride, fmt, kFmtClassClouds, true);
+    return rc;
 }
 
 int lisreg_localmap_insert(lisreg_ctx* c, int map_id, const void* const clouds[5], const int n[5], int stride, int fmt,
@@ -272,8 +272,8 @@ static void transform_bbx(const double in[6], const float M[12], double out[6])
     for (int d = 0; d < 3; ++d) { out[3 + d] = in[3 + d] - cp[d] + cpo[d]; out[d] = in[d] - cp[d] + cpo[d]; }
 }
 
-// Eigen::Affine3f::inverse() of a pose matrix: linear part by the cofactor 3x3 inverse, t' = -L^-1 t (float)
-static void affine_inverse(const float A[12], float Ai[12])
+// Eigen::Affine3f::inverse() of a row-major 3 x 4 [R|t]: linear part by the cofactor 3x3 inverse, t' = -L^-1 t (float)
+static void aff_inverse(const float A[12], float I[12])
 {
     const float a = A[0], b = A[1], cc = A[2], d = A[4], e = A[5], f = A[6], g = A[8], h = A[9], i = A[10];
     const float c00 = e * i - f * h, c01 = f * g - d * i, c02 = d * h - e * g;
@@ -282,8 +282,8 @@ static void affine_inverse(const float A[12], float Ai[12])
                          c01 * id, (a * i - cc * g) * id, (cc * d - a * f) * id,
                          c02 * id, (b * g - a * h) * id, (a * e - b * d) * id };
     for (int r = 0; r < 3; ++r) {
-        Ai[4 * r] = L[3 * r]; Ai[4 * r + 1] = L[3 * r + 1]; Ai[4 * r + 2] = L[3 * r + 2];
-        Ai[4 * r + 3] = -(L[3 * r] * A[3] + L[3 * r + 1] * A[7] + L[3 * r + 2] * A[11]);
+        for (int q = 0; q < 3; ++q) I[4 * r + q] = L[3 * r + q];
+        I[4 * r + 3] = -(L[3 * r] * A[3] + L[3 * r + 1] * A[7] + L[3 * r + 2] * A[11]);
     }
 }
 
@@ -300,7 +300,7 @@ void lisreg_submap_crop_boxes(const double pre_local_bound[6], const float pre_p
         isect[d] = std::max(cur[d], pre[d]) - (double)pad;
         isect[3 + d] = std::min(cur[3 + d], pre[3 + d]) + (double)pad;
     }
-    affine_inverse(Mc, Mi);                          // tran_map.inverse() (:4057), then transform_bbx of the intersection box (:4058)
+    aff_inverse(Mc, Mi);                             // tran_map.inverse() (:4057), then transform_bbx of the intersection box (:4058)
     transform_bbx(isect, Mi, isect_local);
 }
 
@@ -517,10 +517,14 @@ int lisreg_keyframes_push(lisreg_ctx* c, int ring_id, const void* corner, int n_
                           const float pose[6], int max_keep, lisreg_keyframes_info* info)
 {
     if (!c) return LISREG_ERR_ARG;
-    if (!pose || n_corner < 0 || n_surf < 0 || (n_corner > 0 && !corner) || (n_surf > 0 && !surf) || max_keep < 1) return bad(c, "keyframes_push: bad argument");
+    if (!pose || max_keep < 1) return bad(c, "keyframes_push: bad argument");
     const bool devfmt = fmt == LISREG_FMT_DEVICE || fmt == LISREG_FMT_DEVICE_XYZI;
-    if (!devfmt && fmt != LISREG_FMT_XYZIL && fmt != LISREG_FMT_XYZI) return bad(c, "keyframes_push: unknown fmt");
-    if (!devfmt && stride < 12) return bad(c, "keyframes_push: bad stride");
+    // (as before, XYZIL structs are only asked for the 12 bytes of XYZI here, although their label is read)
+    const int cfmt = fmt == LISREG_FMT_XYZIL ? LISREG_FMT_XYZI : fmt;
+    const void* src_h[2] = { corner, surf };
+    const int n[2] = { n_corner, n_surf };
+    for (int k = 0; k < 2; ++k)
+        if (const int rc = check_cloud(c, "keyframes_push", src_h[k], n[k], stride, cfmt, kFmtDevice | fmt_bit(LISREG_FMT_XYZI), true)) return rc;
     if (ring_id < 0 || (size_t)ring_id >= c->keyrings.size() || !c->keyrings[(size_t)ring_id].valid) {
         int rc = lisreg_keyframes_reset(c, ring_id);
         if (rc) return rc;
@@ -529,8 +533,6 @@ int lisreg_keyframes_push(lisreg_ctx* c, int ring_id, const void* corner, int n_
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     KeyframeRing::Frame f;
-    const void* src_h[2] = { corner, surf };
-    const int n[2] = { n_corner, n_surf };
     for (int k = 0; k < 2; ++k) {
         f.n[k] = n[k];
         HIPCHK(c, f.cloud[k].ensure(sizeof(float4) * (size_t)std::max(n[k], 1)));
@@ -620,20 +622,6 @@ int lisreg_keyframes_target(lisreg_ctx* c, int ring_id, float corner_leaf, float
 
 // Eigen::Affine3f arithmetic of updateInitialGuess, step by step in float: row-major 3 x 4 [R|t]
 namespace {
-// Affine3f::inverse(): linear part by the cofactor 3x3 inverse, t' = -L^-1 t
-void aff_inverse(const float A[12], float I[12])
-{
-    const float a = A[0], b = A[1], cc = A[2], d = A[4], e = A[5], f = A[6], g = A[8], h = A[9], i = A[10];
-    const float c00 = e * i - f * h, c01 = f * g - d * i, c02 = d * h - e * g;
-    const float det = a * c00 + b * c01 + cc * c02, id = 1.f / det;
-    const float L[9] = { c00 * id, (cc * h - b * i) * id, (b * f - cc * e) * id,
-                         c01 * id, (a * i - cc * g) * id, (cc * d - a * f) * id,
-                         c02 * id, (b * g - a * h) * id, (a * e - b * d) * id };
-    for (int r = 0; r < 3; ++r) {
-        for (int q = 0; q < 3; ++q) I[4 * r + q] = L[3 * r + q];
-        I[4 * r + 3] = -(L[3 * r] * A[3] + L[3 * r + 1] * A[7] + L[3 * r + 2] * A[11]);
-    }
-}
 // Z = X * Y (affine product, accumulated left to right)
 void aff_mul(const float X[12], const float Y[12], float Z[12])
 {

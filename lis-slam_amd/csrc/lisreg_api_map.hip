@@ -13,31 +13,6 @@ using namespace lisreg;
 
 namespace {
 
-int bad(lisreg_ctx* c, const char* msg) { return ctx_fail(c, LISREG_ERR_ARG, msg); }
-
-// the query / input cloud as 16-B device records: the caller's own memory for LISREG_FMT_DEVICE, else uploaded to mp_pts
-int stage_cloud(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, const float4** out)
-{
-    if (fmt == LISREG_FMT_DEVICE) { *out = static_cast<const float4*>(cloud); return LISREG_OK; }
-    std::vector<lisreg_dpoint> h((size_t)std::max(n, 1));
-    pack_cloud(cloud, n, stride, fmt, h.data());
-    HIPCHK(c, c->mp_pts.ensure(sizeof(float4) * (size_t)std::max(n, 1)));
-    HIPCHK(c, hipMemcpyAsync(c->mp_pts.p, h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // h is a local
-    *out = c->mp_pts.as<float4>();
-    return LISREG_OK;
-}
-
-int check_cloud(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, const char* who)
-{
-    if (n < 0 || (n > 0 && !cloud)) return bad(c, (std::string(who) + ": NULL cloud with n > 0").c_str());
-    if (fmt != LISREG_FMT_DEVICE && fmt != LISREG_FMT_XYZI && fmt != LISREG_FMT_XYZIL && fmt != LISREG_FMT_XYZIRT)
-        return bad(c, (std::string(who) + ": unknown fmt").c_str());
-    if (fmt != LISREG_FMT_DEVICE && stride < 12) return bad(c, (std::string(who) + ": stride < 12").c_str());
-    if (fmt == LISREG_FMT_XYZIL && stride < 22) return bad(c, (std::string(who) + ": XYZIL needs stride >= 22").c_str());
-    return LISREG_OK;
-}
-
 // flags (mp_flag) -> survivors of `cloud` in `out`, input layout and order
 int emit_survivors(lisreg_ctx* c, const void* cloud, const float4* pts, int n, int stride, int fmt, void* out, int* n_out)
 {
@@ -91,7 +66,7 @@ int lisreg_map_index_set(lisreg_ctx* c, int slot, const void* cloud, int n, int 
 {
     if (!c) return LISREG_ERR_ARG;
     if (slot < 0 || slot > 65535) return bad(c, "map_index_set: bad slot");
-    int rc = check_cloud(c, cloud, n, stride, fmt, "map_index_set");
+    int rc = check_cloud(c, "map_index_set", cloud, n, stride, fmt, kFmtPackable, true);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
@@ -99,24 +74,9 @@ int lisreg_map_index_set(lisreg_ctx* c, int slot, const void* cloud, int n, int 
     m.valid = false;
     m.n = n;
     float bb[6] = { 0, 0, 0, 0, 0, 0 };
-    if (fmt == LISREG_FMT_DEVICE) m.raw_ptr = static_cast<const float4*>(cloud);
-    else {
-        std::vector<lisreg_dpoint> h((size_t)std::max(n, 1));
-        pack_cloud(cloud, n, stride, fmt, h.data());
-        HIPCHK(c, m.raw.ensure(sizeof(float4) * (size_t)std::max(n, 1)));
-        if (n > 0) {                                  // behind whatever still searches this slot on the context's stream
-            HIPCHK(c, hipMemcpyAsync(m.raw.p, h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipStreamSynchronize(st));      // h is a local
-        }
-        m.raw_ptr = m.raw.as<float4>();
-    }
-    if (n > 0) {
-        HIPCHK(c, c->bbox_dev.ensure(sizeof(float) * 8));
-        HIPCHK(c, c->bbox_scratch.ensure(sizeof(float) * 6 * 256));
-        launch_bbox(m.raw_ptr, n, c->bbox_dev.as<float>(), c->bbox_scratch.as<float>(), st);
-        HIPCHK(c, hipMemcpyAsync(bb, c->bbox_dev.p, sizeof bb, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
+    rc = stage_records(c, cloud, n, stride, fmt, m.raw, &m.raw_ptr);      // (behind whatever still searches this slot on the context's stream)
+    if (rc) return rc;
+    if (n > 0) { rc = cloud_bbox(c, m.raw_ptr, n, bb); if (rc) return rc; }
     for (int d = 0; d < 6; ++d)
         if (n > 0 && !std::isfinite(bb[d])) return bad(c, "map_index_set: the cloud has infinite coordinates");
     if (n > 0 && !(bb[0] <= bb[3] && bb[1] <= bb[4] && bb[2] <= bb[5])) return bad(c, "map_index_set: the cloud has no finite point (every coordinate is NaN)");
@@ -147,7 +107,7 @@ int lisreg_map_index_set_batch(lisreg_ctx* c, int n_maps, const int* slots, cons
     for (int k = 0; k < n_maps; ++k) {
         if (slots[k] < 0 || slots[k] > 65535) return bad(c, "map_index_set_batch: bad slot");
         for (int j = 0; j < k; ++j) if (slots[j] == slots[k]) return bad(c, "map_index_set_batch: a slot is named twice");
-        const int rc = check_cloud(c, clouds[k], counts[k], stride, fmt, "map_index_set_batch");
+        const int rc = check_cloud(c, "map_index_set_batch", clouds[k], counts[k], stride, fmt, kFmtPackable, true);
         if (rc) return rc;
         total += counts[k];
     }
@@ -164,11 +124,7 @@ int lisreg_map_index_set_batch(lisreg_ctx* c, int n_maps, const int* slots, cons
         std::vector<lisreg_dpoint> h((size_t)std::max<long long>(total, 1));
         long long off = 0;
         for (int k = 0; k < n_maps; ++k) { pack_cloud(clouds[k], counts[k], stride, fmt, h.data() + off); off += counts[k]; }
-        HIPCHK(c, c->map_stage.ensure(sizeof(float4) * (size_t)std::max<long long>(total, 1)));
-        if (total > 0) {
-            HIPCHK(c, hipMemcpyAsync(c->map_stage.p, h.data(), sizeof(float4) * (size_t)total, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipStreamSynchronize(st));      // h is a local
-        }
+        if (const int rc = upload_packed(c, h.data(), (size_t)total, c->map_stage)) return rc;
         off = 0;
         for (int k = 0; k < n_maps; ++k) { src[(size_t)k] = c->map_stage.as<float4>() + off; off += counts[k]; }
     }
@@ -285,7 +241,7 @@ int lisreg_nearest(lisreg_ctx* c, int slot, const void* query, int n, int stride
     if (!c) return LISREG_ERR_ARG;
     if (slot < 0 || c->maps.count(slot) == 0 || !c->maps[slot].valid)
         return ctx_fail(c, LISREG_ERR_NO_TARGET, "nearest: no map index in this slot");
-    int rc = check_cloud(c, query, n, stride, fmt, "nearest");
+    int rc = check_cloud(c, "nearest", query, n, stride, fmt, kFmtPackable, true);
     if (rc) return rc;
     if (!(max_dist >= 0.f)) return bad(c, "nearest: max_dist must be >= 0");
     if (n > 0 && (!idx_out || !sqd_out)) return bad(c, "nearest: NULL output");
@@ -294,7 +250,7 @@ int lisreg_nearest(lisreg_ctx* c, int slot, const void* query, int n, int stride
     hipStream_t st = c->stream;
     const MapIndex& m = c->maps[slot];
     const float4* q = nullptr;
-    rc = stage_cloud(c, query, n, stride, fmt, &q);
+    rc = stage_records(c, query, n, stride, fmt, c->mp_pts, &q);
     if (rc) return rc;
     max_dist = std::min(max_dist, 1.8e19f);        // squared below
     if (fmt == LISREG_FMT_DEVICE) {
@@ -319,7 +275,7 @@ int lisreg_dynamic_filter(lisreg_ctx* c, int slot, const void* cloud, int n, int
     if (!c) return LISREG_ERR_ARG;
     if (slot < 0 || c->maps.count(slot) == 0 || !c->maps[slot].valid)
         return ctx_fail(c, LISREG_ERR_NO_TARGET, "dynamic_filter: no map index in this slot");
-    int rc = check_cloud(c, cloud, n, stride, fmt, "dynamic_filter");
+    int rc = check_cloud(c, "dynamic_filter", cloud, n, stride, fmt, kFmtPackable, true);
     if (rc) return rc;
     if (!n_out || (n > 0 && !out)) return bad(c, "dynamic_filter: NULL output");
     if (center_radius != center_radius || dist_thre_min != dist_thre_min || dist_thre_max != dist_thre_max || near_dist_thre != near_dist_thre)
@@ -332,7 +288,7 @@ int lisreg_dynamic_filter(lisreg_ctx* c, int slot, const void* cloud, int n, int
         return rc ? rc : (n <= 10 ? LISREG_NOT_ENOUGH_FEATURES : LISREG_OK);
     }
     const float4* pts = nullptr;
-    rc = stage_cloud(c, cloud, n, stride, fmt, &pts);
+    rc = stage_records(c, cloud, n, stride, fmt, c->mp_pts, &pts);
     if (rc) return rc;
     HIPCHK(c, c->mp_flag.ensure(sizeof(int) * ((size_t)n + 1)));
     launch_dynamic_flags(pts, n, m.g_dev.as<GridIndex>(), center_radius, near_dist_thre, dist_thre_min, dist_thre_max,
@@ -345,14 +301,14 @@ int lisreg_bbx_filter(lisreg_ctx* c, const void* cloud, int n, int stride, int f
                       void* out, int* n_out)
 {
     if (!c) return LISREG_ERR_ARG;
-    int rc = check_cloud(c, cloud, n, stride, fmt, "bbx_filter");
+    int rc = check_cloud(c, "bbx_filter", cloud, n, stride, fmt, kFmtPackable, true);
     if (rc) return rc;
     if (!bounds || !n_out || (n > 0 && !out)) return bad(c, "bbx_filter: NULL argument");
     *n_out = 0;
     if (n == 0) return LISREG_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const float4* pts = nullptr;
-    rc = stage_cloud(c, cloud, n, stride, fmt, &pts);
+    rc = stage_records(c, cloud, n, stride, fmt, c->mp_pts, &pts);
     if (rc) return rc;
     HIPCHK(c, c->mp_flag.ensure(sizeof(int) * ((size_t)n + 1)));
     launch_bbx_flags(pts, n, bounds, delete_box, c->mp_flag.as<int>(), c->stream);
@@ -363,22 +319,18 @@ int lisreg_bbx_filter(lisreg_ctx* c, const void* cloud, int n, int stride, int f
 int lisreg_cloud_bounds(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, double bounds[6])
 {
     if (!c) return LISREG_ERR_ARG;
-    int rc = check_cloud(c, cloud, n, stride, fmt, "cloud_bounds");
+    int rc = check_cloud(c, "cloud_bounds", cloud, n, stride, fmt, kFmtPackable, true);
     if (rc) return rc;
     if (!bounds) return bad(c, "cloud_bounds: NULL bounds");
     for (int d = 0; d < 3; ++d) { bounds[d] = DBL_MAX; bounds[3 + d] = -DBL_MAX; }
     if (n == 0) return LISREG_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const float4* pts = nullptr;
-    rc = stage_cloud(c, cloud, n, stride, fmt, &pts);
+    rc = stage_records(c, cloud, n, stride, fmt, c->mp_pts, &pts);
     if (rc) return rc;
     float bb[6];
-    HIPCHK(c, c->bbox_dev.ensure(sizeof(float) * 8));
-    HIPCHK(c, c->bbox_scratch.ensure(sizeof(float) * 6 * 256));
-    launch_bbox(pts, n, c->bbox_dev.as<float>(), c->bbox_scratch.as<float>(), c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(bb, c->bbox_dev.p, sizeof bb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    rc = cloud_bbox(c, pts, n, bb);
+    if (rc) return rc;
     for (int d = 0; d < 6; ++d) bounds[d] = (double)bb[d];       // float extremes widened, as the reference's double min/max
     return LISREG_OK;
 }
@@ -514,14 +466,14 @@ int lisreg_icp_align(lisreg_ctx* c, int slot, const void* source, int n, int str
     if (!c) return LISREG_ERR_ARG;
     if (slot < 0 || c->maps.count(slot) == 0 || !c->maps[slot].valid)
         return ctx_fail(c, LISREG_ERR_NO_TARGET, "icp_align: no map index in this slot (setInputTarget)");
-    int rc = check_cloud(c, source, n, stride, fmt, "icp_align");
+    int rc = check_cloud(c, "icp_align", source, n, stride, fmt, kFmtPackable, true);
     if (rc) return rc;
     if (!P || !res) return bad(c, "icp_align: NULL params / result");
     if (!(P->max_corr_dist >= 0) || P->max_iters < 1) return bad(c, "icp_align: bad max_corr_dist / max_iters");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const float4* src = nullptr;
-    rc = stage_cloud(c, source, n, stride, fmt, &src);
+    rc = stage_records(c, source, n, stride, fmt, c->mp_pts, &src);
     if (rc) return rc;
     std::vector<IcpHostItem> its(1);
     its[0] = IcpHostItem{ src, n, slot, guess, P->prev_mse, 0 };
@@ -566,13 +518,12 @@ int lisreg_icp_align_batch(lisreg_ctx* c, const lisreg_icp_item* items, int n_it
     for (int k = 0; k < n_items; ++k) {
         if (items[k].slot < 0 || c->maps.count(items[k].slot) == 0 || !c->maps[items[k].slot].valid)
             return ctx_fail(c, LISREG_ERR_NO_TARGET, "icp_align_batch: an item names a slot without a map index (setInputTarget)");
-        const int rc = check_cloud(c, items[k].source, items[k].n, stride, fmt, "icp_align_batch");
+        const int rc = check_cloud(c, "icp_align_batch", items[k].source, items[k].n, stride, fmt, kFmtPackable, true);
         if (rc) return rc;
         total += items[k].n;
     }
     if (n_items == 0) return LISREG_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
     std::vector<IcpHostItem> its((size_t)n_items);
     if (fmt == LISREG_FMT_DEVICE) {
         for (int k = 0; k < n_items; ++k) its[(size_t)k].src = static_cast<const float4*>(items[k].source);
@@ -581,9 +532,7 @@ int lisreg_icp_align_batch(lisreg_ctx* c, const lisreg_icp_item* items, int n_it
         std::vector<lisreg_dpoint> h((size_t)std::max<long long>(total, 1));
         long long off = 0;
         for (int k = 0; k < n_items; ++k) { pack_cloud(items[k].source, items[k].n, stride, fmt, h.data() + off); off += items[k].n; }
-        HIPCHK(c, c->mp_pts.ensure(sizeof(float4) * (size_t)std::max<long long>(total, 1)));
-        if (total > 0) HIPCHK(c, hipMemcpyAsync(c->mp_pts.p, h.data(), sizeof(float4) * (size_t)total, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipStreamSynchronize(st));      // h is a local
+        if (const int rc = upload_packed(c, h.data(), (size_t)total, c->mp_pts)) return rc;
         off = 0;
         for (int k = 0; k < n_items; ++k) { its[(size_t)k].src = c->mp_pts.as<float4>() + off; off += items[k].n; }
     }
@@ -626,7 +575,7 @@ int lisreg_icp_gn_match(lisreg_ctx* c, int slot, const void* source, int n, int 
     if (!c) return LISREG_ERR_ARG;
     if (slot < 0 || c->maps.count(slot) == 0 || !c->maps[slot].valid)
         return ctx_fail(c, LISREG_ERR_NO_TARGET, "icp_gn_match: no map index in this slot (SetTargetCloud)");
-    int rc = check_cloud(c, source, n, stride, fmt, "icp_gn_match");
+    int rc = check_cloud(c, "icp_gn_match", source, n, stride, fmt, kFmtPackable, true);
     if (rc) return rc;
     if (!predict_pose || !res) return bad(c, "icp_gn_match: NULL predict_pose / result");
     if (max_iterations > 100000u) return bad(c, "icp_gn_match: max_iterations out of range");
@@ -634,7 +583,7 @@ int lisreg_icp_gn_match(lisreg_ctx* c, int slot, const void* source, int n, int 
     hipStream_t st = c->stream;
     const MapIndex& m = c->maps[slot];
     const float4* src = nullptr;
-    rc = stage_cloud(c, source, n, stride, fmt, &src);
+    rc = stage_records(c, source, n, stride, fmt, c->mp_pts, &src);
     if (rc) return rc;
     IcpState h;
     memset(&h, 0, sizeof h);

@@ -319,11 +319,31 @@ struct lisreg_ctx {
 
 namespace lisreg {
 void feeder_stop(lisreg_ctx* c);       // drains the copy and pack streams and joins the packing threads (lisreg_destroy, before the staging goes)
-int  ctx_fail(lisreg_ctx* c, int code, const std::string& msg);
+// ---- lisreg_api_ctx.hip: what the entry points of every translation unit share ------------------------------------------------------
+int  ctx_fail(lisreg_ctx* c, int code, const std::string& msg);     // keeps the text for lisreg_last_error and returns `code`
+int  bad(lisreg_ctx* c, const std::string& msg);                    // ctx_fail(c, LISREG_ERR_ARG, msg)
+// The (cloud, n, stride, fmt) arguments of an entry point.  accepted_formats: the fmt_bit()s this entry point takes — any other value of
+// fmt is refused; allow_empty: n == 0 passes.  Refused besides: n < 0, a NULL cloud with n > 0, and host structs whose stride is too
+// short for what pack_cloud reads of them (12 bytes; XYZIL 22, the label; XYZI_PACKED 16).  Device records: the stride is not read.
+constexpr unsigned fmt_bit(int fmt) { return 1u << fmt; }
+constexpr unsigned kFmtDevice = fmt_bit(LISREG_FMT_DEVICE) | fmt_bit(LISREG_FMT_DEVICE_XYZI);
+constexpr unsigned kFmtPackable = fmt_bit(LISREG_FMT_DEVICE) | fmt_bit(LISREG_FMT_XYZI) | fmt_bit(LISREG_FMT_XYZIL) | fmt_bit(LISREG_FMT_XYZIRT);   // what pack_cloud reads, and records
+constexpr unsigned kFmtSweep = fmt_bit(LISREG_FMT_XYZI) | fmt_bit(LISREG_FMT_XYZI_PACKED) | fmt_bit(LISREG_FMT_DEVICE_XYZI);      // a raw sweep: x y z intensity
+int  check_cloud(lisreg_ctx* c, const char* who, const void* cloud, int n, int stride, int fmt, unsigned accepted_formats, bool allow_empty);
+// do the byte ranges [a, a + na) and [b, b + nb) meet?  (a NULL pointer or an empty range meets nothing)
+bool spans_overlap(const void* a, size_t na, const void* b, size_t nb);
 // the side stream and its fork / join events, created on first use; false if they cannot be made (the caller then runs on one stream)
 bool ensure_side_stream(lisreg_ctx* c);
 // pack PCL structs (stride/format of common.h:9,25-35) into 16-B device records
 void pack_cloud(const void* cloud, int n, int stride, int fmt, lisreg_dpoint* out);
+// n packed records from the caller's local `h` into `into` (grown to fit, at least one record) by a pageable copy on the context's stream,
+// waited for because `h` is a local; n == 0 copies nothing and waits for nothing
+int  upload_packed(lisreg_ctx* c, const lisreg_dpoint* h, size_t n, DevBuf& into);
+// one cloud as 16-byte device records: the caller's own memory for LISREG_FMT_DEVICE, else pack_cloud + upload_packed into `into`
+int  stage_records(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, DevBuf& into, const float4** out);
+// each coordinate's finite minimum and maximum over n > 0 device records: launch_bbox on the context's stream, read back and waited for.
+// A cloud without a finite point gives min > max; Inf coordinates come back as they are: what to refuse is the caller's business
+int  cloud_bbox(lisreg_ctx* c, const float4* pts, int n, float bb[6]);
 // lisreg_upload_cloud's body: fmt is LISREG_FMT_XYZI (payload 0), _XYZIL (uint16 at byte 20), _XYZI_PACKED (the float at byte 12) or
 // kPackIntensity (PCL PointXYZI with the float intensity at byte 16 as the payload)
 constexpr int kPackIntensity = 0x100;
@@ -332,6 +352,7 @@ int  upload_records(lisreg_ctx* c, const void* cloud, int n, int stride_bytes, i
 void make_grid(const float bb[6], int n, GridIndex* g, int* n_cells, int margin_cells = 0);
 SortBuffers sort_buffers(lisreg_ctx* c);
 int  ensure_sort_scratch(lisreg_ctx* c, size_t n_elems, size_t n_buckets);
+// ---- lisreg_api.hip -------------------------------------------------------------------------------------------------------------------
 void ctx_prof_mark(lisreg_ctx* c, int kind_of_next_interval);      // 0 correspondence kernel, 1 solve, 2 index build, -1 nothing
 void ctx_prof_collect(lisreg_ctx* c);
 }  // namespace lisreg

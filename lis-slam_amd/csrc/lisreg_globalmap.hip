@@ -66,7 +66,6 @@ __global__ __launch_bounds__(kTile) void k_submap_gather(const GatherSeg* __rest
     }
 }
 
-int bad(lisreg_ctx* c, const char* msg) { return ctx_fail(c, LISREG_ERR_ARG, msg); }
 
 // segment starts of the gather (n_maps * 5 + 1 entries); LISREG_ERR_NO_TARGET for an id that names no map
 int plan_offsets(lisreg_ctx* c, const char* who, int n_maps, const int* map_ids, unsigned class_mask, std::vector<long long>& off)

@@ -596,7 +596,6 @@ __global__ __launch_bounds__(64) void k_loop_select(const LoopFrame* __restrict_
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 
-int bad(lisreg_ctx* c, const char* msg) { return ctx_fail(c, LISREG_ERR_ARG, msg); }
 
 }  // namespace
 

@@ -281,8 +281,6 @@ __global__ __launch_bounds__(64) void k_ndt_total(const double* __restrict__ par
         for (int k = 0; k < kNdtOut; ++k) out[k] = acc[k];
 }
 
-int bad(lisreg_ctx* c, const std::string& msg) { return ctx_fail(c, LISREG_ERR_ARG, msg); }
-
 struct NdtRun {
     lisreg_ctx*      c;
     const NdtTarget* T;
@@ -333,30 +331,6 @@ int eval_along(NdtRun& r, const double base[6], const double dir[6], double a, b
     return LISREG_OK;
 }
 
-int check_cloud(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, const char* who)
-{
-    if (n <= 0) return bad(c, std::string(who) + ": n <= 0");
-    if (!cloud) return bad(c, std::string(who) + ": NULL cloud");
-    if (fmt != LISREG_FMT_DEVICE && fmt != LISREG_FMT_XYZI && fmt != LISREG_FMT_XYZIL && fmt != LISREG_FMT_XYZIRT)
-        return bad(c, std::string(who) + ": unknown fmt");
-    if (fmt != LISREG_FMT_DEVICE && stride < 12) return bad(c, std::string(who) + ": stride < 12");
-    if (fmt == LISREG_FMT_XYZIL && stride < 22) return bad(c, std::string(who) + ": XYZIL needs stride >= 22");
-    return LISREG_OK;
-}
-
-// the cloud as 16-byte device records: the caller's memory for LISREG_FMT_DEVICE, else packed and uploaded into `buf`
-int stage(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, DevBuf& buf, const float4** out)
-{
-    if (fmt == LISREG_FMT_DEVICE) { *out = static_cast<const float4*>(cloud); return LISREG_OK; }
-    std::vector<lisreg_dpoint> h((size_t)n);
-    pack_cloud(cloud, n, stride, fmt, h.data());
-    HIPCHK(c, buf.ensure(sizeof(float4) * (size_t)n));
-    HIPCHK(c, hipMemcpyAsync(buf.p, h.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // h is a local
-    *out = buf.as<float4>();
-    return LISREG_OK;
-}
-
 int find_target(lisreg_ctx* c, int slot, const lisreg_ndt_params* P, const char* who, NdtTarget** out)
 {
     auto it = c->ndt.find(slot);
@@ -395,22 +369,19 @@ int lisreg_ndt_set_target(lisreg_ctx* c, int slot, const void* cloud, int n, int
     if (slot < 0 || slot > 65535) return bad(c, "ndt_set_target: bad slot");
     int rc = check_params(c, P, "ndt_set_target");
     if (rc) return rc;
-    rc = check_cloud(c, cloud, n, stride, fmt, "ndt_set_target");
+    rc = check_cloud(c, "ndt_set_target", cloud, n, stride, fmt, kFmtPackable, false);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     NdtTarget& T = c->ndt[slot];
     T.valid = false;
     const float4* raw = nullptr;
-    rc = stage(c, cloud, n, stride, fmt, c->ndt_src, &raw);
+    rc = stage_records(c, cloud, n, stride, fmt, c->ndt_src, &raw);
     if (rc) return rc;
     // ---- bounding box (each coordinate's finite minimum / maximum) and the pcl::VoxelGrid geometry ----------------------------------
     float bb[6];
-    HIPCHK(c, c->bbox_dev.ensure(sizeof(float) * 8));
-    HIPCHK(c, c->bbox_scratch.ensure(sizeof(float) * 6 * 256));
-    launch_bbox(raw, n, c->bbox_dev.as<float>(), c->bbox_scratch.as<float>(), st);
-    HIPCHK(c, hipMemcpyAsync(bb, c->bbox_dev.p, sizeof bb, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    rc = cloud_bbox(c, raw, n, bb);
+    if (rc) return rc;
     for (int k = 0; k < 6; ++k)
         if (!std::isfinite(bb[k])) return bad(c, "ndt_set_target: the cloud has infinite coordinates");
     if (!(bb[0] <= bb[3] && bb[1] <= bb[4] && bb[2] <= bb[5])) return bad(c, "ndt_set_target: the cloud has no finite point: no valid voxel");
@@ -515,12 +486,12 @@ int lisreg_ndt_derivatives(lisreg_ctx* c, int slot, const void* source, int n, i
     NdtTarget* T = nullptr;
     rc = find_target(c, slot, P, "ndt_derivatives", &T);
     if (rc) return rc;
-    rc = check_cloud(c, source, n, stride, fmt, "ndt_derivatives");
+    rc = check_cloud(c, "ndt_derivatives", source, n, stride, fmt, kFmtPackable, false);
     if (rc) return rc;
     if (!p || !out) return bad(c, "ndt_derivatives: NULL p / out");
     HIPCHK(c, hipSetDevice(c->device));
     NdtRun r; r.c = c; r.T = T; r.n = n;
-    rc = stage(c, source, n, stride, fmt, c->ndt_src, &r.src);
+    rc = stage_records(c, source, n, stride, fmt, c->ndt_src, &r.src);
     if (rc) return rc;
     gauss_constants(P->outlier_ratio, P->resolution, &r.g1, &r.g2);
     rc = evaluate(r, p, with_hessian != 0);
@@ -539,13 +510,13 @@ int lisreg_ndt_align(lisreg_ctx* c, int slot, const void* source, int n, int str
     NdtTarget* T = nullptr;
     rc = find_target(c, slot, P, "ndt_align", &T);
     if (rc) return rc;
-    rc = check_cloud(c, source, n, stride, fmt, "ndt_align");
+    rc = check_cloud(c, "ndt_align", source, n, stride, fmt, kFmtPackable, false);
     if (rc) return rc;
     if (!res) return bad(c, "ndt_align: NULL result");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     NdtRun r; r.c = c; r.T = T; r.n = n;
-    rc = stage(c, source, n, stride, fmt, c->ndt_src, &r.src);
+    rc = stage_records(c, source, n, stride, fmt, c->ndt_src, &r.src);
     if (rc) return rc;
     gauss_constants(P->outlier_ratio, P->resolution, &r.g1, &r.g2);
     double p[6];

@@ -244,13 +244,6 @@ __global__ __launch_bounds__(256) void k_pt_write(PtSweep one, const PtSweep* __
     if (i == k) hdr[s].half_index = pos;
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    if (!a || !b || na == 0 || nb == 0) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 // the launch sequence over device sweeps; headers land in c->pt_hdr_host (pinned) when the call returns
 int pretreat_device(lisreg_ctx* c, int n_sweeps, std::vector<PtSweep>& sw, const lisreg_pretreat_params& P)
 {
@@ -314,17 +307,16 @@ int lisreg_default_pretreat_params(lisreg_pretreat_params* p)
 int lisreg_pretreat(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, const lisreg_pretreat_params* P, lisreg_pretreat_out* out)
 {
     if (!c) return LISREG_ERR_ARG;
-    if (!out || n < 0 || (n > 0 && !cloud)) return ctx_fail(c, LISREG_ERR_ARG, "pretreat: bad arguments");
+    if (!out) return bad(c, "pretreat: bad arguments");
     if (const int rc = check_params(c, P, "pretreat")) return rc;
     const bool dev = fmt == LISREG_FMT_DEVICE_XYZI;
-    if (!dev && fmt != LISREG_FMT_XYZI && fmt != LISREG_FMT_XYZI_PACKED)
-        return ctx_fail(c, LISREG_ERR_ARG, "pretreat: fmt must be XYZI, XYZI_PACKED or DEVICE_XYZI");
-    if (!dev && stride < (fmt == LISREG_FMT_XYZI ? 20 : 16)) return ctx_fail(c, LISREG_ERR_ARG, "pretreat: bad stride");
+    if (const int rc = check_cloud(c, "pretreat", cloud, n, stride, fmt, kFmtSweep, true)) return rc;
+    if (fmt == LISREG_FMT_XYZI && stride < 20) return bad(c, "pretreat: XYZI needs stride >= 20 (the intensity is read)");
     if (out->capacity < 0 || (out->capacity > 0 && (!out->cloud || (dev && !out->time_device))))
         return ctx_fail(c, LISREG_ERR_ARG, "pretreat: output buffers missing");
     const size_t in_bytes = (size_t)n * (dev ? sizeof(lisreg_dpoint) : (size_t)stride), cap = (size_t)out->capacity;
-    if (overlap(cloud, in_bytes, out->cloud, cap * (dev ? 16 : 32)) ||
-        (dev && (overlap(cloud, in_bytes, out->time_device, cap * 4) || overlap(cloud, in_bytes, out->intensity_device, cap * 4))))
+    if (spans_overlap(cloud, in_bytes, out->cloud, cap * (dev ? 16 : 32)) ||
+        (dev && (spans_overlap(cloud, in_bytes, out->time_device, cap * 4) || spans_overlap(cloud, in_bytes, out->intensity_device, cap * 4))))
         return ctx_fail(c, LISREG_ERR_ARG, "pretreat: the output overlaps the input");
     out->n = 0; out->start_ori = out->end_ori = 0.f; out->half_index = -1;
     if (n == 0) return LISREG_OK;
@@ -390,8 +382,8 @@ int lisreg_pretreat_batch(lisreg_ctx* c, int n_sweeps, const void* const* sweeps
     for (int s = 0; s < n_sweeps; ++s)                                  // no output of the call may lie over an input of the call
         for (int t = 0; t < n_sweeps; ++t) {
             const size_t in_bytes = (size_t)n[t] * 16, cap = (size_t)outs[s].capacity;
-            if (overlap(sweeps[t], in_bytes, outs[s].cloud, cap * 16) || overlap(sweeps[t], in_bytes, outs[s].time_device, cap * 4) ||
-                overlap(sweeps[t], in_bytes, outs[s].intensity_device, cap * 4))
+            if (spans_overlap(sweeps[t], in_bytes, outs[s].cloud, cap * 16) || spans_overlap(sweeps[t], in_bytes, outs[s].time_device, cap * 4) ||
+                spans_overlap(sweeps[t], in_bytes, outs[s].intensity_device, cap * 4))
                 return ctx_fail(c, LISREG_ERR_ARG, "pretreat_batch: an output overlaps an input");
         }
     HIPCHK(c, hipSetDevice(c->device));

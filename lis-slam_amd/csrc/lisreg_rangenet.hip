@@ -316,18 +316,12 @@ __global__ __launch_bounds__(256) void k_rn_knn(RnKnnSweep one, const RnKnnSweep
 }
 
 struct Span { const void* p; size_t bytes; };
-bool spans_overlap(const Span& a, const Span& b)
-{
-    if (!a.p || !b.p || a.bytes == 0 || b.bytes == 0) return false;
-    const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
-    return x < y + b.bytes && y < x + a.bytes;
-}
 // no output may lie over an input or over another output
 bool any_overlap(const std::vector<Span>& in, const std::vector<Span>& out)
 {
     for (size_t a = 0; a < out.size(); ++a) {
-        for (const Span& i : in) if (spans_overlap(out[a], i)) return true;
-        for (size_t b = a + 1; b < out.size(); ++b) if (spans_overlap(out[a], out[b])) return true;
+        for (const Span& i : in) if (spans_overlap(out[a].p, out[a].bytes, i.p, i.bytes)) return true;
+        for (size_t b = a + 1; b < out.size(); ++b) if (spans_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) return true;
     }
     return false;
 }
@@ -507,12 +501,11 @@ int lisreg_rangenet_project(lisreg_ctx* c, const void* cloud, int n, int stride,
                             lisreg_rangenet_out* out)
 {
     if (!c) return LISREG_ERR_ARG;
-    if (!out || n < 0 || (n > 0 && !cloud)) return ctx_fail(c, LISREG_ERR_ARG, "rangenet_project: bad arguments");
+    if (!out) return bad(c, "rangenet_project: bad arguments");
     if (const int rc = check_params(c, P, "rangenet_project")) return rc;
     const bool dev = fmt == LISREG_FMT_DEVICE_XYZI;
-    if (!dev && fmt != LISREG_FMT_XYZI && fmt != LISREG_FMT_XYZI_PACKED)
-        return ctx_fail(c, LISREG_ERR_ARG, "rangenet_project: fmt must be XYZI, XYZI_PACKED or DEVICE_XYZI");
-    if (!dev && stride < (fmt == LISREG_FMT_XYZI ? 20 : 16)) return ctx_fail(c, LISREG_ERR_ARG, "rangenet_project: bad stride");
+    if (const int rc = check_cloud(c, "rangenet_project", cloud, n, stride, fmt, kFmtSweep, true)) return rc;
+    if (fmt == LISREG_FMT_XYZI && stride < 20) return bad(c, "rangenet_project: XYZI needs stride >= 20 (the intensity is read)");
     if (!out->tensor || !out->invalid_mask || (n > 0 && !out->pixel_index))
         return ctx_fail(c, LISREG_ERR_ARG, "rangenet_project: output buffers missing");
     const size_t hw = (size_t)P->img_h * (size_t)P->img_w;
