@@ -267,11 +267,14 @@ void* lisreg_batch_result_device(const lisreg_ctx* ctx);
  * half's 6x6 solves run underneath the other half's correspondence launch — 1: the halves' launches alternate, 2: free-running; same
  * kernels on the same data in the same order per registration, results identical to the bit; measured +1.7 % (mode 2) on
  * BASELINE configs[1], +5.8 % on configs[4], at the price of per-kernel durations that are no longer a launch's own — off),
- * "row_reach" (1 [default]: a batch that takes the cell rows and rebuilds its targets inside every run ("rebuild_targets_each_run") builds
+ * "row_reach" (1: a batch that takes the cell rows and rebuilds its targets inside every run ("rebuild_targets_each_run") builds
  * rows only for the grid cells its queries come within a metre of under their INITIAL poses — lisreg_batch_prepare makes one pass over
  * the batch's source points for that —; a query that reaches a cell without rows takes the cell walk, so results do not depend on it,
- * bit for bit.  A run counts such queries; more than one query-iteration in a thousand and the prepared batch's later runs, and the next
- * 32 batches prepared on the context, build all rows.  0: all rows always),
+ * bit for bit.  2 [default]: of those cells, only the ones a query starts in and the ones within half a metre of a target point (a
+ * target point in the cell's 3 x 3 x 3 block; grids with cells under 0.5 m, where half a metre is two cells, keep the rows of 1): a
+ * query moves from where its initial pose puts it towards the target's surface, not a metre in every direction.  A run counts the
+ * queries that find their cell without rows; more than one query-iteration in a thousand and the prepared batch's later runs, and the
+ * next 32 batches prepared on the context, build all rows.  0: all rows always; other values are refused with LISREG_ERR_ARG),
  * "graph_min_ratio", "cell_min_ratio" (auto takes the cell rows from this many query-iterations per target point: 110), "cell_rows_max_mb",
  * "first_pass_mm" (radius of the cell walk's first pass, >= 0: a negative value is refused with LISREG_ERR_ARG), "count_searches",
  * "early_stop_chunk" (<= -1 auto, 0 never look).  Out-of-range values of the numeric knobs are clamped, not refused: "index_strip_cells"

@@ -13,6 +13,7 @@
 #include "lisreg_ctx.hpp"
 
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -76,12 +77,21 @@ int ensure_graph(lisreg_ctx* c, Target& t, int k, bool launch)
 // search_mode 5: cell rows of target kind k (the index itself must already be enqueued on the stream).  The row count depends on the
 // data, so the first build of a target classifies its cells, reads the count back (one host round trip, at set / prepare time) and sizes the
 // buffers; rebuilds inside a run (rebuild_targets_each_run) reuse that capacity — a cell that does not fit gets no row and its queries walk.
-lisreg::CrowBuffers crow_buffers(Target& t, int k, bool with_reach = false)
+// "row_reach" = 2, `near`: the target has a point within P cells of the cell (Chebyshev, like the 5 x 5 x 5 count).  P is half a metre in
+// cells — in metres, like the dilation: the queries' path from their initial pose to the surface does not shrink with the cells.
+// P = 1 (cells of 0.5 m and more) is the 3 x 3 x 3 count the classification makes for it; P = 2 (smaller cells: never under 0.25 m,
+// make_grid) IS the 5 x 5 x 5 count every cell with rows has anyway, so such grids keep the rows of "row_reach" = 1.
+static int crow_near_cells(float cell) { return std::max(1, (int)std::ceil(0.5f / cell - 1e-3f)); }
+
+lisreg::CrowBuffers crow_buffers(Target& t, int k, bool with_reach = false, bool near_only = false)
 {
     lisreg::CrowBuffers cb;
     cb.need = t.crow_need[k].as<int>(); cb.omask = t.crow_omask[k].as<int>(); cb.scan = t.crow_scan[k].as<int>(); cb.scan_tmp = t.crow_scan_tmp[k].as<int>();
     cb.cap_rows = t.crow_cap[k];
     cb.reach = with_reach && t.g[k].qmark ? t.crow_reach[k].as<unsigned>() : nullptr;      // (never for the classification that SIZES the row buffers)
+    const int P = crow_near_cells(t.g[k].cell);
+    assert(P <= 2);
+    cb.qmark = cb.reach && near_only && P == 1 ? t.g[k].qmark : nullptr;
     return cb;
 }
 
@@ -632,12 +642,8 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
             }
     for (int slot : c->batch_slots)            // query marks for the row build of every run (option "row_reach"): buffers + the pointer in the grid
         for (int k = 0; k < 2; ++k) {
-            const unsigned* before = c->targets[(size_t)slot].g[k].qmark;
             rc = ensure_reach(c, c->targets[(size_t)slot], k, c->mode_now == 5 && c->rebuild_targets_each_run && c->row_reach != 0);
             if (rc) return rc;
-            Target& t = c->targets[(size_t)slot];
-            if (t.g[k].qmark && t.g[k].qmark != before)       // new words: zero once, every run hands them back clean
-                HIPCHK(c, hipMemsetAsync(t.g[k].qmark, 0, sizeof(unsigned) * (size_t)t.g[k].nx * (size_t)t.g[k].ny * (size_t)t.g[k].qmark_w, c->stream));
         }
     if (c->grids_dirty) { rc = upload_grids(c); if (rc) return rc; }
     // table for rebuilding every target index of this batch in ONE launch sequence (rebuild_targets_each_run)
@@ -754,21 +760,27 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
     // part of its map — the lidar's elevation span leaves the upper walls of the benchmark room unseen: a fifth of the cells that would
     // get rows — so every run builds rows only for the cells a query comes within a metre of under its INITIAL pose: one pass over the
     // batch's source points (k_query_marks: the cell each falls into), those marks grown by ceil(1 m / cell) cells (`reach`, read by the
-    // classification of every run), the mark words handed back clean.  They depend on the sources and the initial poses — what this call
-    // is given — not on the target's points, which a run may find changed.
+    // classification of every run).  The mark words are cleared in front of the marking and kept: "row_reach" = 2 reads them as well (the
+    // cells a query starts in).  Both depend on the sources and the initial poses — what this call is given — not on the target's points,
+    // which a run may find changed.
     c->reach_ready = false;
     if (c->reach_backoff > 0) --c->reach_backoff;
     else if (c->mode_now == 5 && c->rebuild_targets_each_run && c->row_reach != 0 && c->lanes_q == 1 && c->n_blocks > 0) {
         bool any = false;
         for (int slot : c->batch_slots) for (int k = 0; k < 2; ++k) any = any || (c->targets[(size_t)slot].g[k].qmark != nullptr && c->targets[(size_t)slot].n[k] > 0);
         if (any) {
+            for (int slot : c->batch_slots)
+                for (int k = 0; k < 2; ++k) {
+                    Target& t = c->targets[(size_t)slot];
+                    if (!t.g[k].qmark || t.n[k] <= 0) continue;
+                    HIPCHK(c, hipMemsetAsync(t.g[k].qmark, 0, sizeof(unsigned) * (size_t)t.g[k].nx * (size_t)t.g[k].ny * (size_t)t.g[k].qmark_w, c->stream));
+                }
             launch_query_marks(c->blocks.as<BlockDesc>(), c->n_blocks, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(), c->items.as<ItemState>(), c->stream);
             for (int slot : c->batch_slots)
                 for (int k = 0; k < 2; ++k) {
                     Target& t = c->targets[(size_t)slot];
                     if (!t.g[k].qmark || t.n[k] <= 0) continue;
                     launch_reach_dilate(t.g[k], t.crow_reach[k].as<unsigned>(), c->stream);
-                    HIPCHK(c, hipMemsetAsync(t.g[k].qmark, 0, sizeof(unsigned) * (size_t)t.g[k].nx * (size_t)t.g[k].ny * (size_t)t.g[k].qmark_w, c->stream));
                 }
             HIPCHK(c, hipGetLastError());
             c->reach_ready = true;
@@ -902,7 +914,7 @@ static int run_impl(lisreg_ctx* c, bool early_stop)
                 Target& t = c->targets[(size_t)slot];
                 const GridIndex g2[2] = { t.g[0], t.g[1] };
                 const int nc2[2] = { t.n_cells[0], t.n_cells[1] };
-                const lisreg::CrowBuffers cb2[2] = { crow_buffers(t, 0, c->reach_now), crow_buffers(t, 1, c->reach_now) };
+                const lisreg::CrowBuffers cb2[2] = { crow_buffers(t, 0, c->reach_now, c->row_reach == 2), crow_buffers(t, 1, c->reach_now, c->row_reach == 2) };
                 int* oz2[2] = { &t.omask_zero[0], &t.omask_zero[1] };
                 launch_crow_rows_pair(g2, nc2, cb2, st, oz2);
             }
@@ -1074,7 +1086,10 @@ int lisreg_set_option(lisreg_ctx* c, const char* name, int value)
     }
     if (!strcmp(name, "graph_min_ratio")) { c->graph_min_ratio = value; c->prepared = false; return LISREG_OK; }
     if (!strcmp(name, "cell_min_ratio")) { c->cell_min_ratio = value; c->prepared = false; return LISREG_OK; }
-    if (!strcmp(name, "row_reach")) { c->row_reach = value; c->reach_backoff = 0; c->prepared = false; return LISREG_OK; }
+    if (!strcmp(name, "row_reach")) {
+        if (value < 0 || value > 2) return bad(c, "row_reach: 0 all rows, 1 rows within a metre of the queries, 2 of those the cells near the target or a query");
+        c->row_reach = value; c->reach_backoff = 0; c->prepared = false; return LISREG_OK;
+    }
     if (!strcmp(name, "cell_rows_max_mb")) {
         c->cell_rows_max_mb = value; c->prepared = false;
         for (auto& t : c->targets) for (int k = 0; k < 2; ++k) {        // a new bound: what was too big may fit now, what fitted may have to be capped

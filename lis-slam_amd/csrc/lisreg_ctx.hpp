@@ -243,7 +243,8 @@ struct lisreg_ctx {
     int       index_build = 2;                          // 0 bucket sort, 1 strip form (error if a grid does not fit it), 2 strip form whenever it fits
     int       strip_cells = 0, strip_cap = 2048;        // cells per strip aimed at (0: 1024 for a batch of one or two targets, else 2048); points per strip of the small-workgroup variant
     bool      strip_now = false;
-    int         row_reach = 1;                          // option "row_reach": rows only for the cells the batch's queries come within two cells of (runs that rebuild their targets)
+    int         row_reach = 2;                          // option "row_reach": rows only for the cells the batch's queries come within a metre of (runs that rebuild their targets);
+                                                        // 2: of those, only the cells a query starts in or that lie within half a metre of a target point
     bool        reach_ready = false;                    // lisreg_batch_prepare made the reach words of this batch's targets
     bool        xcd_cached = false;                     // lisreg_batch_prepare made the dispatch-order table of this batch (runs reuse it)
     int         reach_backoff = 0;                      // batches still to be prepared without the marks after a run that missed too often

@@ -824,6 +824,14 @@ __device__ __forceinline__ bool crow_reached(const GridIndex& g, const unsigned*
 {
     return !reach || ((reach[(size_t)(ix * g.ny + iy) * g.qmark_w + (iz >> 5)] >> (iz & 31)) & 1u) != 0u;
 }
+// qmark != null ("row_reach" = 2; only together with reach): of the reached cells, only those with a target point in their 3 x 3 x 3 block
+// ("near" — a query moves from where its initial pose put it TO the target's surface, not a metre in every direction) and those a query
+// starts in (the undilated marks, same layout as reach) get rows.  The others are -1 like every unreached cell: their queries walk.
+// crow_ask_near: the (few) cells whose rows depend on the 3 x 3 x 3 count — populated, reached, no query of their own.
+__device__ __forceinline__ bool crow_ask_near(const GridIndex& g, const unsigned* __restrict__ qmark, int ix, int iy, int iz)
+{
+    return qmark && ((qmark[(size_t)(ix * g.ny + iy) * g.qmark_w + (iz >> 5)] >> (iz & 31)) & 1u) == 0u;
+}
 
 // Round 6: the octant masks of the tile's cells are made HERE, in LDS (s_mask, behind the staged cell_start rows): the points of the tile's
 // columns and of a one-column rim around it (a point marks cells at most one away; columns adjacent in y are adjacent in memory, so that is
@@ -831,7 +839,8 @@ __device__ __forceinline__ bool crow_reached(const GridIndex& g, const unsigned*
 // their own (k_crow_mark: one or two device-scope atomics per point into a global mask array, 26 us per configs[1] step on the stream's
 // serial head) whose result this kernel read back; a tile reads ~1.3 x its own points instead.  Same masks (crow_mark_point_tile).
 __device__ __forceinline__ void crow_classify_body(const GridIndex& g, int tiles_y, int* __restrict__ need, int* __restrict__ omask,
-                                                   const unsigned* __restrict__ reach, int blk_, int* s_cs, float oct_margin)
+                                                   const unsigned* __restrict__ reach, const unsigned* __restrict__ qmark, int blk_, int* s_cs,
+                                                   float oct_margin)
 {
     //                            // [(kCtX + 2 rim) * (kCtY + 2 rim)][nz + 1] cell_start rows, then [kCtX * kCtY][nz] masks
     constexpr int WX = kCtX + 2 * kCtRim, WY = kCtY + 2 * kCtRim;
@@ -873,22 +882,34 @@ __device__ __forceinline__ void crow_classify_body(const GridIndex& g, int tiles
             }
         const int cid = (ix * g.ny + iy) * g.nz + iz;
         const int m = s_mask[i] & 255;
-        const bool r = cnt5 != 0 && crow_reached(g, reach, ix, iy, iz);
+        bool r = cnt5 != 0 && crow_reached(g, reach, ix, iy, iz);
+        if (r && crow_ask_near(g, qmark, ix, iy, iz)) {
+            const int n0 = max(iz - 1, 0), n1 = min(iz + 1, g.nz - 1);
+            int cnt3 = 0;
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx)
+#pragma unroll
+                for (int dy = -1; dy <= 1; ++dy) {
+                    const int* row = s_cs + ((lx + kCtRim + dx) * WY + (ly + kCtRim + dy)) * nz1;
+                    cnt3 += row[n1 + 1] - row[n0];
+                }
+            r = cnt3 != 0;
+        }
         need[cid] = r ? 1 + __popc(m) : 0;
         omask[cid] = cnt5 ? (r ? (m | (min(cnt5, 0xffff) << 8)) : kCrowUnreached) : 0;
     }
 }
 
 __global__ __launch_bounds__(256) void k_crow_classify(GridIndex g, int tiles_y, int* __restrict__ need, int* __restrict__ omask,
-                                                       const unsigned* __restrict__ reach, float oct_margin)
+                                                       const unsigned* __restrict__ reach, const unsigned* __restrict__ qmark, float oct_margin)
 {
     extern __shared__ int s_cs[];
-    crow_classify_body(g, tiles_y, need, omask, reach, blockIdx.x, s_cs, oct_margin);
+    crow_classify_body(g, tiles_y, need, omask, reach, qmark, blockIdx.x, s_cs, oct_margin);
 }
 
 // the same per cell, straight from memory: grids whose tile does not fit the LDS (z-ranges beyond ~120 cells)
 __device__ __forceinline__ void crow_classify_plain_body(const GridIndex& g, int n_cells, int* __restrict__ need, int* __restrict__ omask,
-                                                         const unsigned* __restrict__ reach, int blk_)
+                                                         const unsigned* __restrict__ reach, const unsigned* __restrict__ qmark, int blk_)
 {
     const int cid = blk_ * 256 + threadIdx.x;
     if (cid >= n_cells) return;
@@ -908,15 +929,25 @@ __device__ __forceinline__ void crow_classify_plain_body(const GridIndex& g, int
         }
     }
     const int m = omask[cid] & 255;
-    const bool r = cnt5 != 0 && crow_reached(g, reach, ix, iy, iz);
+    bool r = cnt5 != 0 && crow_reached(g, reach, ix, iy, iz);
+    if (r && crow_ask_near(g, qmark, ix, iy, iz)) {
+        const int n0 = max(iz - 1, 0), n1 = min(iz + 1, g.nz - 1);
+        int cnt3 = 0;
+        for (int x = max(ix - 1, 0); x <= min(ix + 1, g.nx - 1); ++x)
+            for (int y = max(iy - 1, 0); y <= min(iy + 1, g.ny - 1); ++y) {
+                const int base = (x * g.ny + y) * g.nz;
+                cnt3 += g.cell_start[base + n1 + 1] - g.cell_start[base + n0];
+            }
+        r = cnt3 != 0;
+    }
     need[cid] = r ? 1 + __popc(m) : 0;
     omask[cid] = cnt5 ? (r ? (m | (min(cnt5, 0xffff) << 8)) : kCrowUnreached) : 0;
 }
 
 __global__ __launch_bounds__(256) void k_crow_classify_plain(GridIndex g, int n_cells, int* __restrict__ need, int* __restrict__ omask,
-                                                             const unsigned* __restrict__ reach)
+                                                             const unsigned* __restrict__ reach, const unsigned* __restrict__ qmark)
 {
-    crow_classify_plain_body(g, n_cells, need, omask, reach, blockIdx.x);
+    crow_classify_plain_body(g, n_cells, need, omask, reach, qmark, blockIdx.x);
 }
 
 // The sorts of the cell-row build work on 32-bit keys: the squared distance's float bits with the low 7 bits replaced by a payload (the
@@ -1249,7 +1280,7 @@ void k_crow_build(GridIndex g, int n_cells, const int* __restrict__ need, int* _
 // rows): workgroups [0, nb of job 0) work on job 0, the rest on job 1.  Until round 6 the corner target's (small) launches ran on a side
 // stream underneath the surf target's — two event hops on the critical path of every step (a marker in front of the marks, a wait in front
 // of the first correspondence launch: 6 us each on an otherwise gap-free stream).
-struct CrowJob { GridIndex g; int n_cells; int* need; int* omask; int* scan; int cap; const unsigned* reach; int tiles_y; int plain; int nb; };
+struct CrowJob { GridIndex g; int n_cells; int* need; int* omask; int* scan; int cap; const unsigned* reach; const unsigned* qmark; int tiles_y; int plain; int nb; };
 struct CrowJobs { CrowJob j[2]; };
 __global__ __launch_bounds__(256) void k_crow_mark_pair(CrowJobs J, float margin_cells)
 {
@@ -1263,8 +1294,8 @@ __global__ __launch_bounds__(256) void k_crow_classify_pair(CrowJobs J, float ma
     const int k = (int)blockIdx.x < J.j[0].nb ? 0 : 1;
     const CrowJob& j = J.j[k];
     const int blk = (int)blockIdx.x - (k ? J.j[0].nb : 0);
-    if (j.plain) crow_classify_plain_body(j.g, j.n_cells, j.need, j.omask, j.reach, blk);
-    else crow_classify_body(j.g, j.tiles_y, j.need, j.omask, j.reach, blk, s_cs, margin_cells * j.g.cell);
+    if (j.plain) crow_classify_plain_body(j.g, j.n_cells, j.need, j.omask, j.reach, j.qmark, blk);
+    else crow_classify_body(j.g, j.tiles_y, j.need, j.omask, j.reach, j.qmark, blk, s_cs, margin_cells * j.g.cell);
 }
 __global__ __launch_bounds__(64 * kCrowWPB) __attribute__((amdgpu_waves_per_eu(kCrowWaves, kCrowWaves))) void k_crow_build_pair(CrowJobs J)
 {
@@ -1741,11 +1772,11 @@ void launch_crow_classify(GridIndex g, int n_cells, CrowBuffers cb, hipStream_t 
     const size_t lds = crow_classify_lds(g.nz);
     if (lds <= 64 * 1024) {                                   // the tiled classification makes the marks itself, in LDS
         const int tiles_x = (g.nx + kCtX - 1) / kCtX, tiles_y = (g.ny + kCtY - 1) / kCtY;
-        k_crow_classify<<<tiles_x * tiles_y, 256, lds, st>>>(g, tiles_y, cb.need, cb.omask, g.qmark ? cb.reach : nullptr, margin * g.cell);
+        k_crow_classify<<<tiles_x * tiles_y, 256, lds, st>>>(g, tiles_y, cb.need, cb.omask, g.qmark ? cb.reach : nullptr, g.qmark && cb.reach ? cb.qmark : nullptr, margin * g.cell);
     } else {
         if (!zero_already) (void)hipMemsetAsync(cb.omask, 0, sizeof(int) * (size_t)n_cells, st);
         k_crow_mark<<<(g.n + 255) / 256, 256, 0, st>>>(g, margin * g.cell, cb.omask);
-        k_crow_classify_plain<<<(n_cells + 255) / 256, 256, 0, st>>>(g, n_cells, cb.need, cb.omask, g.qmark ? cb.reach : nullptr);
+        k_crow_classify_plain<<<(n_cells + 255) / 256, 256, 0, st>>>(g, n_cells, cb.need, cb.omask, g.qmark ? cb.reach : nullptr, g.qmark && cb.reach ? cb.qmark : nullptr);
     }
     exclusive_scan(cb.need, cb.scan, cb.scan_tmp, n_cells, st);
 }
@@ -1768,6 +1799,7 @@ void launch_crow_rows_pair(const GridIndex g[2], const int n_cells[2], const Cro
         CrowJob& j = J.j[k];
         j.g = g[k]; j.n_cells = n_cells[k]; j.need = cb[k].need; j.omask = cb[k].omask; j.scan = cb[k].scan; j.cap = cb[k].cap_rows;
         j.reach = g[k].qmark ? cb[k].reach : nullptr;
+        j.qmark = j.reach ? cb[k].qmark : nullptr;
         if (!on[k]) continue;
         j.plain = crow_classify_lds(g[k].nz) > 64 * 1024 ? 1 : 0;          // (the tiled classification makes its marks itself, in LDS)
         const bool zero_already = omask_zero_cells[k] && *omask_zero_cells[k] >= n_cells[k];

@@ -40,7 +40,8 @@ struct GridIndex {
     // query marks (round 6; null: every populated cell gets its rows): one bit per cell — column (ix * ny + iy) owns qmark_w consecutive
     // 32-bit words, bit iz & 31 of word iz >> 5 — set by k_query_marks for the cells the batch's queries fall into under their INITIAL
     // poses.  The row build of a run leaves out the cells no query of the batch comes within a metre of (crow_tab -1: a query that gets
-    // there all the same takes the cell walk — results never depend on the marks).
+    // there all the same takes the cell walk — results never depend on the marks).  lisreg_batch_prepare clears the words BEFORE it marks:
+    // they stay valid for the batch's runs (CrowBuffers::qmark reads them).
     unsigned*     qmark;
     int           qmark_w;
 };
@@ -188,7 +189,9 @@ void launch_build_graph_one(GridIndex g, hipStream_t st);
 // cell rows of one target (search_mode 5).  classify: need[cell] = rows the cell wants (0 / 1 / 8), scan[cell] = first row, scan[n_cells] = rows
 // in all; build: crow_tab, then one wave per row (at most cap_rows of them: cells past the capacity get no row and their queries walk)
 struct CrowBuffers { int* need; int* omask; int* scan; int* scan_tmp; int cap_rows;
-                     const unsigned* reach = nullptr; };       // reach: the query marks grown by a metre (same layout as GridIndex::qmark), or null
+                     const unsigned* reach = nullptr;          // reach: the query marks grown by a metre (same layout as GridIndex::qmark), or null
+                     const unsigned* qmark = nullptr; };       // with reach ("row_reach" = 2): the marks themselves — of the reached cells only those a
+                                                               // query starts in or with a target point in their 3 x 3 x 3 block get rows; null: reach alone
 // Query marks (lisreg_index.hip): launch_query_marks sets, for every source point of the batch under its item's CURRENT pose cache (the
 // initial pose right after launch_reset_items), the bit of the grid cell it falls into (clamped into the grid: what the cell-row scan
 // does with a query outside); launch_reach_dilate ORs the marks of the (2 D + 1)^3 block around every cell into `reach`, D = ceil(1 m / cell) >= 2.
