@@ -368,7 +368,9 @@ int  lisreg_get_trace(lisreg_ctx* ctx, float* buf, int max_iters);
 
 /* Per-kernel timing of the last align/batch_run when enabled (HIP events on the context's stream):
  * out[0] = total ms in the correspondence+normal-equation kernel, out[1] = its launch count,
- * out[2] = total ms in the solve/update kernel, out[3] = its launch count, out[4] = index build ms. */
+ * out[2] = total ms in the solve/update kernel, out[3] = its launch count, out[4] = index build ms.
+ * After a lisreg_vgicp_* call: out[0] / out[1] = the linearisations and their number, out[2] = the voxel sort and statistics,
+ * out[4] = the distributions (search grid, k-nearest search, covariances). */
 int  lisreg_set_profiling(lisreg_ctx* ctx, int enable);
 int  lisreg_get_timing(lisreg_ctx* ctx, double out[5]);
 
@@ -927,6 +929,72 @@ int  lisreg_ndt_get_voxels(lisreg_ctx* ctx, int slot, int* cell_ids, int* counts
                            int* n_out);
 int  lisreg_ndt_derivatives(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
                             const lisreg_ndt_params* params, const double p[6], int with_hessian, double out[28],
+                            long long* n_pairs);
+
+/* ---- §7k: voxelised GICP registration (loop-closure verification) ----------------------------------------------------
+ * select_registration_method("FAST_VGICP") is the verifier detectLoopClosureForSubMap's authors chose last
+ * (src/node/subMapOptmizationNode.cpp:2771, commented out); src/core/registration.cpp:156-187 carries the whole fast_gicp family
+ * as a comment because it would not link.  The method (Koide et al. 2021): every point of either cloud gets a distribution from
+ * its k nearest points within its own cloud, regularised to a plane (eigenvalues 1, 1, plane_epsilon); the target is cut into
+ * voxels of edge `resolution` holding the mean of their points and of their points' covariances; a source point is paired with the
+ * voxel it falls into (DIRECT1) and a Levenberg-Marquardt loop minimises the sum of sqrt(N) d^T (C_voxel + R C_a R^T)^-1 d over
+ * the pairs.  The DEFINITION is tests/vgicp_ref.py (fast_gicp's source is not available to this project); DESIGN.md §7k lists where
+ * it picks a reading of fast_gicp it cannot verify.  NaN points are no points: never a neighbour, in no voxel, in no pair.
+ * The GPU makes the distributions (an exact k-nearest search, one query per lane), the voxel statistics and every linearisation
+ * (fp64, fixed-order sums: two evaluations of the same input give the same bits); the 6 x 6 solve and the LM loop run on the host in
+ * double.  There is no fitness score: a caller who wants one has aligned_out and lisreg_nearest. */
+typedef struct lisreg_vgicp_params {
+    double resolution;                  /* voxel edge */
+    double transformation_epsilon;      /* a step is converged when max|exp(delta).t| is below this ... */
+    double rotation_epsilon;            /* ... and max|exp(delta).R - I| below this */
+    double lm_init_lambda_factor;       /* lambda starts at this times max|diag H| of the first linearisation */
+    double plane_epsilon;               /* the smallest eigenvalue of a regularised covariance */
+    int    k_correspondences;           /* points per distribution, 4 .. 32 */
+    int    max_iters;                   /* outer iterations (linearisations) */
+    int    lm_max_iterations;           /* trials per outer iteration */
+    int    reserved;
+} lisreg_vgicp_params;
+typedef struct lisreg_vgicp_info {
+    int dims[3];                        /* voxel grid of the target */
+    int n_voxels;                       /* voxels holding at least one point */
+    int n_points;                       /* finite points of the target */
+} lisreg_vgicp_info;
+typedef struct lisreg_vgicp_result {
+    double final_transform[16];         /* row-major 4x4, in double: the steps are far below a float's resolution of a map coordinate */
+    int    converged;
+    int    iters;                       /* outer iterations */
+    int    n_evals;                     /* evaluations of the error (with or without H) */
+    int    n_rejected;                  /* trials whose step was rejected */
+    long long n_pairs_last;             /* (source point, voxel) pairs of the last evaluation */
+    double error;                       /* at final_transform */
+    double lambda;                      /* the damping the loop ended with */
+} lisreg_vgicp_result;
+/* kind 0 (the reference's commented FAST_VGICP block + fast_gicp's defaults as remembered): {1.0, 0.01, 2e-3, 1e-9, 1e-3, 20, 50, 10} */
+int  lisreg_vgicp_default_params(int kind, lisreg_vgicp_params* p);
+/* The distributions and voxel statistics of `cloud` into VGICP slot `slot` (0 .. 65535; VGICP slots are apart from the map-index
+ * and the NDT slots).  Uses resolution, k_correspondences and plane_epsilon of `params`.  Refused (LISREG_ERR_ARG): n <= 0, fewer
+ * finite points than k_correspondences, an infinite coordinate, resolution <= 0, k_correspondences outside 4 .. 32, a grid of more
+ * than 2^26 cells (the voxel table is dense).  info may be NULL. */
+int  lisreg_vgicp_set_target(lisreg_ctx* ctx, int slot, const void* cloud, int n, int stride_bytes, int fmt,
+                             const lisreg_vgicp_params* params, lisreg_vgicp_info* info);
+/* guess = row-major 4x4 or NULL for identity; aligned_out: NULL, or room for n points of the input layout (the source under
+ * final_transform rounded to float).  Host PCL structs or LISREG_FMT_DEVICE records.  params->resolution must be the slot's, and the
+ * slot must hold a target (LISREG_ERR_ARG otherwise).  The source's distributions are made by every call; a source with fewer finite
+ * points than k_correspondences is refused.  A source without a pair at the guess returns converged = 0, iters = 0 and the guess. */
+int  lisreg_vgicp_align(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
+                        const lisreg_vgicp_params* params, const float* guess, lisreg_vgicp_result* result, void* aligned_out);
+/* test hooks.  _covariances: the distribution of every point of a cloud — cov6_out [n][6] = xx, xy, xz, yy, yz, zz (NaN rows for
+ * NaN points), neighbours_out [n][k] (may be NULL) = the k nearest points' indices by ascending (distance, index), -1 rows for NaN
+ * points; plane_epsilon is 1e-3; cell_edge > 0 forces the cell edge of the search grid (0: chosen from the cloud's density) — the
+ * results do not depend on it.  _get_voxels: the voxels of a slot in ascending cell order (cell id = i + j * dims[0] + k * dims[0] *
+ * dims[1]; means [3], cov6 of the mean covariance; *n_out = their number, copied only if it fits `capacity`).  _linearize: one
+ * linearisation at T (row-major 4x4): out[28] = error, b [6], upper triangle of H row by row [21] (zeros without with_hessian). */
+int  lisreg_vgicp_covariances(lisreg_ctx* ctx, const void* cloud, int n, int stride_bytes, int fmt, int k, double* cov6_out,
+                              int* neighbours_out, float cell_edge);
+int  lisreg_vgicp_get_voxels(lisreg_ctx* ctx, int slot, int* cell_ids, int* counts, double* means, double* cov6, int capacity,
+                             int* n_out);
+int  lisreg_vgicp_linearize(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
+                            const lisreg_vgicp_params* params, const double T[16], int with_hessian, double out[28],
                             long long* n_pairs);
 
 /* ---- loop-closure candidate detection: FEPSC (src/core/epscGeneration.cpp) -------------------------------------------

@@ -121,6 +121,17 @@ struct NdtTarget {
     DevBuf    table;               // [dims product] ints: cell -> voxel with a Gaussian, -1 none
 };
 
+// the voxel statistics of one VGICP target (lisreg_vgicp.hip: lisreg_vgicp_set_target)
+struct VgicpTarget {
+    bool      valid = false;
+    int       n_voxels = 0, n_points = 0;
+    int       dims[3] = { 1, 1, 1 }, min_b[3] = { 0, 0, 0 };
+    double    resolution = 0;
+    DevBuf    stats;               // [n_voxels][10] doubles: mean, upper triangle of the mean covariance, points
+    DevBuf    cell;                // [n_voxels] ints: cell id
+    DevBuf    table;               // [dims product] ints: cell -> voxel, -1 none
+};
+
 // device-resident sliding local map (lisreg_api_localmap.hip)
 struct LocalMap {
     bool   valid = false;
@@ -230,6 +241,13 @@ struct lisreg_ctx {
     std::map<int, lisreg::NdtTarget> ndt;
     lisreg::DevBuf ndt_pts, ndt_src, ndt_part, ndt_out, ndt_cnt;
     lisreg::PinnedBuf ndt_host;
+    // VGICP registration (lisreg_vgicp.hip): targets by slot (apart from the map-index and the NDT slots); of the cloud whose
+    // distributions were made last (a target being set, or a source): the staged records, finite flags, their scan, the finite points and
+    // their indices, the same points by search-grid cell with the cells' starts, the covariances, neighbour rows and covariance rows of the
+    // test hook; per-workgroup partial sums and their total, the finite-point count; pinned landing area of one evaluation
+    std::map<int, lisreg::VgicpTarget> vgicp;
+    lisreg::DevBuf vg_raw, vg_flag, vg_pos, vg_pts, vg_idx, vg_sorted, vg_cells, vg_cov, vg_nbr, vg_rows, vg_part, vg_out, vg_cnt;
+    lisreg::PinnedBuf vg_host;
     lisreg::PinnedBuf done_host;            // one int
     lisreg::PinnedBuf stage_host;           // pinned staging of the per-batch tables
     lisreg::Event stage_done;

@@ -6,6 +6,7 @@
 // in double, one 29-double read-back per evaluation.  No CPU fallback.
 #include "lisreg_ctx.hpp"
 #include "lisreg_ndt_host.hpp"
+#include "lisreg_jacobi3.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -41,32 +42,12 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
-// cyclic Jacobi on the symmetric 3 x 3 (a00 .. a22), eigenvectors in the columns of v; every index is a compile-time constant
-#define NDT_ROT(app, aqq, apq, arp, arq, v0p, v0q, v1p, v1q, v2p, v2q)                                  \
-    if (apq != 0.0) {                                                                                     \
-        const double th = (aqq - app) / (2.0 * apq);                                                      \
-        const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));                    \
-        const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;                                           \
-        app -= t * apq; aqq += t * apq; apq = 0.0;                                                        \
-        const double rp = cs * arp - sn * arq, rq = sn * arp + cs * arq; arp = rp; arq = rq;              \
-        double x;                                                                                         \
-        x = cs * v0p - sn * v0q; v0q = sn * v0p + cs * v0q; v0p = x;                                      \
-        x = cs * v1p - sn * v1q; v1q = sn * v1p + cs * v1q; v1p = x;                                      \
-        x = cs * v2p - sn * v2q; v2q = sn * v2p + cs * v2q; v2p = x;                                      \
-    }
-
 // the Gaussian of one voxel from its mean-centred second moments S (already divided by n - 1): eigen-decomposition, the two smaller
 // eigenvalues raised to mult * the largest, inverse = V diag(1 / lambda) V^T.  False: not a valid voxel.
 __device__ bool ndt_gaussian(double a00, double a01, double a02, double a11, double a12, double a22, double mult, double ic[6])
 {
-    double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;
-    for (int sweep = 0; sweep < 40; ++sweep) {
-        const double off = fabs(a01) + fabs(a02) + fabs(a12);
-        if (!(off > 1.0e-22 * (fabs(a00) + fabs(a11) + fabs(a22)))) break;         // also ends on NaN
-        NDT_ROT(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21)
-        NDT_ROT(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22)
-        NDT_ROT(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22)
-    }
+    double v00, v01, v02, v10, v11, v12, v20, v21, v22;
+    jacobi3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
     const double lmax = fmax(a00, fmax(a11, a22));
     if (a00 < 0.0 || a11 < 0.0 || a22 < 0.0 || !(lmax > 0.0)) return false;
     const double fl = mult * lmax;

@@ -1,0 +1,713 @@
+// lisreg_vgicp.hip — voxelised GICP registration: the loop-closure verifier the reference's authors chose last and could
+// not link (select_registration_method("FAST_VGICP"), src/core/registration.cpp:156-187, src/node/subMapOptmizationNode.cpp:2771).
+// The definition is tests/vgicp_ref.py.  GPU: the distribution of every point of a cloud (its k nearest points within the cloud by an
+// exact shell walk over a uniform grid, one query per lane, then mean, covariance and the plane regularisation, fp64), the target's
+// per-voxel statistics (the NDT build's sort, one lane or one wavefront per voxel) and one linearisation per call (one lane per source
+// point, fp64, sums in a fixed order: the same input gives the same bits).  Host: the 6 x 6 solve and the Levenberg-Marquardt loop in
+// double, one 29-double read-back per evaluation.  No CPU fallback.
+#include "lisreg_ctx.hpp"
+#include "lisreg_vgicp_host.hpp"
+#include "lisreg_jacobi3.hpp"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+
+using namespace lisreg;
+using namespace lisreg::vgicp_host;
+
+namespace {
+
+constexpr int kVgBig = 48;             // voxels with more points get a wavefront each, the others a lane (the NDT build's split)
+constexpr int kVgRec = 10;             // doubles per voxel: mean [3], upper triangle of the mean covariance [6], points
+constexpr long long kVgMaxCells = 1LL << 26;        // the voxel table is dense
+constexpr long long kVgKnnMaxCells = 1LL << 22;     // so is the search grid of a cloud
+constexpr int kVgKnnMaxDim = 2048;                  // cells per axis of the search grid (the walk's rounding slack is sized for this)
+
+__device__ __forceinline__ double vg_wave_sum(double v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// ---- NaN points are no points: the finite records, in input order ---------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_vg_flag(const float4* __restrict__ in, int n, int* __restrict__ flag)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = in[i];
+    flag[i] = (p.x == p.x && p.y == p.y && p.z == p.z) ? 1 : 0;
+}
+
+// ---- the k nearest points of every point within its own cloud, and its distribution ------------------------------------------------
+struct VgKnn {
+    const float4* sorted;       // [m] by grid cell, ascending index inside a cell; .w = index among the finite points
+    const int*    cell_start;   // [nx * ny * nz + 1], cell = (ix * ny + iy) * nz + iz
+    const float4* pts;          // [m] the finite points in input order
+    const int*    orig;         // [m] -> index in the caller's cloud
+    int    m, k;
+    float  ox, oy, oz, cell, inv_cell;
+    int    nx, ny, nz;
+    double plane_eps;
+    double* cov;                // [m][6] upper triangle of C_i, by index among the finite points
+    int*    nbr;                // [n][k] by the CALLER's index, ascending (distance, index); may be null
+};
+
+__device__ __forceinline__ int vg_cell(float v, float origin, float inv_cell, int n)
+{
+    int c = (int)floorf((v - origin) * inv_cell);                  // the arithmetic of the index build (cell_coord)
+    return c < 0 ? 0 : (c >= n ? n - 1 : c);
+}
+
+// One query per lane.  The KT best (distance, index) pairs live in registers: the list is only ever touched through fully unrolled
+// loops, so no entry is addressed dynamically.  Shells of cells are walked outward from the query's cell — shell r is the surface of the
+// (2 r + 1)^3 block, clipped to the grid; the z runs of a column are contiguous in the sorted array — until the k-th best distance is
+// no larger than the distance from the query to the nearest face of the visited block that still has cells behind it.  That distance is
+// reduced by 1e-3 cell: a point's cell comes from float arithmetic ((x - origin) * inv_cell, relative error about 1e-7 of at most
+// kVgKnnMaxDim cells), so a point of an unvisited cell can lie that little inside the face.  The result therefore does not depend on
+// the cell edge: it is the k smallest (distance, index) pairs of the whole cloud.
+template <int KT>
+__global__ __launch_bounds__(64) void k_vg_knn(VgKnn A)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= A.m) return;
+    const float4 q = A.sorted[s];
+    const int self = __float_as_int(q.w);
+    const double qx = (double)q.x, qy = (double)q.y, qz = (double)q.z;
+    const int cx = vg_cell(q.x, A.ox, A.inv_cell, A.nx), cy = vg_cell(q.y, A.oy, A.inv_cell, A.ny), cz = vg_cell(q.z, A.oz, A.inv_cell, A.nz);
+    double bd[KT];
+    int    bi[KT];
+#pragma unroll
+    for (int j = 0; j < KT; ++j) { bd[j] = HUGE_VAL; bi[j] = 0x7fffffff; }
+    double wd = HUGE_VAL;                                           // the k-th best so far
+    int    wi = 0x7fffffff;
+    const int k = A.k;
+    const double cell = (double)A.cell, slack = 1.0e-3 * (double)A.cell;
+
+    auto scan = [&](int a, int b) {
+        for (int j = a; j < b; ++j) {
+            const float4 p = A.sorted[j];
+            const double dx = (double)p.x - qx, dy = (double)p.y - qy, dz = (double)p.z - qz;
+            const double d = (dx * dx + dy * dy) + dz * dz;
+            const int id = __float_as_int(p.w);
+            if (!(d < wd || (d == wd && id < wi))) continue;
+#pragma unroll
+            for (int e = KT - 1; e >= 1; --e) {
+                const bool lt_prev = d < bd[e - 1] || (d == bd[e - 1] && id < bi[e - 1]);
+                const bool lt_cur  = d < bd[e] || (d == bd[e] && id < bi[e]);
+                const double nd = lt_prev ? bd[e - 1] : (lt_cur ? d : bd[e]);
+                const int    ni = lt_prev ? bi[e - 1] : (lt_cur ? id : bi[e]);
+                bd[e] = nd; bi[e] = ni;
+            }
+            if (d < bd[0] || (d == bd[0] && id < bi[0])) { bd[0] = d; bi[0] = id; }
+#pragma unroll
+            for (int e = 0; e < KT; ++e)
+                if (e == k - 1) { wd = bd[e]; wi = bi[e]; }
+        }
+    };
+
+    const int rmax = max(max(A.nx, A.ny), A.nz);
+    for (int r = 0; r <= rmax; ++r) {
+        const int x0 = max(cx - r, 0), x1 = min(cx + r, A.nx - 1);
+        const int y0 = max(cy - r, 0), y1 = min(cy + r, A.ny - 1);
+        const int z0 = max(cz - r, 0), z1 = min(cz + r, A.nz - 1);
+        for (int ix = x0; ix <= x1; ++ix)
+            for (int iy = y0; iy <= y1; ++iy) {
+                const int base = (ix * A.ny + iy) * A.nz;
+                const bool rim = ix == cx - r || ix == cx + r || iy == cy - r || iy == cy + r;
+                // a rim column is new over its whole z range; inside the rim only the two caps are (r >= 1 there)
+                for (int part = 0; part < (rim ? 1 : 2); ++part) {
+                    const int za = rim ? z0 : (part == 0 ? cz - r : cz + r), zb = rim ? z1 : za;
+                    if (za < 0 || zb >= A.nz) continue;
+                    scan(A.cell_start[base + za], A.cell_start[base + zb + 1]);
+                }
+            }
+        double lim = HUGE_VAL;                                      // distance to the nearest face with unvisited cells behind it
+        if (cx - r > 0)        lim = fmin(lim, qx - ((double)A.ox + (double)(cx - r) * cell));
+        if (cx + r < A.nx - 1) lim = fmin(lim, ((double)A.ox + (double)(cx + r + 1) * cell) - qx);
+        if (cy - r > 0)        lim = fmin(lim, qy - ((double)A.oy + (double)(cy - r) * cell));
+        if (cy + r < A.ny - 1) lim = fmin(lim, ((double)A.oy + (double)(cy + r + 1) * cell) - qy);
+        if (cz - r > 0)        lim = fmin(lim, qz - ((double)A.oz + (double)(cz - r) * cell));
+        if (cz + r < A.nz - 1) lim = fmin(lim, ((double)A.oz + (double)(cz + r + 1) * cell) - qz);
+        if (lim == HUGE_VAL) break;                                 // the whole grid has been visited
+        lim -= slack;
+        if (lim > 0.0 && wd <= lim * lim) break;
+    }
+
+    // the k points again: two passes, in the list's order
+    if (A.nbr) {
+        int* row = A.nbr + (size_t)A.orig[self] * (size_t)k;
+#pragma unroll
+        for (int e = 0; e < KT; ++e)
+            if (e < k) row[e] = A.orig[bi[e]];
+    }
+    double m0 = 0, m1 = 0, m2 = 0;
+#pragma unroll
+    for (int e = 0; e < KT; ++e)
+        if (e < k) { const float4 p = A.pts[bi[e]]; m0 += (double)p.x; m1 += (double)p.y; m2 += (double)p.z; }
+    const double kk = (double)k;
+    m0 /= kk; m1 /= kk; m2 /= kk;
+    double a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0;
+#pragma unroll
+    for (int e = 0; e < KT; ++e)
+        if (e < k) {
+            const float4 p = A.pts[bi[e]];
+            const double d0 = (double)p.x - m0, d1 = (double)p.y - m1, d2 = (double)p.z - m2;
+            a00 += d0 * d0; a01 += d0 * d1; a02 += d0 * d2; a11 += d1 * d1; a12 += d1 * d2; a22 += d2 * d2;
+        }
+    a00 /= kk; a01 /= kk; a02 /= kk; a11 /= kk; a12 /= kk; a22 /= kk;
+    double v00, v01, v02, v10, v11, v12, v20, v21, v22;
+    jacobi3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
+    // the eigenvector of the smallest eigenvalue (the first of equal ones: any unit vector of a degenerate neighbourhood will do)
+    const bool s1 = a11 < a00;
+    const double l01 = s1 ? a11 : a00;
+    const bool s2 = a22 < l01;
+    double n0 = s2 ? v02 : (s1 ? v01 : v00), n1 = s2 ? v12 : (s1 ? v11 : v10), n2 = s2 ? v22 : (s1 ? v21 : v20);
+    const double nn = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+    n0 /= nn; n1 /= nn; n2 /= nn;
+    const double f = 1.0 - A.plane_eps;
+    double* o = A.cov + (size_t)self * 6;
+    o[0] = 1.0 - f * n0 * n0; o[1] = -f * n0 * n1; o[2] = -f * n0 * n2;
+    o[3] = 1.0 - f * n1 * n1; o[4] = -f * n1 * n2; o[5] = 1.0 - f * n2 * n2;
+}
+
+// cov6 rows by the caller's index: NaN rows for the points that are none
+__global__ __launch_bounds__(256) void k_vg_cov_rows(const double* __restrict__ cov, const int* __restrict__ flag, const int* __restrict__ pos,
+                                                     int n, double* __restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (flag[i]) {
+        const double* r = cov + (size_t)pos[i] * 6;
+#pragma unroll
+        for (int e = 0; e < 6; ++e) out[(size_t)i * 6 + e] = r[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 6; ++e) out[(size_t)i * 6 + e] = (double)NAN;
+    }
+}
+
+// ---- target voxels ----------------------------------------------------------------------------------------------------------------
+struct VgBuild {
+    const float4*   pts;        // the finite points
+    const double*   cov;        // [m][6]
+    const int*      order;      // sorted position -> point
+    const uint32_t* sidx;       // sorted position -> cell id
+    const int*      vstart;     // [n_vox + 1]
+    int             n_vox;
+    long long       n_cells;
+    double*         stats;      // [n_vox][kVgRec]
+    int*            cell;       // [n_vox]
+    int*            table;      // [n_cells], -1 on entry
+};
+
+// WAVE: the 64 lanes of a wavefront share voxel v (every lane ends up with the same sums: the butterfly adds the same pairs everywhere)
+template <bool WAVE>
+__device__ __forceinline__ void vg_voxel(const VgBuild& B, int v, int lane)
+{
+    const int a = B.vstart[v], b = B.vstart[v + 1];
+    const int step = WAVE ? 64 : 1;
+    double s[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) s[e] = 0.0;
+    for (int j = a + lane; j < b; j += step) {
+        const int i = B.order[j];
+        const float4 p = B.pts[i];
+        const double* c = B.cov + (size_t)i * 6;
+        s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z;
+#pragma unroll
+        for (int e = 0; e < 6; ++e) s[3 + e] += c[e];
+    }
+    if (WAVE) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) s[e] = vg_wave_sum(s[e]);
+    }
+    if (lane != 0) return;
+    const double cnt = (double)(b - a);
+    const uint32_t cid = B.sidx[a];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) B.stats[(size_t)v * kVgRec + e] = s[e] / cnt;
+    B.stats[(size_t)v * kVgRec + 9] = cnt;
+    B.cell[v] = (int)cid;
+    if ((long long)cid < B.n_cells) B.table[cid] = v;
+}
+
+__global__ __launch_bounds__(256) void k_vg_stats_small(VgBuild B)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= B.n_vox) return;
+    if (B.vstart[v + 1] - B.vstart[v] > kVgBig) return;        // k_vg_stats_big
+    vg_voxel<false>(B, v, 0);
+}
+
+__global__ __launch_bounds__(64) void k_vg_stats_big(VgBuild B)
+{
+    const int v = blockIdx.x;
+    if (v >= B.n_vox) return;
+    if (B.vstart[v + 1] - B.vstart[v] <= kVgBig) return;       // the whole wavefront leaves together
+    vg_voxel<true>(B, v, (int)threadIdx.x);
+}
+
+// ---- one linearisation ------------------------------------------------------------------------------------------------------------
+struct VgGrid {
+    const double* stats;
+    const int*    table;
+    int    d0, d1, d2, m0, m1, m2;
+    double inv_res;
+};
+struct VgPose { double R[9], t[3]; };
+
+// one lane per source point, one wavefront per workgroup, one partial record per workgroup
+template <bool HESS>
+__global__ __launch_bounds__(64) void k_vgicp_linearize(const float4* __restrict__ src, const double* __restrict__ cov, int n, VgGrid G,
+                                                        VgPose P, double* __restrict__ part)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    double acc[28];
+#pragma unroll
+    for (int k = 0; k < 28; ++k) acc[k] = 0.0;
+    double pairs = 0.0;
+    if (i < n) {
+        const float4 s = src[i];
+        const double a0 = (double)s.x, a1 = (double)s.y, a2 = (double)s.z;
+        const double x0 = ((P.R[0] * a0 + P.R[1] * a1) + P.R[2] * a2) + P.t[0];
+        const double x1 = ((P.R[3] * a0 + P.R[4] * a1) + P.R[5] * a2) + P.t[1];
+        const double x2 = ((P.R[6] * a0 + P.R[7] * a1) + P.R[8] * a2) + P.t[2];
+        // the cell in the floating-point domain first: a point far off the map, a huge or a NaN coordinate fails a comparison here and
+        // never becomes an integer
+        const double f0 = floor(x0 * G.inv_res) - (double)G.m0, f1 = floor(x1 * G.inv_res) - (double)G.m1, f2 = floor(x2 * G.inv_res) - (double)G.m2;
+        int v = -1;
+        if (f0 >= 0.0 && f0 < (double)G.d0 && f1 >= 0.0 && f1 < (double)G.d1 && f2 >= 0.0 && f2 < (double)G.d2)
+            v = G.table[(long long)f0 + (long long)f1 * G.d0 + (long long)f2 * (long long)G.d0 * G.d1];
+        if (v >= 0) {
+            const double* __restrict__ rec = G.stats + (size_t)v * kVgRec;
+            const double* __restrict__ ca = cov + (size_t)i * 6;
+            const double d[3] = { rec[0] - x0, rec[1] - x1, rec[2] - x2 };
+            const double C[3][3] = { { ca[0], ca[1], ca[2] }, { ca[1], ca[3], ca[4] }, { ca[2], ca[4], ca[5] } };
+            double RC[3][3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) RC[r][c] = (P.R[3 * r] * C[0][c] + P.R[3 * r + 1] * C[1][c]) + P.R[3 * r + 2] * C[2][c];
+            auto rcr = [&](int r, int c) { return (RC[r][0] * P.R[3 * c] + RC[r][1] * P.R[3 * c + 1]) + RC[r][2] * P.R[3 * c + 2]; };
+            const double s00 = rec[3] + rcr(0, 0), s01 = rec[4] + rcr(0, 1), s02 = rec[5] + rcr(0, 2);
+            const double s11 = rec[6] + rcr(1, 1), s12 = rec[7] + rcr(1, 2), s22 = rec[8] + rcr(2, 2);
+            // M = S^-1, closed form (S is symmetric positive definite with eigenvalues between 2 plane_epsilon and 2)
+            const double c00 = s11 * s22 - s12 * s12, c01 = s02 * s12 - s01 * s22, c02 = s01 * s12 - s02 * s11;
+            const double det = (s00 * c00 + s01 * c01) + s02 * c02;
+            const double id = 1.0 / det;
+            const double M[3][3] = { { c00 * id, c01 * id, c02 * id },
+                                     { c01 * id, (s00 * s22 - s02 * s02) * id, (s01 * s02 - s00 * s12) * id },
+                                     { c02 * id, (s01 * s02 - s00 * s12) * id, (s00 * s11 - s01 * s01) * id } };
+            const double w = sqrt(rec[9]);
+            double Md[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) Md[r] = (M[r][0] * d[0] + M[r][1] * d[1]) + M[r][2] * d[2];
+            // J = [skew(x) | -I], column by column
+            const double J[6][3] = { { 0.0, x2, -x1 }, { -x2, 0.0, x0 }, { x1, -x0, 0.0 }, { -1.0, 0.0, 0.0 }, { 0.0, -1.0, 0.0 }, { 0.0, 0.0, -1.0 } };
+            pairs = 1.0;
+            acc[0] = w * ((d[0] * Md[0] + d[1] * Md[1]) + d[2] * Md[2]);
+#pragma unroll
+            for (int a = 0; a < 6; ++a) acc[1 + a] = w * ((J[a][0] * Md[0] + J[a][1] * Md[1]) + J[a][2] * Md[2]);
+            if (HESS) {
+                double MJ[6][3];
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) MJ[a][r] = (M[r][0] * J[a][0] + M[r][1] * J[a][1]) + M[r][2] * J[a][2];
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int b = a; b < 6; ++b)
+                        acc[7 + a * 6 - a * (a - 1) / 2 + (b - a)] = w * ((J[a][0] * MJ[b][0] + J[a][1] * MJ[b][1]) + J[a][2] * MJ[b][2]);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 28; ++k) acc[k] = vg_wave_sum(acc[k]);
+    pairs = vg_wave_sum(pairs);
+    if (threadIdx.x == 0) {
+        double* o = part + (size_t)blockIdx.x * kOut;
+#pragma unroll
+        for (int k = 0; k < 28; ++k) o[k] = acc[k];
+        o[28] = pairs;
+    }
+}
+
+// the partial records added in a fixed order: lane l takes records l, l + 64, ..., then the butterfly
+__global__ __launch_bounds__(64) void k_vgicp_total(const double* __restrict__ part, int n_part, double* __restrict__ out)
+{
+    double acc[kOut];
+#pragma unroll
+    for (int k = 0; k < kOut; ++k) acc[k] = 0.0;
+    for (int b = (int)threadIdx.x; b < n_part; b += 64)
+#pragma unroll
+        for (int k = 0; k < kOut; ++k) acc[k] += part[(size_t)b * kOut + k];
+#pragma unroll
+    for (int k = 0; k < kOut; ++k) acc[k] = vg_wave_sum(acc[k]);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < kOut; ++k) out[k] = acc[k];
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+int check_params(lisreg_ctx* c, const lisreg_vgicp_params* P, const char* who)
+{
+    if (!P) return bad(c, std::string(who) + ": NULL params");
+    if (!(P->resolution > 0) || !std::isfinite(P->resolution)) return bad(c, std::string(who) + ": resolution <= 0");
+    if (P->k_correspondences < 4 || P->k_correspondences > 32) return bad(c, std::string(who) + ": k_correspondences outside 4 .. 32");
+    if (!(P->transformation_epsilon > 0) || !(P->rotation_epsilon > 0) || !(P->lm_init_lambda_factor > 0) || P->max_iters < 0 ||
+        P->lm_max_iterations < 1 || !(P->plane_epsilon > 0 && P->plane_epsilon <= 1))
+        return bad(c, std::string(who) + ": bad transformation_epsilon / rotation_epsilon / lm_init_lambda_factor / max_iters / lm_max_iterations / plane_epsilon");
+    return LISREG_OK;
+}
+
+int find_target(lisreg_ctx* c, int slot, const lisreg_vgicp_params* P, const char* who, VgicpTarget** out)
+{
+    auto it = c->vgicp.find(slot);
+    if (slot < 0 || it == c->vgicp.end() || !it->second.valid)
+        return bad(c, std::string(who) + ": no VGICP target in this slot (lisreg_vgicp_set_target)");
+    if (P && P->resolution != it->second.resolution) return bad(c, std::string(who) + ": params->resolution differs from the slot's");
+    *out = &it->second;
+    return LISREG_OK;
+}
+
+// The distributions of one cloud of n device records: afterwards c->vg_pts holds its *m_out finite points in input order, c->vg_idx
+// their indices in the cloud, c->vg_flag / c->vg_pos the finite flags and their exclusive scan, c->vg_cov the m x 6 covariances and, if
+// nbr_dev is given, nbr_dev the n x k neighbour rows.  bb: the finite bounding box.  edge: the search grid's cell edge, <= 0: chosen
+// from the cloud's density so that the 27 cells around a query hold a few tens of points.
+int distributions(lisreg_ctx* c, const char* who, const float4* raw, int n, int k, double plane_eps, float edge, float bb[6], int* m_out,
+                  int* nbr_dev)
+{
+    hipStream_t st = c->stream;
+    int rc = cloud_bbox(c, raw, n, bb);
+    if (rc) return rc;
+    for (int e = 0; e < 6; ++e)
+        if (std::isinf(bb[e])) return bad(c, std::string(who) + ": the cloud has infinite coordinates");
+    HIPCHK(c, c->vg_flag.ensure(sizeof(int) * ((size_t)n + 1)));
+    HIPCHK(c, c->vg_pos.ensure(sizeof(int) * ((size_t)n + 2)));
+    HIPCHK(c, c->vg_idx.ensure(sizeof(int) * ((size_t)n + 1)));
+    HIPCHK(c, c->vg_cnt.ensure(sizeof(int) * 4));
+    HIPCHK(c, c->scan_tmp.ensure(sizeof(int) * ((size_t)n / 2048 + 4)));
+    k_vg_flag<<<(n + 255) / 256, 256, 0, st>>>(raw, n, c->vg_flag.as<int>());
+    launch_compact(n, c->vg_flag.as<int>(), c->vg_pos.as<int>(), c->scan_tmp.as<int>(), c->vg_idx.as<int>(), c->vg_cnt.as<int>(), st);
+    HIPCHK(c, hipGetLastError());
+    int m = 0;
+    HIPCHK(c, hipMemcpyAsync(&m, c->vg_cnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (m < 0 || m > n) return ctx_fail(c, LISREG_ERR_HIP, std::string(who) + ": the compaction returned an impossible count");
+    if (m < k || !(bb[0] <= bb[3] && bb[1] <= bb[4] && bb[2] <= bb[5]))
+        return bad(c, std::string(who) + ": the cloud has fewer finite points than k_correspondences");
+    *m_out = m;
+    HIPCHK(c, c->vg_pts.ensure(sizeof(float4) * (size_t)m));
+    ctx_prof_mark(c, 2);                                           // lisreg_get_timing: "index" = the search grid, the search, the covariances
+    launch_gather_points(raw, c->vg_idx.as<int>(), m, c->vg_pts.as<float4>(), st);
+    // ---- the search grid ---------------------------------------------------------------------------------------------------------
+    const double ex[3] = { (double)bb[3] - bb[0], (double)bb[4] - bb[1], (double)bb[5] - bb[2] };
+    double cell = edge;
+    if (!(cell > 0)) {
+        // lidar clouds are surfaces over a ground plane: with 4 points per cell footprint the 3 x 3 columns around a query hold about 36
+        const double area = std::max(ex[0], 1.0e-3) * std::max(ex[1], 1.0e-3);
+        cell = std::sqrt(4.0 * area / (double)m);
+    }
+    cell = std::max(cell, 1.0e-4);
+    GridIndex g;
+    memset(&g, 0, sizeof g);
+    for (;;) {
+        const double nx = floor(ex[0] / cell) + 1, ny = floor(ex[1] / cell) + 1, nz = floor(ex[2] / cell) + 1;
+        if (nx <= kVgKnnMaxDim && ny <= kVgKnnMaxDim && nz <= kVgKnnMaxDim && nx * ny * nz <= (double)kVgKnnMaxCells) {
+            g.nx = (int)nx; g.ny = (int)ny; g.nz = (int)nz;
+            break;
+        }
+        cell *= 1.26;
+    }
+    g.n = m; g.ox = bb[0]; g.oy = bb[1]; g.oz = bb[2]; g.cell = (float)cell; g.inv_cell = 1.f / g.cell;
+    const int n_cells = g.nx * g.ny * g.nz;
+    rc = ensure_sort_scratch(c, (size_t)m, (size_t)n_cells + 1);
+    if (rc) return rc;
+    HIPCHK(c, c->vg_sorted.ensure(sizeof(float4) * (size_t)m));
+    HIPCHK(c, c->vg_cells.ensure(sizeof(int) * ((size_t)n_cells + 2)));
+    HIPCHK(c, c->vg_cov.ensure(sizeof(double) * 6 * (size_t)m));
+    launch_build_target(c->vg_pts.as<float4>(), m, g, c->vg_sorted.as<float4>(), c->vg_cells.as<int>(), n_cells, sort_buffers(c), st);
+    VgKnn A;
+    A.sorted = c->vg_sorted.as<float4>(); A.cell_start = c->vg_cells.as<int>(); A.pts = c->vg_pts.as<float4>(); A.orig = c->vg_idx.as<int>();
+    A.m = m; A.k = k; A.ox = g.ox; A.oy = g.oy; A.oz = g.oz; A.cell = g.cell; A.inv_cell = g.inv_cell; A.nx = g.nx; A.ny = g.ny; A.nz = g.nz;
+    A.plane_eps = plane_eps; A.cov = c->vg_cov.as<double>(); A.nbr = nbr_dev;
+    if (k <= 20) k_vg_knn<20><<<(m + 63) / 64, 64, 0, st>>>(A);
+    else         k_vg_knn<32><<<(m + 63) / 64, 64, 0, st>>>(A);
+    ctx_prof_mark(c, -1);
+    HIPCHK(c, hipGetLastError());
+    return LISREG_OK;
+}
+
+struct VgRun {
+    lisreg_ctx*        c;
+    const VgicpTarget* T;
+    const float4*      src;      // the source's finite points
+    const double*      cov;
+    int                n;
+    int                n_evals = 0;
+};
+
+int evaluate(VgRun& r, const double T[16], bool hess, double out[kOut])
+{
+    lisreg_ctx* c = r.c;
+    hipStream_t st = c->stream;
+    VgPose P;
+    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) P.R[3 * i + j] = T[4 * i + j]; P.t[i] = T[4 * i + 3]; }
+    VgGrid G;
+    G.stats = r.T->stats.as<double>(); G.table = r.T->table.as<int>();
+    G.d0 = r.T->dims[0]; G.d1 = r.T->dims[1]; G.d2 = r.T->dims[2];
+    G.m0 = r.T->min_b[0]; G.m1 = r.T->min_b[1]; G.m2 = r.T->min_b[2];
+    G.inv_res = 1.0 / r.T->resolution;
+    const int nb = (r.n + 63) / 64;
+    HIPCHK(c, c->vg_part.ensure(sizeof(double) * kOut * (size_t)nb));
+    HIPCHK(c, c->vg_out.ensure(sizeof(double) * kOut));
+    HIPCHK(c, c->vg_host.ensure(sizeof(double) * kOut, sizeof(double) * 64));
+    ctx_prof_mark(c, 0);                                           // "assoc" = the linearisations (both launches), one interval each
+    if (hess) k_vgicp_linearize<true><<<nb, 64, 0, st>>>(r.src, r.cov, r.n, G, P, c->vg_part.as<double>());
+    else      k_vgicp_linearize<false><<<nb, 64, 0, st>>>(r.src, r.cov, r.n, G, P, c->vg_part.as<double>());
+    k_vgicp_total<<<1, 64, 0, st>>>(c->vg_part.as<double>(), nb, c->vg_out.as<double>());
+    ctx_prof_mark(c, -1);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->vg_host.p, c->vg_out.p, sizeof(double) * kOut, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(out, c->vg_host.p, sizeof(double) * kOut);
+    ++r.n_evals;
+    return LISREG_OK;
+}
+
+// the checks and the staging every entry point with a source shares: its distributions end up in c->vg_pts / c->vg_cov
+int stage_source(lisreg_ctx* c, const char* who, int slot, const void* source, int n, int stride, int fmt, const lisreg_vgicp_params* P,
+                 VgRun* r, const float4** raw)
+{
+    int rc = check_params(c, P, who);
+    if (rc) return rc;
+    VgicpTarget* T = nullptr;
+    rc = find_target(c, slot, P, who, &T);
+    if (rc) return rc;
+    rc = check_cloud(c, who, source, n, stride, fmt, kFmtPackable, false);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = stage_records(c, source, n, stride, fmt, c->vg_raw, raw);
+    if (rc) return rc;
+    float bb[6];
+    int m = 0;
+    rc = distributions(c, who, *raw, n, P->k_correspondences, P->plane_epsilon, 0.f, bb, &m, nullptr);
+    if (rc) return rc;
+    r->c = c; r->T = T; r->src = c->vg_pts.as<float4>(); r->cov = c->vg_cov.as<double>(); r->n = m;
+    return LISREG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lisreg_vgicp_default_params(int kind, lisreg_vgicp_params* p)
+{
+    if (!p || kind != 0) return LISREG_ERR_ARG;
+    *p = lisreg_vgicp_params{ 1.0, 0.01, 2.0e-3, 1.0e-9, 1.0e-3, 20, 50, 10, 0 };
+    return LISREG_OK;
+}
+
+int lisreg_vgicp_set_target(lisreg_ctx* c, int slot, const void* cloud, int n, int stride, int fmt, const lisreg_vgicp_params* P,
+                            lisreg_vgicp_info* info)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (slot < 0 || slot > 65535) return bad(c, "vgicp_set_target: bad slot");
+    int rc = check_params(c, P, "vgicp_set_target");
+    if (rc) return rc;
+    rc = check_cloud(c, "vgicp_set_target", cloud, n, stride, fmt, kFmtPackable, false);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    VgicpTarget& T = c->vgicp[slot];
+    T.valid = false;
+    const float4* raw = nullptr;
+    rc = stage_records(c, cloud, n, stride, fmt, c->vg_raw, &raw);
+    if (rc) return rc;
+    float bb[6];
+    int m = 0;
+    rc = distributions(c, "vgicp_set_target", raw, n, P->k_correspondences, P->plane_epsilon, 0.f, bb, &m, nullptr);
+    if (rc) return rc;
+    // ---- the voxel geometry (pcl::VoxelGrid's, as the NDT target's) ------------------------------------------------------------------
+    const float inv = 1.0f / (float)P->resolution;
+    VoxelDesc d;
+    long long div_b[3];
+    const double lim = 2.0e9;
+    for (int k = 0; k < 3; ++k) {
+        const double lo = floor((double)(bb[k] * inv)), hi = floor((double)(bb[3 + k] * inv));
+        if (!(fabs(lo) < lim && fabs(hi) < lim)) return bad(c, "vgicp_set_target: the grid has more than 2^26 cells (resolution too small for this cloud)");
+        T.min_b[k] = (int)floorf(bb[k] * inv);
+        div_b[k] = (long long)floorf(bb[3 + k] * inv) - T.min_b[k] + 1;
+    }
+    if (div_b[0] > kVgMaxCells || div_b[1] > kVgMaxCells || div_b[2] > kVgMaxCells || div_b[0] * div_b[1] > kVgMaxCells ||
+        div_b[0] * div_b[1] * div_b[2] > kVgMaxCells)
+        return bad(c, "vgicp_set_target: the grid has more than 2^26 cells (the voxel table is dense; resolution too small for this cloud)");
+    const long long total = div_b[0] * div_b[1] * div_b[2];
+    for (int k = 0; k < 3; ++k) T.dims[k] = (int)div_b[k];
+    d.inv_leaf = inv; d.min_b0 = T.min_b[0]; d.min_b1 = T.min_b[1]; d.min_b2 = T.min_b[2];
+    d.mul1 = T.dims[0]; d.mul2 = T.dims[0] * T.dims[1];
+    const long long max_buckets = 1LL << 22;
+    d.span = (uint32_t)std::max(1LL, (total + max_buckets - 1) / max_buckets);
+    const int n_buckets = (int)((total + d.span - 1) / d.span);
+    // ---- sort by voxel, voxel starts (the launches of lisreg_voxel_downsample) -------------------------------------------------------
+    rc = ensure_sort_scratch(c, (size_t)m, (size_t)std::max(n_buckets, m) + 1);
+    if (rc) return rc;
+    HIPCHK(c, c->vox_order.ensure(sizeof(int) * (size_t)m));
+    HIPCHK(c, c->vox_sidx.ensure(sizeof(uint32_t) * (size_t)m));
+    HIPCHK(c, c->vox_head.ensure(sizeof(int) * ((size_t)m + 1)));
+    HIPCHK(c, c->vox_slot.ensure(sizeof(int) * ((size_t)m + 2)));
+    ctx_prof_mark(c, 1);                                           // "solve" = the voxel sort and statistics (with the wait for the voxel count)
+    launch_voxel_sort(c->vg_pts.as<float4>(), m, d, n_buckets, sort_buffers(c), c->vox_order.as<int>(), c->vox_sidx.as<uint32_t>(),
+                      c->vox_head.as<int>(), c->vox_slot.as<int>(), st);
+    int n_vox = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_vox, c->vox_slot.as<int>() + m, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (n_vox < 1 || n_vox > m) return ctx_fail(c, LISREG_ERR_HIP, "vgicp_set_target: the voxel sort returned an impossible voxel count");
+    HIPCHK(c, c->vox_start.ensure(sizeof(int) * ((size_t)n_vox + 2)));
+    launch_voxel_starts(m, c->vox_head.as<int>(), c->vox_slot.as<int>(), c->vox_start.as<int>(), st);
+    // ---- the statistics -----------------------------------------------------------------------------------------------------------------
+    HIPCHK(c, T.stats.ensure(sizeof(double) * kVgRec * (size_t)n_vox));
+    HIPCHK(c, T.cell.ensure(sizeof(int) * (size_t)n_vox));
+    HIPCHK(c, T.table.ensure(sizeof(int) * (size_t)total));
+    HIPCHK(c, hipMemsetAsync(T.table.p, 0xFF, sizeof(int) * (size_t)total, st));
+    VgBuild B;
+    B.pts = c->vg_pts.as<float4>(); B.cov = c->vg_cov.as<double>(); B.order = c->vox_order.as<int>(); B.sidx = c->vox_sidx.as<uint32_t>();
+    B.vstart = c->vox_start.as<int>(); B.n_vox = n_vox; B.n_cells = total;
+    B.stats = T.stats.as<double>(); B.cell = T.cell.as<int>(); B.table = T.table.as<int>();
+    k_vg_stats_small<<<(n_vox + 255) / 256, 256, 0, st>>>(B);
+    k_vg_stats_big<<<n_vox, 64, 0, st>>>(B);
+    ctx_prof_mark(c, -1);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(st));
+    ctx_prof_collect(c);
+    T.n_voxels = n_vox; T.n_points = m; T.resolution = P->resolution;
+    if (info) { for (int k = 0; k < 3; ++k) info->dims[k] = T.dims[k]; info->n_voxels = n_vox; info->n_points = m; }
+    T.valid = true;
+    return LISREG_OK;
+}
+
+int lisreg_vgicp_covariances(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, int k, double* cov6_out, int* neighbours_out,
+                             float cell_edge)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (k < 4 || k > 32) return bad(c, "vgicp_covariances: k outside 4 .. 32");
+    if (!cov6_out) return bad(c, "vgicp_covariances: NULL cov6_out");
+    if (!(cell_edge >= 0.f) || !std::isfinite(cell_edge)) return bad(c, "vgicp_covariances: cell_edge < 0");
+    int rc = check_cloud(c, "vgicp_covariances", cloud, n, stride, fmt, kFmtPackable, false);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const float4* raw = nullptr;
+    rc = stage_records(c, cloud, n, stride, fmt, c->vg_raw, &raw);
+    if (rc) return rc;
+    if (neighbours_out) {
+        HIPCHK(c, c->vg_nbr.ensure(sizeof(int) * (size_t)n * (size_t)k));
+        HIPCHK(c, hipMemsetAsync(c->vg_nbr.p, 0xFF, sizeof(int) * (size_t)n * (size_t)k, st));      // -1 rows for the points that are none
+    }
+    float bb[6];
+    int m = 0;
+    rc = distributions(c, "vgicp_covariances", raw, n, k, 1.0e-3, cell_edge, bb, &m, neighbours_out ? c->vg_nbr.as<int>() : nullptr);
+    if (rc) return rc;
+    HIPCHK(c, c->vg_rows.ensure(sizeof(double) * 6 * (size_t)n));
+    k_vg_cov_rows<<<(n + 255) / 256, 256, 0, st>>>(c->vg_cov.as<double>(), c->vg_flag.as<int>(), c->vg_pos.as<int>(), n, c->vg_rows.as<double>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(cov6_out, c->vg_rows.p, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (neighbours_out) HIPCHK(c, hipMemcpyAsync(neighbours_out, c->vg_nbr.p, sizeof(int) * (size_t)n * (size_t)k, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    ctx_prof_collect(c);
+    return LISREG_OK;
+}
+
+int lisreg_vgicp_get_voxels(lisreg_ctx* c, int slot, int* cell_ids, int* counts, double* means, double* cov6, int capacity, int* n_out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    VgicpTarget* T = nullptr;
+    int rc = find_target(c, slot, nullptr, "vgicp_get_voxels", &T);
+    if (rc) return rc;
+    if (!n_out || capacity < 0) return bad(c, "vgicp_get_voxels: bad arguments");
+    *n_out = T->n_voxels;
+    if (T->n_voxels > capacity) return LISREG_OK;
+    if (!cell_ids || !counts || !means || !cov6) return bad(c, "vgicp_get_voxels: NULL output");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<double> st((size_t)T->n_voxels * kVgRec);
+    HIPCHK(c, hipMemcpyAsync(st.data(), T->stats.p, sizeof(double) * st.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cell_ids, T->cell.p, sizeof(int) * (size_t)T->n_voxels, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int v = 0; v < T->n_voxels; ++v) {
+        const double* r = &st[(size_t)v * kVgRec];
+        counts[v] = (int)r[9];
+        memcpy(means + 3 * (size_t)v, r, sizeof(double) * 3);
+        memcpy(cov6 + 6 * (size_t)v, r + 3, sizeof(double) * 6);
+    }
+    return LISREG_OK;
+}
+
+int lisreg_vgicp_linearize(lisreg_ctx* c, int slot, const void* source, int n, int stride, int fmt, const lisreg_vgicp_params* P,
+                           const double T[16], int with_hessian, double out[28], long long* n_pairs)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (!T || !out) return bad(c, "vgicp_linearize: NULL T / out");
+    VgRun r;
+    const float4* raw = nullptr;
+    int rc = stage_source(c, "vgicp_linearize", slot, source, n, stride, fmt, P, &r, &raw);
+    if (rc) return rc;
+    double o[kOut];
+    rc = evaluate(r, T, with_hessian != 0, o);
+    if (rc) return rc;
+    memcpy(out, o, sizeof(double) * 28);
+    if (n_pairs) *n_pairs = (long long)o[28];
+    ctx_prof_collect(c);
+    return LISREG_OK;
+}
+
+int lisreg_vgicp_align(lisreg_ctx* c, int slot, const void* source, int n, int stride, int fmt, const lisreg_vgicp_params* P,
+                       const float* guess, lisreg_vgicp_result* res, void* aligned_out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (!res) return bad(c, "vgicp_align: NULL result");
+    VgRun r;
+    const float4* raw = nullptr;
+    int rc = stage_source(c, "vgicp_align", slot, source, n, stride, fmt, P, &r, &raw);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    double T0[16];
+    for (int k = 0; k < 16; ++k) T0[k] = guess ? (double)guess[k] : (k % 5 == 0 ? 1.0 : 0.0);
+    T0[12] = T0[13] = T0[14] = 0.0; T0[15] = 1.0;
+    const LmParams lp{ P->transformation_epsilon, P->rotation_epsilon, P->lm_init_lambda_factor, P->max_iters, P->lm_max_iterations };
+    LmResult lr;
+    rc = lm_optimise([&](const double T[16], bool hess, double out[kOut]) { return evaluate(r, T, hess, out); }, T0, lp, &lr);
+    if (rc) return rc;
+    ctx_prof_collect(c);
+    memcpy(res->final_transform, lr.T, sizeof lr.T);
+    res->converged = lr.converged; res->iters = lr.iters; res->n_evals = lr.n_evals; res->n_rejected = lr.n_rejected;
+    res->n_pairs_last = lr.n_pairs_last; res->error = lr.error; res->lambda = lr.lambda;
+    if (aligned_out) {                                    // the source under the final transformation (in float, like lisreg_transform_cloud)
+        float F[12];
+        for (int k = 0; k < 12; ++k) F[k] = (float)lr.T[k];
+        HIPCHK(c, c->vox_M.ensure(sizeof(float) * 12));
+        HIPCHK(c, hipMemcpyAsync(c->vox_M.p, F, sizeof F, hipMemcpyHostToDevice, st));
+        if (fmt == LISREG_FMT_DEVICE) {
+            launch_transform_cloud(raw, n, c->vox_M.as<float>(), static_cast<float4*>(aligned_out), st);
+            HIPCHK(c, hipStreamSynchronize(st));
+        } else {
+            HIPCHK(c, c->vg_sorted.ensure(sizeof(float4) * (size_t)n));
+            launch_transform_cloud(raw, n, c->vox_M.as<float>(), c->vg_sorted.as<float4>(), st);
+            std::vector<float4> hp((size_t)n);
+            HIPCHK(c, hipMemcpyAsync(hp.data(), c->vg_sorted.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            const unsigned char* b = static_cast<const unsigned char*>(source);
+            unsigned char* o = static_cast<unsigned char*>(aligned_out);
+            for (int i = 0; i < n; ++i) {
+                if (o != b) memcpy(o + (size_t)i * (size_t)stride, b + (size_t)i * (size_t)stride, (size_t)stride);
+                memcpy(o + (size_t)i * (size_t)stride, &hp[(size_t)i], 12);
+            }
+        }
+    }
+    return LISREG_OK;
+}
+
+}  // extern "C"

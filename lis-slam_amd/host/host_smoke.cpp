@@ -123,6 +123,17 @@ int main()
                 ndt.info().n_valid, ndt.info().n_voxels, (int)ndt.hasConverged(), ndt.getFinalNumIteration(), ndt.result().n_evals,
                 ndt.getTransformationProbability(), ndt.getFitnessScore(), Nm[3], Nm[7], Nm[11], std::atan2(Nm[4], Nm[0]));
     ok = ok && ndt.info().n_valid > 0 && ndtOut.size() == surf.size();      // the pose is held against the definition in tests/test_ndt.py
+    // VGICP as the commented select_registration_method("FAST_VGICP") would run it (registration.cpp:156-187)
+    VgicpRegistration<PointType> vg(reg.handle(), 0, 3);
+    vg.setResolution(1.0); vg.setInputTarget(mapSurf);
+    vg.setInputSource(&surf);
+    PointCloud<PointType> vgOut;
+    vg.align(vgOut, Fm);
+    const float* Vm = vg.getFinalTransformation();
+    std::printf("VGICP: %d voxels of %d points, converged=%d iterations=%d evaluations=%d rejected=%d error=%g fitness=%g t=[%g %g %g] yaw=%g\n",
+                vg.info().n_voxels, vg.info().n_points, (int)vg.hasConverged(), vg.getFinalNumIteration(), vg.result().n_evals,
+                vg.result().n_rejected, vg.result().error, vg.getFitnessScore(), Vm[3], Vm[7], Vm[11], std::atan2(Vm[4], Vm[0]));
+    ok = ok && vg.info().n_voxels > 0 && vgOut.size() == surf.size();      // the pose is held against the definition in tests/test_vgicp.py
     // OptimizedICPGN (registration.cpp:19-115) on the same pair
     OptimizedICPGN<PointType> gn(reg.handle(), 2, 15, 4.0f);
     gn.SetTargetCloud(mapSurf);

@@ -49,6 +49,8 @@ ABI_SYMBOLS = [
     "lisreg_rangenet_label_batch",
     "lisreg_default_rangenet_knn_params", "lisreg_rangenet_knn_weights", "lisreg_rangenet_label_knn", "lisreg_rangenet_label_knn_batch",
     "lisreg_ndt_default_params", "lisreg_ndt_set_target", "lisreg_ndt_align", "lisreg_ndt_get_voxels", "lisreg_ndt_derivatives",
+    "lisreg_vgicp_default_params", "lisreg_vgicp_set_target", "lisreg_vgicp_align", "lisreg_vgicp_covariances", "lisreg_vgicp_get_voxels",
+    "lisreg_vgicp_linearize",
 ]
 
 
@@ -88,6 +90,26 @@ class NdtResult(C.Structure):
         return dict(T=np.array(list(self.final_transform), np.float32).reshape(4, 4), p=np.array(list(self.p)),
                     converged=bool(self.converged), iters=self.iters, n_evals=self.n_evals, n_pairs_last=self.n_pairs_last,
                     score=self.score, trans_probability=self.trans_probability)
+
+
+class VgicpParams(C.Structure):
+    _fields_ = [("resolution", C.c_double), ("transformation_epsilon", C.c_double), ("rotation_epsilon", C.c_double),
+                ("lm_init_lambda_factor", C.c_double), ("plane_epsilon", C.c_double), ("k_correspondences", C.c_int),
+                ("max_iters", C.c_int), ("lm_max_iterations", C.c_int), ("reserved", C.c_int)]
+
+
+class VgicpInfo(C.Structure):
+    _fields_ = [("dims", C.c_int * 3), ("n_voxels", C.c_int), ("n_points", C.c_int)]
+
+
+class VgicpResult(C.Structure):
+    _fields_ = [("final_transform", C.c_double * 16), ("converged", C.c_int), ("iters", C.c_int), ("n_evals", C.c_int),
+                ("n_rejected", C.c_int), ("n_pairs_last", C.c_longlong), ("error", C.c_double), ("lambda_", C.c_double)]
+
+    def as_dict(self):
+        return dict(T=np.array(list(self.final_transform), np.float64).reshape(4, 4), converged=bool(self.converged), iters=self.iters,
+                    n_evals=self.n_evals, n_rejected=self.n_rejected, n_pairs_last=self.n_pairs_last, error=self.error,
+                    lam=self.lambda_)
 
 
 class GuessInput(C.Structure):
@@ -450,8 +472,26 @@ def lib():
         L.lisreg_ndt_get_voxels.argtypes = [vp, C.c_int, ip, ip, dbl, dbl, C.c_int, ip]
         L.lisreg_ndt_derivatives.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(NdtParams), dbl, C.c_int, dbl,
                                              C.POINTER(C.c_longlong)]
+        L.lisreg_vgicp_default_params.argtypes = [C.c_int, C.POINTER(VgicpParams)]
+        L.lisreg_vgicp_set_target.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VgicpParams), C.POINTER(VgicpInfo)]
+        L.lisreg_vgicp_align.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VgicpParams), fp, C.POINTER(VgicpResult), vp]
+        L.lisreg_vgicp_covariances.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, dbl, ip, C.c_float]
+        L.lisreg_vgicp_get_voxels.argtypes = [vp, C.c_int, ip, ip, dbl, dbl, C.c_int, ip]
+        L.lisreg_vgicp_linearize.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VgicpParams), dbl, C.c_int, dbl,
+                                             C.POINTER(C.c_longlong)]
         _lib = L
     return _lib
+
+
+def vgicp_default_params(kind: int = 0, **overrides) -> VgicpParams:
+    p = VgicpParams()
+    if lib().lisreg_vgicp_default_params(kind, C.byref(p)):
+        raise LisregError(ERR_ARG, "lisreg_vgicp_default_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
 
 
 def ndt_default_params(kind: int = 0, **overrides) -> NdtParams:
@@ -1495,6 +1535,60 @@ class Context:
         pairs = C.c_longlong(0)
         dp = C.POINTER(C.c_double)
         self._chk(self._L.lisreg_ndt_derivatives(self._h, slot, ptr, n, stride, fmt, C.byref(params), p.ctypes.data_as(dp),
+                                                 1 if with_hessian else 0, out.ctypes.data_as(dp), C.byref(pairs)))
+        return out, pairs.value
+
+    # -- §7k: VGICP registration -------------------------------------------------------------------------
+    def vgicp_set_target(self, slot: int, cloud, params: "VgicpParams") -> dict:
+        """distributions + voxel statistics of the target; cloud = host PCL-struct array or (device_ptr, n)"""
+        ptr, n, stride, fmt, _keep = self._cloud_args(cloud)
+        info = VgicpInfo()
+        self._chk(self._L.lisreg_vgicp_set_target(self._h, slot, ptr, n, stride, fmt, C.byref(params), C.byref(info)))
+        return dict(dims=list(info.dims), n_voxels=info.n_voxels, n_points=info.n_points)
+
+    def vgicp_align(self, slot: int, source, params: "VgicpParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
+        """FastVGICP::align against the VGICP target in `slot`; returns the result dict (+ 'aligned')."""
+        ptr, n, stride, fmt, keep = self._cloud_args(source)
+        res = VgicpResult()
+        g = None if guess is None else np.ascontiguousarray(guess, np.float32).ravel().ctypes.data_as(C.POINTER(C.c_float))
+        out = np.zeros_like(keep) if (want_aligned and keep is not None) else None
+        o = C.c_void_p(out_ptr) if out_ptr else (_vp(out) if out is not None else None)
+        self._chk(self._L.lisreg_vgicp_align(self._h, slot, ptr, n, stride, fmt, C.byref(params), g, C.byref(res), o))
+        d = res.as_dict()
+        if out is not None:
+            d["aligned"] = out
+        return d
+
+    def vgicp_covariances(self, cloud, k: int = 20, want_neighbours: bool = True, cell_edge: float = 0.0):
+        """(cov6 [n, 6] with NaN rows for NaN points, neighbours [n, k] or None) of every point's distribution"""
+        ptr, n, stride, fmt, _keep = self._cloud_args(cloud)
+        cov = np.zeros((max(n, 1), 6))
+        nbr = np.zeros((max(n, 1), max(k, 1)), np.int32) if want_neighbours else None
+        self._chk(self._L.lisreg_vgicp_covariances(self._h, ptr, n, stride, fmt, k, cov.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   nbr.ctypes.data_as(C.POINTER(C.c_int)) if want_neighbours else None, cell_edge))
+        return cov[:n], (nbr[:n] if want_neighbours else None)
+
+    def vgicp_get_voxels(self, slot: int) -> dict:
+        """the voxels of a VGICP target in ascending cell order: cell_ids, counts, means [m, 3], cov6 [m, 6]"""
+        m = C.c_int(0)
+        self._chk(self._L.lisreg_vgicp_get_voxels(self._h, slot, None, None, None, None, 0, C.byref(m)))
+        cap = max(m.value, 1)
+        ids, cnt = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        means, cv = np.zeros((cap, 3)), np.zeros((cap, 6))
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        self._chk(self._L.lisreg_vgicp_get_voxels(self._h, slot, ids.ctypes.data_as(ip), cnt.ctypes.data_as(ip), means.ctypes.data_as(dp),
+                                                  cv.ctypes.data_as(dp), cap, C.byref(m)))
+        k = m.value
+        return dict(cell_ids=ids[:k], counts=cnt[:k], means=means[:k], cov6=cv[:k])
+
+    def vgicp_linearize(self, slot: int, source, params: "VgicpParams", T, with_hessian: bool = True):
+        """one linearisation at T (4x4): (out [28] = error, b, H upper triangle; pairs)"""
+        ptr, n, stride, fmt, _keep = self._cloud_args(source)
+        T = np.ascontiguousarray(T, np.float64).reshape(16)
+        out = np.zeros(28)
+        pairs = C.c_longlong(0)
+        dp = C.POINTER(C.c_double)
+        self._chk(self._L.lisreg_vgicp_linearize(self._h, slot, ptr, n, stride, fmt, C.byref(params), T.ctypes.data_as(dp),
                                                  1 if with_hessian else 0, out.ctypes.data_as(dp), C.byref(pairs)))
         return out, pairs.value
 
