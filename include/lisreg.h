@@ -370,7 +370,8 @@ int  lisreg_get_trace(lisreg_ctx* ctx, float* buf, int max_iters);
  * out[0] = total ms in the correspondence+normal-equation kernel, out[1] = its launch count,
  * out[2] = total ms in the solve/update kernel, out[3] = its launch count, out[4] = index build ms.
  * After a lisreg_vgicp_* call: out[0] / out[1] = the linearisations and their number, out[2] = the voxel sort and statistics,
- * out[4] = the distributions (search grid, k-nearest search, covariances). */
+ * out[4] = the distributions (search grid, k-nearest search, covariances).  After a lisreg_fgicp_* call: out[0] / out[1] = the sum
+ * launches and their number, out[2] / out[3] = the search launches and their number, out[4] = the distributions. */
 int  lisreg_set_profiling(lisreg_ctx* ctx, int enable);
 int  lisreg_get_timing(lisreg_ctx* ctx, double out[5]);
 
@@ -996,6 +997,70 @@ int  lisreg_vgicp_get_voxels(lisreg_ctx* ctx, int slot, int* cell_ids, int* coun
 int  lisreg_vgicp_linearize(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
                             const lisreg_vgicp_params* params, const double T[16], int with_hessian, double out[28],
                             long long* n_pairs);
+
+/* ---- §7l: FastGICP registration (loop-closure verification) --------------------------------------------------------------
+ * select_registration_method("FAST_GICP") (src/core/registration.cpp:157-166: FastGICP, transformation epsilon 0.01, 50 iterations,
+ * max correspondence distance 5, correspondence randomness 20) is the other verifier of the fast_gicp family that
+ * detectLoopClosureForSubMap's call (src/node/subMapOptmizationNode.cpp:2771) can name.  The method: every point of either cloud
+ * gets the distribution of §7k; at every linearisation each transformed source point is paired with its NEAREST target point — an
+ * exact search, squared distances in double from the float coordinates, ties to the lower index — if that point is nearer than
+ * max_correspondence_distance (strictly), and a Levenberg-Marquardt loop (§7k's) minimises the sum of d^T (C_b + R C_a R^T)^-1 d over
+ * the pairs.  An error evaluation inside the loop reuses the pairs and the matrices of the last linearisation.  The DEFINITION is
+ * tests/fgicp_ref.py (fast_gicp's source is not available to this project); DESIGN.md §7l lists where it picks a reading of fast_gicp
+ * it cannot verify.  NaN points are no points: never a neighbour, never a correspondent, in no pair.  The GPU makes the distributions,
+ * every search (one query per lane over the target's search grid, fp64) and every sum (fixed order: two evaluations of the same input
+ * give the same bits); the 6 x 6 solve and the LM loop run on the host in double.  There is no fitness score: a caller who wants one
+ * has aligned_out and lisreg_nearest. */
+typedef struct lisreg_fgicp_params {
+    double max_correspondence_distance; /* a nearest point this far away or further is no pair */
+    double transformation_epsilon;      /* a step is converged when max|exp(delta).t| is below this ... */
+    double rotation_epsilon;            /* ... and max|exp(delta).R - I| below this */
+    double lm_init_lambda_factor;       /* lambda starts at this times max|diag H| of the first linearisation */
+    double plane_epsilon;               /* the smallest eigenvalue of a regularised covariance */
+    int    k_correspondences;           /* points per distribution ("correspondence randomness"), 4 .. 32 */
+    int    max_iters;                   /* outer iterations (linearisations) */
+    int    lm_max_iterations;           /* trials per outer iteration */
+    int    reserved;
+} lisreg_fgicp_params;
+typedef struct lisreg_fgicp_info {
+    int grid_dims[3];                   /* cells of the target's search grid */
+    int n_points;                       /* finite points of the target */
+} lisreg_fgicp_info;
+typedef struct lisreg_fgicp_result {
+    double final_transform[16];         /* row-major 4x4, in double */
+    int    converged;
+    int    iters;                       /* outer iterations */
+    int    n_evals;                     /* evaluations of the error (with or without H) */
+    int    n_rejected;                  /* trials whose step was rejected */
+    long long n_pairs_last;             /* pairs of the last linearisation */
+    double error;                       /* at final_transform, over the pairs of the last linearisation */
+    double lambda;                      /* the damping the loop ended with */
+} lisreg_fgicp_result;
+/* kind 0 (the reference's commented FAST_GICP block + fast_gicp's defaults as remembered): {5.0, 0.01, 2e-3, 1e-9, 1e-3, 20, 50, 10};
+ * kind 1: the same with max_correspondence_distance = FLT_MAX, fast_gicp's own default (no cut-off) */
+int  lisreg_fgicp_default_params(int kind, lisreg_fgicp_params* p);
+/* The distributions and the search grid of `cloud` into FastGICP slot `slot` (0 .. 65535; FastGICP slots are a numbering of their
+ * own, apart from the map-index, the NDT and the VGICP slots).  Uses k_correspondences and plane_epsilon of `params`.  Refused
+ * (LISREG_ERR_ARG): n <= 0, fewer finite points than k_correspondences, an infinite coordinate, k_correspondences outside 4 .. 32,
+ * max_correspondence_distance <= 0 or NaN.  info may be NULL.  cell_edge 0: the search grid's cell edge is chosen from the cloud's
+ * density; > 0 forces it: results do not depend on it. */
+int  lisreg_fgicp_set_target(lisreg_ctx* ctx, int slot, const void* cloud, int n, int stride_bytes, int fmt,
+                             const lisreg_fgicp_params* params, lisreg_fgicp_info* info, float cell_edge);
+/* guess = row-major 4x4 or NULL for identity; aligned_out: NULL, or room for n points of the input layout (the source under
+ * final_transform rounded to float).  Host PCL structs or LISREG_FMT_DEVICE records.  The slot must hold a target (LISREG_ERR_ARG
+ * otherwise).  The source's distributions are made by every call; a source with fewer finite points than k_correspondences is
+ * refused.  A source without a pair at the guess returns converged = 0, iters = 0, n_evals = 1 and the guess. */
+int  lisreg_fgicp_align(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
+                        const lisreg_fgicp_params* params, const float* guess, lisreg_fgicp_result* result, void* aligned_out);
+/* test hooks.  _correspondences: the search at T (row-major 4x4) — index_out [n] = the correspondent's index in the caller's target
+ * cloud, -1 for a source point without one or a NaN point; sqdist_out [n] (may be NULL) = its squared distance, NaN where -1.
+ * _linearize: pairs and their matrices from a search at T_pairs, then out[28] = error, b [6], upper triangle of H row by row [21]
+ * (zeros without with_hessian) at T_eval (NULL: T_pairs) — the reuse of the pairs by an error evaluation, as one call. */
+int  lisreg_fgicp_correspondences(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
+                                  const lisreg_fgicp_params* params, const double T[16], int* index_out, double* sqdist_out);
+int  lisreg_fgicp_linearize(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
+                            const lisreg_fgicp_params* params, const double T_pairs[16], const double* T_eval, int with_hessian,
+                            double out[28], long long* n_pairs);
 
 /* ---- loop-closure candidate detection: FEPSC (src/core/epscGeneration.cpp) -------------------------------------------
  * EPSCGeneration::loopDetection (:663-992) with UsingFEPSCFlag (config/params.yaml:22-28), as loopClosureThread calls it for every

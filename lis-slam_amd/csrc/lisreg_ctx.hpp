@@ -132,6 +132,18 @@ struct VgicpTarget {
     DevBuf    table;               // [dims product] ints: cell -> voxel, -1 none
 };
 
+// one FastGICP target (lisreg_fgicp.hip: lisreg_fgicp_set_target): its own copies of what the distributions leave in the context's scratch
+struct FgicpTarget {
+    bool      valid = false;
+    int       n_points = 0;        // finite points
+    GridIndex grid;                // the search grid (pts = sorted, cell_start = cells)
+    float     bb[6] = { 0, 0, 0, 0, 0, 0 };   // the finite bounding box
+    DevBuf    sorted;              // [n_points] float4 by grid cell, .w = index among the finite points
+    DevBuf    cells;               // [nx * ny * nz + 1] ints
+    DevBuf    orig;                // [n_points] ints: index among the finite points -> index in the caller's cloud
+    DevBuf    cov;                 // [n_points][6] doubles by index among the finite points
+};
+
 // device-resident sliding local map (lisreg_api_localmap.hip)
 struct LocalMap {
     bool   valid = false;
@@ -248,6 +260,11 @@ struct lisreg_ctx {
     std::map<int, lisreg::VgicpTarget> vgicp;
     lisreg::DevBuf vg_raw, vg_flag, vg_pos, vg_pts, vg_idx, vg_sorted, vg_cells, vg_cov, vg_nbr, vg_rows, vg_part, vg_out, vg_cnt;
     lisreg::PinnedBuf vg_host;
+    // FastGICP registration (lisreg_fgicp.hip): targets by slot (a numbering of their own); of the source being aligned: the sorted
+    // position of every finite point's correspondent (-1: none), the six entries of its M, its squared distance (the test hook); the
+    // correspondence rows of the test hook by the caller's index
+    std::map<int, lisreg::FgicpTarget> fgicp;
+    lisreg::DevBuf fg_pair, fg_M, fg_d2, fg_rows_i, fg_rows_d;
     lisreg::PinnedBuf done_host;            // one int
     lisreg::PinnedBuf stage_host;           // pinned staging of the per-batch tables
     lisreg::Event stage_done;
@@ -371,6 +388,17 @@ int  upload_records(lisreg_ctx* c, const void* cloud, int n, int stride_bytes, i
 void make_grid(const float bb[6], int n, GridIndex* g, int* n_cells, int margin_cells = 0);
 SortBuffers sort_buffers(lisreg_ctx* c);
 int  ensure_sort_scratch(lisreg_ctx* c, size_t n_elems, size_t n_buckets);
+// ---- lisreg_vgicp.hip: what the fast_gicp family's units share -----------------------------------------------------------------------------
+// The distributions of one cloud of n device records (the k nearest points of every finite point within the cloud, plane-regularised
+// covariances): afterwards c->vg_pts holds its *m_out finite points in input order, c->vg_idx their indices in the cloud, c->vg_flag /
+// c->vg_pos the finite flags and their exclusive scan, c->vg_sorted / c->vg_cells the same points by search-grid cell, c->vg_cov the
+// m x 6 covariances by index among the finite points and, if nbr_dev is given, nbr_dev the n x k neighbour rows.  bb: the finite bounding
+// box.  edge: the search grid's cell edge, <= 0: chosen from the cloud's density.  grid_out (may be null): the search grid.  All of it
+// is the context's scratch: the next call overwrites it.
+int  vg_distributions(lisreg_ctx* c, const char* who, const float4* raw, int n, int k, double plane_eps, float edge, float bb[6], int* m_out,
+                      int* nbr_dev, GridIndex* grid_out);
+// out[29] = the n_part partial records of 29 doubles added in a fixed order (one wavefront)
+void launch_vgicp_total(const double* part, int n_part, double* out, hipStream_t st);
 // ---- lisreg_api.hip -------------------------------------------------------------------------------------------------------------------
 void ctx_prof_mark(lisreg_ctx* c, int kind_of_next_interval);      // 0 correspondence kernel, 1 solve, 2 index build, -1 nothing
 void ctx_prof_collect(lisreg_ctx* c);

@@ -374,12 +374,15 @@ int find_target(lisreg_ctx* c, int slot, const lisreg_vgicp_params* P, const cha
     return LISREG_OK;
 }
 
+}  // namespace
+
 // The distributions of one cloud of n device records: afterwards c->vg_pts holds its *m_out finite points in input order, c->vg_idx
 // their indices in the cloud, c->vg_flag / c->vg_pos the finite flags and their exclusive scan, c->vg_cov the m x 6 covariances and, if
 // nbr_dev is given, nbr_dev the n x k neighbour rows.  bb: the finite bounding box.  edge: the search grid's cell edge, <= 0: chosen
-// from the cloud's density so that the 27 cells around a query hold a few tens of points.
-int distributions(lisreg_ctx* c, const char* who, const float4* raw, int n, int k, double plane_eps, float edge, float bb[6], int* m_out,
-                  int* nbr_dev)
+// from the cloud's density so that the 27 cells around a query hold a few tens of points.  grid_out, if given, receives the search grid
+// (pts / cell_start = c->vg_sorted / c->vg_cells).  Declared in lisreg_ctx.hpp: lisreg_fgicp.hip makes its distributions with it too.
+int lisreg::vg_distributions(lisreg_ctx* c, const char* who, const float4* raw, int n, int k, double plane_eps, float edge, float bb[6],
+                             int* m_out, int* nbr_dev, GridIndex* grid_out)
 {
     hipStream_t st = c->stream;
     int rc = cloud_bbox(c, raw, n, bb);
@@ -439,7 +442,21 @@ int distributions(lisreg_ctx* c, const char* who, const float4* raw, int n, int 
     else         k_vg_knn<32><<<(m + 63) / 64, 64, 0, st>>>(A);
     ctx_prof_mark(c, -1);
     HIPCHK(c, hipGetLastError());
+    if (grid_out) { *grid_out = g; grid_out->pts = c->vg_sorted.as<float4>(); grid_out->cell_start = c->vg_cells.as<int>(); }
     return LISREG_OK;
+}
+
+void lisreg::launch_vgicp_total(const double* part, int n_part, double* out, hipStream_t st)
+{
+    k_vgicp_total<<<1, 64, 0, st>>>(part, n_part, out);
+}
+
+namespace {
+
+int distributions(lisreg_ctx* c, const char* who, const float4* raw, int n, int k, double plane_eps, float edge, float bb[6], int* m_out,
+                  int* nbr_dev)
+{
+    return vg_distributions(c, who, raw, n, k, plane_eps, edge, bb, m_out, nbr_dev, nullptr);
 }
 
 struct VgRun {

@@ -552,6 +552,58 @@ private:
     double fitness_ = 1.7976931348623157e308;
 };
 
+// ---- fast_gicp::FastGICP as select_registration_method("FAST_GICP") sets it up -------------------------------------------
+// (src/core/registration.cpp:157-166, commented out in the reference like the rest of the fast_gicp family), with the pcl::Registration
+// surface the loop-closure code uses.  fgicp_slot: the FastGICP target slot; map_slot: a map-index slot of the same target for
+// getFitnessScore (mean squared k = 1 distance of the aligned source, unbounded like PCL's default) — FastGICP itself has no fitness score.
+template <class PointT>
+class FastGicpRegistration {
+public:
+    FastGicpRegistration(lisreg_ctx* ctx, int fgicp_slot, int map_slot) : tree_(ctx, map_slot), fgicp_slot_(fgicp_slot) { lisreg_fgicp_default_params(0, &prm_); }
+    void setMaxCorrespondenceDistance(double d) { prm_.max_correspondence_distance = d; }
+    void setCorrespondenceRandomness(int k) { prm_.k_correspondences = k; if (target_) setInputTarget(*target_); }
+    void setTransformationEpsilon(double e) { prm_.transformation_epsilon = e; }
+    void setRotationEpsilon(double e) { prm_.rotation_epsilon = e; }
+    void setMaximumIterations(int n) { prm_.max_iters = n; }
+    void setInputTarget(const PointCloud<PointT>& cloud) {
+        target_ = &cloud;
+        check(lisreg_fgicp_set_target(tree_.ctx(), fgicp_slot_, cloud.points.data(), (int)cloud.size(), (int)sizeof(PointT), SearchTree<PointT>::fmt(), &prm_, &info_, 0.f));
+        tree_.setInputCloud(cloud);
+    }
+    void setInputSource(const PointCloud<PointT>* cloud) { source_ = cloud; }
+    void align(PointCloud<PointT>& output, const float* guess = nullptr) {
+        if (!source_) throw RegistrationError(LISREG_ERR_ARG, "FastGICP: no input source");
+        output.points.resize(source_->size());
+        check(lisreg_fgicp_align(tree_.ctx(), fgicp_slot_, source_->points.data(), (int)source_->size(), (int)sizeof(PointT),
+                                 SearchTree<PointT>::fmt(), &prm_, guess, &res_, output.points.data()));
+        for (int k = 0; k < 16; ++k) final_[k] = (float)res_.final_transform[k];
+        std::vector<int> idx(output.size());
+        std::vector<float> d2(output.size());
+        check(lisreg_nearest(tree_.ctx(), tree_.slot(), output.points.data(), (int)output.size(), (int)sizeof(PointT), SearchTree<PointT>::fmt(),
+                             1e18f, idx.data(), d2.data()));
+        double sum = 0; size_t nr = 0;
+        for (size_t i = 0; i < d2.size(); ++i) if (idx[i] >= 0) { sum += d2[i]; ++nr; }
+        fitness_ = nr ? sum / (double)nr : 1.7976931348623157e308;
+    }
+    bool hasConverged() const { return res_.converged != 0; }
+    double getFitnessScore() const { return fitness_; }
+    const float* getFinalTransformation() const { return final_; }                  // row-major 4x4 (result().final_transform holds it in double)
+    int getFinalNumIteration() const { return res_.iters; }
+    const lisreg_fgicp_info& info() const { return info_; }
+    const lisreg_fgicp_result& result() const { return res_; }
+private:
+    void check(int rc) { if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(tree_.ctx())); }
+    SearchTree<PointT> tree_;
+    int fgicp_slot_;
+    const PointCloud<PointT>* target_ = nullptr;
+    const PointCloud<PointT>* source_ = nullptr;
+    lisreg_fgicp_params prm_{};
+    lisreg_fgicp_info   info_{};
+    lisreg_fgicp_result res_{};
+    float  final_[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    double fitness_ = 1.7976931348623157e308;
+};
+
 // OptimizedICPGN (src/include/registration.h:44-70, src/core/registration.cpp:8-115): same constructor and calls
 template <class PointT>
 class OptimizedICPGN {

@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "lisreg_ndt_default_params", "lisreg_ndt_set_target", "lisreg_ndt_align", "lisreg_ndt_get_voxels", "lisreg_ndt_derivatives",
     "lisreg_vgicp_default_params", "lisreg_vgicp_set_target", "lisreg_vgicp_align", "lisreg_vgicp_covariances", "lisreg_vgicp_get_voxels",
     "lisreg_vgicp_linearize",
+    "lisreg_fgicp_default_params", "lisreg_fgicp_set_target", "lisreg_fgicp_align", "lisreg_fgicp_correspondences", "lisreg_fgicp_linearize",
 ]
 
 
@@ -110,6 +111,20 @@ class VgicpResult(C.Structure):
         return dict(T=np.array(list(self.final_transform), np.float64).reshape(4, 4), converged=bool(self.converged), iters=self.iters,
                     n_evals=self.n_evals, n_rejected=self.n_rejected, n_pairs_last=self.n_pairs_last, error=self.error,
                     lam=self.lambda_)
+
+
+class FgicpParams(C.Structure):
+    _fields_ = [("max_correspondence_distance", C.c_double), ("transformation_epsilon", C.c_double), ("rotation_epsilon", C.c_double),
+                ("lm_init_lambda_factor", C.c_double), ("plane_epsilon", C.c_double), ("k_correspondences", C.c_int),
+                ("max_iters", C.c_int), ("lm_max_iterations", C.c_int), ("reserved", C.c_int)]
+
+
+class FgicpInfo(C.Structure):
+    _fields_ = [("grid_dims", C.c_int * 3), ("n_points", C.c_int)]
+
+
+class FgicpResult(VgicpResult):
+    """the fields of VgicpResult, in the same order"""
 
 
 class GuessInput(C.Structure):
@@ -479,8 +494,25 @@ def lib():
         L.lisreg_vgicp_get_voxels.argtypes = [vp, C.c_int, ip, ip, dbl, dbl, C.c_int, ip]
         L.lisreg_vgicp_linearize.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VgicpParams), dbl, C.c_int, dbl,
                                              C.POINTER(C.c_longlong)]
+        L.lisreg_fgicp_default_params.argtypes = [C.c_int, C.POINTER(FgicpParams)]
+        L.lisreg_fgicp_set_target.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), C.POINTER(FgicpInfo), C.c_float]
+        L.lisreg_fgicp_align.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), fp, C.POINTER(FgicpResult), vp]
+        L.lisreg_fgicp_correspondences.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), dbl, ip, dbl]
+        L.lisreg_fgicp_linearize.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), dbl, dbl, C.c_int, dbl,
+                                             C.POINTER(C.c_longlong)]
         _lib = L
     return _lib
+
+
+def fgicp_default_params(kind: int = 0, **overrides) -> FgicpParams:
+    p = FgicpParams()
+    if lib().lisreg_fgicp_default_params(kind, C.byref(p)):
+        raise LisregError(ERR_ARG, "lisreg_fgicp_default_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
 
 
 def vgicp_default_params(kind: int = 0, **overrides) -> VgicpParams:
@@ -1590,6 +1622,51 @@ class Context:
         dp = C.POINTER(C.c_double)
         self._chk(self._L.lisreg_vgicp_linearize(self._h, slot, ptr, n, stride, fmt, C.byref(params), T.ctypes.data_as(dp),
                                                  1 if with_hessian else 0, out.ctypes.data_as(dp), C.byref(pairs)))
+        return out, pairs.value
+
+    # -- §7l: FastGICP registration ----------------------------------------------------------------------
+    def fgicp_set_target(self, slot: int, cloud, params: "FgicpParams", cell_edge: float = 0.0) -> dict:
+        """distributions + search grid of the target; cloud = host PCL-struct array or (device_ptr, n)"""
+        ptr, n, stride, fmt, _keep = self._cloud_args(cloud)
+        info = FgicpInfo()
+        self._chk(self._L.lisreg_fgicp_set_target(self._h, slot, ptr, n, stride, fmt, C.byref(params), C.byref(info), cell_edge))
+        return dict(grid_dims=list(info.grid_dims), n_points=info.n_points)
+
+    def fgicp_align(self, slot: int, source, params: "FgicpParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
+        """FastGICP::align against the FastGICP target in `slot`; returns the result dict (+ 'aligned')."""
+        ptr, n, stride, fmt, keep = self._cloud_args(source)
+        res = FgicpResult()
+        g = None if guess is None else np.ascontiguousarray(guess, np.float32).ravel().ctypes.data_as(C.POINTER(C.c_float))
+        out = np.zeros_like(keep) if (want_aligned and keep is not None) else None
+        o = C.c_void_p(out_ptr) if out_ptr else (_vp(out) if out is not None else None)
+        self._chk(self._L.lisreg_fgicp_align(self._h, slot, ptr, n, stride, fmt, C.byref(params), g, C.byref(res), o))
+        d = res.as_dict()
+        if out is not None:
+            d["aligned"] = out
+        return d
+
+    def fgicp_correspondences(self, slot: int, source, params: "FgicpParams", T, want_sqdist: bool = True):
+        """the search at T (4x4): (index [n] in the caller's target cloud, -1 none; squared distance [n], NaN where -1, or None)"""
+        ptr, n, stride, fmt, _keep = self._cloud_args(source)
+        T = np.ascontiguousarray(T, np.float64).reshape(16)
+        idx = np.zeros(max(n, 1), np.int32)
+        sq = np.zeros(max(n, 1)) if want_sqdist else None
+        dp = C.POINTER(C.c_double)
+        self._chk(self._L.lisreg_fgicp_correspondences(self._h, slot, ptr, n, stride, fmt, C.byref(params), T.ctypes.data_as(dp),
+                                                       idx.ctypes.data_as(C.POINTER(C.c_int)), sq.ctypes.data_as(dp) if want_sqdist else None))
+        return idx[:n], (sq[:n] if want_sqdist else None)
+
+    def fgicp_linearize(self, slot: int, source, params: "FgicpParams", T_pairs, with_hessian: bool = True, T_eval=None):
+        """pairs and M from a search at T_pairs, the sums at T_eval (None: T_pairs): (out [28] = error, b, H upper triangle; pairs)"""
+        ptr, n, stride, fmt, _keep = self._cloud_args(source)
+        T = np.ascontiguousarray(T_pairs, np.float64).reshape(16)
+        Te = None if T_eval is None else np.ascontiguousarray(T_eval, np.float64).reshape(16)
+        out = np.zeros(28)
+        pairs = C.c_longlong(0)
+        dp = C.POINTER(C.c_double)
+        self._chk(self._L.lisreg_fgicp_linearize(self._h, slot, ptr, n, stride, fmt, C.byref(params), T.ctypes.data_as(dp),
+                                                 None if Te is None else Te.ctypes.data_as(dp), 1 if with_hessian else 0,
+                                                 out.ctypes.data_as(dp), C.byref(pairs)))
         return out, pairs.value
 
     def set_profiling(self, on: bool):
