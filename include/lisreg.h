@@ -1009,8 +1009,8 @@ int  lisreg_vgicp_linearize(lisreg_ctx* ctx, int slot, const void* source, int n
  * tests/fgicp_ref.py (fast_gicp's source is not available to this project); DESIGN.md §7l lists where it picks a reading of fast_gicp
  * it cannot verify.  NaN points are no points: never a neighbour, never a correspondent, in no pair.  The GPU makes the distributions,
  * every search (one query per lane over the target's search grid, fp64) and every sum (fixed order: two evaluations of the same input
- * give the same bits); the 6 x 6 solve and the LM loop run on the host in double.  There is no fitness score: a caller who wants one
- * has aligned_out and lisreg_nearest. */
+ * give the same bits); the 6 x 6 solve and the LM loop run on the host in double.  A single alignment has no fitness score (a caller
+ * who wants one has aligned_out and lisreg_nearest); the batch form below (§7m) computes one per item. */
 typedef struct lisreg_fgicp_params {
     double max_correspondence_distance; /* a nearest point this far away or further is no pair */
     double transformation_epsilon;      /* a step is converged when max|exp(delta).t| is below this ... */
@@ -1061,6 +1061,42 @@ int  lisreg_fgicp_correspondences(lisreg_ctx* ctx, int slot, const void* source,
 int  lisreg_fgicp_linearize(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
                             const lisreg_fgicp_params* params, const double T_pairs[16], const double* T_eval, int with_hessian,
                             double out[28], long long* n_pairs);
+
+/* ---- §7m: FastGICP verification of a candidate list as one call ---------------------------------------------------------------
+ * The candidate loop of detectLoopClosureForSubMap (src/node/subMapOptmizationNode.cpp:2779-2846) aligns one key-frame cloud against
+ * every candidate submap from that candidate's initial pose and keeps the candidate with the lowest getFitnessScore() among those
+ * that hasConverged().  lisreg_fgicp_align_batch runs that loop as one call: item k aligns sources[items[k].source] against the
+ * target of FastGICP slot items[k].slot from items[k].guess, and results[k] is what lisreg_fgicp_align returns for the same
+ * arguments alone, to the bit, in every field.  The distributions of a source are made once per call however many items name it; a
+ * source no item names is neither checked nor staged.  The Levenberg-Marquardt loops of all items advance in lockstep rounds: one
+ * round answers the outstanding evaluation of every unfinished item with one search launch (the items that linearise), two sum
+ * launches, one launch of fixed-order totals, one copy and one synchronisation; info->n_rounds is the largest n_evals of the items.
+ * fitness (may be NULL: no fitness pass, best = -1): fitness[k] = the mean, over the finite source points, of the squared distance to
+ * the nearest finite target point at results[k].final_transform — in double from the float coordinates as §7l's search defines it,
+ * without a cut-off (PCL's getFitnessScore() default), for every item, converged or not; two calls give the same bits.
+ * info->best: the items are walked in order, an item with converged == 0 or fitness > the best so far is skipped, any other one is
+ * taken (:2834-2840; equal scores go to the later item); -1 if none converged.  The DEFINITION is tests/fgicp_batch_ref.py.
+ * Refused (LISREG_ERR_ARG) for the whole batch, with `results` untouched: NULL items / results / sources / n with n_items > 0, a
+ * source index outside 0 .. n_sources - 1, a slot without a target, params lisreg_fgicp_align refuses, and a NAMED source it
+ * refuses (n <= 0, a NULL cloud, a short stride, an infinite coordinate, fewer finite points than k_correspondences; the last two
+ * are found while the distributions are made, before any alignment work).  n_items == 0 is LISREG_OK with best = -1.  All sources of
+ * a call share stride_bytes and fmt (host PCL structs or LISREG_FMT_DEVICE records).  Device memory the batch keeps (grow-only):
+ * 52 bytes per (item, finite source point) for the pairs and their matrices, 64 per finite source point.  No per-item aligned_out
+ * and no per-item params. */
+typedef struct lisreg_fgicp_item {
+    int          source;   /* index into sources[] */
+    int          slot;     /* lisreg_fgicp_set_target(slot) */
+    const float* guess;    /* row-major 4x4, NULL = identity */
+} lisreg_fgicp_item;
+typedef struct lisreg_fgicp_batch_info {
+    int best;              /* see above; -1 if no item converged */
+    int n_rounds;          /* host round trips of the LM phase */
+    int n_sources_staged;  /* distributions actually computed */
+    int reserved;
+} lisreg_fgicp_batch_info;
+int  lisreg_fgicp_align_batch(lisreg_ctx* ctx, const void* const* sources, const int* n, int n_sources, int stride_bytes, int fmt,
+                              const lisreg_fgicp_item* items, int n_items, const lisreg_fgicp_params* params,
+                              lisreg_fgicp_result* results, double* fitness, lisreg_fgicp_batch_info* info);
 
 /* ---- loop-closure candidate detection: FEPSC (src/core/epscGeneration.cpp) -------------------------------------------
  * EPSCGeneration::loopDetection (:663-992) with UsingFEPSCFlag (config/params.yaml:22-28), as loopClosureThread calls it for every

@@ -265,6 +265,10 @@ struct lisreg_ctx {
     // correspondence rows of the test hook by the caller's index
     std::map<int, lisreg::FgicpTarget> fgicp;
     lisreg::DevBuf fg_pair, fg_M, fg_d2, fg_rows_i, fg_rows_d;
+    // lisreg_fgicp_align_batch (lisreg_fgicp_batch.hip): the sources' finite points and covariances, the items' pairs and M, the work
+    // table of a round, its partial and total records; grow-only, like the rest
+    lisreg::DevBuf fgb_src, fgb_cov, fgb_pair, fgb_M, fgb_work, fgb_part, fgb_out;
+    lisreg::PinnedBuf fgb_host_work, fgb_host_out;
     lisreg::PinnedBuf done_host;            // one int
     lisreg::PinnedBuf stage_host;           // pinned staging of the per-batch tables
     lisreg::Event stage_done;

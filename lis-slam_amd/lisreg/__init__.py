@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "lisreg_vgicp_default_params", "lisreg_vgicp_set_target", "lisreg_vgicp_align", "lisreg_vgicp_covariances", "lisreg_vgicp_get_voxels",
     "lisreg_vgicp_linearize",
     "lisreg_fgicp_default_params", "lisreg_fgicp_set_target", "lisreg_fgicp_align", "lisreg_fgicp_correspondences", "lisreg_fgicp_linearize",
+    "lisreg_fgicp_align_batch",
 ]
 
 
@@ -125,6 +126,23 @@ class FgicpInfo(C.Structure):
 
 class FgicpResult(VgicpResult):
     """the fields of VgicpResult, in the same order"""
+
+
+class FgicpItemC(C.Structure):
+    """lisreg_fgicp_item"""
+    _fields_ = [("source", C.c_int), ("slot", C.c_int), ("guess", C.POINTER(C.c_float))]
+
+
+class FgicpBatchInfo(C.Structure):
+    _fields_ = [("best", C.c_int), ("n_rounds", C.c_int), ("n_sources_staged", C.c_int), ("reserved", C.c_int)]
+
+
+class FgicpItem:
+    """one alignment of a batch: sources[source] against the FastGICP target in `slot` from `guess` (4x4 or None = identity)"""
+
+    def __init__(self, source: int, slot: int, guess=None):
+        self.source, self.slot = int(source), int(slot)
+        self.guess = None if guess is None else np.ascontiguousarray(guess, np.float32).reshape(16).copy()
 
 
 class GuessInput(C.Structure):
@@ -498,6 +516,8 @@ def lib():
         L.lisreg_fgicp_set_target.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), C.POINTER(FgicpInfo), C.c_float]
         L.lisreg_fgicp_align.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), fp, C.POINTER(FgicpResult), vp]
         L.lisreg_fgicp_correspondences.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), dbl, ip, dbl]
+        L.lisreg_fgicp_align_batch.argtypes = [vp, C.POINTER(vp), ip, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpItemC), C.c_int,
+                                               C.POINTER(FgicpParams), C.POINTER(FgicpResult), dbl, C.POINTER(FgicpBatchInfo)]
         L.lisreg_fgicp_linearize.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), dbl, dbl, C.c_int, dbl,
                                              C.POINTER(C.c_longlong)]
         _lib = L
@@ -1668,6 +1688,28 @@ class Context:
                                                  None if Te is None else Te.ctypes.data_as(dp), 1 if with_hessian else 0,
                                                  out.ctypes.data_as(dp), C.byref(pairs)))
         return out, pairs.value
+
+    # -- §7m: FastGICP verification of a candidate list -----------------------------------------------------
+    def fgicp_align_batch(self, sources, items, params: "FgicpParams", want_fitness: bool = True):
+        """lisreg_fgicp_align_batch: sources = a list of clouds (all host PCL-struct arrays of one dtype, or all (device_ptr, n)),
+        items = a list of FgicpItem.  Returns (results: a list of fgicp_align's dicts, fitness [n_items] or None, info dict)."""
+        args = [self._cloud_args(s) for s in sources]
+        if len({(a[2], a[3]) for a in args}) > 1:
+            raise ValueError("fgicp_align_batch: the sources of one call share one layout")
+        stride, fmt = (args[0][2], args[0][3]) if args else (16, FMT_DEVICE)
+        ptrs = (C.c_void_p * max(len(args), 1))(*[a[0] for a in args])
+        ns = (C.c_int * max(len(args), 1))(*[a[1] for a in args])
+        its = (FgicpItemC * max(len(items), 1))()
+        for k, it in enumerate(items):
+            its[k].source, its[k].slot = it.source, it.slot
+            its[k].guess = None if it.guess is None else it.guess.ctypes.data_as(C.POINTER(C.c_float))
+        res = (FgicpResult * max(len(items), 1))()
+        fit = np.zeros(max(len(items), 1)) if want_fitness else None
+        info = FgicpBatchInfo()
+        self._chk(self._L.lisreg_fgicp_align_batch(self._h, ptrs, ns, len(args), stride, fmt, its, len(items), C.byref(params), res,
+                                                   fit.ctypes.data_as(C.POINTER(C.c_double)) if want_fitness else None, C.byref(info)))
+        return ([res[k].as_dict() for k in range(len(items))], fit[:len(items)] if want_fitness else None,
+                dict(best=info.best, n_rounds=info.n_rounds, n_sources_staged=info.n_sources_staged))
 
     def set_profiling(self, on: bool):
         self._chk(self._L.lisreg_set_profiling(self._h, 1 if on else 0))
