@@ -370,7 +370,9 @@ int  lisreg_get_trace(lisreg_ctx* ctx, float* buf, int max_iters);
  * out[0] = total ms in the correspondence+normal-equation kernel, out[1] = its launch count,
  * out[2] = total ms in the solve/update kernel, out[3] = its launch count, out[4] = index build ms.
  * After a lisreg_vgicp_* call: out[0] / out[1] = the linearisations and their number, out[2] = the voxel sort and statistics,
- * out[4] = the distributions (search grid, k-nearest search, covariances).  After a lisreg_fgicp_* call: out[0] / out[1] = the sum
+ * out[4] = the distributions (search grid, k-nearest search, covariances); after lisreg_vgicp_align_batch out[0] / out[1] = the
+ * rounds' linearisation and total launches (one interval per round) and their number, out[2] / out[3] = the fitness search, out[4] =
+ * the distributions of every staged source.  After a lisreg_fgicp_* call: out[0] / out[1] = the sum
  * launches and their number, out[2] / out[3] = the search launches and their number, out[4] = the distributions. */
 int  lisreg_set_profiling(lisreg_ctx* ctx, int enable);
 int  lisreg_get_timing(lisreg_ctx* ctx, double out[5]);
@@ -943,7 +945,8 @@ int  lisreg_ndt_derivatives(lisreg_ctx* ctx, int slot, const void* source, int n
  * it picks a reading of fast_gicp it cannot verify.  NaN points are no points: never a neighbour, in no voxel, in no pair.
  * The GPU makes the distributions (an exact k-nearest search, one query per lane), the voxel statistics and every linearisation
  * (fp64, fixed-order sums: two evaluations of the same input give the same bits); the 6 x 6 solve and the LM loop run on the host in
- * double.  There is no fitness score: a caller who wants one has aligned_out and lisreg_nearest. */
+ * double.  A single alignment has no fitness score (a caller who wants one has aligned_out and lisreg_nearest); the batch form below
+ * (§7n) computes one per item. */
 typedef struct lisreg_vgicp_params {
     double resolution;                  /* voxel edge */
     double transformation_epsilon;      /* a step is converged when max|exp(delta).t| is below this ... */
@@ -975,7 +978,9 @@ int  lisreg_vgicp_default_params(int kind, lisreg_vgicp_params* p);
 /* The distributions and voxel statistics of `cloud` into VGICP slot `slot` (0 .. 65535; VGICP slots are apart from the map-index
  * and the NDT slots).  Uses resolution, k_correspondences and plane_epsilon of `params`.  Refused (LISREG_ERR_ARG): n <= 0, fewer
  * finite points than k_correspondences, an infinite coordinate, resolution <= 0, k_correspondences outside 4 .. 32, a grid of more
- * than 2^26 cells (the voxel table is dense).  info may be NULL. */
+ * than 2^26 cells (the voxel table is dense).  info may be NULL.  Besides the voxels the slot keeps the search grid its distributions
+ * were made with, for the fitness score of lisreg_vgicp_align_batch: 16 bytes per finite point and 4 per grid cell (3.2 MB for a
+ * target of 200 000 points). */
 int  lisreg_vgicp_set_target(lisreg_ctx* ctx, int slot, const void* cloud, int n, int stride_bytes, int fmt,
                              const lisreg_vgicp_params* params, lisreg_vgicp_info* info);
 /* guess = row-major 4x4 or NULL for identity; aligned_out: NULL, or room for n points of the input layout (the source under
@@ -997,6 +1002,46 @@ int  lisreg_vgicp_get_voxels(lisreg_ctx* ctx, int slot, int* cell_ids, int* coun
 int  lisreg_vgicp_linearize(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
                             const lisreg_vgicp_params* params, const double T[16], int with_hessian, double out[28],
                             long long* n_pairs);
+
+/* ---- §7n: VGICP verification of a candidate list as one call -------------------------------------------------------------------
+ * The candidate loop of detectLoopClosureForSubMap (src/node/subMapOptmizationNode.cpp:2779-2846) with the verifier its authors
+ * wrote down last (select_registration_method("FAST_VGICP"), :2771): lisreg_vgicp_align_batch is lisreg_fgicp_align_batch (§7m, below)
+ * read for VGICP.  Item k aligns sources[items[k].source] against the target of VGICP slot items[k].slot from items[k].guess, and
+ * results[k] is what lisreg_vgicp_align returns for the same arguments alone, to the bit, in every field.  The distributions of a
+ * source are made once per call however many items name it; a source no item names is neither checked nor staged.  The
+ * Levenberg-Marquardt loops of all items advance in lockstep rounds: one round answers the outstanding evaluation of every unfinished
+ * item with two linearisation launches (the items that want the Hessian, the error evaluations), one launch of fixed-order totals,
+ * one copy and one synchronisation; info->n_rounds is the largest n_evals of the items.
+ * fitness (may be NULL: no fitness pass, best = -1): fitness[k] = the mean, over the finite source points, of the squared distance to
+ * the nearest finite target point at results[k].final_transform — x' = ((R0 a0 + R1 a1) + R2 a2) + t and ((dx dx + dy dy) + dz dz) in
+ * double from the float coordinates as §7l's search defines it, ties to the lower index, without a cut-off (PCL's getFitnessScore()
+ * default), for every item, converged or not; two calls give the same bits.  The search runs over the grid lisreg_vgicp_set_target
+ * keeps with the slot.
+ * info->best: the best score starts at DBL_MAX; the items are walked in order, an item with converged == 0 or fitness > the best so
+ * far is skipped, any other one is taken (:2834-2840; equal scores go to the later item); -1 if none converged.  The DEFINITION is
+ * tests/vgicp_batch_ref.py.
+ * Refused (LISREG_ERR_ARG) for the whole batch, with `results` and `fitness` untouched: NULL items / results / sources / n with
+ * n_items > 0, a source index outside 0 .. n_sources - 1, a slot without a target, params lisreg_vgicp_align refuses (among them a
+ * params->resolution that differs from ANY named slot's), a NAMED source it refuses (n <= 0, a NULL cloud, a short stride, an infinite
+ * coordinate, fewer finite points than k_correspondences; the last two are found while the distributions are made, before any
+ * alignment work), and a batch of more than INT_MAX / 29 wavefronts (items x source points / 64).  n_items == 0 is LISREG_OK with
+ * best = -1.  All sources of a call share stride_bytes and fmt (host PCL structs or LISREG_FMT_DEVICE records).  Device memory the
+ * batch keeps (grow-only): 64 bytes per finite source point, 232 per (item, 64 source points).  No per-item aligned_out and no
+ * per-item params. */
+typedef struct lisreg_vgicp_item {
+    int          source;   /* index into sources[] */
+    int          slot;     /* lisreg_vgicp_set_target(slot) */
+    const float* guess;    /* row-major 4x4, NULL = identity */
+} lisreg_vgicp_item;
+typedef struct lisreg_vgicp_batch_info {
+    int best;              /* -1 if no item converged (or fitness == NULL) */
+    int n_rounds;          /* host round trips of the LM phase = the largest n_evals of the items */
+    int n_sources_staged;  /* distributions actually computed */
+    int reserved;
+} lisreg_vgicp_batch_info;
+int  lisreg_vgicp_align_batch(lisreg_ctx* ctx, const void* const* sources, const int* n, int n_sources, int stride_bytes, int fmt,
+                              const lisreg_vgicp_item* items, int n_items, const lisreg_vgicp_params* params,
+                              lisreg_vgicp_result* results, double* fitness, lisreg_vgicp_batch_info* info);
 
 /* ---- §7l: FastGICP registration (loop-closure verification) --------------------------------------------------------------
  * select_registration_method("FAST_GICP") (src/core/registration.cpp:157-166: FastGICP, transformation epsilon 0.01, 50 iterations,

@@ -121,7 +121,8 @@ struct NdtTarget {
     DevBuf    table;               // [dims product] ints: cell -> voxel with a Gaussian, -1 none
 };
 
-// the voxel statistics of one VGICP target (lisreg_vgicp.hip: lisreg_vgicp_set_target)
+// the voxel statistics of one VGICP target (lisreg_vgicp.hip: lisreg_vgicp_set_target), and its own copy of the search grid the
+// distributions were made with (the fitness score of lisreg_vgicp_align_batch searches it)
 struct VgicpTarget {
     bool      valid = false;
     int       n_voxels = 0, n_points = 0;
@@ -130,6 +131,10 @@ struct VgicpTarget {
     DevBuf    stats;               // [n_voxels][10] doubles: mean, upper triangle of the mean covariance, points
     DevBuf    cell;                // [n_voxels] ints: cell id
     DevBuf    table;               // [dims product] ints: cell -> voxel, -1 none
+    GridIndex grid;                // the search grid (pts = sorted, cell_start = cells)
+    float     bb[6] = { 0, 0, 0, 0, 0, 0 };   // the finite bounding box
+    DevBuf    sorted;              // [n_points] float4 by grid cell, .w = index among the finite points
+    DevBuf    cells;               // [nx * ny * nz + 1] ints
 };
 
 // one FastGICP target (lisreg_fgicp.hip: lisreg_fgicp_set_target): its own copies of what the distributions leave in the context's scratch
@@ -269,6 +274,10 @@ struct lisreg_ctx {
     // table of a round, its partial and total records; grow-only, like the rest
     lisreg::DevBuf fgb_src, fgb_cov, fgb_pair, fgb_M, fgb_work, fgb_part, fgb_out;
     lisreg::PinnedBuf fgb_host_work, fgb_host_out;
+    // lisreg_vgicp_align_batch (lisreg_vgicp_batch.hip): the sources' finite points and covariances, the work table of a round, its
+    // partial and total records; grow-only, like the rest
+    lisreg::DevBuf vgb_src, vgb_cov, vgb_work, vgb_part, vgb_out;
+    lisreg::PinnedBuf vgb_host_work, vgb_host_out;
     lisreg::PinnedBuf done_host;            // one int
     lisreg::PinnedBuf stage_host;           // pinned staging of the per-batch tables
     lisreg::Event stage_done;

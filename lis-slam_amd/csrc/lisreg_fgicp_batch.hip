@@ -6,7 +6,7 @@
 // added in k_vgicp_total's order, and the Levenberg-Marquardt loop is lm_optimise turned inside out (lisreg_lm_stepper.hpp).  What the
 // batch saves: a source's distributions are made once per call, and the outstanding evaluations of ALL unfinished items are answered by
 // one round of launches and one synchronisation.  No LDS, no atomics, no CPU fallback.
-#include "lisreg_fgicp_lane.hpp"
+#include "lisreg_batch_rounds.hpp"
 #include "lisreg_lm_stepper.hpp"
 
 #include <cfloat>
@@ -31,16 +31,6 @@ struct FgWork {
     int       n;           // finite points of the source
     int       reserved;
 };
-
-// the entry of workgroup g: the last e in [lo, hi) with wg_start[e] <= g.  g comes from blockIdx alone: the walk is scalar
-__device__ __forceinline__ int fg_entry_of(const int* __restrict__ wg_start, int lo, int hi, int g)
-{
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (wg_start[mid] <= g) lo = mid; else hi = mid;
-    }
-    return __builtin_amdgcn_readfirstlane(lo);
-}
 
 // The search of every linearising entry (entries [0, n_lin) of the round): lanes 64 b .. 64 b + 63 of the entry's source, as k_fgicp_pairs
 __global__ __launch_bounds__(64) void k_fgicp_pairs_batch(const FgWork* __restrict__ work, const int* __restrict__ wg_start, int n_lin,
@@ -107,26 +97,6 @@ __global__ __launch_bounds__(64) void k_fgicp_fitness_batch(const FgWork* __rest
     }
     d2 = fg_wave_sum(d2);
     if (threadIdx.x == 0) part[g] = d2;
-}
-
-// One wavefront per entry: its partial records of W doubles added in k_vgicp_total's order (lane l takes records l, l + 64, ... one
-// after the other, then the butterfly from 32 down to 1)
-template <int W>
-__global__ __launch_bounds__(64) void k_fgicp_total_batch(const double* __restrict__ part, const int* __restrict__ wg_start, double* __restrict__ out)
-{
-    const int e = blockIdx.x;
-    const int p0 = wg_start[e], n_part = wg_start[e + 1] - p0;
-    double acc[W];
-#pragma unroll
-    for (int k = 0; k < W; ++k) acc[k] = 0.0;
-    for (int b = (int)threadIdx.x; b < n_part; b += 64)
-#pragma unroll
-        for (int k = 0; k < W; ++k) acc[k] += part[(size_t)(p0 + b) * W + k];
-#pragma unroll
-    for (int k = 0; k < W; ++k) acc[k] = fg_wave_sum(acc[k]);
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < W; ++k) out[(size_t)e * W + k] = acc[k];
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------

@@ -5,8 +5,7 @@
 // per-voxel statistics (the NDT build's sort, one lane or one wavefront per voxel) and one linearisation per call (one lane per source
 // point, fp64, sums in a fixed order: the same input gives the same bits).  Host: the 6 x 6 solve and the Levenberg-Marquardt loop in
 // double, one 29-double read-back per evaluation.  No CPU fallback.
-#include "lisreg_ctx.hpp"
-#include "lisreg_vgicp_host.hpp"
+#include "lisreg_vgicp_lane.hpp"
 #include "lisreg_jacobi3.hpp"
 
 #include <algorithm>
@@ -20,17 +19,9 @@ using namespace lisreg::vgicp_host;
 namespace {
 
 constexpr int kVgBig = 48;             // voxels with more points get a wavefront each, the others a lane (the NDT build's split)
-constexpr int kVgRec = 10;             // doubles per voxel: mean [3], upper triangle of the mean covariance [6], points
 constexpr long long kVgMaxCells = 1LL << 26;        // the voxel table is dense
 constexpr long long kVgKnnMaxCells = 1LL << 22;     // so is the search grid of a cloud
 constexpr int kVgKnnMaxDim = 2048;                  // cells per axis of the search grid (the walk's rounding slack is sized for this)
-
-__device__ __forceinline__ double vg_wave_sum(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 // ---- NaN points are no points: the finite records, in input order ---------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_vg_flag(const float4* __restrict__ in, int n, int* __restrict__ flag)
@@ -251,83 +242,14 @@ __global__ __launch_bounds__(64) void k_vg_stats_big(VgBuild B)
 }
 
 // ---- one linearisation ------------------------------------------------------------------------------------------------------------
-struct VgGrid {
-    const double* stats;
-    const int*    table;
-    int    d0, d1, d2, m0, m1, m2;
-    double inv_res;
-};
-struct VgPose { double R[9], t[3]; };
-
-// one lane per source point, one wavefront per workgroup, one partial record per workgroup
+// one lane per source point (vg_linearize_lane of lisreg_vgicp_lane.hpp), one wavefront per workgroup, one partial record per workgroup
 template <bool HESS>
 __global__ __launch_bounds__(64) void k_vgicp_linearize(const float4* __restrict__ src, const double* __restrict__ cov, int n, VgGrid G,
                                                         VgPose P, double* __restrict__ part)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
-    double acc[28];
-#pragma unroll
-    for (int k = 0; k < 28; ++k) acc[k] = 0.0;
-    double pairs = 0.0;
-    if (i < n) {
-        const float4 s = src[i];
-        const double a0 = (double)s.x, a1 = (double)s.y, a2 = (double)s.z;
-        const double x0 = ((P.R[0] * a0 + P.R[1] * a1) + P.R[2] * a2) + P.t[0];
-        const double x1 = ((P.R[3] * a0 + P.R[4] * a1) + P.R[5] * a2) + P.t[1];
-        const double x2 = ((P.R[6] * a0 + P.R[7] * a1) + P.R[8] * a2) + P.t[2];
-        // the cell in the floating-point domain first: a point far off the map, a huge or a NaN coordinate fails a comparison here and
-        // never becomes an integer
-        const double f0 = floor(x0 * G.inv_res) - (double)G.m0, f1 = floor(x1 * G.inv_res) - (double)G.m1, f2 = floor(x2 * G.inv_res) - (double)G.m2;
-        int v = -1;
-        if (f0 >= 0.0 && f0 < (double)G.d0 && f1 >= 0.0 && f1 < (double)G.d1 && f2 >= 0.0 && f2 < (double)G.d2)
-            v = G.table[(long long)f0 + (long long)f1 * G.d0 + (long long)f2 * (long long)G.d0 * G.d1];
-        if (v >= 0) {
-            const double* __restrict__ rec = G.stats + (size_t)v * kVgRec;
-            const double* __restrict__ ca = cov + (size_t)i * 6;
-            const double d[3] = { rec[0] - x0, rec[1] - x1, rec[2] - x2 };
-            const double C[3][3] = { { ca[0], ca[1], ca[2] }, { ca[1], ca[3], ca[4] }, { ca[2], ca[4], ca[5] } };
-            double RC[3][3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) RC[r][c] = (P.R[3 * r] * C[0][c] + P.R[3 * r + 1] * C[1][c]) + P.R[3 * r + 2] * C[2][c];
-            auto rcr = [&](int r, int c) { return (RC[r][0] * P.R[3 * c] + RC[r][1] * P.R[3 * c + 1]) + RC[r][2] * P.R[3 * c + 2]; };
-            const double s00 = rec[3] + rcr(0, 0), s01 = rec[4] + rcr(0, 1), s02 = rec[5] + rcr(0, 2);
-            const double s11 = rec[6] + rcr(1, 1), s12 = rec[7] + rcr(1, 2), s22 = rec[8] + rcr(2, 2);
-            // M = S^-1, closed form (S is symmetric positive definite with eigenvalues between 2 plane_epsilon and 2)
-            const double c00 = s11 * s22 - s12 * s12, c01 = s02 * s12 - s01 * s22, c02 = s01 * s12 - s02 * s11;
-            const double det = (s00 * c00 + s01 * c01) + s02 * c02;
-            const double id = 1.0 / det;
-            const double M[3][3] = { { c00 * id, c01 * id, c02 * id },
-                                     { c01 * id, (s00 * s22 - s02 * s02) * id, (s01 * s02 - s00 * s12) * id },
-                                     { c02 * id, (s01 * s02 - s00 * s12) * id, (s00 * s11 - s01 * s01) * id } };
-            const double w = sqrt(rec[9]);
-            double Md[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) Md[r] = (M[r][0] * d[0] + M[r][1] * d[1]) + M[r][2] * d[2];
-            // J = [skew(x) | -I], column by column
-            const double J[6][3] = { { 0.0, x2, -x1 }, { -x2, 0.0, x0 }, { x1, -x0, 0.0 }, { -1.0, 0.0, 0.0 }, { 0.0, -1.0, 0.0 }, { 0.0, 0.0, -1.0 } };
-            pairs = 1.0;
-            acc[0] = w * ((d[0] * Md[0] + d[1] * Md[1]) + d[2] * Md[2]);
-#pragma unroll
-            for (int a = 0; a < 6; ++a) acc[1 + a] = w * ((J[a][0] * Md[0] + J[a][1] * Md[1]) + J[a][2] * Md[2]);
-            if (HESS) {
-                double MJ[6][3];
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) MJ[a][r] = (M[r][0] * J[a][0] + M[r][1] * J[a][1]) + M[r][2] * J[a][2];
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int b = a; b < 6; ++b)
-                        acc[7 + a * 6 - a * (a - 1) / 2 + (b - a)] = w * ((J[a][0] * MJ[b][0] + J[a][1] * MJ[b][1]) + J[a][2] * MJ[b][2]);
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 28; ++k) acc[k] = vg_wave_sum(acc[k]);
-    pairs = vg_wave_sum(pairs);
+    double acc[28], pairs;
+    vg_linearize_lane<HESS>(i < n, src + i, cov + (size_t)i * 6, G, P, acc, pairs);
     if (threadIdx.x == 0) {
         double* o = part + (size_t)blockIdx.x * kOut;
 #pragma unroll
@@ -375,6 +297,23 @@ int find_target(lisreg_ctx* c, int slot, const lisreg_vgicp_params* P, const cha
 }
 
 }  // namespace
+
+// the one copy of the checks, for lisreg_vgicp_batch.hip
+int lisreg::vg_check_params(lisreg_ctx* c, const lisreg_vgicp_params* P, const char* who) { return check_params(c, P, who); }
+int lisreg::vg_find_target(lisreg_ctx* c, int slot, const lisreg_vgicp_params* P, const char* who, VgicpTarget** out)
+{
+    return find_target(c, slot, P, who, out);
+}
+
+VgGrid lisreg::vg_grid_view(const VgicpTarget& T)
+{
+    VgGrid G;
+    G.stats = T.stats.as<double>(); G.table = T.table.as<int>();
+    G.d0 = T.dims[0]; G.d1 = T.dims[1]; G.d2 = T.dims[2];
+    G.m0 = T.min_b[0]; G.m1 = T.min_b[1]; G.m2 = T.min_b[2];
+    G.inv_res = 1.0 / T.resolution;
+    return G;
+}
 
 // The distributions of one cloud of n device records: afterwards c->vg_pts holds its *m_out finite points in input order, c->vg_idx
 // their indices in the cloud, c->vg_flag / c->vg_pos the finite flags and their exclusive scan, c->vg_cov the m x 6 covariances and, if
@@ -474,11 +413,7 @@ int evaluate(VgRun& r, const double T[16], bool hess, double out[kOut])
     hipStream_t st = c->stream;
     VgPose P;
     for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) P.R[3 * i + j] = T[4 * i + j]; P.t[i] = T[4 * i + 3]; }
-    VgGrid G;
-    G.stats = r.T->stats.as<double>(); G.table = r.T->table.as<int>();
-    G.d0 = r.T->dims[0]; G.d1 = r.T->dims[1]; G.d2 = r.T->dims[2];
-    G.m0 = r.T->min_b[0]; G.m1 = r.T->min_b[1]; G.m2 = r.T->min_b[2];
-    G.inv_res = 1.0 / r.T->resolution;
+    const VgGrid G = vg_grid_view(*r.T);
     const int nb = (r.n + 63) / 64;
     HIPCHK(c, c->vg_part.ensure(sizeof(double) * kOut * (size_t)nb));
     HIPCHK(c, c->vg_out.ensure(sizeof(double) * kOut));
@@ -547,8 +482,18 @@ int lisreg_vgicp_set_target(lisreg_ctx* c, int slot, const void* cloud, int n, i
     if (rc) return rc;
     float bb[6];
     int m = 0;
-    rc = distributions(c, "vgicp_set_target", raw, n, P->k_correspondences, P->plane_epsilon, 0.f, bb, &m, nullptr);
+    GridIndex g;
+    rc = vg_distributions(c, "vgicp_set_target", raw, n, P->k_correspondences, P->plane_epsilon, 0.f, bb, &m, nullptr, &g);
     if (rc) return rc;
+    // the search grid of the distributions stays with the slot (the batch's fitness score searches it): its own copies, made before the
+    // voxel sort reuses any scratch
+    const size_t n_grid_cells = (size_t)g.nx * (size_t)g.ny * (size_t)g.nz;
+    HIPCHK(c, T.sorted.ensure(sizeof(float4) * (size_t)m));
+    HIPCHK(c, T.cells.ensure(sizeof(int) * (n_grid_cells + 1)));
+    HIPCHK(c, hipMemcpyAsync(T.sorted.p, c->vg_sorted.p, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(T.cells.p, c->vg_cells.p, sizeof(int) * (n_grid_cells + 1), hipMemcpyDeviceToDevice, st));
+    T.grid = g; T.grid.pts = T.sorted.as<float4>(); T.grid.cell_start = T.cells.as<int>();
+    for (int k = 0; k < 6; ++k) T.bb[k] = bb[k];
     // ---- the voxel geometry (pcl::VoxelGrid's, as the NDT target's) ------------------------------------------------------------------
     const float inv = 1.0f / (float)P->resolution;
     VoxelDesc d;

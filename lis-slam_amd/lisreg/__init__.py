@@ -50,7 +50,7 @@ ABI_SYMBOLS = [
     "lisreg_default_rangenet_knn_params", "lisreg_rangenet_knn_weights", "lisreg_rangenet_label_knn", "lisreg_rangenet_label_knn_batch",
     "lisreg_ndt_default_params", "lisreg_ndt_set_target", "lisreg_ndt_align", "lisreg_ndt_get_voxels", "lisreg_ndt_derivatives",
     "lisreg_vgicp_default_params", "lisreg_vgicp_set_target", "lisreg_vgicp_align", "lisreg_vgicp_covariances", "lisreg_vgicp_get_voxels",
-    "lisreg_vgicp_linearize",
+    "lisreg_vgicp_linearize", "lisreg_vgicp_align_batch",
     "lisreg_fgicp_default_params", "lisreg_fgicp_set_target", "lisreg_fgicp_align", "lisreg_fgicp_correspondences", "lisreg_fgicp_linearize",
     "lisreg_fgicp_align_batch",
 ]
@@ -143,6 +143,18 @@ class FgicpItem:
     def __init__(self, source: int, slot: int, guess=None):
         self.source, self.slot = int(source), int(slot)
         self.guess = None if guess is None else np.ascontiguousarray(guess, np.float32).reshape(16).copy()
+
+
+class VgicpItemC(FgicpItemC):
+    """lisreg_vgicp_item: the fields of lisreg_fgicp_item, in the same order"""
+
+
+class VgicpBatchInfo(FgicpBatchInfo):
+    """lisreg_vgicp_batch_info: the fields of lisreg_fgicp_batch_info, in the same order"""
+
+
+class VgicpItem(FgicpItem):
+    """one alignment of a batch: sources[source] against the VGICP target in `slot` from `guess` (4x4 or None = identity)"""
 
 
 class GuessInput(C.Structure):
@@ -512,6 +524,8 @@ def lib():
         L.lisreg_vgicp_get_voxels.argtypes = [vp, C.c_int, ip, ip, dbl, dbl, C.c_int, ip]
         L.lisreg_vgicp_linearize.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VgicpParams), dbl, C.c_int, dbl,
                                              C.POINTER(C.c_longlong)]
+        L.lisreg_vgicp_align_batch.argtypes = [vp, C.POINTER(vp), ip, C.c_int, C.c_int, C.c_int, C.POINTER(VgicpItemC), C.c_int,
+                                               C.POINTER(VgicpParams), C.POINTER(VgicpResult), dbl, C.POINTER(VgicpBatchInfo)]
         L.lisreg_fgicp_default_params.argtypes = [C.c_int, C.POINTER(FgicpParams)]
         L.lisreg_fgicp_set_target.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), C.POINTER(FgicpInfo), C.c_float]
         L.lisreg_fgicp_align.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), fp, C.POINTER(FgicpResult), vp]
@@ -1707,6 +1721,28 @@ class Context:
         fit = np.zeros(max(len(items), 1)) if want_fitness else None
         info = FgicpBatchInfo()
         self._chk(self._L.lisreg_fgicp_align_batch(self._h, ptrs, ns, len(args), stride, fmt, its, len(items), C.byref(params), res,
+                                                   fit.ctypes.data_as(C.POINTER(C.c_double)) if want_fitness else None, C.byref(info)))
+        return ([res[k].as_dict() for k in range(len(items))], fit[:len(items)] if want_fitness else None,
+                dict(best=info.best, n_rounds=info.n_rounds, n_sources_staged=info.n_sources_staged))
+
+    # -- §7n: VGICP verification of a candidate list ---------------------------------------------------------
+    def vgicp_align_batch(self, sources, items, params: "VgicpParams", want_fitness: bool = True):
+        """lisreg_vgicp_align_batch: sources = a list of clouds (all host PCL-struct arrays of one dtype, or all (device_ptr, n)),
+        items = a list of VgicpItem.  Returns (results: a list of vgicp_align's dicts, fitness [n_items] or None, info dict)."""
+        args = [self._cloud_args(s) for s in sources]
+        if len({(a[2], a[3]) for a in args}) > 1:
+            raise ValueError("vgicp_align_batch: the sources of one call share one layout")
+        stride, fmt = (args[0][2], args[0][3]) if args else (16, FMT_DEVICE)
+        ptrs = (C.c_void_p * max(len(args), 1))(*[a[0] for a in args])
+        ns = (C.c_int * max(len(args), 1))(*[a[1] for a in args])
+        its = (VgicpItemC * max(len(items), 1))()
+        for k, it in enumerate(items):
+            its[k].source, its[k].slot = it.source, it.slot
+            its[k].guess = None if it.guess is None else it.guess.ctypes.data_as(C.POINTER(C.c_float))
+        res = (VgicpResult * max(len(items), 1))()
+        fit = np.zeros(max(len(items), 1)) if want_fitness else None
+        info = VgicpBatchInfo()
+        self._chk(self._L.lisreg_vgicp_align_batch(self._h, ptrs, ns, len(args), stride, fmt, its, len(items), C.byref(params), res,
                                                    fit.ctypes.data_as(C.POINTER(C.c_double)) if want_fitness else None, C.byref(info)))
         return ([res[k].as_dict() for k in range(len(items))], fit[:len(items)] if want_fitness else None,
                 dict(best=info.best, n_rounds=info.n_rounds, n_sources_staged=info.n_sources_staged))
