@@ -337,6 +337,24 @@ int  lisreg_test_solve_steps(lisreg_ctx* ctx, int n_items, int n_steps, const in
                              const lisreg_imu* imu, const lisreg_params* params,
                              float* trace_out, float* state_out, float* results_out);
 
+/* Diagnostics (tests): the grid of the map index of `slot` (lisreg_map_index_set): dims = {n, nx, ny, nz, n_cells}, geom = {ox, oy, oz,
+ * cell edge} — an empty map has nx = ny = nz = 0 and one cell.  Either output may be NULL. */
+int  lisreg_get_map_grid(lisreg_ctx* ctx, int slot, int* dims, float* geom);
+
+/* Test hook: ONE chosen form of the exact k = 1 search (lisreg_nn1.hip) per query, on the map index of `slot` (lisreg_map_index_set):
+ * form 1, 4, 8 = the column walk nn1_search<Q> with that many lanes per query (what lisreg_nearest, the dynamic filter, ICP-GN and small
+ * ICP batches run), form 0 = the flattened one-lane walk nn1_search_flat of large ICP batches — the device functions production calls.
+ * All forms must return the same point: the lexicographic minimum of (squared distance, original index) within max_dist.
+ *   queries[n][3]   host, x y z
+ *   seeds[n]        host, or NULL for none: the "probably near" point the ICP kernels hand the search, which must never change the result.
+ *                   >= 0: an ORIGINAL index into the map cloud (translated here to the position in the cell-sorted array the search takes);
+ *                   -1: no seed; -2: nn1_cell_seed(query), the seed of ICP's first iteration; a value >= the map's size is passed on as
+ *                   it is (the search must ignore it)
+ *   idx_out[n]      host: ORIGINAL index of the nearest map point, -1 none;  sqd_out[n]: the search's squared distance (as lisreg_nearest)
+ * Runs on the context's stream in buffers of the call's own and returns with the outputs complete.  n = 0: OK, nothing touched. */
+int  lisreg_test_nn1(lisreg_ctx* ctx, int slot, const float* queries, int n, float max_dist, int form, const int* seeds,
+                     int* idx_out, float* sqd_out);
+
 /* Diagnostics (tests): the search index of target `slot`, kind 0 = corner / 1 = surf, as it stands in HBM after the work queued on
  * the context's stream: dims = {n, nx, ny, nz, n_cells}, geom = {ox, oy, oz, cell edge}, the cell-sorted records
  * (x, y, z, bit-cast original index; ordered by cell (ix * ny + iy) * nz + iz, then original index) and cell_start[n_cells + 1].
@@ -613,8 +631,11 @@ int  lisreg_map_index_set_batch(lisreg_ctx* ctx, int n_maps, const int* slots, c
                                 int stride_bytes, int fmt);
 /* nearestKSearch(query, k = 1) for a whole cloud: idx_out[i] = index into the map cloud of the nearest point, or -1 when it
  * is farther than max_dist (pass a huge value for the reference's unbounded search); sqd_out[i] = squared distance in float,
- * accumulated x, y, z like FLANN's L2_Simple.  Equidistant candidates resolve to the smallest index.  idx_out / sqd_out are
- * host arrays, or device arrays when fmt is LISREG_FMT_DEVICE. */
+ * accumulated x, y, z like FLANN's L2_Simple.  Equidistant candidates resolve to the smallest index.  A point at exactly max_dist
+ * is found (d2 <= max_dist * max_dist, the product formed in float after max_dist is clipped to 1.8e19).  Where idx_out[i] is -1 — nothing
+ * within max_dist, a NaN query, an empty map — sqd_out[i] is the first float above that product (the bound the search started from; a
+ * denormal for max_dist = 0), never a distance.  NaN map points are never returned.  idx_out / sqd_out are host arrays, or device
+ * arrays when fmt is LISREG_FMT_DEVICE. */
 int  lisreg_nearest(lisreg_ctx* ctx, int slot, const void* query, int n, int stride_bytes, int fmt, float max_dist,
                     int* idx_out, float* sqd_out);
 /* SubMapManager::map_scan_feature_pts_distance_removal (subMap.h:1064-1100): drop the points of `cloud` within

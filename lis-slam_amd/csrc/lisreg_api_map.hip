@@ -269,6 +269,73 @@ int lisreg_nearest(lisreg_ctx* c, int slot, const void* query, int n, int stride
     return LISREG_OK;
 }
 
+// Diagnostics: the grid make_grid laid out for the map index of `slot`
+int lisreg_get_map_grid(lisreg_ctx* c, int slot, int* dims, float* geom)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (slot < 0 || c->maps.count(slot) == 0 || !c->maps[slot].valid)
+        return ctx_fail(c, LISREG_ERR_NO_TARGET, "get_map_grid: no map index in this slot");
+    const MapIndex& m = c->maps[slot];
+    if (dims) { dims[0] = m.n; dims[1] = m.g.nx; dims[2] = m.g.ny; dims[3] = m.g.nz; dims[4] = m.n_cells; }
+    if (geom) { geom[0] = m.g.ox; geom[1] = m.g.oy; geom[2] = m.g.oz; geom[3] = m.g.cell; }
+    return LISREG_OK;
+}
+
+// Test hook: one chosen form of the k = 1 search per query, with a caller-given seed (lisreg_nn1.hip: k_test_nn1), in buffers of the
+// call's own.  Seeds name ORIGINAL indices; the search takes positions in the cell-sorted array, so the sorted records are read back and
+// the permutation inverted on the host (every point of the cloud has a record; its .w is its original index).
+int lisreg_test_nn1(lisreg_ctx* c, int slot, const float* queries, int n, float max_dist, int form, const int* seeds, int* idx_out,
+                    float* sqd_out)
+{
+    if (!c) return LISREG_ERR_ARG;
+    if (slot < 0 || c->maps.count(slot) == 0 || !c->maps[slot].valid)
+        return ctx_fail(c, LISREG_ERR_NO_TARGET, "test_nn1: no map index in this slot");
+    if (form != 0 && form != 1 && form != 4 && form != 8) return bad(c, "test_nn1: form must be 0 (flattened walk), 1, 4 or 8 (lanes of the column walk)");
+    if (!(max_dist >= 0.f)) return bad(c, "test_nn1: max_dist must be >= 0");
+    if (n < 0 || (n > 0 && (!queries || !idx_out || !sqd_out))) return bad(c, "test_nn1: NULL queries / output");
+    if (n == 0) return LISREG_OK;
+    const MapIndex& m = c->maps[slot];
+    if (m.n >= (1 << 28)) return bad(c, "test_nn1: a map of 2^28 points or more (the flattened walk addresses its records by 32-bit byte offsets)");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    std::vector<float4> hq((size_t)n);
+    for (int i = 0; i < n; ++i) hq[(size_t)i] = make_float4(queries[3 * (size_t)i], queries[3 * (size_t)i + 1], queries[3 * (size_t)i + 2], 0.f);
+    std::vector<int> hs;
+    if (seeds) {
+        hs.assign(seeds, seeds + n);
+        bool any = false;
+        for (int i = 0; i < n; ++i) any = any || (hs[(size_t)i] >= 0 && hs[(size_t)i] < m.n);
+        if (any) {
+            std::vector<float4> rec((size_t)m.n);
+            HIPCHK(c, hipMemcpyAsync(rec.data(), m.sorted.p, sizeof(float4) * (size_t)m.n, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            std::vector<int> pos((size_t)m.n, -1);
+            for (int j = 0; j < m.n; ++j) {
+                int w; memcpy(&w, &rec[(size_t)j].w, sizeof w);
+                if (w >= 0 && w < m.n) pos[(size_t)w] = j;
+            }
+            for (int i = 0; i < n; ++i)
+                if (hs[(size_t)i] >= 0 && hs[(size_t)i] < m.n) hs[(size_t)i] = pos[(size_t)hs[(size_t)i]];
+        }
+    }
+    DevBuf dq, ds, di, dd;
+    HIPCHK(c, dq.ensure(sizeof(float4) * (size_t)n));
+    HIPCHK(c, di.ensure(sizeof(int) * (size_t)n));
+    HIPCHK(c, dd.ensure(sizeof(float) * (size_t)n));
+    HIPCHK(c, hipMemcpyAsync(dq.p, hq.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, st));
+    if (seeds) {
+        HIPCHK(c, ds.ensure(sizeof(int) * (size_t)n));
+        HIPCHK(c, hipMemcpyAsync(ds.p, hs.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+    }
+    max_dist = std::min(max_dist, 1.8e19f);        // squared below, as lisreg_nearest
+    launch_test_nn1(dq.as<float4>(), n, m.g_dev.as<GridIndex>(), max_dist, form, seeds ? ds.as<int>() : nullptr, di.as<int>(), dd.as<float>(), st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(idx_out, di.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(sqd_out, dd.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));           // (hq / hs are locals; the buffers are freed on return)
+    return LISREG_OK;
+}
+
 int lisreg_dynamic_filter(lisreg_ctx* c, int slot, const void* cloud, int n, int stride, int fmt, float center_radius,
                           float dist_thre_min, float dist_thre_max, float near_dist_thre, void* out, int* n_out)
 {

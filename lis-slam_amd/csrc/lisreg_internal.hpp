@@ -325,6 +325,9 @@ void launch_gather_points(const float4* pts, const int* idx, int n, float4* out,
 void launch_nn1(const float4* q, int n, const GridIndex* grid_dev, float max_dist, int* idx_out, float* d2_out, hipStream_t st);
 void launch_dynamic_flags(const float4* pts, int n, const GridIndex* grid_dev, float center_radius, float near_thre, float dmin,
                           float dmax, int* flag, hipStream_t st);
+// test hook (lisreg_test_nn1): one chosen form of the search per query; seeds (device, or null) are positions in the sorted array
+void launch_test_nn1(const float4* q, int n, const GridIndex* grid_dev, float max_dist, int form, const int* seeds, int* idx_out,
+                     float* d2_out, hipStream_t st);
 // §8 f-4: device-side state of one pcl::IterativeClosestPoint::align
 struct IcpState {
     float  F[16];            // final_transformation_ (row-major 4x4)

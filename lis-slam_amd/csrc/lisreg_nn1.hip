@@ -40,7 +40,9 @@ __device__ __forceinline__ int nn1_search(float qx, float qy, float qz, const Gr
     const gptr_f4 pts = (gptr_f4)g.pts;
     const gptr_i32 cells = (gptr_i32)g.cell_start;
     float best = __uint_as_float(__float_as_uint(max_d2) + 1u);      // strictly-less test below must admit d2 == max_d2
-    int bi = -1, bw = 0x7fffffff;                                    // bw = original index of the best (ties: smallest wins)
+    // bw = original index of the best (ties: smallest wins).  While nothing is held it is INT_MIN, which no index is below: a candidate
+    // at EXACTLY the bound above (one ulp past the cap) must not enter through the tie rule — as in nn1_search_flat
+    int bi = -1, bw = (int)0x80000000;
     if (g.n <= 0) { *d2_out = best; return -1; }
     const int sub = Q > 1 ? (int)(threadIdx.x & (Q - 1)) : 0;
     if (seed >= 0 && seed < g.n) {
@@ -68,7 +70,11 @@ __device__ __forceinline__ int nn1_search(float qx, float qy, float qz, const Gr
                 const float xl = g.ox + (float)ix * g.cell, yl = g.oy + (float)iy * g.cell;
                 const float dx = fmaxf(fmaxf(xl - qx, qx - (xl + g.cell)) - kEps, 0.f);
                 const float dy = fmaxf(fmaxf(yl - qy, qy - (yl + g.cell)) - kEps, 0.f);
-                if (dx * dx + dy * dy < fminf(best, lim)) {
+                // (<=, not <: a column AT the best distance can still hold a tie with a smaller index.  `<=` visits a superset of the columns
+                // `<` does — in practice the same ones for best > 0, where the millimetre of slack already lets every column that holds a tied
+                // point through; at best == 0 — a seed that coincides with the query — `<` would skip the query's own column and with it
+                // the seed's duplicates)
+                if (dx * dx + dy * dy <= fminf(best, lim)) {
                     const int base = (ix * g.ny + iy) * g.nz;
                     const int js = cells[base + cz0], je = cells[base + cz1 + 1];
                     for (int j = js; j < je; j += 4) {
@@ -142,7 +148,10 @@ __device__ __forceinline__ int nn1_search_flat(float qx, float qy, float qz, con
         const int cy0 = max(gcoord(qy - rad, g.oy, g.inv_cell), 0), cy1 = min(gcoord(qy + rad, g.oy, g.inv_cell), g.ny - 1);
         const int cz0 = max(gcoord(qz - rad, g.oz, g.inv_cell), 0), cz1 = min(gcoord(qz + rad, g.oz, g.inv_cell), g.nz - 1);
         int ix = cx0, iy = cy0;
-        if (cz0 > cz1 || cx0 > cx1 || cy0 > cy1) ix = cx1 + 1;          // an empty box (a non-finite query has one): nothing to step through
+        // an empty box (a query outside the grid by more than the radius): nothing to step through.  A NaN coordinate does NOT give one:
+        // gcoord converts NaN to cell 0, so the box is the slab 0..0 on that axis (a single cell for an all-NaN query) and is walked; its
+        // candidates' distances are NaN, which neither `m <= best` nor the full rule ever inserts — such a query returns -1
+        if (cz0 > cz1 || cx0 > cx1 || cy0 > cy1) ix = cx1 + 1;
         while (ix <= cx1) {
             int cnt = 0, grp = 0;
             // phase 1: up to kNn1Cap non-empty runs (grp: their groups of four candidates)
@@ -277,6 +286,31 @@ __global__ __launch_bounds__(256) void k_nn1(const float4* __restrict__ q, int n
     const GridIndex g = *gp;
     float d2;
     const int bi = nn1_search<Q>(q[i].x, q[i].y, q[i].z, g, max_d2, &d2);
+    if ((threadIdx.x & (Q - 1)) != 0) return;
+    idx_out[i] = bi < 0 ? -1 : __float_as_int(g.pts[bi].w);      // ORIGINAL index in the caller's map cloud
+    d2_out[i] = d2;
+}
+
+// Test hook (lisreg_test_nn1): ONE chosen form of the search per query — F = 1, 4, 8: nn1_search<F>; F = 0: nn1_search_flat — with the
+// seed the caller names: a position in the sorted array (the host has translated it), -1 none, -2 nn1_cell_seed(query) as the first ICP
+// iteration takes it; anything else goes to the search as it is.  The functions production calls, not copies of them.
+template <int F>
+__global__ __launch_bounds__(256) void k_test_nn1(const float4* __restrict__ q, int n, const GridIndex* __restrict__ gp, float max_d2,
+                                                  const int* __restrict__ seeds, int* __restrict__ idx_out, float* __restrict__ d2_out)
+{
+    constexpr int Q = F == 0 ? 1 : F;
+    const int i = (blockIdx.x * 256 + threadIdx.x) / Q;
+    if (i >= n) return;
+    const GridIndex g = *gp;
+    const float4 p = q[i];
+    int seed = seeds ? seeds[i] : -1;
+    if (seed == -2) seed = nn1_cell_seed(p.x, p.y, p.z, g);
+    float d2;
+    int bi;
+    if constexpr (F == 0) {
+        __shared__ int2 s_runs[kNn1Cap][256];                     // run lists of the flattened search, as k_icp_assoc<1> holds them
+        bi = nn1_search_flat(p.x, p.y, p.z, g, max_d2, &d2, seed, s_runs);
+    } else bi = nn1_search<Q>(p.x, p.y, p.z, g, max_d2, &d2, seed);
     if ((threadIdx.x & (Q - 1)) != 0) return;
     idx_out[i] = bi < 0 ? -1 : __float_as_int(g.pts[bi].w);      // ORIGINAL index in the caller's map cloud
     d2_out[i] = d2;
@@ -811,6 +845,19 @@ void launch_nn1(const float4* q, int n, const GridIndex* grid_dev, float max_dis
     LISREG_DISPATCH_Q(lanes, (k_nn1<1><<<nb, 256, 0, st>>>(q, n, grid_dev, m2, idx_out, d2_out)),
                              (k_nn1<4><<<nb, 256, 0, st>>>(q, n, grid_dev, m2, idx_out, d2_out)),
                              (k_nn1<8><<<nb, 256, 0, st>>>(q, n, grid_dev, m2, idx_out, d2_out)));
+}
+
+// test hook: form 0 = the flattened walk, 1 / 4 / 8 = the column walk with that many lanes per query (the caller has checked `form`)
+void launch_test_nn1(const float4* q, int n, const GridIndex* grid_dev, float max_dist, int form, const int* seeds, int* idx_out,
+                     float* d2_out, hipStream_t st)
+{
+    if (n <= 0) return;
+    const int lanes = form == 0 ? 1 : form, nb = (int)(((long long)n * lanes + 255) / 256);
+    const float m2 = max_dist * max_dist;
+    if (form == 0)      k_test_nn1<0><<<nb, 256, 0, st>>>(q, n, grid_dev, m2, seeds, idx_out, d2_out);
+    else if (form == 1) k_test_nn1<1><<<nb, 256, 0, st>>>(q, n, grid_dev, m2, seeds, idx_out, d2_out);
+    else if (form == 4) k_test_nn1<4><<<nb, 256, 0, st>>>(q, n, grid_dev, m2, seeds, idx_out, d2_out);
+    else                k_test_nn1<8><<<nb, 256, 0, st>>>(q, n, grid_dev, m2, seeds, idx_out, d2_out);
 }
 
 }  // namespace lisreg

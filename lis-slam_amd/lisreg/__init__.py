@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "lisreg_device_count", "lisreg_create", "lisreg_destroy", "lisreg_last_error", "lisreg_set_stream",
     "lisreg_get_stream", "lisreg_default_params", "lisreg_set_target", "lisreg_set_target_slot",
     "lisreg_target_from_classes", "lisreg_align", "lisreg_align_batch", "lisreg_batch_prepare", "lisreg_batch_run",
-    "lisreg_batch_fetch", "lisreg_stage_host_items", "lisreg_upload_cloud", "lisreg_concat_device", "lisreg_batch_result_device", "lisreg_set_option", "lisreg_get_option", "lisreg_get_counters", "lisreg_get_neighbors", "lisreg_test_fit_models", "lisreg_test_solve_steps", "lisreg_get_target_index", "lisreg_get_target_graph", "lisreg_get_target_cell_rows", "lisreg_keyframes_reset", "lisreg_keyframes_push", "lisreg_keyframes_target", "lisreg_get_trace",
+    "lisreg_batch_fetch", "lisreg_stage_host_items", "lisreg_upload_cloud", "lisreg_concat_device", "lisreg_batch_result_device", "lisreg_set_option", "lisreg_get_option", "lisreg_get_counters", "lisreg_get_neighbors", "lisreg_test_fit_models", "lisreg_test_solve_steps", "lisreg_test_nn1", "lisreg_get_map_grid", "lisreg_get_target_index", "lisreg_get_target_graph", "lisreg_get_target_cell_rows", "lisreg_keyframes_reset", "lisreg_keyframes_push", "lisreg_keyframes_target", "lisreg_get_trace",
     "lisreg_set_profiling", "lisreg_get_timing", "lisreg_pose_to_matrix", "lisreg_transform_update",
     "lisreg_comm_unique_id", "lisreg_comm_init", "lisreg_gather_results", "lisreg_comm_destroy",
     "lisreg_voxel_downsample", "lisreg_voxel_downsample_multi", "lisreg_transform_cloud",
@@ -465,6 +465,8 @@ def lib():
         L.lisreg_map_index_set.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
         L.lisreg_map_index_set_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int]
         L.lisreg_nearest.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
+        L.lisreg_get_map_grid.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_float)]
+        L.lisreg_test_nn1.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int, ip, ip, C.POINTER(C.c_float)]
         L.lisreg_dynamic_filter.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                             C.c_float, vp, ip]
         L.lisreg_bbx_filter.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, dp, C.c_int, vp, ip]
@@ -1327,6 +1329,29 @@ class Context:
         sqd = np.zeros(len(query), np.float32)
         self._chk(self._L.lisreg_nearest(self._h, slot, _vp(query), len(query), query.dtype.itemsize, _fmt_of(query),
                                          max_dist, idx.ctypes.data_as(C.c_void_p), sqd.ctypes.data_as(C.c_void_p)))
+        return idx, sqd
+
+    def map_grid(self, slot: int) -> dict:
+        """Diagnostics (lisreg_get_map_grid): dict(n, dims=(nx, ny, nz), n_cells, o=float32[3], cell) of the map index of `slot`."""
+        d = np.zeros(5, np.int32); g = np.zeros(4, np.float32)
+        self._chk(self._L.lisreg_get_map_grid(self._h, int(slot), d.ctypes.data_as(C.POINTER(C.c_int)), g.ctypes.data_as(C.POINTER(C.c_float))))
+        return dict(n=int(d[0]), dims=(int(d[1]), int(d[2]), int(d[3])), n_cells=int(d[4]), o=g[:3].copy(), cell=g[3])
+
+    def test_nn1(self, slot: int, queries: np.ndarray, max_dist: float, form: int, seeds=None):
+        """Test hook (lisreg_test_nn1): ONE form of the k = 1 search per query — form 1, 4, 8: nn1_search<Q>, 0: nn1_search_flat — on
+        queries[n, 3]; seeds[n] (or None): original map indices, -1 none, -2 the cell seed of ICP's first iteration.  Returns
+        (idx [n] int32 original index or -1, squared distance [n] float32)."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, 3)
+        n = q.shape[0]
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(seeds, np.int32).ravel()
+            assert len(sd) == n
+        idx = np.zeros(n, np.int32)
+        sqd = np.zeros(n, np.float32)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        self._chk(self._L.lisreg_test_nn1(self._h, int(slot), q.ctypes.data_as(fp), n, float(max_dist), int(form),
+                                          None if sd is None else sd.ctypes.data_as(ip), idx.ctypes.data_as(ip), sqd.ctypes.data_as(fp)))
         return idx, sqd
 
     def nearest_device(self, slot: int, q_ptr: int, n: int, max_dist: float, idx_ptr: int, sqd_ptr: int):

@@ -121,6 +121,9 @@ def test_hip_nearest_matches_oracle(oracle, gpu_ctx, seed, n_map):
     d = qx - mx[idx]
     assert np.array_equal((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2], d2)     # idx really is that point
     assert (idx == o_idx).mean() > 0.999                                # ties may differ (smallest index here)
+    # ... and the rule itself, exactly, for every query: brute force over all pairs (tests/nn1_ref.py; threaded blocks, a few seconds)
+    import nn1_ref
+    assert np.array_equal(idx, nn1_ref.nearest(mx, qx)[0])
     for cap in (0.2, 1.0, 3.0):
         idx_c, d2_c = gpu_ctx.nearest(5, q, cap)
         inside = o_d2 <= f32(cap) * f32(cap)
