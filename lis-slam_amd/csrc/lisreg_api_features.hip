@@ -35,8 +35,10 @@ int lisreg_extract_features_deskew(lisreg_ctx* c, const void* cloud, int n, int 
     if (fmt == LISREG_FMT_XYZIRT && stride < 22) return bad(c, "extract_features: XYZIRT needs stride >= 22 (the ring)");
     const bool deskew = dk && dk->enabled && n > 0;
     if (deskew) {
-        if (dk->imu_pointer_cur < 1 || dk->imu_pointer_cur > (1 << 20) || !dk->imu_time || !dk->imu_rot_x || !dk->imu_rot_y || !dk->imu_rot_z)
-            return bad(c, "extract_features: de-skew needs IMU tables with imu_pointer_cur >= 1");
+        // imu_pointer_cur == 0 is a table of one entry: findRotation (:376-387) hands every point that entry's rotation, as the CPU
+        // restatement does (the reference itself leaves imuAvailable false then, :263, which is the caller's `enabled`)
+        if (dk->imu_pointer_cur < 0 || dk->imu_pointer_cur > (1 << 20) || !dk->imu_time || !dk->imu_rot_x || !dk->imu_rot_y || !dk->imu_rot_z)
+            return bad(c, "extract_features: de-skew needs IMU tables with imu_pointer_cur >= 0");
         if (fmt == LISREG_FMT_DEVICE && !dk->time_device) return bad(c, "extract_features: de-skew of device records needs time_device");
         if (fmt == LISREG_FMT_XYZIRT && stride < 28) return bad(c, "extract_features: de-skew needs the time field (stride >= 28)");
     }
