@@ -313,7 +313,9 @@ int  lisreg_get_neighbors(lisreg_ctx* ctx, int* out, int n_elems);
  * float[n][3] (the TRANSFORMED query point), label weight 1.  exact != 0 runs the exact-arithmetic build of the same source.
  * out: host float[n][10]: kind 1: pa, pb, pc, pd (NaN = plane rejected), 1 if the closed form produced it / 0 if the QR did,
  * coeff x, y, z, intensity (:808-811), 1 if accepted (s > accept_s, :813); kind 0: centroid x, y, z and two components of the line
- * direction (NaN = lambda-ratio test failed), coeff x, y, z, intensity (:729-732), accepted (:734). */
+ * direction (NaN = lambda-ratio test failed), coeff x, y, z, intensity (:729-732), accepted (:734); kind 2: cornerOptimization's
+ * eigen-solver alone: the two largest eigenvalues of the scatter matrix, the line direction x, y, z, 1 if the closed form was
+ * certified / 0 if the Jacobi ran (always 0 in the exact build), 1 if the lambda-ratio test passed, 0, 0, accepted. */
 int  lisreg_test_fit_models(lisreg_ctx* ctx, int kind, int n, const float* neighbours, const float* queries,
                             const lisreg_params* params, int exact, float* out);
 

@@ -1427,7 +1427,7 @@ int lisreg_test_fit_models(lisreg_ctx* c, int kind, int n, const float* neighbou
                            int exact, float* out)
 {
     if (!c) return LISREG_ERR_ARG;
-    if ((kind != 0 && kind != 1) || n < 0 || !params || (n > 0 && (!neighbours || !queries || !out)))
+    if (kind < 0 || kind > 2 || n < 0 || !params || (n > 0 && (!neighbours || !queries || !out)))
         return bad(c, "test_fit_models: bad arguments");
     if (n == 0) return LISREG_OK;
     HIPCHK(c, hipSetDevice(c->device));

@@ -87,7 +87,8 @@ __device__ __forceinline__ float hypot_f(float a, float b)
         if ((y) < 0.f) { s = -s; t = -t; }
 
 // Largest eigenvector and the two largest eigenvalues of the symmetric 3x3 {a11..a33}.
-//   production build: cyclic Jacobi, at most six sweeps (same eigen-system to a few ulp, no pivot search);
+//   production build: cyclic Jacobi, at most six sweeps (same eigen-system to a few ulp, no pivot search) — run only for the lanes
+//     that eigen_top_closed below does not certify;
 //   exact build: cv::eigen as OpenCV 3.2 runs it on CV_32F (JacobiImpl_): the pivot is the largest off-diagonal element found through
 //     the per-row / per-column maximum tables indR / indC, which are refreshed only for the two rotated indices — the stale
 //     entries are part of the algorithm and are carried here (for n = 3: indR[0] in {1, 2} and indC[2] in {0, 1}; indR[1] = 2 and
@@ -195,11 +196,85 @@ __device__ __forceinline__ void eigen_sym3(float a11, float a12, float a13, floa
     v0[0] = x; v0[1] = y; v0[2] = z;
 }
 
+// The production corner fit's eigen-solver: the two largest eigenvalues and the top eigenvector of the scatter matrix in closed form,
+// WITH a certificate — `true` only where the accept test `l0 > ratio * l1` provably comes out as the cyclic Jacobi's above would make
+// it; any other lane (`false`) runs that Jacobi as before.  tests/corner_eigen_model.py restates it in numpy and measures it on the
+// benchmark's neighbourhoods (profiles/r07_corner_eigen.md: four Jacobi sweeps per wavefront before; 2 lanes in 10 000 handed back).
+//   1. lambda ~ l0 from the characteristic polynomial of the trace-shifted, scaled matrix (A - T/3 I) / p, 6 p^2 = |A - T/3 I|_F^2:
+//      y^3 - 3 y - 2 r = 0, r = det / 2 in [-1, 1], largest root 2 cos(acos(r) / 3) in [1, 2].  Newton from 1 + sqrt((1 + r) / 2) (exact at
+//      r = -1 and 1, 3.2e-2 off at worst) converges from either side; two steps leave 2.7e-7 for r >= 0, where every neighbourhood that
+//      passes a ratio of 3 lies (r >= 0.54), and 5e-6 near r = -1 (l0 ~ l1).  lambda = T/3 + p y.
+//   2. v = the largest of the three cross products of rows of A - lambda I, normalised; u1 = the first row of that pair, normalised
+//      (the rows are orthogonal to the eigenvector); u2 = v x u1.  Q = [v u1 u2] is orthonormal up to |Q^T Q - I| <= 32 u + 2 |v . u1|.
+//   3. rho = v.Av, B = [u1 u2]^T A [u1 u2] with eigenvalues mu1 >= mu2 (mean +- hypot: no cancellation), c = [u1 u2]^T A v.
+// Q^T A Q = diag(rho, B) + offdiag(c).  Whatever steps 1 and 2 did, the sorted {rho, mu1, mu2} are therefore within
+//      delta = (|Q^T Q - I| + 36 u + 4 u) T + |c|      (u = 2^-24, T = trace >= |A|_2)
+// of A's eigenvalues: Ostrowski for the basis, Weyl for c, 3 * 12 u T for the rounding of the nine three-term products (12 u T each,
+// spectral norm of a 3 x 3 of them), 4 u T for the 2 x 2 solve.  A lane is certified only with |v . u1| <= 8 u (+ 3 u of that product's
+// own rounding) and max |c_i| <= 45 u T (|c| <= 64 u T): delta <= 158 u T.  The Jacobi's own eigenvalues carry <= 128 u T (18 rotations
+// of <= 6 u |A| backward error each by the time four sweeps are through, plus the 3e-30 it may leave; measured: 5 u T for either).
+// So the test is the Jacobi's wherever |top - ratio * second| > (1 + ratio) (158 + 128 + 1) u T — the guard band; inside it, `false`.
+// An accepted lane also needs rho on top and rho - mu1 >= T / 8: then sin(angle(v, eigenvector)) <= |c| / gap <= 512 u (measured:
+// 3e-7 rad from the Jacobi's direction), and the sign of v is immaterial (corner_eval's two points are c +- 0.1 v).  Rejected lanes
+// do not use v.  NaN and infinity (five coincident points: p = 0) fail every comparison: `false`.  T outside [1e-12, 1e12] m^2 (products
+// of three entries leave the normal range) is not certified either.
+constexpr float kEigU = 5.9604645e-8f;                   // 2^-24
+constexpr float kEigBarE = 8.f * kEigU, kEigBarC = 45.f * kEigU, kEigGuard = 287.f * kEigU, kEigGap = 0.125f;
+__device__ __forceinline__ bool eigen_top_closed(float a11, float a12, float a13, float a22, float a23, float a33, float ratio,
+                                                 float& l0, float& l1, float v0[3])
+{
+    const float T = a11 + a22 + a33, q = T * (1.f / 3.f);
+    const float d1 = a11 - q, d2 = a22 - q, d3 = a33 - q;
+    const float p2 = ((d1 * d1 + d2 * d2 + d3 * d3) + 2.f * (a12 * a12 + a13 * a13 + a23 * a23)) * (1.f / 6.f);
+    const float det = d1 * (d2 * d3 - a23 * a23) - a12 * (a12 * d3 - a13 * a23) + a13 * (a12 * a23 - a13 * d2);
+    const float ip = __builtin_amdgcn_rsqf(p2), p = p2 * ip;
+    const float r = det * (0.5f * (ip * ip * ip));
+    float y = 1.f + __builtin_amdgcn_sqrtf(fmaxf(0.5f + 0.5f * r, 0.f));
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const float y2 = y * y;
+        y -= ((y2 - 3.f) * y - 2.f * r) * __builtin_amdgcn_rcpf(3.f * y2 - 3.f);
+    }
+    const float lam = q + p * y;
+    // rows of A - lambda I: R1 = (e1, a12, a13), R2 = (a12, e2, a23), R3 = (a13, a23, e3)
+    const float e1 = a11 - lam, e2 = a22 - lam, e3 = a33 - lam;
+    const float c12x = a12 * a23 - a13 * e2, c12y = a13 * a12 - e1 * a23, c12z = e1 * e2 - a12 * a12;      // R1 x R2
+    const float c13x = a12 * e3 - a13 * a23, c13y = a13 * a13 - e1 * e3, c13z = e1 * a23 - a12 * a13;      // R1 x R3
+    const float c23x = e2 * e3 - a23 * a23, c23y = a23 * a13 - a12 * e3, c23z = a12 * a23 - e2 * a13;      // R2 x R3
+    const float n12 = c12x * c12x + c12y * c12y + c12z * c12z;
+    const float n13 = c13x * c13x + c13y * c13y + c13z * c13z;
+    const float n23 = c23x * c23x + c23y * c23y + c23z * c23z;
+    float vx = c12x, vy = c12y, vz = c12z, n2 = n12;
+    if (n13 > n2) { vx = c13x; vy = c13y; vz = c13z; n2 = n13; }
+    float ux = e1, uy = a12, uz = a13;
+    if (n23 > n2) { vx = c23x; vy = c23y; vz = c23z; n2 = n23; ux = a12; uy = e2; uz = a23; }
+    const float iv = __builtin_amdgcn_rsqf(n2);
+    vx *= iv; vy *= iv; vz *= iv;
+    const float iu = __builtin_amdgcn_rsqf(ux * ux + uy * uy + uz * uz);
+    ux *= iu; uy *= iu; uz *= iu;
+    const float wx = vy * uz - vz * uy, wy = vz * ux - vx * uz, wz = vx * uy - vy * ux;                   // u2 = v x u1
+    const float avx = a11 * vx + a12 * vy + a13 * vz, avy = a12 * vx + a22 * vy + a23 * vz, avz = a13 * vx + a23 * vy + a33 * vz;
+    const float aux = a11 * ux + a12 * uy + a13 * uz, auy = a12 * ux + a22 * uy + a23 * uz, auz = a13 * ux + a23 * uy + a33 * uz;
+    const float awx = a11 * wx + a12 * wy + a13 * wz, awy = a12 * wx + a22 * wy + a23 * wz, awz = a13 * wx + a23 * wy + a33 * wz;
+    const float rho = vx * avx + vy * avy + vz * avz;
+    const float b11 = ux * aux + uy * auy + uz * auz, b12 = wx * aux + wy * auy + wz * auz, b22 = wx * awx + wy * awy + wz * awz;
+    const float cc1 = ux * avx + uy * avy + uz * avz, cc2 = wx * avx + wy * avy + wz * avz;
+    const float e = vx * ux + vy * uy + vz * uz;
+    const float mean = 0.5f * (b11 + b22), h = 0.5f * (b11 - b22);
+    const float s = __builtin_amdgcn_sqrtf(h * h + b12 * b12);
+    const float mu1 = mean + s, mu2 = mean - s;
+    const float top = fmaxf(rho, mu1), second = fmaxf(fminf(rho, mu1), mu2);
+    const bool certified = fmaxf(fabsf(cc1), fabsf(cc2)) <= kEigBarC * T && fabsf(e) <= kEigBarE && T >= 1e-12f && T <= 1e12f;
+    const float margin = top - ratio * second, band = (1.f + ratio) * (kEigGuard * T);
+    l0 = top; l1 = second; v0[0] = vx; v0[1] = vy; v0[2] = vz;
+    return certified && (margin < -band || (margin > band && rho - mu1 >= kEigGap * T));
+}
+
 // cornerOptimization body for one point (odomEstimationNode.cpp:658-742), split in two:
 //   corner_model : depends only on the five neighbours (centroid, principal direction, lambda0 > 3*lambda1 test);
 //   corner_eval  : depends on the transformed query point (line residual, robust weight, accept test).
-// m0 = (cx, cy, cz, valid ? 1 : NaN), m1 = (vx, vy, vz, 0).
-__device__ __forceinline__ void corner_model(const float4 nb[5], const DevParams& P, float4& m0, float4& m1)
+// m0 = (cx, cy, cz, valid ? 1 : NaN), m1 = (vx, vy, vz, 0).  eig (test hook only): l0, l1, 1 where the closed form was certified.
+__device__ __forceinline__ void corner_model(const float4 nb[5], const DevParams& P, float4& m0, float4& m1, float* eig = nullptr)
 {
     float cx = 0, cy = 0, cz = 0;
 #pragma unroll
@@ -212,11 +287,14 @@ __device__ __forceinline__ void corner_model(const float4 nb[5], const DevParams
         a11 += ax * ax; a12 += ax * ay; a13 += ax * az; a22 += ay * ay; a23 += ay * az; a33 += az * az;
     }
     a11 = fdiv5(a11); a12 = fdiv5(a12); a13 = fdiv5(a13); a22 = fdiv5(a22); a23 = fdiv5(a23); a33 = fdiv5(a33);
-    float l0, l1, v[3];
-    eigen_sym3(a11, a12, a13, a22, a23, a33, l0, l1, v);
-    const bool ok = l0 > P.line_ratio * l1;                               // :692
+    float l0 = 0.f, l1 = 0.f, v[3] = { 0.f, 0.f, 0.f };
+    bool closed = false;
+    if (!kExactArith) closed = eigen_top_closed(a11, a12, a13, a22, a23, a33, P.line_ratio, l0, l1, v);
+    if (!closed) eigen_sym3(a11, a12, a13, a22, a23, a33, l0, l1, v);    // a wavefront without such a lane branches past it
+    const bool ok = l0 > P.line_ratio * l1;                               // :692 (closed form: outside the guard band, the same decision)
     m0 = make_float4(cx, cy, cz, ok ? 1.f : __int_as_float(0x7fc00000));
     m1 = make_float4(v[0], v[1], v[2], 0.f);
+    if (eig) { eig[0] = l0; eig[1] = l1; eig[2] = closed ? 1.f : 0.f; }
 }
 
 __device__ __forceinline__ bool corner_eval(const float4 m0, const float4 m1, float x0, float y0, float z0, float w,
@@ -1398,8 +1476,14 @@ __global__ __launch_bounds__(64) void k_test_fit_models(int kind, int n, const f
         o[5] = cf[0]; o[6] = cf[1]; o[7] = cf[2]; o[8] = cf[3]; o[9] = ok ? 1.f : 0.f;
     } else {
         float4 m0, m1;
-        corner_model(nb, P, m0, m1);
+        float eig[3];
+        corner_model(nb, P, m0, m1, eig);
         const bool ok = corner_eval(m0, m1, qx, qy, qz, 1.f, P, cf);
+        if (kind == 2) {     // the eigen-solver's own outputs
+            o[0] = eig[0]; o[1] = eig[1]; o[2] = m1.x; o[3] = m1.y; o[4] = m1.z; o[5] = eig[2];
+            o[6] = m0.w == 1.f ? 1.f : 0.f; o[7] = o[8] = 0.f; o[9] = ok ? 1.f : 0.f;
+            return;
+        }
         o[0] = m0.x; o[1] = m0.y; o[2] = m0.z; o[3] = m1.x; o[4] = m1.y;
         o[5] = cf[0]; o[6] = cf[1]; o[7] = cf[2]; o[8] = cf[3]; o[9] = ok ? 1.f : 0.f;
     }

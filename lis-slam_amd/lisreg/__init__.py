@@ -706,7 +706,7 @@ class Context:
         return out
 
     def test_fit_models(self, kind: int, neighbours: np.ndarray, queries: np.ndarray, params, exact: bool = False) -> np.ndarray:
-        """Test hook: the device functions of the residual models (kind 1 = surfOptimization's body, 0 = cornerOptimization's) on
+        """Test hook: the device functions of the residual models (kind 1 = surfOptimization's body, 0 = cornerOptimization's, 2 = its eigen-solver alone) on
         neighbours[n, 5, 3] / queries[n, 3]; returns float32[n, 10] as include/lisreg.h describes."""
         nb = np.ascontiguousarray(neighbours, np.float32).reshape(-1, 15)
         q = np.ascontiguousarray(queries, np.float32).reshape(-1, 3)
