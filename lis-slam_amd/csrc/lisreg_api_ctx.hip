@@ -1,5 +1,5 @@
 // lisreg_api_ctx.hip — what every translation unit behind the C ABI shares (declared in lisreg_ctx.hpp): the error text, the argument
-// checks of a cloud, the packing and staging of host clouds, the bounding-box read-back, the sort scratch and the grid geometry.
+// checks of a cloud, the packing and staging of host clouds, the aligned cloud an align() hands out, the bounding-box read-back, the sort scratch and the grid geometry.
 // Host code only: no kernel lives here.
 #include "lisreg_ctx.hpp"
 
@@ -78,6 +78,31 @@ int stage_records(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, 
     pack_cloud(cloud, n, stride, fmt, h.data());
     if (const int rc = upload_packed(c, h.data(), (size_t)std::max(n, 0), into)) return rc;
     *out = into.as<float4>();
+    return LISREG_OK;
+}
+
+int emit_aligned(lisreg_ctx* c, const float4* raw, int n, const float Rt[12], const void* source, int stride, int fmt, DevBuf& scratch,
+                 void* aligned_out)
+{
+    hipStream_t st = c->stream;
+    HIPCHK(c, c->vox_M.ensure(sizeof(float) * 12));
+    HIPCHK(c, hipMemcpyAsync(c->vox_M.p, Rt, sizeof(float) * 12, hipMemcpyHostToDevice, st));
+    if (fmt == LISREG_FMT_DEVICE) {
+        launch_transform_cloud(raw, n, c->vox_M.as<float>(), static_cast<float4*>(aligned_out), st);
+        HIPCHK(c, hipStreamSynchronize(st));
+        return LISREG_OK;
+    }
+    HIPCHK(c, scratch.ensure(sizeof(float4) * (size_t)n));
+    launch_transform_cloud(raw, n, c->vox_M.as<float>(), scratch.as<float4>(), st);
+    std::vector<float4> hp((size_t)n);
+    HIPCHK(c, hipMemcpyAsync(hp.data(), scratch.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const unsigned char* b = static_cast<const unsigned char*>(source);
+    unsigned char* o = static_cast<unsigned char*>(aligned_out);
+    for (int i = 0; i < n; ++i) {
+        if (o != b) memcpy(o + (size_t)i * (size_t)stride, b + (size_t)i * (size_t)stride, (size_t)stride);
+        memcpy(o + (size_t)i * (size_t)stride, &hp[(size_t)i], 12);
+    }
     return LISREG_OK;
 }
 

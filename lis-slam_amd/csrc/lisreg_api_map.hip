@@ -538,7 +538,6 @@ int lisreg_icp_align(lisreg_ctx* c, int slot, const void* source, int n, int str
     if (!P || !res) return bad(c, "icp_align: NULL params / result");
     if (!(P->max_corr_dist >= 0) || P->max_iters < 1) return bad(c, "icp_align: bad max_corr_dist / max_iters");
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
     const float4* src = nullptr;
     rc = stage_records(c, source, n, stride, fmt, c->mp_pts, &src);
     if (rc) return rc;
@@ -549,26 +548,8 @@ int lisreg_icp_align(lisreg_ctx* c, int slot, const void* source, int n, int str
     if (rc) return rc;
     const IcpState& h = hs[0];
     icp_fill_result(h, res);
-    if (aligned_out && n > 0) {                       // `output` of align(): the source under the final transformation
-        HIPCHK(c, c->vox_M.ensure(sizeof(float) * 12));
-        HIPCHK(c, hipMemcpyAsync(c->vox_M.p, h.F, sizeof(float) * 12, hipMemcpyHostToDevice, st));     // rows 0..2 of F = [R|t]
-        if (fmt == LISREG_FMT_DEVICE) {
-            launch_transform_cloud(src, n, c->vox_M.as<float>(), static_cast<float4*>(aligned_out), st);
-            HIPCHK(c, hipStreamSynchronize(st));
-        } else {
-            HIPCHK(c, c->mp_out.ensure(sizeof(float4) * (size_t)n));
-            launch_transform_cloud(src, n, c->vox_M.as<float>(), c->mp_out.as<float4>(), st);
-            std::vector<float4> hp((size_t)n);
-            HIPCHK(c, hipMemcpyAsync(hp.data(), c->mp_out.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            const unsigned char* b = static_cast<const unsigned char*>(source);
-            unsigned char* o = static_cast<unsigned char*>(aligned_out);
-            for (int i = 0; i < n; ++i) {
-                if (o != b) memcpy(o + (size_t)i * (size_t)stride, b + (size_t)i * (size_t)stride, (size_t)stride);
-                memcpy(o + (size_t)i * (size_t)stride, &hp[(size_t)i], 12);
-            }
-        }
-    }
+    // `output` of align(): the source under the final transformation (rows 0..2 of F = [R|t])
+    if (aligned_out && n > 0) return emit_aligned(c, src, n, h.F, source, stride, fmt, c->mp_out, aligned_out);
     return LISREG_OK;
 }
 
@@ -674,26 +655,7 @@ int lisreg_icp_gn_match(lisreg_ctx* c, int slot, const void* source, int n, int 
     memcpy(res->final_transform, h.F, sizeof h.F);
     res->steps_applied = h.iters; res->n_corr_last = h.n_corr; res->reserved = 0;
     res->fitness = h.fit_n > 0 ? (float)(h.fit_sum / (double)h.fit_n) : FLT_MAX;
-    if (transformed_out && n > 0) {
-        HIPCHK(c, c->vox_M.ensure(sizeof(float) * 12));
-        HIPCHK(c, hipMemcpyAsync(c->vox_M.p, h.F, sizeof(float) * 12, hipMemcpyHostToDevice, st));
-        if (fmt == LISREG_FMT_DEVICE) {
-            launch_transform_cloud(src, n, c->vox_M.as<float>(), static_cast<float4*>(transformed_out), st);
-            HIPCHK(c, hipStreamSynchronize(st));
-        } else {
-            HIPCHK(c, c->mp_out.ensure(sizeof(float4) * (size_t)n));
-            launch_transform_cloud(src, n, c->vox_M.as<float>(), c->mp_out.as<float4>(), st);
-            std::vector<float4> hp((size_t)n);
-            HIPCHK(c, hipMemcpyAsync(hp.data(), c->mp_out.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            const unsigned char* b = static_cast<const unsigned char*>(source);
-            unsigned char* o = static_cast<unsigned char*>(transformed_out);
-            for (int i = 0; i < n; ++i) {
-                if (o != b) memcpy(o + (size_t)i * (size_t)stride, b + (size_t)i * (size_t)stride, (size_t)stride);
-                memcpy(o + (size_t)i * (size_t)stride, &hp[(size_t)i], 12);
-            }
-        }
-    }
+    if (transformed_out && n > 0) return emit_aligned(c, src, n, h.F, source, stride, fmt, c->mp_out, transformed_out);
     return LISREG_OK;
 }
 

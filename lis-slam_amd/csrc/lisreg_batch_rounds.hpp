@@ -1,7 +1,7 @@
 // lisreg_batch_rounds.hpp — what the rounds of the two batch verifiers share on the device (lisreg_fgicp_batch.hip, DESIGN.md §7m, and
-// lisreg_vgicp_batch.hip, §7n): how a workgroup finds its entry in the round's work table, and the fixed-order totals of an entry's
-// partial records.  One source for both units; the anonymous namespace gives each unit a kernel of its own in its own code object.
-// Not installed.
+// lisreg_vgicp_batch.hip, §7n): how a workgroup finds its entry in the round's work table, the fixed-order totals of an entry's
+// partial records, and the fitness search.  One source for both units; the anonymous namespace gives each unit a kernel of its own in
+// its own code object.  The host side of the rounds is lisreg_batch_driver.hpp.  Not installed.
 #pragma once
 #include "lisreg_fgicp_lane.hpp"
 
@@ -36,6 +36,40 @@ __global__ __launch_bounds__(64) void k_fgicp_total_batch(const double* __restri
     if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < W; ++k) out[(size_t)e * W + k] = acc[k];
+}
+
+// One item at its final pose, for the fitness pass of either family: the search grid of its target (the search reads the points and the
+// cells only: cov may be null)
+struct FgFitWork {
+    FgTarget  A;
+    FgPose    P;
+    long long src_off;     // the source's first finite point in the batch's point buffer
+    int       n;           // finite points of the source
+    int       reserved;
+};
+
+// The fitness pass: the nearest finite target point of every finite source point at the item's final pose, without a cut-off; the
+// wavefront's sum of the squared distances goes to the workgroup's partial.
+__global__ __launch_bounds__(64) void k_fgicp_fitness_batch(const FgFitWork* __restrict__ work, const int* __restrict__ wg_start, int n_entries,
+                                                            const float4* __restrict__ src, double* __restrict__ part)
+{
+    const int g = blockIdx.x;
+    const int e = fg_entry_of(wg_start, 0, n_entries, g);
+    const FgFitWork* __restrict__ w = work + e;
+    const int n = w->n;
+    const int i = (g - wg_start[e]) * 64 + (int)threadIdx.x;
+    double d2 = 0.0;
+    if (i < n) {
+        const FgTarget A = w->A;
+        const FgPose   P = w->P;
+        double qx, qy, qz, bd;
+        int    bj;
+        fg_transform(P, src[(size_t)w->src_off + (size_t)i], qx, qy, qz);
+        fg_search_lane(A, qx, qy, qz, HUGE_VAL, HUGE_VAL, bd, bj);
+        d2 = bj >= 0 ? bd : 0.0;
+    }
+    d2 = fg_wave_sum(d2);
+    if (threadIdx.x == 0) part[g] = d2;
 }
 
 }  // namespace

@@ -79,6 +79,13 @@ struct Stream : OwnedHandle<hipStream_t, hipStreamDestroy> {
     hipError_t create(unsigned flags) { reset(); const hipError_t e = hipStreamCreateWithFlags(&h, flags); if (e != hipSuccess) h = nullptr; return e; }
 };
 
+// What a batch verifier keeps between calls (lisreg_batch_driver.hpp): the sources' finite points and covariances, the work table of a
+// round, its partial and total records, and the pinned host sides of the table and of the totals; grow-only, like the rest
+struct BatchBufs {
+    DevBuf    src, cov, work, part, out;
+    PinnedBuf host_work, host_out;
+};
+
 struct Target {
     bool      valid = false;
     int       n[2] = { 0, 0 };
@@ -270,14 +277,10 @@ struct lisreg_ctx {
     // correspondence rows of the test hook by the caller's index
     std::map<int, lisreg::FgicpTarget> fgicp;
     lisreg::DevBuf fg_pair, fg_M, fg_d2, fg_rows_i, fg_rows_d;
-    // lisreg_fgicp_align_batch (lisreg_fgicp_batch.hip): the sources' finite points and covariances, the items' pairs and M, the work
-    // table of a round, its partial and total records; grow-only, like the rest
-    lisreg::DevBuf fgb_src, fgb_cov, fgb_pair, fgb_M, fgb_work, fgb_part, fgb_out;
-    lisreg::PinnedBuf fgb_host_work, fgb_host_out;
-    // lisreg_vgicp_align_batch (lisreg_vgicp_batch.hip): the sources' finite points and covariances, the work table of a round, its
-    // partial and total records; grow-only, like the rest
-    lisreg::DevBuf vgb_src, vgb_cov, vgb_work, vgb_part, vgb_out;
-    lisreg::PinnedBuf vgb_host_work, vgb_host_out;
+    // lisreg_fgicp_align_batch (lisreg_fgicp_batch.hip) and lisreg_vgicp_align_batch (lisreg_vgicp_batch.hip): a set of buffers each
+    // (a call of one family leaves the other's alone), and the pairs and M FastGICP's items keep from a search to the sums after it
+    lisreg::BatchBufs fgb, vgb;
+    lisreg::DevBuf fgb_pair, fgb_M;
     lisreg::PinnedBuf done_host;            // one int
     lisreg::PinnedBuf stage_host;           // pinned staging of the per-batch tables
     lisreg::Event stage_done;
@@ -390,6 +393,11 @@ void pack_cloud(const void* cloud, int n, int stride, int fmt, lisreg_dpoint* ou
 int  upload_packed(lisreg_ctx* c, const lisreg_dpoint* h, size_t n, DevBuf& into);
 // one cloud as 16-byte device records: the caller's own memory for LISREG_FMT_DEVICE, else pack_cloud + upload_packed into `into`
 int  stage_records(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, DevBuf& into, const float4** out);
+// `output` of an align(): the n staged records `raw` under Rt = [R|t] (3 x 4, row-major, float, like lisreg_transform_cloud) into
+// aligned_out, waited for.  LISREG_FMT_DEVICE: 16-byte records in device memory; else the caller's structs (`source`, `stride`) with
+// their x y z replaced, by way of `scratch`
+int  emit_aligned(lisreg_ctx* c, const float4* raw, int n, const float Rt[12], const void* source, int stride, int fmt, DevBuf& scratch,
+                  void* aligned_out);
 // each coordinate's finite minimum and maximum over n > 0 device records: launch_bbox on the context's stream, read back and waited for.
 // A cloud without a finite point gives min > max; Inf coordinates come back as they are: what to refuse is the caller's business
 int  cloud_bbox(lisreg_ctx* c, const float4* pts, int n, float bb[6]);

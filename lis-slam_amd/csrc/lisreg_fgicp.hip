@@ -7,6 +7,7 @@
 // pairs at any pose (an error evaluation reuses the pairs and the M of the last linearisation).  Sums in a fixed order: the same input
 // gives the same bits.  No CPU fallback.
 #include "lisreg_fgicp_lane.hpp"
+#include "lisreg_lm_stepper.hpp"
 #include "lisreg_jacobi3.hpp"
 
 #include <cfloat>
@@ -94,13 +95,6 @@ struct FgRun {
     double             max_d;
 };
 
-FgPose pose_of(const double T[16])
-{
-    FgPose P;
-    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) P.R[3 * i + j] = T[4 * i + j]; P.t[i] = T[4 * i + 3]; }
-    return P;
-}
-
 // the search at T: pairs and M into c->fg_pair / c->fg_M (and the squared distances into c->fg_d2 if wanted)
 int search(FgRun& r, const double T[16], bool want_d2)
 {
@@ -108,7 +102,7 @@ int search(FgRun& r, const double T[16], bool want_d2)
     const FgicpTarget& G = *r.T;
     const FgTarget A = fg_target_view(G);
     ctx_prof_mark(c, 1);                                           // lisreg_get_timing: "solve" = the search launches, one interval each
-    k_fgicp_pairs<<<(r.n + 63) / 64, 64, 0, c->stream>>>(r.src, r.cov, r.n, A, pose_of(T), r.max_d, r.max_d * r.max_d, c->fg_pair.as<int>(),
+    k_fgicp_pairs<<<(r.n + 63) / 64, 64, 0, c->stream>>>(r.src, r.cov, r.n, A, pose_of<FgPose>(T), r.max_d, r.max_d * r.max_d, c->fg_pair.as<int>(),
                                                           c->fg_M.as<double>(), want_d2 ? c->fg_d2.as<double>() : nullptr);
     ctx_prof_mark(c, -1);
     HIPCHK(c, hipGetLastError());
@@ -124,7 +118,7 @@ int sums(FgRun& r, const double T[16], bool hess, double out[kOut])
     HIPCHK(c, c->vg_part.ensure(sizeof(double) * kOut * (size_t)nb));
     HIPCHK(c, c->vg_out.ensure(sizeof(double) * kOut));
     HIPCHK(c, c->vg_host.ensure(sizeof(double) * kOut, sizeof(double) * 64));
-    const FgPose P = pose_of(T);
+    const FgPose P = pose_of<FgPose>(T);
     ctx_prof_mark(c, 0);                                           // "assoc" = the sum launches (with the fixed-order total), one interval each
     if (hess) k_fgicp_sums<true><<<nb, 64, 0, st>>>(r.src, c->fg_pair.as<int>(), c->fg_M.as<double>(), r.n, r.T->sorted.as<float4>(), P, c->vg_part.as<double>());
     else      k_fgicp_sums<false><<<nb, 64, 0, st>>>(r.src, c->fg_pair.as<int>(), c->fg_M.as<double>(), r.n, r.T->sorted.as<float4>(), P, c->vg_part.as<double>());
@@ -290,39 +284,17 @@ int lisreg_fgicp_align(lisreg_ctx* c, int slot, const void* source, int n, int s
     const float4* raw = nullptr;
     int rc = stage_source(c, "fgicp_align", slot, source, n, stride, fmt, P, &r, &raw);
     if (rc) return rc;
-    hipStream_t st = c->stream;
     double T0[16];
-    for (int k = 0; k < 16; ++k) T0[k] = guess ? (double)guess[k] : (k % 5 == 0 ? 1.0 : 0.0);
-    T0[12] = T0[13] = T0[14] = 0.0; T0[15] = 1.0;
-    const LmParams lp{ P->transformation_epsilon, P->rotation_epsilon, P->lm_init_lambda_factor, P->max_iters, P->lm_max_iterations };
+    guess_to_T0(guess, T0);
     LmResult lr;
-    rc = lm_optimise([&](const double T[16], bool hess, double out[kOut]) { return evaluate(r, T, hess, out); }, T0, lp, &lr);
+    rc = lm_optimise([&](const double T[16], bool hess, double out[kOut]) { return evaluate(r, T, hess, out); }, T0, lm_params_of(*P), &lr);
     if (rc) return rc;
     ctx_prof_collect(c);
-    memcpy(res->final_transform, lr.T, sizeof lr.T);
-    res->converged = lr.converged; res->iters = lr.iters; res->n_evals = lr.n_evals; res->n_rejected = lr.n_rejected;
-    res->n_pairs_last = lr.n_pairs_last; res->error = lr.error; res->lambda = lr.lambda;
+    lm_result_to(lr, res);
     if (aligned_out) {                                    // the source under the final transformation (in float, like lisreg_transform_cloud)
         float F[12];
         for (int k = 0; k < 12; ++k) F[k] = (float)lr.T[k];
-        HIPCHK(c, c->vox_M.ensure(sizeof(float) * 12));
-        HIPCHK(c, hipMemcpyAsync(c->vox_M.p, F, sizeof F, hipMemcpyHostToDevice, st));
-        if (fmt == LISREG_FMT_DEVICE) {
-            launch_transform_cloud(raw, n, c->vox_M.as<float>(), static_cast<float4*>(aligned_out), st);
-            HIPCHK(c, hipStreamSynchronize(st));
-        } else {
-            HIPCHK(c, c->vg_sorted.ensure(sizeof(float4) * (size_t)n));
-            launch_transform_cloud(raw, n, c->vox_M.as<float>(), c->vg_sorted.as<float4>(), st);
-            std::vector<float4> hp((size_t)n);
-            HIPCHK(c, hipMemcpyAsync(hp.data(), c->vg_sorted.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            const unsigned char* b = static_cast<const unsigned char*>(source);
-            unsigned char* o = static_cast<unsigned char*>(aligned_out);
-            for (int i = 0; i < n; ++i) {
-                if (o != b) memcpy(o + (size_t)i * (size_t)stride, b + (size_t)i * (size_t)stride, (size_t)stride);
-                memcpy(o + (size_t)i * (size_t)stride, &hp[(size_t)i], 12);
-            }
-        }
+        return emit_aligned(c, raw, n, F, source, stride, fmt, c->vg_sorted, aligned_out);
     }
     return LISREG_OK;
 }

@@ -1,8 +1,11 @@
-// lisreg_lm_stepper.hpp — lm_optimise (lisreg_vgicp_host.hpp) turned inside out: the state of one Levenberg-Marquardt run that asks for
-// one evaluation at a time and is resumed with its answer, so that a driver can hold many runs and answer the outstanding requests of
-// all of them with one round of launches (lisreg_fgicp_batch.hip).  Fed the out[29] records lm_optimise's eval would
-// return, it asks for the same (T, with_hessian) sequence and fills the same LmResult, bit for bit: every statement below is the one of
-// lm_optimise at the same place of the loop, only the loop counters live in the struct.  Plain C++ (no HIP).  Not installed.
+// lisreg_lm_stepper.hpp — the Levenberg-Marquardt loop of the fast_gicp family (LsqRegistration::step_lm as tests/vgicp_ref.py restates
+// it), the only one in csrc/: the state of one run that asks for one evaluation at a time and is resumed with its answer.  A batch
+// driver holds many runs and answers the outstanding requests of all of them with one round of launches (lisreg_batch_driver.hpp,
+// DESIGN.md §7m); a single aligner answers them one by one (lm_optimise below).  lambda starts at init_lambda_factor max|diag H| of the
+// first linearisation and is carried across the outer iterations; NOT (rho >= 0) is a rejection; a trial loop that runs out, or a system
+// that is not positive definite, ends the alignment unconverged.  No NaN can reach T: a step is applied only after solve_damped vouched
+// for a finite delta.  host/lm_stepper_check.cpp holds the same loop in closed form and compares the two on scripted evaluations.
+// Plain C++ (no HIP).  Not installed.
 #pragma once
 #include "lisreg_vgicp_host.hpp"
 
@@ -121,6 +124,20 @@ private:
         return false;
     }
 };
+
+// One run with its evaluations answered on the spot: eval(T, with_hessian, out[29]) -> 0 or an error code (returned at once)
+template <class Eval>
+int lm_optimise(Eval&& eval, const double T0[16], const LmParams& P, LmResult* res)
+{
+    LmStepper lm;
+    double out[kOut];
+    lm.start(T0, P);
+    do {
+        if (const int rc = eval(lm.req_T, lm.req_hessian, out)) return rc;
+    } while (lm.feed(out));
+    *res = lm.res;
+    return 0;
+}
 
 }  // namespace vgicp_host
 }  // namespace lisreg

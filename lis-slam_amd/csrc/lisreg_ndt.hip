@@ -495,7 +495,6 @@ int lisreg_ndt_align(lisreg_ctx* c, int slot, const void* source, int n, int str
     if (rc) return rc;
     if (!res) return bad(c, "ndt_align: NULL result");
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
     NdtRun r; r.c = c; r.T = T; r.n = n;
     rc = stage_records(c, source, n, stride, fmt, c->ndt_src, &r.src);
     if (rc) return rc;
@@ -557,26 +556,8 @@ int lisreg_ndt_align(lisreg_ctx* c, int slot, const void* source, int n, int str
     res->converged = converged ? 1 : 0; res->iters = iters; res->n_evals = r.n_evals; res->reserved = 0;
     res->n_pairs_last = (long long)r.out[28];
     res->score = r.out[0]; res->trans_probability = r.out[0] / (double)n;
-    if (aligned_out) {                                    // `output` of align(): the source under the final transformation
-        HIPCHK(c, c->vox_M.ensure(sizeof(float) * 12));
-        HIPCHK(c, hipMemcpyAsync(c->vox_M.p, F, sizeof(float) * 12, hipMemcpyHostToDevice, st));
-        if (fmt == LISREG_FMT_DEVICE) {
-            launch_transform_cloud(r.src, n, c->vox_M.as<float>(), static_cast<float4*>(aligned_out), st);
-            HIPCHK(c, hipStreamSynchronize(st));
-        } else {
-            HIPCHK(c, c->ndt_pts.ensure(sizeof(float4) * (size_t)n));
-            launch_transform_cloud(r.src, n, c->vox_M.as<float>(), c->ndt_pts.as<float4>(), st);
-            std::vector<float4> hp((size_t)n);
-            HIPCHK(c, hipMemcpyAsync(hp.data(), c->ndt_pts.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            const unsigned char* b = static_cast<const unsigned char*>(source);
-            unsigned char* o = static_cast<unsigned char*>(aligned_out);
-            for (int i = 0; i < n; ++i) {
-                if (o != b) memcpy(o + (size_t)i * (size_t)stride, b + (size_t)i * (size_t)stride, (size_t)stride);
-                memcpy(o + (size_t)i * (size_t)stride, &hp[(size_t)i], 12);
-            }
-        }
-    }
+    // `output` of align(): the source under the final transformation
+    if (aligned_out) return emit_aligned(c, r.src, n, F, source, stride, fmt, c->ndt_pts, aligned_out);
     return LISREG_OK;
 }
 

@@ -6,6 +6,7 @@
 // point, fp64, sums in a fixed order: the same input gives the same bits).  Host: the 6 x 6 solve and the Levenberg-Marquardt loop in
 // double, one 29-double read-back per evaluation.  No CPU fallback.
 #include "lisreg_vgicp_lane.hpp"
+#include "lisreg_lm_stepper.hpp"
 #include "lisreg_jacobi3.hpp"
 
 #include <algorithm>
@@ -411,8 +412,7 @@ int evaluate(VgRun& r, const double T[16], bool hess, double out[kOut])
 {
     lisreg_ctx* c = r.c;
     hipStream_t st = c->stream;
-    VgPose P;
-    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) P.R[3 * i + j] = T[4 * i + j]; P.t[i] = T[4 * i + 3]; }
+    const VgPose P = pose_of<VgPose>(T);
     const VgGrid G = vg_grid_view(*r.T);
     const int nb = (r.n + 63) / 64;
     HIPCHK(c, c->vg_part.ensure(sizeof(double) * kOut * (size_t)nb));
@@ -635,39 +635,17 @@ int lisreg_vgicp_align(lisreg_ctx* c, int slot, const void* source, int n, int s
     const float4* raw = nullptr;
     int rc = stage_source(c, "vgicp_align", slot, source, n, stride, fmt, P, &r, &raw);
     if (rc) return rc;
-    hipStream_t st = c->stream;
     double T0[16];
-    for (int k = 0; k < 16; ++k) T0[k] = guess ? (double)guess[k] : (k % 5 == 0 ? 1.0 : 0.0);
-    T0[12] = T0[13] = T0[14] = 0.0; T0[15] = 1.0;
-    const LmParams lp{ P->transformation_epsilon, P->rotation_epsilon, P->lm_init_lambda_factor, P->max_iters, P->lm_max_iterations };
+    guess_to_T0(guess, T0);
     LmResult lr;
-    rc = lm_optimise([&](const double T[16], bool hess, double out[kOut]) { return evaluate(r, T, hess, out); }, T0, lp, &lr);
+    rc = lm_optimise([&](const double T[16], bool hess, double out[kOut]) { return evaluate(r, T, hess, out); }, T0, lm_params_of(*P), &lr);
     if (rc) return rc;
     ctx_prof_collect(c);
-    memcpy(res->final_transform, lr.T, sizeof lr.T);
-    res->converged = lr.converged; res->iters = lr.iters; res->n_evals = lr.n_evals; res->n_rejected = lr.n_rejected;
-    res->n_pairs_last = lr.n_pairs_last; res->error = lr.error; res->lambda = lr.lambda;
+    lm_result_to(lr, res);
     if (aligned_out) {                                    // the source under the final transformation (in float, like lisreg_transform_cloud)
         float F[12];
         for (int k = 0; k < 12; ++k) F[k] = (float)lr.T[k];
-        HIPCHK(c, c->vox_M.ensure(sizeof(float) * 12));
-        HIPCHK(c, hipMemcpyAsync(c->vox_M.p, F, sizeof F, hipMemcpyHostToDevice, st));
-        if (fmt == LISREG_FMT_DEVICE) {
-            launch_transform_cloud(raw, n, c->vox_M.as<float>(), static_cast<float4*>(aligned_out), st);
-            HIPCHK(c, hipStreamSynchronize(st));
-        } else {
-            HIPCHK(c, c->vg_sorted.ensure(sizeof(float4) * (size_t)n));
-            launch_transform_cloud(raw, n, c->vox_M.as<float>(), c->vg_sorted.as<float4>(), st);
-            std::vector<float4> hp((size_t)n);
-            HIPCHK(c, hipMemcpyAsync(hp.data(), c->vg_sorted.p, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            const unsigned char* b = static_cast<const unsigned char*>(source);
-            unsigned char* o = static_cast<unsigned char*>(aligned_out);
-            for (int i = 0; i < n; ++i) {
-                if (o != b) memcpy(o + (size_t)i * (size_t)stride, b + (size_t)i * (size_t)stride, (size_t)stride);
-                memcpy(o + (size_t)i * (size_t)stride, &hp[(size_t)i], 12);
-            }
-        }
+        return emit_aligned(c, raw, n, F, source, stride, fmt, c->vg_sorted, aligned_out);
     }
     return LISREG_OK;
 }

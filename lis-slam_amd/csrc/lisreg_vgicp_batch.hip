@@ -4,20 +4,15 @@
 // (select_registration_method("FAST_VGICP"), :2771).  The definition is tests/vgicp_batch_ref.py: the loop of single alignments plus the
 // fitness score and the `best` rule of §7m.  Every item of a batch gets the bits lisreg_vgicp_align returns for it alone: the lanes run
 // the same body (lisreg_vgicp_lane.hpp) over the same partition of the source into wavefronts, the partial records are added in
-// k_vgicp_total's order (lisreg_batch_rounds.hpp), and the Levenberg-Marquardt loop is lm_optimise turned inside out
-// (lisreg_lm_stepper.hpp).  What the batch saves: a source's distributions are made once per call, and the outstanding evaluations of
-// ALL unfinished items are answered by one round of launches and one synchronisation.  VGICP derives its pairs again at every
-// evaluation, so an item owns no device memory.  The fitness score searches the grid lisreg_vgicp_set_target keeps with the slot, with
-// FastGICP's search (lisreg_fgicp_lane.hpp).  No LDS, no atomics, no CPU fallback.
+// k_vgicp_total's order (lisreg_batch_rounds.hpp), and the Levenberg-Marquardt loop is the single aligner's (lisreg_lm_stepper.hpp).
+// What the batch saves: a source's distributions are made once per call, and the outstanding evaluations of ALL unfinished items are
+// answered by one round of launches and one synchronisation.  VGICP derives its pairs again at every evaluation, so an item owns no
+// device memory.  The fitness score searches the grid lisreg_vgicp_set_target keeps with the slot, with FastGICP's search
+// (lisreg_fgicp_lane.hpp).  This unit holds the linearising kernel and what it launches per round; the host side of a call is the
+// driver both batch units share (lisreg_batch_driver.hpp).  No LDS, no atomics, no CPU fallback.
 #include "lisreg_batch_rounds.hpp"
 #include "lisreg_vgicp_lane.hpp"
-#include "lisreg_lm_stepper.hpp"
-
-#include <cfloat>
-#include <climits>
-#include <cmath>
-#include <cstring>
-#include <vector>
+#include "lisreg_batch_driver.hpp"
 
 using namespace lisreg;
 using namespace lisreg::vgicp_host;
@@ -31,15 +26,6 @@ struct VgWork {
     VgPose    P;
     long long src_off;     // the source's first finite point in the batch's point / covariance buffers
     int       n;           // finite points of the source
-    int       reserved;
-};
-
-// One item at its final pose, for the fitness pass: the search grid of its target instead of the voxels
-struct VgFitWork {
-    FgTarget  A;           // cov = nullptr: the search reads the points and the cells only
-    FgPose    P;
-    long long src_off;
-    int       n;
     int       reserved;
 };
 
@@ -69,50 +55,47 @@ __global__ __launch_bounds__(64) void k_vgicp_linearize_batch(const VgWork* __re
     }
 }
 
-// The fitness pass: the nearest finite target point of every finite source point at the item's final pose, without a cut-off; the
-// wavefront's sum of the squared distances goes to the workgroup's partial.
-__global__ __launch_bounds__(64) void k_vgicp_fitness_batch(const VgFitWork* __restrict__ work, const int* __restrict__ wg_start, int n_entries,
-                                                            const float4* __restrict__ src, double* __restrict__ part)
-{
-    const int g = blockIdx.x;
-    const int e = fg_entry_of(wg_start, 0, n_entries, g);
-    const VgFitWork* __restrict__ w = work + e;
-    const int n = w->n;
-    const int i = (g - wg_start[e]) * 64 + (int)threadIdx.x;
-    double d2 = 0.0;
-    if (i < n) {
-        const FgTarget A = w->A;
-        const FgPose   P = w->P;
-        double qx, qy, qz, bd;
-        int    bj;
-        fg_transform(P, src[(size_t)w->src_off + (size_t)i], qx, qy, qz);
-        fg_search_lane(A, qx, qy, qz, HUGE_VAL, HUGE_VAL, bd, bj);
-        d2 = bj >= 0 ? bd : 0.0;
+// ---- host: what VGICP supplies to the driver of lisreg_batch_driver.hpp -------------------------------------------------------------------
+struct VgBatch {
+    static constexpr const char* kWho = "vgicp_align_batch";
+    using Params = lisreg_vgicp_params;
+    using ItemC  = lisreg_vgicp_item;
+    using Result = lisreg_vgicp_result;
+    using Info   = lisreg_vgicp_batch_info;
+    using Target = VgicpTarget;
+    using Work   = VgWork;
+    static constexpr bool kFitnessTotalsApart = false;             // the fitness pass: "solve" = the search with its totals, one interval
+
+    static BatchBufs& bufs(lisreg_ctx* c) { return c->vgb; }
+    static int check_params(lisreg_ctx* c, const Params* P) { return vg_check_params(c, P, kWho); }
+    // (with P: params->resolution must be the resolution of EVERY named slot)
+    static int find_target(lisreg_ctx* c, int slot, const Params* P, Target** T) { return vg_find_target(c, slot, P, kWho, T); }
+    static hipError_t ensure_lanes(lisreg_ctx*, long long) { return hipSuccess; }      // an item owns no device memory
+
+    // the search's view of the grid a slot keeps (cov = nullptr: the search reads the points and the cells only)
+    static FgTarget fit_view(const Target& G)
+    {
+        FgTarget A;
+        A.sorted = G.sorted.as<float4>(); A.cell_start = G.cells.as<int>(); A.cov = nullptr;
+        A.ox = G.grid.ox; A.oy = G.grid.oy; A.oz = G.grid.oz; A.cell = G.grid.cell; A.nx = G.grid.nx; A.ny = G.grid.ny; A.nz = G.grid.nz;
+        for (int k = 0; k < 3; ++k) { A.b0[k] = (double)G.bb[k]; A.b1[k] = (double)G.bb[3 + k]; }
+        return A;
     }
-    d2 = fg_wave_sum(d2);
-    if (threadIdx.x == 0) part[g] = d2;
-}
 
-// ---- host ---------------------------------------------------------------------------------------------------------------------------
-constexpr const char* kWho = "vgicp_align_batch";
+    static void fill(const Target& T, const double Tm[16], long long src_off, long long, int n, Work* w)
+    {
+        w->G = vg_grid_view(T);
+        w->P = vgicp_host::pose_of<VgPose>(Tm);
+        w->src_off = src_off; w->n = n; w->reserved = 0;
+    }
 
-struct Source { bool used = false; int m = 0; long long off = 0; };
-struct Item { LmStepper lm; const VgicpTarget* T = nullptr; int src = 0, nb = 0; };
-
-// where the work table of a round lives in its buffer: the entries (of the larger of the two kinds), then the n_entries + 1 workgroup starts
-constexpr size_t kEntryBytes = sizeof(VgWork) > sizeof(VgFitWork) ? sizeof(VgWork) : sizeof(VgFitWork);
-size_t starts_offset(int n_items) { return kEntryBytes * (size_t)n_items; }
-size_t table_bytes(int n_items) { return starts_offset(n_items) + sizeof(int) * ((size_t)n_items + 1); }
-
-// the search's view of the grid a slot keeps
-FgTarget fit_view(const VgicpTarget& G)
-{
-    FgTarget A;
-    A.sorted = G.sorted.as<float4>(); A.cell_start = G.cells.as<int>(); A.cov = nullptr;
-    A.ox = G.grid.ox; A.oy = G.grid.oy; A.oz = G.grid.oz; A.cell = G.grid.cell; A.nx = G.grid.nx; A.ny = G.grid.ny; A.nz = G.grid.nz;
-    for (int k = 0; k < 3; ++k) { A.b0[k] = (double)G.bb[k]; A.b1[k] = (double)G.bb[3 + k]; }
-    return A;
-}
+    static void launch_round(lisreg_ctx* c, const Params&, const BatchRound<Work>& r)
+    {
+        ctx_prof_mark(c, 0);                                       // lisreg_get_timing: "assoc" = the evaluations of a round (with the totals), one interval
+        if (r.n_lin) k_vgicp_linearize_batch<true><<<r.g_lin, 64, 0, r.st>>>(r.work, r.start, 0, r.n_lin, r.src, r.cov, r.part);
+        if (r.ne > r.n_lin) k_vgicp_linearize_batch<false><<<r.g - r.g_lin, 64, 0, r.st>>>(r.work, r.start, r.n_lin, r.ne, r.src, r.cov, r.part);
+    }
+};
 
 }  // namespace
 
@@ -120,161 +103,5 @@ extern "C" int lisreg_vgicp_align_batch(lisreg_ctx* c, const void* const* source
                                         const lisreg_vgicp_item* items, int n_items, const lisreg_vgicp_params* P,
                                         lisreg_vgicp_result* results, double* fitness, lisreg_vgicp_batch_info* info)
 {
-    if (!c) return LISREG_ERR_ARG;
-    if (n_items < 0 || n_sources < 0) return bad(c, std::string(kWho) + ": n_items < 0 or n_sources < 0");
-    if (info) *info = lisreg_vgicp_batch_info{ -1, 0, 0, 0 };
-    if (n_items == 0) return LISREG_OK;
-    // ---- every refusal that needs no device, for the whole batch ----------------------------------------------------------------
-    if (!items || !results || !sources || !n) return bad(c, std::string(kWho) + ": NULL items / results / sources / n");
-    int rc = vg_check_params(c, P, kWho);
-    if (rc) return rc;
-    std::vector<Source> S((size_t)n_sources);
-    std::vector<Item>   I((size_t)n_items);
-    for (int k = 0; k < n_items; ++k) {
-        if (items[k].source < 0 || items[k].source >= n_sources) return bad(c, std::string(kWho) + ": an item's source index is out of range");
-        VgicpTarget* T = nullptr;
-        rc = vg_find_target(c, items[k].slot, P, kWho, &T);        // (with P: params->resolution must be the resolution of EVERY named slot)
-        if (rc) return rc;
-        I[k].T = T; I[k].src = items[k].source;
-        S[items[k].source].used = true;
-    }
-    size_t cap = 0;
-    for (int s = 0; s < n_sources; ++s) {
-        if (!S[s].used) continue;                                  // a source no item names is neither checked nor staged
-        rc = check_cloud(c, kWho, sources[s], n[s], stride, fmt, kFmtPackable, false);
-        if (rc) return rc;
-        cap += (size_t)n[s];
-    }
-    // ---- the sources' distributions, once each; a cloud they refuse (too few finite points, an infinite coordinate) ends the call
-    // before any alignment work, with `results` untouched.  The context's scratch is overwritten by the next source: the batch keeps copies
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    HIPCHK(c, c->vgb_src.ensure(sizeof(float4) * cap));
-    HIPCHK(c, c->vgb_cov.ensure(sizeof(double) * 6 * cap));
-    long long off = 0;
-    int n_staged = 0;
-    for (int s = 0; s < n_sources; ++s) {
-        if (!S[s].used) continue;
-        const float4* raw = nullptr;
-        rc = stage_records(c, sources[s], n[s], stride, fmt, c->vg_raw, &raw);
-        if (rc) return rc;
-        float bb[6];
-        int m = 0;
-        rc = vg_distributions(c, kWho, raw, n[s], P->k_correspondences, P->plane_epsilon, 0.f, bb, &m, nullptr, nullptr);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->vgb_src.as<float4>() + off, c->vg_pts.p, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->vgb_cov.as<double>() + 6 * off, c->vg_cov.p, sizeof(double) * 6 * (size_t)m, hipMemcpyDeviceToDevice, st));
-        S[s].m = m; S[s].off = off;
-        off += m;
-        ++n_staged;
-    }
-    // ---- the round's storage: one partial record per workgroup, one total per item -----------------------------------------------------
-    long long wgs = 0;
-    for (int k = 0; k < n_items; ++k) { I[k].nb = (S[I[k].src].m + 63) / 64; wgs += I[k].nb; }
-    if (wgs > (long long)INT_MAX / kOut) return bad(c, std::string(kWho) + ": the batch is too large (items x source points)");
-    HIPCHK(c, c->vgb_part.ensure(sizeof(double) * kOut * (size_t)wgs));
-    HIPCHK(c, c->vgb_out.ensure(sizeof(double) * kOut * (size_t)n_items));
-    HIPCHK(c, c->vgb_work.ensure(table_bytes(n_items)));
-    HIPCHK(c, c->vgb_host_work.ensure(table_bytes(n_items), table_bytes(n_items) + table_bytes(n_items) / 2));
-    HIPCHK(c, c->vgb_host_out.ensure(sizeof(double) * kOut * (size_t)n_items, sizeof(double) * kOut * ((size_t)n_items + (size_t)n_items / 2)));
-    int* const     h_start = reinterpret_cast<int*>(static_cast<char*>(c->vgb_host_work.p) + starts_offset(n_items));
-    const int*     d_start = reinterpret_cast<const int*>(static_cast<const char*>(c->vgb_work.p) + starts_offset(n_items));
-    const float4*  d_src = c->vgb_src.as<float4>();
-    // the table of a round goes up in two copies: the entries and, behind them, the starts (the gap between them is not read)
-    auto upload = [&](int ne, size_t entry_bytes) -> hipError_t {
-        hipError_t e = hipMemcpyAsync(c->vgb_work.p, c->vgb_host_work.p, entry_bytes * (size_t)ne, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        return hipMemcpyAsync(const_cast<int*>(d_start), h_start, sizeof(int) * ((size_t)ne + 1), hipMemcpyHostToDevice, st);
-    };
-    // ---- the LM phase, in lockstep rounds: every unfinished item has one request outstanding -----------------------------------------
-    const LmParams lp{ P->transformation_epsilon, P->rotation_epsilon, P->lm_init_lambda_factor, P->max_iters, P->lm_max_iterations };
-    for (int k = 0; k < n_items; ++k) {
-        const float* guess = items[k].guess;
-        double T0[16];
-        for (int q = 0; q < 16; ++q) T0[q] = guess ? (double)guess[q] : (q % 5 == 0 ? 1.0 : 0.0);
-        T0[12] = T0[13] = T0[14] = 0.0; T0[15] = 1.0;
-        I[k].lm.start(T0, lp);
-    }
-    VgWork* const  h_work = c->vgb_host_work.as<VgWork>();
-    const VgWork*  d_work = c->vgb_work.as<VgWork>();
-    std::vector<int> order((size_t)n_items);
-    int n_rounds = 0;
-    for (;;) {
-        int ne = 0, n_lin = 0;
-        for (int k = 0; k < n_items; ++k) if (!I[k].lm.finished() && I[k].lm.req_hessian) order[ne++] = k;
-        n_lin = ne;
-        for (int k = 0; k < n_items; ++k) if (!I[k].lm.finished() && !I[k].lm.req_hessian) order[ne++] = k;
-        if (!ne) break;
-        int g = 0;
-        for (int e = 0; e < ne; ++e) {
-            const Item& it = I[order[e]];
-            const double* T = it.lm.req_T;
-            VgWork* w = h_work + e;
-            w->G = vg_grid_view(*it.T);
-            for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) w->P.R[3 * i + j] = T[4 * i + j]; w->P.t[i] = T[4 * i + 3]; }
-            w->src_off = S[it.src].off; w->n = S[it.src].m; w->reserved = 0;
-            h_start[e] = g; g += it.nb;
-        }
-        h_start[ne] = g;
-        const int g_lin = h_start[n_lin];
-        HIPCHK(c, upload(ne, sizeof(VgWork)));
-        ctx_prof_mark(c, 0);                                       // lisreg_get_timing: "assoc" = the evaluations of a round (with the totals), one interval
-        if (n_lin) k_vgicp_linearize_batch<true><<<g_lin, 64, 0, st>>>(d_work, d_start, 0, n_lin, d_src, c->vgb_cov.as<double>(),
-                                                                        c->vgb_part.as<double>());
-        if (ne > n_lin) k_vgicp_linearize_batch<false><<<g - g_lin, 64, 0, st>>>(d_work, d_start, n_lin, ne, d_src, c->vgb_cov.as<double>(),
-                                                                                 c->vgb_part.as<double>());
-        k_fgicp_total_batch<kOut><<<ne, 64, 0, st>>>(c->vgb_part.as<double>(), d_start, c->vgb_out.as<double>());
-        ctx_prof_mark(c, -1);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->vgb_host_out.p, c->vgb_out.p, sizeof(double) * kOut * (size_t)ne, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        const double* out = c->vgb_host_out.as<double>();
-        for (int e = 0; e < ne; ++e) I[order[e]].lm.feed(out + (size_t)e * kOut);
-        ++n_rounds;
-    }
-    // ---- the fitness pass: every item at its final pose, converged or not -------------------------------------------------------------
-    std::vector<double> fit;
-    if (fitness) {
-        VgFitWork* const h_fit = c->vgb_host_work.as<VgFitWork>();
-        int g = 0;
-        for (int k = 0; k < n_items; ++k) {
-            const double* T = I[k].lm.res.T;
-            VgFitWork* w = h_fit + k;
-            w->A = fit_view(*I[k].T);
-            for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) w->P.R[3 * i + j] = T[4 * i + j]; w->P.t[i] = T[4 * i + 3]; }
-            w->src_off = S[I[k].src].off; w->n = S[I[k].src].m; w->reserved = 0;
-            h_start[k] = g; g += I[k].nb;
-        }
-        h_start[n_items] = g;
-        HIPCHK(c, upload(n_items, sizeof(VgFitWork)));
-        ctx_prof_mark(c, 1);                                       // "solve" = the fitness search (with its totals), one interval
-        k_vgicp_fitness_batch<<<g, 64, 0, st>>>(c->vgb_work.as<VgFitWork>(), d_start, n_items, d_src, c->vgb_part.as<double>());
-        k_fgicp_total_batch<1><<<n_items, 64, 0, st>>>(c->vgb_part.as<double>(), d_start, c->vgb_out.as<double>());
-        ctx_prof_mark(c, -1);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->vgb_host_out.p, c->vgb_out.p, sizeof(double) * (size_t)n_items, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        fit.assign(c->vgb_host_out.as<double>(), c->vgb_host_out.as<double>() + n_items);
-        for (int k = 0; k < n_items; ++k) fit[k] /= (double)S[I[k].src].m;
-    } else {
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    ctx_prof_collect(c);
-    // ---- nothing can fail any more: the results, and the winner as subMapOptmizationNode.cpp:2834-2840 picks it -------------------------
-    int best = -1;
-    double best_score = DBL_MAX;
-    for (int k = 0; k < n_items; ++k) {
-        const LmResult& lr = I[k].lm.res;
-        lisreg_vgicp_result* res = results + k;
-        memcpy(res->final_transform, lr.T, sizeof lr.T);
-        res->converged = lr.converged; res->iters = lr.iters; res->n_evals = lr.n_evals; res->n_rejected = lr.n_rejected;
-        res->n_pairs_last = lr.n_pairs_last; res->error = lr.error; res->lambda = lr.lambda;
-        if (!fitness) continue;
-        fitness[k] = fit[k];
-        if (lr.converged == 0 || fit[k] > best_score) continue;
-        best_score = fit[k];
-        best = k;
-    }
-    if (info) *info = lisreg_vgicp_batch_info{ best, n_rounds, n_staged, 0 };
-    return LISREG_OK;
+    return batch_align<VgBatch>(c, sources, n, n_sources, stride, fmt, items, n_items, P, results, fitness, info);
 }

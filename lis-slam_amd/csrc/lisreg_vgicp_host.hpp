@@ -1,6 +1,7 @@
-// lisreg_vgicp_host.hpp — the host half of the VGICP registration (lisreg_vgicp.hip): the SE(3) exponential, the damped 6 x 6 solve and
-// the Levenberg-Marquardt bookkeeping, in double, statement by statement what tests/vgicp_ref.py defines.  Plain C++ (no HIP), so that
-// it can be compiled and checked on its own.  Not installed.
+// lisreg_vgicp_host.hpp — the host half of the VGICP registration (lisreg_vgicp.hip): the SE(3) exponential, the damped 6 x 6 solve, the
+// convergence test and the parameter / result records of the Levenberg-Marquardt loop (the loop itself: lisreg_lm_stepper.hpp), in
+// double, statement by statement what tests/vgicp_ref.py defines, and the small conversions the family's entry points share.  Plain C++
+// (no HIP), so that it can be compiled and checked on its own.  Not installed.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -100,72 +101,36 @@ struct LmResult {
     double error, lambda;
 };
 
-// The Levenberg-Marquardt loop of LsqRegistration::step_lm as tests/vgicp_ref.py restates it.  eval(T, with_hessian, out[29]) -> 0 or an
-// error code (returned at once).  lambda starts at init_lambda_factor max|diag H| of the first linearisation and is carried across the
-// outer iterations; NOT (rho >= 0) is a rejection; a trial loop that runs out, or a system that is not positive definite, ends the
-// alignment unconverged.  No NaN can reach T: a step is applied only after solve_damped vouched for a finite delta.
-template <class Eval>
-int lm_optimise(Eval&& eval, const double T0[16], const LmParams& P, LmResult* res)
+// ---- what the four entry points of the fast_gicp family (the two aligners and their batch forms) do around the loop ---------------
+// the start of a run: the caller's row-major 4 x 4 (NULL: the identity) in double, the last row forced to 0 0 0 1
+inline void guess_to_T0(const float* guess, double T0[16])
 {
-    double T[16], out[kOut];
-    memcpy(T, T0, sizeof T);
-    int rc = eval(T, true, out);
-    if (rc) return rc;
-    res->converged = 0; res->iters = 0; res->n_evals = 1; res->n_rejected = 0;
-    double e = out[0], lam = 0.0;
-    long long pairs = (long long)out[28];
-    if (pairs > 0) {
-        for (int k = 0, q = 7; k < 6; q += 6 - k, ++k) lam = std::max(lam, fabs(out[q]));         // the diagonal of the packed triangle
-        lam *= P.init_lambda_factor;
-        for (int it = 0; it < P.max_iters; ++it) {
-            if (it) {
-                rc = eval(T, true, out);
-                if (rc) return rc;
-                ++res->n_evals;
-                e = out[0]; pairs = (long long)out[28];
-            }
-            res->iters = it + 1;
-            double H[36], b[6];
-            for (int k = 0; k < 6; ++k) b[k] = out[1 + k];
-            for (int i = 0, q = 7; i < 6; ++i)
-                for (int j = i; j < 6; ++j, ++q) H[6 * i + j] = H[6 * j + i] = out[q];
-            double nu = 2.0;
-            bool stop = false, accepted = false;
-            for (int trial = 0; trial < P.lm_max_iterations; ++trial) {
-                double delta[6], E[16], Tn[16], o2[kOut];
-                if (!solve_damped(H, b, lam, delta)) { stop = true; break; }
-                se3_exp(delta, E);
-                mul_rigid(E, T, Tn);
-                rc = eval(Tn, false, o2);
-                if (rc) return rc;
-                ++res->n_evals;
-                const double en = o2[0];
-                pairs = (long long)o2[28];
-                double den = 0.0;
-                for (int k = 0; k < 6; ++k) den += delta[k] * (lam * delta[k] - b[k]);
-                const double rho = (e - en) / den;
-                const bool dconv = delta_converged(delta, P.rotation_epsilon, P.transformation_epsilon);
-                if (!(rho >= 0.0)) {
-                    ++res->n_rejected;
-                    if (dconv) { res->converged = 1; stop = true; break; }
-                    lam = nu * lam; nu = 2.0 * nu;
-                    continue;
-                }
-                memcpy(T, Tn, sizeof T);
-                e = en;
-                const double c = 2.0 * rho - 1.0;
-                lam = lam * std::max(1.0 / 3.0, 1.0 - c * c * c);
-                accepted = true;
-                if (dconv) { res->converged = 1; stop = true; }
-                break;
-            }
-            if (!accepted) stop = true;                             // rejected while converged, not positive definite, or out of trials
-            if (stop) break;
-        }
-    }
-    memcpy(res->T, T, sizeof T);
-    res->error = e; res->lambda = lam; res->n_pairs_last = pairs;
-    return 0;
+    for (int k = 0; k < 16; ++k) T0[k] = guess ? (double)guess[k] : (k % 5 == 0 ? 1.0 : 0.0);
+    T0[12] = T0[13] = T0[14] = 0.0; T0[15] = 1.0;
+}
+
+// R[9], t[3] of a row-major 4 x 4 (VgPose, FgPose)
+template <class Pose>
+inline Pose pose_of(const double T[16])
+{
+    Pose P;
+    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) P.R[3 * i + j] = T[4 * i + j]; P.t[i] = T[4 * i + 3]; }
+    return P;
+}
+
+// lisreg_vgicp_params / lisreg_fgicp_params -> LmParams, LmResult -> lisreg_vgicp_result / lisreg_fgicp_result
+template <class Params>
+inline LmParams lm_params_of(const Params& P)
+{
+    return LmParams{ P.transformation_epsilon, P.rotation_epsilon, P.lm_init_lambda_factor, P.max_iters, P.lm_max_iterations };
+}
+
+template <class Result>
+inline void lm_result_to(const LmResult& lr, Result* res)
+{
+    memcpy(res->final_transform, lr.T, sizeof lr.T);
+    res->converged = lr.converged; res->iters = lr.iters; res->n_evals = lr.n_evals; res->n_rejected = lr.n_rejected;
+    res->n_pairs_last = lr.n_pairs_last; res->error = lr.error; res->lambda = lr.lambda;
 }
 
 }  // namespace vgicp_host

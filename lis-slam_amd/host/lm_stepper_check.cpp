@@ -1,4 +1,6 @@
-// lm_stepper_check.cpp — LmStepper (csrc/lisreg_lm_stepper.hpp) against lm_optimise (csrc/lisreg_vgicp_host.hpp) on scripted
+// lm_stepper_check.cpp — LmStepper (csrc/lisreg_lm_stepper.hpp), the library's only Levenberg-Marquardt loop, against the same loop
+// in closed form (lm_closed_loop below: what the single aligners ran as lm_optimise before they, too, went through the stepper; it is
+// kept here as the independent restatement and is never a wrapper around the stepper) on scripted
 // evaluations.  A script is a table of out[29] records: call k of eval gets record k (the last one again when the
 // table runs out), whatever T is asked for, so both drivers see the same answers as long as they ask the same questions in the same
 // order.  Compared per script: the request sequence (the bytes of T and the with_hessian flag of every call) and the bytes of every
@@ -14,6 +16,74 @@
 using namespace lisreg::vgicp_host;
 
 namespace {
+
+// The Levenberg-Marquardt loop of LsqRegistration::step_lm as tests/vgicp_ref.py restates it.  eval(T, with_hessian, out[29]) -> 0 or an
+// error code (returned at once).  lambda starts at init_lambda_factor max|diag H| of the first linearisation and is carried across the
+// outer iterations; NOT (rho >= 0) is a rejection; a trial loop that runs out, or a system that is not positive definite, ends the
+// alignment unconverged.  No NaN can reach T: a step is applied only after solve_damped vouched for a finite delta.
+template <class Eval>
+int lm_closed_loop(Eval&& eval, const double T0[16], const LmParams& P, LmResult* res)
+{
+    double T[16], out[kOut];
+    memcpy(T, T0, sizeof T);
+    int rc = eval(T, true, out);
+    if (rc) return rc;
+    res->converged = 0; res->iters = 0; res->n_evals = 1; res->n_rejected = 0;
+    double e = out[0], lam = 0.0;
+    long long pairs = (long long)out[28];
+    if (pairs > 0) {
+        for (int k = 0, q = 7; k < 6; q += 6 - k, ++k) lam = std::max(lam, fabs(out[q]));         // the diagonal of the packed triangle
+        lam *= P.init_lambda_factor;
+        for (int it = 0; it < P.max_iters; ++it) {
+            if (it) {
+                rc = eval(T, true, out);
+                if (rc) return rc;
+                ++res->n_evals;
+                e = out[0]; pairs = (long long)out[28];
+            }
+            res->iters = it + 1;
+            double H[36], b[6];
+            for (int k = 0; k < 6; ++k) b[k] = out[1 + k];
+            for (int i = 0, q = 7; i < 6; ++i)
+                for (int j = i; j < 6; ++j, ++q) H[6 * i + j] = H[6 * j + i] = out[q];
+            double nu = 2.0;
+            bool stop = false, accepted = false;
+            for (int trial = 0; trial < P.lm_max_iterations; ++trial) {
+                double delta[6], E[16], Tn[16], o2[kOut];
+                if (!solve_damped(H, b, lam, delta)) { stop = true; break; }
+                se3_exp(delta, E);
+                mul_rigid(E, T, Tn);
+                rc = eval(Tn, false, o2);
+                if (rc) return rc;
+                ++res->n_evals;
+                const double en = o2[0];
+                pairs = (long long)o2[28];
+                double den = 0.0;
+                for (int k = 0; k < 6; ++k) den += delta[k] * (lam * delta[k] - b[k]);
+                const double rho = (e - en) / den;
+                const bool dconv = delta_converged(delta, P.rotation_epsilon, P.transformation_epsilon);
+                if (!(rho >= 0.0)) {
+                    ++res->n_rejected;
+                    if (dconv) { res->converged = 1; stop = true; break; }
+                    lam = nu * lam; nu = 2.0 * nu;
+                    continue;
+                }
+                memcpy(T, Tn, sizeof T);
+                e = en;
+                const double c = 2.0 * rho - 1.0;
+                lam = lam * std::max(1.0 / 3.0, 1.0 - c * c * c);
+                accepted = true;
+                if (dconv) { res->converged = 1; stop = true; }
+                break;
+            }
+            if (!accepted) stop = true;                             // rejected while converged, not positive definite, or out of trials
+            if (stop) break;
+        }
+    }
+    memcpy(res->T, T, sizeof T);
+    res->error = e; res->lambda = lam; res->n_pairs_last = pairs;
+    return 0;
+}
 
 struct Rng {                                          // splitmix64: the same scripts everywhere
     uint64_t s;
@@ -106,8 +176,8 @@ int main(int argc, char** argv)
         Scripted a{ s, 0, {} }, b{ s, 0, {} };
         LmResult want;
         memset(&want, 0, sizeof want);
-        const int rc = lm_optimise([&](const double T[16], bool hess, double out[kOut]) { memcpy(out, a.answer(T, hess), sizeof(double) * kOut); return 0; },
-                                   s.T0, s.P, &want);
+        const int rc = lm_closed_loop([&](const double T[16], bool hess, double out[kOut]) { memcpy(out, a.answer(T, hess), sizeof(double) * kOut); return 0; },
+                                      s.T0, s.P, &want);
         LmStepper st;
         st.start(s.T0, s.P);
         for (bool more = true; more;) more = st.feed(b.answer(st.req_T, st.req_hessian));

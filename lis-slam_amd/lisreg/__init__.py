@@ -1637,18 +1637,22 @@ class Context:
         self._chk(self._L.lisreg_vgicp_set_target(self._h, slot, ptr, n, stride, fmt, C.byref(params), C.byref(info)))
         return dict(dims=list(info.dims), n_voxels=info.n_voxels, n_points=info.n_points)
 
-    def vgicp_align(self, slot: int, source, params: "VgicpParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
-        """FastVGICP::align against the VGICP target in `slot`; returns the result dict (+ 'aligned')."""
+    def _gicp_align(self, fn, result_type, slot, source, params, guess, want_aligned, out_ptr) -> dict:
+        """one alignment of the fast_gicp family through `fn`; returns the result dict (+ 'aligned')."""
         ptr, n, stride, fmt, keep = self._cloud_args(source)
-        res = VgicpResult()
+        res = result_type()
         g = None if guess is None else np.ascontiguousarray(guess, np.float32).ravel().ctypes.data_as(C.POINTER(C.c_float))
         out = np.zeros_like(keep) if (want_aligned and keep is not None) else None
         o = C.c_void_p(out_ptr) if out_ptr else (_vp(out) if out is not None else None)
-        self._chk(self._L.lisreg_vgicp_align(self._h, slot, ptr, n, stride, fmt, C.byref(params), g, C.byref(res), o))
+        self._chk(fn(self._h, slot, ptr, n, stride, fmt, C.byref(params), g, C.byref(res), o))
         d = res.as_dict()
         if out is not None:
             d["aligned"] = out
         return d
+
+    def vgicp_align(self, slot: int, source, params: "VgicpParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
+        """FastVGICP::align against the VGICP target in `slot`; returns the result dict (+ 'aligned')."""
+        return self._gicp_align(self._L.lisreg_vgicp_align, VgicpResult, slot, source, params, guess, want_aligned, out_ptr)
 
     def vgicp_covariances(self, cloud, k: int = 20, want_neighbours: bool = True, cell_edge: float = 0.0):
         """(cov6 [n, 6] with NaN rows for NaN points, neighbours [n, k] or None) of every point's distribution"""
@@ -1693,16 +1697,7 @@ class Context:
 
     def fgicp_align(self, slot: int, source, params: "FgicpParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
         """FastGICP::align against the FastGICP target in `slot`; returns the result dict (+ 'aligned')."""
-        ptr, n, stride, fmt, keep = self._cloud_args(source)
-        res = FgicpResult()
-        g = None if guess is None else np.ascontiguousarray(guess, np.float32).ravel().ctypes.data_as(C.POINTER(C.c_float))
-        out = np.zeros_like(keep) if (want_aligned and keep is not None) else None
-        o = C.c_void_p(out_ptr) if out_ptr else (_vp(out) if out is not None else None)
-        self._chk(self._L.lisreg_fgicp_align(self._h, slot, ptr, n, stride, fmt, C.byref(params), g, C.byref(res), o))
-        d = res.as_dict()
-        if out is not None:
-            d["aligned"] = out
-        return d
+        return self._gicp_align(self._L.lisreg_fgicp_align, FgicpResult, slot, source, params, guess, want_aligned, out_ptr)
 
     def fgicp_correspondences(self, slot: int, source, params: "FgicpParams", T, want_sqdist: bool = True):
         """the search at T (4x4): (index [n] in the caller's target cloud, -1 none; squared distance [n], NaN where -1, or None)"""
@@ -1728,49 +1723,39 @@ class Context:
                                                  out.ctypes.data_as(dp), C.byref(pairs)))
         return out, pairs.value
 
-    # -- §7m: FastGICP verification of a candidate list -----------------------------------------------------
-    def fgicp_align_batch(self, sources, items, params: "FgicpParams", want_fitness: bool = True):
-        """lisreg_fgicp_align_batch: sources = a list of clouds (all host PCL-struct arrays of one dtype, or all (device_ptr, n)),
-        items = a list of FgicpItem.  Returns (results: a list of fgicp_align's dicts, fitness [n_items] or None, info dict)."""
+    # -- §7m, §7n: FastGICP / VGICP verification of a candidate list -----------------------------------------
+    def _gicp_align_batch(self, fn, item_type, result_type, info_type, who, sources, items, params, want_fitness):
+        """one batch call of the fast_gicp family through `fn`; returns (results: a list of the single call's dicts, fitness [n_items] or
+        None, info dict)."""
         args = [self._cloud_args(s) for s in sources]
         if len({(a[2], a[3]) for a in args}) > 1:
-            raise ValueError("fgicp_align_batch: the sources of one call share one layout")
+            raise ValueError(who + ": the sources of one call share one layout")
         stride, fmt = (args[0][2], args[0][3]) if args else (16, FMT_DEVICE)
         ptrs = (C.c_void_p * max(len(args), 1))(*[a[0] for a in args])
         ns = (C.c_int * max(len(args), 1))(*[a[1] for a in args])
-        its = (FgicpItemC * max(len(items), 1))()
+        its = (item_type * max(len(items), 1))()
         for k, it in enumerate(items):
             its[k].source, its[k].slot = it.source, it.slot
             its[k].guess = None if it.guess is None else it.guess.ctypes.data_as(C.POINTER(C.c_float))
-        res = (FgicpResult * max(len(items), 1))()
+        res = (result_type * max(len(items), 1))()
         fit = np.zeros(max(len(items), 1)) if want_fitness else None
-        info = FgicpBatchInfo()
-        self._chk(self._L.lisreg_fgicp_align_batch(self._h, ptrs, ns, len(args), stride, fmt, its, len(items), C.byref(params), res,
-                                                   fit.ctypes.data_as(C.POINTER(C.c_double)) if want_fitness else None, C.byref(info)))
+        info = info_type()
+        self._chk(fn(self._h, ptrs, ns, len(args), stride, fmt, its, len(items), C.byref(params), res,
+                     fit.ctypes.data_as(C.POINTER(C.c_double)) if want_fitness else None, C.byref(info)))
         return ([res[k].as_dict() for k in range(len(items))], fit[:len(items)] if want_fitness else None,
                 dict(best=info.best, n_rounds=info.n_rounds, n_sources_staged=info.n_sources_staged))
 
-    # -- §7n: VGICP verification of a candidate list ---------------------------------------------------------
+    def fgicp_align_batch(self, sources, items, params: "FgicpParams", want_fitness: bool = True):
+        """lisreg_fgicp_align_batch: sources = a list of clouds (all host PCL-struct arrays of one dtype, or all (device_ptr, n)),
+        items = a list of FgicpItem.  Returns (results: a list of fgicp_align's dicts, fitness [n_items] or None, info dict)."""
+        return self._gicp_align_batch(self._L.lisreg_fgicp_align_batch, FgicpItemC, FgicpResult, FgicpBatchInfo, "fgicp_align_batch",
+                                      sources, items, params, want_fitness)
+
     def vgicp_align_batch(self, sources, items, params: "VgicpParams", want_fitness: bool = True):
         """lisreg_vgicp_align_batch: sources = a list of clouds (all host PCL-struct arrays of one dtype, or all (device_ptr, n)),
         items = a list of VgicpItem.  Returns (results: a list of vgicp_align's dicts, fitness [n_items] or None, info dict)."""
-        args = [self._cloud_args(s) for s in sources]
-        if len({(a[2], a[3]) for a in args}) > 1:
-            raise ValueError("vgicp_align_batch: the sources of one call share one layout")
-        stride, fmt = (args[0][2], args[0][3]) if args else (16, FMT_DEVICE)
-        ptrs = (C.c_void_p * max(len(args), 1))(*[a[0] for a in args])
-        ns = (C.c_int * max(len(args), 1))(*[a[1] for a in args])
-        its = (VgicpItemC * max(len(items), 1))()
-        for k, it in enumerate(items):
-            its[k].source, its[k].slot = it.source, it.slot
-            its[k].guess = None if it.guess is None else it.guess.ctypes.data_as(C.POINTER(C.c_float))
-        res = (VgicpResult * max(len(items), 1))()
-        fit = np.zeros(max(len(items), 1)) if want_fitness else None
-        info = VgicpBatchInfo()
-        self._chk(self._L.lisreg_vgicp_align_batch(self._h, ptrs, ns, len(args), stride, fmt, its, len(items), C.byref(params), res,
-                                                   fit.ctypes.data_as(C.POINTER(C.c_double)) if want_fitness else None, C.byref(info)))
-        return ([res[k].as_dict() for k in range(len(items))], fit[:len(items)] if want_fitness else None,
-                dict(best=info.best, n_rounds=info.n_rounds, n_sources_staged=info.n_sources_staged))
+        return self._gicp_align_batch(self._L.lisreg_vgicp_align_batch, VgicpItemC, VgicpResult, VgicpBatchInfo, "vgicp_align_batch",
+                                      sources, items, params, want_fitness)
 
     def set_profiling(self, on: bool):
         self._chk(self._L.lisreg_set_profiling(self._h, 1 if on else 0))

@@ -130,16 +130,38 @@ def test_both_units_share_one_copy_of_the_lane_body_and_of_the_round_helpers():
     assert [f for f, t in text.items() if "sqrt(rec[9])" in t] == ["lisreg_vgicp_lane.hpp"]
     for unit in ("lisreg_vgicp.hip", "lisreg_vgicp_batch.hip"):
         assert '#include "lisreg_vgicp_lane.hpp"' in text[unit] and "vg_linearize_lane<HESS>(" in text[unit], unit
+    # the host side of a call exists once: the totals of a round are launched from the driver header only, and both units include it
+    for needle in ("k_fgicp_total_batch<kOut>", "k_fgicp_total_batch<1>", "int batch_align("):
+        assert [f for f, t in text.items() if needle in t] == ["lisreg_batch_driver.hpp"], needle
     for unit in ("lisreg_fgicp_batch.hip", "lisreg_vgicp_batch.hip"):
-        assert '#include "lisreg_batch_rounds.hpp"' in text[unit] and "k_fgicp_total_batch<kOut>" in text[unit], unit
+        assert '#include "lisreg_batch_rounds.hpp"' in text[unit] and '#include "lisreg_batch_driver.hpp"' in text[unit], unit
+        assert text[unit].count("batch_align<") == 1, unit
+    # one fitness kernel, defined beside the totals and launched from the driver
+    assert [f for f, t in text.items() if re.search(r"void k_\w*fitness_batch\(", t)] == ["lisreg_batch_rounds.hpp"]
+    assert len(re.findall(r"void k_\w*fitness_batch\(", text["lisreg_batch_rounds.hpp"])) == 1
+    assert [f for f, t in text.items() if re.search(r"k_\w*fitness_batch<<<", t)] == ["lisreg_batch_driver.hpp"]
+    # one Levenberg-Marquardt loop: solve_damped is defined once and called from one place, the stepper
+    calls = {f: t.count("solve_damped(") for f, t in text.items() if "solve_damped(" in t}
+    assert calls == {"lisreg_vgicp_host.hpp": 1, "lisreg_lm_stepper.hpp": 1}, calls
+    assert "bool solve_damped(" in text["lisreg_vgicp_host.hpp"]
+    # one copy of the aligned-cloud output: its stride-wise loop occurs once, in emit_aligned (lisreg_transform_cloud, which takes a
+    # 6-DoF pose and host structs without staging them, keeps the loop of its own), and no aligner transforms a cloud itself
+    loops = {f: t.count("if (o != b) memcpy(o + (size_t)i * (size_t)stride") for f, t in text.items()}
+    assert {f: k for f, k in loops.items() if k} == {"lisreg_api_ctx.hip": 1, "lisreg_api_cloud.hip": 1}, loops
+    assert text["lisreg_api_cloud.hip"].count("int lisreg_transform_cloud(") == 1 and "int emit_aligned(" in text["lisreg_api_ctx.hip"]
+    for unit, sites in (("lisreg_vgicp.hip", 1), ("lisreg_fgicp.hip", 1), ("lisreg_ndt.hip", 1), ("lisreg_api_map.hip", 2)):
+        assert text[unit].count("emit_aligned(") == sites and "launch_transform_cloud(" not in text[unit], unit
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert "lisreg_vgicp_batch.hip" in re.search(r"^SRCS\s*=(.*)$", mk, re.M).group(1)
     for unit in ("lisreg_vgicp", "lisreg_vgicp_batch", "lisreg_fgicp_batch"):
         assert re.search(r"^FPC_%s := off$" % unit, mk, re.M), unit
     assert "lisreg_vgicp_lane.hpp" in re.search(r"^HDR_lisreg_vgicp := (.*)$", mk, re.M).group(1)
     hdrs = re.search(r"^HDR_lisreg_vgicp_batch := (.*)$", mk, re.M).group(1).split()
-    assert {"lisreg_batch_rounds.hpp", "lisreg_vgicp_lane.hpp", "lisreg_fgicp_lane.hpp", "lisreg_lm_stepper.hpp"} <= set(hdrs)
-    assert "lisreg_batch_rounds.hpp" in re.search(r"^HDR_lisreg_fgicp_batch := (.*)$", mk, re.M).group(1)
+    assert {"lisreg_batch_driver.hpp", "lisreg_batch_rounds.hpp", "lisreg_vgicp_lane.hpp", "lisreg_fgicp_lane.hpp", "lisreg_lm_stepper.hpp"} <= set(hdrs)
+    hdrs = re.search(r"^HDR_lisreg_fgicp_batch := (.*)$", mk, re.M).group(1).split()
+    assert {"lisreg_batch_driver.hpp", "lisreg_batch_rounds.hpp", "lisreg_lm_stepper.hpp"} <= set(hdrs)
+    for unit in ("lisreg_vgicp", "lisreg_fgicp"):
+        assert "lisreg_lm_stepper.hpp" in re.search(r"^HDR_%s := (.*)$" % unit, mk, re.M).group(1), unit
     # the batch unit keeps to the constraints of its kernels
     body = text["lisreg_vgicp_batch.hip"]
     assert "__shared__" not in body and "atomicAdd" not in body and "atomicCAS" not in body
