@@ -1,5 +1,7 @@
 // lisreg_api_cloud.hip — C-ABI entry points of SURVEY.md §8 f-1: the voxel grid of one cloud and of K clouds at once, the concatenation of
-// device clouds and the rigid transform of a cloud.  Kernels: lisreg_features.hip.  Host code only.
+// device clouds and the rigid transform of a cloud; and, from the same pcl::VoxelGrid keys, the voxel sort and the dense voxel table the
+// NDT and VGICP targets are built on (voxel_sort_cloud, voxel_table_build; declared in lisreg_ctx.hpp).  Kernels: lisreg_index.hip,
+// lisreg_features.hip.  Host code only.
 #include "lisreg_ctx.hpp"
 
 #include <algorithm>
@@ -11,8 +13,17 @@ using namespace lisreg;
 
 namespace {
 
+// pcl::VoxelGrid's min_b_ and div_b_ (voxel_grid.hpp) of the box `bb` at the inverse leaf size `inv`
+void voxel_bounds(const float bb[6], float inv, int min_b[3], long long div_b[3])
+{
+    for (int k = 0; k < 3; ++k) {
+        min_b[k] = (int)floorf(bb[k] * inv);
+        div_b[k] = (long long)floorf(bb[3 + k] * inv) - min_b[k] + 1;
+    }
+}
+
 // pcl::VoxelGrid's geometry (voxel_grid.hpp) of a cloud with bounding box `bb`: the voxel index of a point and the number of voxels the
-// box spans.  d->span is left to the caller (it follows from how many buckets the sort may use).  false: "Leaf size is too small for the
+// box spans.  d->span is left to the sort (it follows from how many buckets it may use).  false: "Leaf size is too small for the
 // input dataset" — the index would overflow int32.  Both voxel entry points take their geometry from here: that is what makes the multi
 // form's results those of K single calls.
 bool voxel_geometry(const float bb[6], float leaf, VoxelDesc* d, long long* total)
@@ -21,17 +32,106 @@ bool voxel_geometry(const float bb[6], float leaf, VoxelDesc* d, long long* tota
     const long long dx = (long long)((bb[3] - bb[0]) * inv) + 1, dy = (long long)((bb[4] - bb[1]) * inv) + 1,
                     dz = (long long)((bb[5] - bb[2]) * inv) + 1;
     if (dx * dy * dz > 2147483647LL) return false;
-    const int min_b[3] = { (int)floorf(bb[0] * inv), (int)floorf(bb[1] * inv), (int)floorf(bb[2] * inv) };
-    const int max_b[3] = { (int)floorf(bb[3] * inv), (int)floorf(bb[4] * inv), (int)floorf(bb[5] * inv) };
-    int div_b[3];
-    for (int k = 0; k < 3; ++k) div_b[k] = max_b[k] - min_b[k] + 1;
+    int min_b[3];
+    long long div_b[3];
+    voxel_bounds(bb, inv, min_b, div_b);
     d->inv_leaf = inv; d->min_b0 = min_b[0]; d->min_b1 = min_b[1]; d->min_b2 = min_b[2];
-    d->mul1 = div_b[0]; d->mul2 = div_b[0] * div_b[1];
-    *total = (long long)div_b[0] * div_b[1] * div_b[2];
+    d->mul1 = (int)div_b[0]; d->mul2 = (int)(div_b[0] * div_b[1]);
+    *total = div_b[0] * div_b[1] * div_b[2];
     return true;
 }
 
 }  // namespace
+
+int lisreg::voxel_sort_cloud(lisreg_ctx* c, const char* who, const float4* pts, int n, VoxelDesc d, long long total, int mark, int* n_vox)
+{
+    hipStream_t st = c->stream;
+    const long long max_buckets = 1LL << 22;
+    d.span = (uint32_t)std::max(1LL, (total + max_buckets - 1) / max_buckets);
+    const int n_buckets = (int)((total + d.span - 1) / d.span);
+    const int rc = ensure_sort_scratch(c, (size_t)n, (size_t)std::max(n_buckets, n) + 1);
+    if (rc) return rc;
+    HIPCHK(c, c->vox_order.ensure(sizeof(int) * (size_t)n));
+    HIPCHK(c, c->vox_sidx.ensure(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(c, c->vox_head.ensure(sizeof(int) * ((size_t)n + 1)));
+    HIPCHK(c, c->vox_slot.ensure(sizeof(int) * ((size_t)n + 2)));
+    if (mark >= 0) ctx_prof_mark(c, mark);
+    launch_voxel_sort(pts, n, d, n_buckets, sort_buffers(c), c->vox_order.as<int>(), c->vox_sidx.as<uint32_t>(), c->vox_head.as<int>(),
+                      c->vox_slot.as<int>(), st);
+    *n_vox = 0;
+    HIPCHK(c, hipMemcpyAsync(n_vox, c->vox_slot.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (*n_vox < 1 || *n_vox > n) return ctx_fail(c, LISREG_ERR_HIP, std::string(who) + ": the voxel sort returned an impossible voxel count");
+    return LISREG_OK;
+}
+
+// The shared build of the NDT and the VGICP target: pcl::VoxelGrid's keys, so both families see the voxels
+// lisreg_voxel_downsample sees, in the same order
+int lisreg::voxel_table_build(lisreg_ctx* c, const char* who, const char* table_word, const float4* pts, int n, const float bb[6],
+                              double resolution, int mark, VoxelTable& T)
+{
+    hipStream_t st = c->stream;
+    const float inv = 1.0f / (float)resolution;
+    const long long max_cells = 1LL << 26;
+    for (int k = 0; k < 3; ++k) {
+        const double lo = floor((double)(bb[k] * inv)), hi = floor((double)(bb[3 + k] * inv));
+        if (!(fabs(lo) < 2.0e9 && fabs(hi) < 2.0e9)) return bad(c, std::string(who) + ": the grid has more than 2^26 cells (resolution too small for this cloud)");
+    }
+    long long div_b[3];
+    voxel_bounds(bb, inv, T.min_b, div_b);
+    if (div_b[0] > max_cells || div_b[1] > max_cells || div_b[2] > max_cells || div_b[0] * div_b[1] > max_cells ||
+        div_b[0] * div_b[1] * div_b[2] > max_cells)
+        return bad(c, std::string(who) + ": the grid has more than 2^26 cells (the " + table_word + " is dense; resolution too small for this cloud)");
+    const long long total = div_b[0] * div_b[1] * div_b[2];
+    for (int k = 0; k < 3; ++k) T.dims[k] = (int)div_b[k];
+    VoxelDesc d;
+    d.inv_leaf = inv; d.min_b0 = T.min_b[0]; d.min_b1 = T.min_b[1]; d.min_b2 = T.min_b[2];
+    d.mul1 = T.dims[0]; d.mul2 = T.dims[0] * T.dims[1];
+    int n_vox = 0;
+    const int rc = voxel_sort_cloud(c, who, pts, n, d, total, mark, &n_vox);
+    if (rc) return rc;
+    HIPCHK(c, c->vox_start.ensure(sizeof(int) * ((size_t)n_vox + 2)));
+    launch_voxel_starts(n, c->vox_head.as<int>(), c->vox_slot.as<int>(), c->vox_start.as<int>(), st);
+    HIPCHK(c, T.stats.ensure(sizeof(double) * kVoxelRec * (size_t)n_vox));
+    HIPCHK(c, T.cell.ensure(sizeof(int) * (size_t)n_vox));
+    HIPCHK(c, T.table.ensure(sizeof(int) * (size_t)total));
+    HIPCHK(c, hipMemsetAsync(T.table.p, 0xFF, sizeof(int) * (size_t)total, st));
+    T.n_voxels = n_vox; T.resolution = resolution;
+    return LISREG_OK;
+}
+
+VoxelView lisreg::voxel_table_view(const VoxelTable& T)
+{
+    VoxelView G;
+    G.stats = T.stats.as<double>(); G.table = T.table.as<int>();
+    G.d0 = T.dims[0]; G.d1 = T.dims[1]; G.d2 = T.dims[2];
+    G.m0 = T.min_b[0]; G.m1 = T.min_b[1]; G.m2 = T.min_b[2];
+    G.inv_res = 1.0 / T.resolution;
+    return G;
+}
+
+int lisreg::voxel_table_read(lisreg_ctx* c, const VoxelTable& T, const DevBuf* flag, int* cell_ids, int* counts, double* means, double* sym6,
+                             int capacity)
+{
+    const size_t nv = (size_t)T.n_voxels;
+    std::vector<double> st(nv * kVoxelRec);
+    std::vector<int> ce(nv), fl(flag ? nv : 0);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(st.data(), T.stats.p, sizeof(double) * st.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ce.data(), T.cell.p, sizeof(int) * nv, hipMemcpyDeviceToHost, c->stream));
+    if (flag) HIPCHK(c, hipMemcpyAsync(fl.data(), flag->p, sizeof(int) * nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int m = 0;
+    for (size_t v = 0; v < nv && m < capacity; ++v) {
+        if (flag && !fl[v]) continue;
+        const double* r = &st[v * kVoxelRec];
+        cell_ids[m] = ce[v]; counts[m] = (int)r[9];
+        memcpy(means + 3 * (size_t)m, r, sizeof(double) * 3);
+        memcpy(sym6 + 6 * (size_t)m, r + 3, sizeof(double) * 6);
+        ++m;
+    }
+    return LISREG_OK;
+}
 
 extern "C" {
 
@@ -92,21 +192,9 @@ int lisreg_voxel_downsample(lisreg_ctx* c, const void* in, int n, int stride, in
         *n_out = n;
         return LISREG_LEAF_TOO_SMALL;
     }
-    const long long max_buckets = 1LL << 22;
-    d.span = (uint32_t)std::max(1LL, (total + max_buckets - 1) / max_buckets);
-    const int n_buckets = (int)((total + d.span - 1) / d.span);
     // ---- sort by voxel index, count voxels ------------------------------------------------------------------------
-    int rc = ensure_sort_scratch(c, (size_t)n, (size_t)std::max(n_buckets, n) + 1);
-    if (rc) return rc;
-    HIPCHK(c, c->vox_order.ensure(sizeof(int) * (size_t)n));
-    HIPCHK(c, c->vox_sidx.ensure(sizeof(uint32_t) * (size_t)n));
-    HIPCHK(c, c->vox_head.ensure(sizeof(int) * ((size_t)n + 1)));
-    HIPCHK(c, c->vox_slot.ensure(sizeof(int) * ((size_t)n + 2)));
-    launch_voxel_sort(pts, n, d, n_buckets, sort_buffers(c), c->vox_order.as<int>(), c->vox_sidx.as<uint32_t>(),
-                      c->vox_head.as<int>(), c->vox_slot.as<int>(), st);
     int n_vox = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_vox, c->vox_slot.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    if (const int rc = voxel_sort_cloud(c, "voxel_downsample", pts, n, d, total, -1, &n_vox)) return rc;
     *n_out = n_vox;
     if (n_vox > out_capacity) return bad(c, "voxel_downsample: out_capacity too small (see *n_out)");
     // ---- centroids ---------------------------------------------------------------------------------------------------

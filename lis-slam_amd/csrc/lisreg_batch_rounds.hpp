@@ -18,21 +18,15 @@ __device__ __forceinline__ int fg_entry_of(const int* __restrict__ wg_start, int
     return __builtin_amdgcn_readfirstlane(lo);
 }
 
-// One wavefront per entry: its partial records of W doubles added in k_vgicp_total's order (lane l takes records l, l + 64, ... one
-// after the other, then the butterfly from 32 down to 1)
+// One wavefront per entry: its partial records of W doubles added by the single call's sum_records (lisreg_fp64_sums.hpp: lane l takes
+// records l, l + 64, ... one after the other, then the butterfly from 32 down to 1)
 template <int W>
 __global__ __launch_bounds__(64) void k_fgicp_total_batch(const double* __restrict__ part, const int* __restrict__ wg_start, double* __restrict__ out)
 {
     const int e = blockIdx.x;
     const int p0 = wg_start[e], n_part = wg_start[e + 1] - p0;
     double acc[W];
-#pragma unroll
-    for (int k = 0; k < W; ++k) acc[k] = 0.0;
-    for (int b = (int)threadIdx.x; b < n_part; b += 64)
-#pragma unroll
-        for (int k = 0; k < W; ++k) acc[k] += part[(size_t)(p0 + b) * W + k];
-#pragma unroll
-    for (int k = 0; k < W; ++k) acc[k] = fg_wave_sum(acc[k]);
+    sum_records<W>(part + (size_t)p0 * W, n_part, acc);
     if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < W; ++k) out[(size_t)e * W + k] = acc[k];
@@ -68,7 +62,7 @@ __global__ __launch_bounds__(64) void k_fgicp_fitness_batch(const FgFitWork* __r
         fg_search_lane(A, qx, qy, qz, HUGE_VAL, HUGE_VAL, bd, bj);
         d2 = bj >= 0 ? bd : 0.0;
     }
-    d2 = fg_wave_sum(d2);
+    d2 = wave_sum(d2);
     if (threadIdx.x == 0) part[g] = d2;
 }
 

@@ -117,27 +117,40 @@ struct MapIndex {
     const float4* raw_ptr = nullptr;
 };
 
-// the Gaussians of one NDT target (lisreg_ndt.hip: lisreg_ndt_set_target)
-struct NdtTarget {
-    bool      valid = false;
-    int       n_voxels = 0, n_occupied = 0, n_valid = 0;
+// The dense voxel table of one target cloud (voxel_table_build in lisreg_api_cloud.hip): pcl::VoxelGrid's geometry at `resolution`, one
+// record of kVoxelRec doubles per occupied voxel in ascending cell order, and the cell -> voxel table.  What a record holds behind the
+// mean is its family's business (the statistics kernels of lisreg_ndt.hip / lisreg_vgicp.hip fill stats, cell and table)
+constexpr int kVoxelRec = 10;      // doubles per voxel: mean [3], a symmetric 3 x 3 as its upper triangle [6], points
+struct VoxelTable {
+    int       n_voxels = 0;
     int       dims[3] = { 1, 1, 1 }, min_b[3] = { 0, 0, 0 };
     double    resolution = 0;
-    DevBuf    stats;               // [n_voxels][10] doubles: mean, upper triangle of the inverse covariance, finite points
-    DevBuf    vflag, cell;         // [n_voxels] ints: became a Gaussian / cell id
-    DevBuf    table;               // [dims product] ints: cell -> voxel with a Gaussian, -1 none
-};
-
-// the voxel statistics of one VGICP target (lisreg_vgicp.hip: lisreg_vgicp_set_target), and its own copy of the search grid the
-// distributions were made with (the fitness score of lisreg_vgicp_align_batch searches it)
-struct VgicpTarget {
-    bool      valid = false;
-    int       n_voxels = 0, n_points = 0;
-    int       dims[3] = { 1, 1, 1 }, min_b[3] = { 0, 0, 0 };
-    double    resolution = 0;
-    DevBuf    stats;               // [n_voxels][10] doubles: mean, upper triangle of the mean covariance, points
+    DevBuf    stats;               // [n_voxels][kVoxelRec] doubles
     DevBuf    cell;                // [n_voxels] ints: cell id
     DevBuf    table;               // [dims product] ints: cell -> voxel, -1 none
+};
+// the kernels' view of a table (voxel_table_view)
+struct VoxelView {
+    const double* stats;
+    const int*    table;
+    int    d0, d1, d2, m0, m1, m2;
+    double inv_res;
+};
+
+// the Gaussians of one NDT target (lisreg_ndt.hip: lisreg_ndt_set_target): stats = mean, upper triangle of the inverse covariance, finite
+// points; the table names the voxels that became a Gaussian only
+struct NdtTarget : VoxelTable {
+    bool      valid = false;
+    int       n_occupied = 0, n_valid = 0;
+    DevBuf    vflag;               // [n_voxels] ints: became a Gaussian
+};
+
+// the voxel statistics of one VGICP target (lisreg_vgicp.hip: lisreg_vgicp_set_target): stats = mean, upper triangle of the mean
+// covariance, points; and its own copy of the search grid the distributions were made with (the fitness score of
+// lisreg_vgicp_align_batch searches it)
+struct VgicpTarget : VoxelTable {
+    bool      valid = false;
+    int       n_points = 0;
     GridIndex grid;                // the search grid (pts = sorted, cell_start = cells)
     float     bb[6] = { 0, 0, 0, 0, 0, 0 };   // the finite bounding box
     DevBuf    sorted;              // [n_points] float4 by grid cell, .w = index among the finite points
@@ -260,18 +273,20 @@ struct lisreg_ctx {
     int               gm_flip = 0;
     lisreg::DevBuf map_stage;                          // lisreg_map_index_set_batch: host clouds of a batch, packed, in one upload
     lisreg::DevBuf mp_pts, mp_flag, mp_pos, mp_idx, mp_cnt, mp_d2, mp_out, icp_state, icp_partials, icp_cur, icp_items, map_tab, map_tsegs, map_tblocks;
+    // one evaluation of the NDT, VGICP and FastGICP verifiers (eval_totals in lisreg_fp64_sums.hpp): per-workgroup partial sums, their
+    // total and its pinned landing area
+    lisreg::DevBuf eval_part, eval_out;
+    lisreg::PinnedBuf eval_host;
     // NDT registration (lisreg_ndt.hip): targets by slot (apart from the map-index slots), the cleaned target cloud and the staged source,
-    // per-workgroup partial sums and their total, the voxel counters; pinned landing area of one evaluation
+    // the voxel counters
     std::map<int, lisreg::NdtTarget> ndt;
-    lisreg::DevBuf ndt_pts, ndt_src, ndt_part, ndt_out, ndt_cnt;
-    lisreg::PinnedBuf ndt_host;
+    lisreg::DevBuf ndt_pts, ndt_src, ndt_cnt;
     // VGICP registration (lisreg_vgicp.hip): targets by slot (apart from the map-index and the NDT slots); of the cloud whose
     // distributions were made last (a target being set, or a source): the staged records, finite flags, their scan, the finite points and
     // their indices, the same points by search-grid cell with the cells' starts, the covariances, neighbour rows and covariance rows of the
-    // test hook; per-workgroup partial sums and their total, the finite-point count; pinned landing area of one evaluation
+    // test hook; the finite-point count
     std::map<int, lisreg::VgicpTarget> vgicp;
-    lisreg::DevBuf vg_raw, vg_flag, vg_pos, vg_pts, vg_idx, vg_sorted, vg_cells, vg_cov, vg_nbr, vg_rows, vg_part, vg_out, vg_cnt;
-    lisreg::PinnedBuf vg_host;
+    lisreg::DevBuf vg_raw, vg_flag, vg_pos, vg_pts, vg_idx, vg_sorted, vg_cells, vg_cov, vg_nbr, vg_rows, vg_cnt;
     // FastGICP registration (lisreg_fgicp.hip): targets by slot (a numbering of their own); of the source being aligned: the sorted
     // position of every finite point's correspondent (-1: none), the six entries of its M, its squared distance (the test hook); the
     // correspondence rows of the test hook by the caller's index
@@ -418,8 +433,22 @@ int  ensure_sort_scratch(lisreg_ctx* c, size_t n_elems, size_t n_buckets);
 // is the context's scratch: the next call overwrites it.
 int  vg_distributions(lisreg_ctx* c, const char* who, const float4* raw, int n, int k, double plane_eps, float edge, float bb[6], int* m_out,
                       int* nbr_dev, GridIndex* grid_out);
-// out[29] = the n_part partial records of 29 doubles added in a fixed order (one wavefront)
-void launch_vgicp_total(const double* part, int n_part, double* out, hipStream_t st);
+// out[29] = the n_part partial records of 29 doubles added in a fixed order (one wavefront: sum_records of lisreg_fp64_sums.hpp)
+void launch_eval_total(const double* part, int n_part, double* out, hipStream_t st);
+// ---- lisreg_api_cloud.hip: the voxel sort of one cloud and the voxel table of a target ---------------------------------------------------
+// n device records sorted by the voxel index of `d` (d.span is set here, for at most 2^22 buckets over `total` cells): afterwards
+// c->vox_order / c->vox_sidx hold the sorted positions' records and cell ids, c->vox_head / c->vox_slot the voxel heads and their scan;
+// *n_vox = the occupied voxels, read back and waited for.  mark >= 0: that profiling interval is opened in front of the sort.
+int  voxel_sort_cloud(lisreg_ctx* c, const char* who, const float4* pts, int n, VoxelDesc d, long long total, int mark, int* n_vox);
+// The table of n device records (no NaN coordinate among them) with the finite bounding box bb at `resolution`, ready for the family's
+// statistics kernels: T's geometry, voxel_sort_cloud, c->vox_start = the voxels' starts, T.stats / T.cell sized and T.table all -1.
+// Refused: a grid of more than 2^26 cells (the table is dense; `table_word` names it in the text: "cell table", "voxel table").
+int  voxel_table_build(lisreg_ctx* c, const char* who, const char* table_word, const float4* pts, int n, const float bb[6], double resolution,
+                       int mark, VoxelTable& T);
+VoxelView voxel_table_view(const VoxelTable& T);
+// the records of a table on the host, those with flag[v] != 0 only if `flag` is given ([n_voxels] ints on the device), at most `capacity`:
+// cell ids, point counts, means [3] and the six doubles behind them
+int  voxel_table_read(lisreg_ctx* c, const VoxelTable& T, const DevBuf* flag, int* cell_ids, int* counts, double* means, double* sym6, int capacity);
 // ---- lisreg_api.hip -------------------------------------------------------------------------------------------------------------------
 void ctx_prof_mark(lisreg_ctx* c, int kind_of_next_interval);      // 0 correspondence kernel, 1 solve, 2 index build, -1 nothing
 void ctx_prof_collect(lisreg_ctx* c);

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(64) void k_fgicp_pairs(const float4* __restrict__ s
 }
 
 // The 28 sums and the pair count over the stored pairs at P (fg_sums_lane).  One lane per source point, one wavefront per workgroup, one
-// partial record per workgroup (the shape of k_vgicp_linearize); launch_vgicp_total adds them.
+// partial record per workgroup (the shape of k_vgicp_linearize); eval_totals adds them.
 template <bool HESS>
 __global__ __launch_bounds__(64) void k_fgicp_sums(const float4* __restrict__ src, const int* __restrict__ pair, const double* __restrict__ M6,
                                                    int n, const float4* __restrict__ tgt_sorted, FgPose P, double* __restrict__ part)
@@ -113,22 +113,13 @@ int search(FgRun& r, const double T[16], bool want_d2)
 int sums(FgRun& r, const double T[16], bool hess, double out[kOut])
 {
     lisreg_ctx* c = r.c;
-    hipStream_t st = c->stream;
     const int nb = (r.n + 63) / 64;
-    HIPCHK(c, c->vg_part.ensure(sizeof(double) * kOut * (size_t)nb));
-    HIPCHK(c, c->vg_out.ensure(sizeof(double) * kOut));
-    HIPCHK(c, c->vg_host.ensure(sizeof(double) * kOut, sizeof(double) * 64));
     const FgPose P = pose_of<FgPose>(T);
-    ctx_prof_mark(c, 0);                                           // "assoc" = the sum launches (with the fixed-order total), one interval each
-    if (hess) k_fgicp_sums<true><<<nb, 64, 0, st>>>(r.src, c->fg_pair.as<int>(), c->fg_M.as<double>(), r.n, r.T->sorted.as<float4>(), P, c->vg_part.as<double>());
-    else      k_fgicp_sums<false><<<nb, 64, 0, st>>>(r.src, c->fg_pair.as<int>(), c->fg_M.as<double>(), r.n, r.T->sorted.as<float4>(), P, c->vg_part.as<double>());
-    launch_vgicp_total(c->vg_part.as<double>(), nb, c->vg_out.as<double>(), st);
-    ctx_prof_mark(c, -1);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->vg_host.p, c->vg_out.p, sizeof(double) * kOut, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    memcpy(out, c->vg_host.p, sizeof(double) * kOut);
-    return LISREG_OK;
+    return eval_totals(c, nb, [&](double* part) {
+        ctx_prof_mark(c, 0);                                       // "assoc" = the sum launches (with the fixed-order total), one interval each
+        if (hess) k_fgicp_sums<true><<<nb, 64, 0, c->stream>>>(r.src, c->fg_pair.as<int>(), c->fg_M.as<double>(), r.n, r.T->sorted.as<float4>(), P, part);
+        else      k_fgicp_sums<false><<<nb, 64, 0, c->stream>>>(r.src, c->fg_pair.as<int>(), c->fg_M.as<double>(), r.n, r.T->sorted.as<float4>(), P, part);
+    }, true, out);
 }
 
 // one evaluation as the LM loop asks for it: a linearisation searches, an error evaluation reuses the pairs and the M of the last one

@@ -3,7 +3,7 @@
 // and picks the winner by getFitnessScore() and hasConverged().  The definition is tests/fgicp_batch_ref.py: the loop of single
 // alignments plus the fitness score and the `best` rule.  Every item of a batch gets the bits lisreg_fgicp_align returns for it alone:
 // the lanes run the same bodies (lisreg_fgicp_lane.hpp) over the same partition of the source into wavefronts, the partial records are
-// added in k_vgicp_total's order, and the Levenberg-Marquardt loop is the single aligner's (lisreg_lm_stepper.hpp).  What the batch
+// added in the single call's order (sum_records of lisreg_fp64_sums.hpp), and the Levenberg-Marquardt loop is the single aligner's (lisreg_lm_stepper.hpp).  What the batch
 // saves: a source's distributions are made once per call, and the outstanding evaluations of ALL unfinished items are answered by one
 // round of launches and one synchronisation.  This unit holds the search and sum kernels and what they are launched with per round; the
 // host side of a call is the driver both batch units share (lisreg_batch_driver.hpp).  No LDS, no atomics, no CPU fallback.

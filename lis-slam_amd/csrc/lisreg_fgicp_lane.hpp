@@ -1,9 +1,10 @@
 // lisreg_fgicp_lane.hpp — what one lane of the FastGICP kernels computes, shared by the single alignment
 // (lisreg_fgicp.hip) and the batch (lisreg_fgicp_batch.hip, §7m): the search of one query, the matrix of one pair, the 28 terms of one
-// pair and the wavefront butterfly.  Both units are built with -ffp-contract=off and inline these bodies, so a lane of either computes
-// the same bits from the same input.  Also the few host helpers of lisreg_fgicp.hip that the batch shares.  Not installed.
+// pair and the wavefront sums (lisreg_fp64_sums.hpp).  Both units are built with -ffp-contract=off and inline these bodies, so a lane
+// of either computes the same bits from the same input.  Also the few host helpers of lisreg_fgicp.hip that the batch shares.  Not
+// installed.
 #pragma once
-#include "lisreg_ctx.hpp"
+#include "lisreg_fp64_sums.hpp"
 #include "lisreg_vgicp_host.hpp"
 
 #include <string>
@@ -20,12 +21,7 @@ struct FgTarget {
 };
 struct FgPose { double R[9], t[3]; };
 
-__device__ __forceinline__ double fg_wave_sum(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
+static_assert(vgicp_host::kOut == kEvalOut, "one evaluation is 29 doubles in every family");
 
 __device__ __forceinline__ void fg_transform(const FgPose& P, const float4 s, double& x0, double& x1, double& x2)
 {
@@ -177,8 +173,8 @@ __device__ __forceinline__ void fg_sums_lane(int j, const float4* __restrict__ s
         }
     }
 #pragma unroll
-    for (int k = 0; k < 28; ++k) acc[k] = fg_wave_sum(acc[k]);
-    pairs = fg_wave_sum(pairs);
+    for (int k = 0; k < 28; ++k) acc[k] = wave_sum(acc[k]);
+    pairs = wave_sum(pairs);
 }
 
 // ---- lisreg_fgicp.hip: the host checks of every FastGICP entry point (one copy) --------------------------------------------------------

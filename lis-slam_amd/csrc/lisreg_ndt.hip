@@ -1,10 +1,11 @@
 // lisreg_ndt.hip — Normal Distributions Transform registration: the loop-closure verifier the reference names first
 // (pcl::NormalDistributionsTransform, src/core/registration.cpp:147-155, src/node/subMapOptmizationNode.cpp:2756-2760).
-// The definition is tests/ndt_ref.py.  GPU: the target's per-voxel Gaussians (pcl::VoxelGrid keys of lisreg_index.hip, then one lane or
-// one wavefront per voxel, fp64) and one evaluation of score / gradient / Hessian per call (one lane per source point, fp64, sums in a
-// fixed order: no floating-point atomics, the same input gives the same bits).  Host: the 6 x 6 solve and the More-Thuente line search
-// in double, one 29-double read-back per evaluation.  No CPU fallback.
-#include "lisreg_ctx.hpp"
+// The definition is tests/ndt_ref.py.  GPU: the target's per-voxel Gaussians (the voxel table of voxel_table_build, lisreg_api_cloud.hip,
+// then one lane or one wavefront per voxel, fp64) and one evaluation of score / gradient / Hessian per call (one lane per source point,
+// fp64, sums in a fixed order: no floating-point atomics, the same input gives the same bits).  Host: the 6 x 6 solve and the
+// More-Thuente line search in double, one 29-double read-back per evaluation (eval_totals).  The butterfly, the total, the round trip
+// and the statistics' launch shell are the ones VGICP and FastGICP use (lisreg_fp64_sums.hpp).  No CPU fallback.
+#include "lisreg_fp64_sums.hpp"
 #include "lisreg_ndt_host.hpp"
 #include "lisreg_jacobi3.hpp"
 
@@ -18,11 +19,6 @@ using namespace lisreg::ndt_host;
 
 namespace {
 
-constexpr int kNdtBig   = 48;          // voxels with more points get a wavefront each (k_ndt_stats_big), the others a lane
-constexpr int kNdtRec   = 10;          // doubles per voxel: mean [3], upper triangle of the inverse covariance [6], finite points
-constexpr int kNdtOut   = 29;          // score, gradient [6], Hessian upper triangle [21], pairs
-constexpr long long kNdtMaxCells = 1LL << 26;
-
 // ---- target: NaN points out of the way ------------------------------------------------------------------------------------------
 // A point with a NaN coordinate belongs to no voxel.  It is moved onto the box's minimum corner and marked in .w, so that the voxel keys
 // of every record are inside the grid whatever a float -> int conversion makes of a NaN; the statistics skip the marked records.
@@ -33,13 +29,6 @@ __global__ __launch_bounds__(256) void k_ndt_clean(const float4* __restrict__ in
     const float4 p = in[i];
     const bool bad = p.x != p.x || p.y != p.y || p.z != p.z;
     out[i] = bad ? make_float4(lx, ly, lz, 1.0f) : make_float4(p.x, p.y, p.z, 0.0f);
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 // the Gaussian of one voxel from its mean-centred second moments S (already divided by n - 1): eigen-decomposition, the two smaller
@@ -72,16 +61,17 @@ struct NdtBuild {
     int             n_vox, min_pts;
     long long       n_cells;
     double          mult;
-    double*         stats;      // [n_vox][kNdtRec]
+    double*         stats;      // [n_vox][kVoxelRec]
     int*            vflag;      // [n_vox]
     int*            cell;       // [n_vox]
     int*            table;      // [n_cells], -1 on entry
     int*            counters;   // [0] voxels with a finite point, [1] valid voxels
+    template <bool WAVE> static __device__ void voxel(const NdtBuild& B, int v, int lane);
 };
 
 // WAVE: the 64 lanes of a wavefront share voxel v (every lane ends up with the same sums: the butterfly adds the same pairs everywhere)
 template <bool WAVE>
-__device__ __forceinline__ void ndt_voxel(const NdtBuild& B, int v, int lane)
+__device__ __forceinline__ void NdtBuild::voxel(const NdtBuild& B, int v, int lane)
 {
     const int a = B.vstart[v], b = B.vstart[v + 1];
     const int step = WAVE ? 64 : 1;
@@ -94,9 +84,9 @@ __device__ __forceinline__ void ndt_voxel(const NdtBuild& B, int v, int lane)
     if (WAVE) { s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); cnt = wave_sum(cnt); }
     const int n = (int)cnt;
     const uint32_t cid = B.sidx[a];
-    double rec[kNdtRec];
+    double rec[kVoxelRec];
 #pragma unroll
-    for (int k = 0; k < kNdtRec; ++k) rec[k] = 0.0;
+    for (int k = 0; k < kVoxelRec; ++k) rec[k] = 0.0;
     rec[9] = cnt;
     bool ok = n >= B.min_pts && n >= 2;
     if (ok) {                                                  // uniform across the wavefront: no lane leaves the shuffles below alone
@@ -118,7 +108,7 @@ __device__ __forceinline__ void ndt_voxel(const NdtBuild& B, int v, int lane)
     }
     if (lane != 0) return;
 #pragma unroll
-    for (int k = 0; k < kNdtRec; ++k) B.stats[(size_t)v * kNdtRec + k] = rec[k];
+    for (int k = 0; k < kVoxelRec; ++k) B.stats[(size_t)v * kVoxelRec + k] = rec[k];
     B.vflag[v] = ok ? 1 : 0;
     B.cell[v] = (int)cid;
     if (n > 0) atomicAdd(&B.counters[0], 1);
@@ -128,33 +118,12 @@ __device__ __forceinline__ void ndt_voxel(const NdtBuild& B, int v, int lane)
     }
 }
 
-__global__ __launch_bounds__(256) void k_ndt_stats_small(NdtBuild B)
-{
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    if (v >= B.n_vox) return;
-    if (B.vstart[v + 1] - B.vstart[v] > kNdtBig) return;       // k_ndt_stats_big
-    ndt_voxel<false>(B, v, 0);
-}
-
-__global__ __launch_bounds__(64) void k_ndt_stats_big(NdtBuild B)
-{
-    const int v = blockIdx.x;
-    if (v >= B.n_vox) return;
-    if (B.vstart[v + 1] - B.vstart[v] <= kNdtBig) return;      // the whole wavefront leaves together
-    ndt_voxel<true>(B, v, (int)threadIdx.x);
-}
-
 // ---- one evaluation --------------------------------------------------------------------------------------------------------------
-struct NdtGrid {
-    const double* stats;
-    const int*    table;
-    int    d0, d1, d2, m0, m1, m2;
-    double inv_res, r2, g1, g2;                                 // 1 / resolution, resolution^2, the Gaussian constants d1, d2
-};
+struct NdtGauss { double r2, g1, g2; };                         // resolution^2, the Gaussian constants d1, d2
 
 // one lane per source point, one wavefront per workgroup, one partial record per workgroup
 template <bool HESS>
-__global__ __launch_bounds__(64) void k_ndt_eval(const float4* __restrict__ src, int n, NdtGrid G, NdtPose P, double* __restrict__ part)
+__global__ __launch_bounds__(64) void k_ndt_eval(const float4* __restrict__ src, int n, VoxelView G, NdtGauss K, NdtPose P, double* __restrict__ part)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
     double acc[28];
@@ -195,19 +164,19 @@ __global__ __launch_bounds__(64) void k_ndt_eval(const float4* __restrict__ src,
                     if (x < 0 || x >= G.d0) continue;
                     const int v = G.table[x + y * G.d0 + z * (long long)G.d0 * G.d1];
                     if (v < 0) continue;
-                    const double* __restrict__ rec = G.stats + (size_t)v * kNdtRec;
+                    const double* __restrict__ rec = G.stats + (size_t)v * kVoxelRec;
                     const double q0 = t0 - rec[0], q1 = t1 - rec[1], q2 = t2 - rec[2];
-                    if (!((q0 * q0 + q1 * q1) + q2 * q2 <= G.r2)) continue;
+                    if (!((q0 * q0 + q1 * q1) + q2 * q2 <= K.r2)) continue;
                     const double C[3][3] = { { rec[3], rec[4], rec[5] }, { rec[4], rec[6], rec[7] }, { rec[5], rec[7], rec[8] } };
                     double cq[3];
 #pragma unroll
                     for (int r = 0; r < 3; ++r) cq[r] = (C[r][0] * q0 + C[r][1] * q1) + C[r][2] * q2;
-                    const double e = exp(-G.g2 * ((q0 * cq[0] + q1 * cq[1]) + q2 * cq[2]) / 2.0);
+                    const double e = exp(-K.g2 * ((q0 * cq[0] + q1 * cq[1]) + q2 * cq[2]) / 2.0);
                     pairs += 1.0;
-                    acc[0] += -G.g1 * e;
-                    double w = G.g2 * e;
+                    acc[0] += -K.g1 * e;
+                    double w = K.g2 * e;
                     if (w > 1.0 || w < 0.0 || w != w) continue;
-                    w *= G.g1;
+                    w *= K.g1;
                     double cJ[6];
 #pragma unroll
                     for (int a = 0; a < 6; ++a) cJ[a] = (cq[0] * J[a][0] + cq[1] * J[a][1]) + cq[2] * J[a][2];
@@ -223,7 +192,7 @@ __global__ __launch_bounds__(64) void k_ndt_eval(const float4* __restrict__ src,
                         for (int a = 0; a < 6; ++a)
 #pragma unroll
                             for (int b = a; b < 6; ++b) {
-                                double t = -G.g2 * cJ[a] * cJ[b] + ((J[b][0] * CJ[a][0] + J[b][1] * CJ[a][1]) + J[b][2] * CJ[a][2]);
+                                double t = -K.g2 * cJ[a] * cJ[b] + ((J[b][0] * CJ[a][0] + J[b][1] * CJ[a][1]) + J[b][2] * CJ[a][2]);
                                 if (a >= 3) {
                                     const int h = a == 3 ? b - 3 : (a == 4 ? b - 1 : 5);          // aa ab ac | bb bc | cc
                                     t += (cq[0] * Hv[h][0] + cq[1] * Hv[h][1]) + cq[2] * Hv[h][2];
@@ -239,27 +208,11 @@ __global__ __launch_bounds__(64) void k_ndt_eval(const float4* __restrict__ src,
     for (int k = 0; k < 28; ++k) acc[k] = wave_sum(acc[k]);
     pairs = wave_sum(pairs);
     if (threadIdx.x == 0) {
-        double* o = part + (size_t)blockIdx.x * kNdtOut;
+        double* o = part + (size_t)blockIdx.x * kEvalOut;
 #pragma unroll
         for (int k = 0; k < 28; ++k) o[k] = acc[k];
         o[28] = pairs;
     }
-}
-
-// the partial records added in a fixed order: lane l takes records l, l + 64, ..., then the butterfly
-__global__ __launch_bounds__(64) void k_ndt_total(const double* __restrict__ part, int n_part, double* __restrict__ out)
-{
-    double acc[kNdtOut];
-#pragma unroll
-    for (int k = 0; k < kNdtOut; ++k) acc[k] = 0.0;
-    for (int b = (int)threadIdx.x; b < n_part; b += 64)
-#pragma unroll
-        for (int k = 0; k < kNdtOut; ++k) acc[k] += part[(size_t)b * kNdtOut + k];
-#pragma unroll
-    for (int k = 0; k < kNdtOut; ++k) acc[k] = wave_sum(acc[k]);
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < kNdtOut; ++k) out[k] = acc[k];
 }
 
 struct NdtRun {
@@ -268,34 +221,24 @@ struct NdtRun {
     const float4*    src;
     int              n;
     double           g1, g2;
-    double           out[kNdtOut];
+    double           out[kEvalOut];
     int              n_evals = 0;
 };
 
 int evaluate(NdtRun& r, const double p[6], bool hess)
 {
     lisreg_ctx* c = r.c;
-    hipStream_t st = c->stream;
     NdtPose P;
     pose_matrices(p, &P);
-    NdtGrid G;
-    G.stats = r.T->stats.as<double>(); G.table = r.T->table.as<int>();
-    G.d0 = r.T->dims[0]; G.d1 = r.T->dims[1]; G.d2 = r.T->dims[2];
-    G.m0 = r.T->min_b[0]; G.m1 = r.T->min_b[1]; G.m2 = r.T->min_b[2];
-    G.inv_res = 1.0 / r.T->resolution; G.r2 = r.T->resolution * r.T->resolution; G.g1 = r.g1; G.g2 = r.g2;
+    const VoxelView G = voxel_table_view(*r.T);
+    const NdtGauss K = { r.T->resolution * r.T->resolution, r.g1, r.g2 };
     const int nb = (r.n + 63) / 64;
-    HIPCHK(c, c->ndt_part.ensure(sizeof(double) * kNdtOut * (size_t)nb));
-    HIPCHK(c, c->ndt_out.ensure(sizeof(double) * kNdtOut));
-    HIPCHK(c, c->ndt_host.ensure(sizeof(double) * kNdtOut, sizeof(double) * 64));
-    if (hess) k_ndt_eval<true><<<nb, 64, 0, st>>>(r.src, r.n, G, P, c->ndt_part.as<double>());
-    else      k_ndt_eval<false><<<nb, 64, 0, st>>>(r.src, r.n, G, P, c->ndt_part.as<double>());
-    k_ndt_total<<<1, 64, 0, st>>>(c->ndt_part.as<double>(), nb, c->ndt_out.as<double>());
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->ndt_host.p, c->ndt_out.p, sizeof(double) * kNdtOut, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    memcpy(r.out, c->ndt_host.p, sizeof(double) * kNdtOut);
-    ++r.n_evals;
-    return LISREG_OK;
+    const int rc = eval_totals(c, nb, [&](double* part) {
+        if (hess) k_ndt_eval<true><<<nb, 64, 0, c->stream>>>(r.src, r.n, G, K, P, part);
+        else      k_ndt_eval<false><<<nb, 64, 0, c->stream>>>(r.src, r.n, G, K, P, part);
+    }, false, r.out);
+    if (!rc) ++r.n_evals;
+    return rc;
 }
 
 // phi(a), phi'(a) along `dir` from `base`
@@ -366,63 +309,27 @@ int lisreg_ndt_set_target(lisreg_ctx* c, int slot, const void* cloud, int n, int
     for (int k = 0; k < 6; ++k)
         if (!std::isfinite(bb[k])) return bad(c, "ndt_set_target: the cloud has infinite coordinates");
     if (!(bb[0] <= bb[3] && bb[1] <= bb[4] && bb[2] <= bb[5])) return bad(c, "ndt_set_target: the cloud has no finite point: no valid voxel");
-    const float inv = 1.0f / (float)P->resolution;
-    VoxelDesc d;
-    long long div_b[3];
-    const double lim = 2.0e9;
-    for (int k = 0; k < 3; ++k) {
-        const double lo = floor((double)(bb[k] * inv)), hi = floor((double)(bb[3 + k] * inv));
-        if (!(fabs(lo) < lim && fabs(hi) < lim)) return bad(c, "ndt_set_target: the grid has more than 2^26 cells (resolution too small for this cloud)");
-        T.min_b[k] = (int)floorf(bb[k] * inv);
-        div_b[k] = (long long)floorf(bb[3 + k] * inv) - T.min_b[k] + 1;
-    }
-    if (div_b[0] > kNdtMaxCells || div_b[1] > kNdtMaxCells || div_b[2] > kNdtMaxCells || div_b[0] * div_b[1] > kNdtMaxCells ||
-        div_b[0] * div_b[1] * div_b[2] > kNdtMaxCells)
-        return bad(c, "ndt_set_target: the grid has more than 2^26 cells (the cell table is dense; resolution too small for this cloud)");
-    const long long total = div_b[0] * div_b[1] * div_b[2];
-    for (int k = 0; k < 3; ++k) T.dims[k] = (int)div_b[k];
-    d.inv_leaf = inv; d.min_b0 = T.min_b[0]; d.min_b1 = T.min_b[1]; d.min_b2 = T.min_b[2];
-    d.mul1 = T.dims[0]; d.mul2 = T.dims[0] * T.dims[1];
-    const long long max_buckets = 1LL << 22;
-    d.span = (uint32_t)std::max(1LL, (total + max_buckets - 1) / max_buckets);
-    const int n_buckets = (int)((total + d.span - 1) / d.span);
-    // ---- NaN points aside, sort by voxel, voxel starts (the launches of lisreg_voxel_downsample) -------------------------------------
+    // ---- NaN points aside, then the voxel table (the sort of lisreg_voxel_downsample) ------------------------------------------------
     HIPCHK(c, c->ndt_pts.ensure(sizeof(float4) * (size_t)n));
     k_ndt_clean<<<(n + 255) / 256, 256, 0, st>>>(raw, n, bb[0], bb[1], bb[2], c->ndt_pts.as<float4>());
-    rc = ensure_sort_scratch(c, (size_t)n, (size_t)std::max(n_buckets, n) + 1);
+    rc = voxel_table_build(c, "ndt_set_target", "cell table", c->ndt_pts.as<float4>(), n, bb, P->resolution, -1, T);
     if (rc) return rc;
-    HIPCHK(c, c->vox_order.ensure(sizeof(int) * (size_t)n));
-    HIPCHK(c, c->vox_sidx.ensure(sizeof(uint32_t) * (size_t)n));
-    HIPCHK(c, c->vox_head.ensure(sizeof(int) * ((size_t)n + 1)));
-    HIPCHK(c, c->vox_slot.ensure(sizeof(int) * ((size_t)n + 2)));
-    launch_voxel_sort(c->ndt_pts.as<float4>(), n, d, n_buckets, sort_buffers(c), c->vox_order.as<int>(), c->vox_sidx.as<uint32_t>(),
-                      c->vox_head.as<int>(), c->vox_slot.as<int>(), st);
-    int n_vox = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_vox, c->vox_slot.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (n_vox < 1 || n_vox > n) return ctx_fail(c, LISREG_ERR_HIP, "ndt_set_target: the voxel sort returned an impossible voxel count");
-    HIPCHK(c, c->vox_start.ensure(sizeof(int) * ((size_t)n_vox + 2)));
-    launch_voxel_starts(n, c->vox_head.as<int>(), c->vox_slot.as<int>(), c->vox_start.as<int>(), st);
     // ---- the Gaussians ------------------------------------------------------------------------------------------------------------------
-    HIPCHK(c, T.stats.ensure(sizeof(double) * kNdtRec * (size_t)n_vox));
+    const int n_vox = T.n_voxels;
     HIPCHK(c, T.vflag.ensure(sizeof(int) * (size_t)n_vox));
-    HIPCHK(c, T.cell.ensure(sizeof(int) * (size_t)n_vox));
-    HIPCHK(c, T.table.ensure(sizeof(int) * (size_t)total));
     HIPCHK(c, c->ndt_cnt.ensure(sizeof(int) * 4));
-    HIPCHK(c, hipMemsetAsync(T.table.p, 0xFF, sizeof(int) * (size_t)total, st));
     HIPCHK(c, hipMemsetAsync(c->ndt_cnt.p, 0, sizeof(int) * 4, st));
     NdtBuild B;
     B.pts = c->ndt_pts.as<float4>(); B.order = c->vox_order.as<int>(); B.sidx = c->vox_sidx.as<uint32_t>(); B.vstart = c->vox_start.as<int>();
-    B.n_vox = n_vox; B.min_pts = P->min_points_per_voxel; B.n_cells = total; B.mult = P->min_covar_eigvalue_mult;
+    B.n_vox = n_vox; B.min_pts = P->min_points_per_voxel; B.n_cells = (long long)T.dims[0] * T.dims[1] * T.dims[2]; B.mult = P->min_covar_eigvalue_mult;
     B.stats = T.stats.as<double>(); B.vflag = T.vflag.as<int>(); B.cell = T.cell.as<int>(); B.table = T.table.as<int>();
     B.counters = c->ndt_cnt.as<int>();
-    k_ndt_stats_small<<<(n_vox + 255) / 256, 256, 0, st>>>(B);
-    k_ndt_stats_big<<<n_vox, 64, 0, st>>>(B);
+    launch_voxel_stats(B, st);
     HIPCHK(c, hipGetLastError());
     int cnt[2] = { 0, 0 };
     HIPCHK(c, hipMemcpyAsync(cnt, c->ndt_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    T.n_voxels = n_vox; T.n_occupied = cnt[0]; T.n_valid = cnt[1]; T.resolution = P->resolution;
+    T.n_occupied = cnt[0]; T.n_valid = cnt[1];
     if (info) { for (int k = 0; k < 3; ++k) info->dims[k] = T.dims[k]; info->n_voxels = cnt[0]; info->n_valid = cnt[1]; info->reserved = 0; }
     if (cnt[1] < 1) return bad(c, "ndt_set_target: the target has no valid voxel (min_points_per_voxel points with a positive-definite covariance)");
     T.valid = true;
@@ -439,23 +346,7 @@ int lisreg_ndt_get_voxels(lisreg_ctx* c, int slot, int* cell_ids, int* counts, d
     *n_out = T->n_valid;
     if (T->n_valid > capacity) return LISREG_OK;
     if (!cell_ids || !counts || !means || !icov6) return bad(c, "ndt_get_voxels: NULL output");
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<double> st((size_t)T->n_voxels * kNdtRec);
-    std::vector<int> fl((size_t)T->n_voxels), ce((size_t)T->n_voxels);
-    HIPCHK(c, hipMemcpyAsync(st.data(), T->stats.p, sizeof(double) * st.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(fl.data(), T->vflag.p, sizeof(int) * fl.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(ce.data(), T->cell.p, sizeof(int) * ce.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int m = 0;
-    for (int v = 0; v < T->n_voxels && m < capacity; ++v) {
-        if (!fl[(size_t)v]) continue;
-        const double* r = &st[(size_t)v * kNdtRec];
-        cell_ids[m] = ce[(size_t)v]; counts[m] = (int)r[9];
-        memcpy(means + 3 * (size_t)m, r, sizeof(double) * 3);
-        memcpy(icov6 + 6 * (size_t)m, r + 3, sizeof(double) * 6);
-        ++m;
-    }
-    return LISREG_OK;
+    return voxel_table_read(c, *T, &T->vflag, cell_ids, counts, means, icov6, capacity);
 }
 
 int lisreg_ndt_derivatives(lisreg_ctx* c, int slot, const void* source, int n, int stride, int fmt, const lisreg_ndt_params* P,

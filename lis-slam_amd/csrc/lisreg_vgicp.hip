@@ -2,9 +2,10 @@
 // not link (select_registration_method("FAST_VGICP"), src/core/registration.cpp:156-187, src/node/subMapOptmizationNode.cpp:2771).
 // The definition is tests/vgicp_ref.py.  GPU: the distribution of every point of a cloud (its k nearest points within the cloud by an
 // exact shell walk over a uniform grid, one query per lane, then mean, covariance and the plane regularisation, fp64), the target's
-// per-voxel statistics (the NDT build's sort, one lane or one wavefront per voxel) and one linearisation per call (one lane per source
-// point, fp64, sums in a fixed order: the same input gives the same bits).  Host: the 6 x 6 solve and the Levenberg-Marquardt loop in
-// double, one 29-double read-back per evaluation.  No CPU fallback.
+// per-voxel statistics (the voxel table of voxel_table_build, lisreg_api_cloud.hip, as the NDT target's; one lane or one wavefront per
+// voxel) and one linearisation per call (one lane per source point, fp64, sums in a fixed order: the same input gives the same bits).
+// Host: the 6 x 6 solve and the Levenberg-Marquardt loop in double, one 29-double read-back per evaluation (eval_totals).  This unit also
+// holds the one total kernel of the three verifiers (launch_eval_total).  No CPU fallback.
 #include "lisreg_vgicp_lane.hpp"
 #include "lisreg_lm_stepper.hpp"
 #include "lisreg_jacobi3.hpp"
@@ -19,9 +20,7 @@ using namespace lisreg::vgicp_host;
 
 namespace {
 
-constexpr int kVgBig = 48;             // voxels with more points get a wavefront each, the others a lane (the NDT build's split)
-constexpr long long kVgMaxCells = 1LL << 26;        // the voxel table is dense
-constexpr long long kVgKnnMaxCells = 1LL << 22;     // so is the search grid of a cloud
+constexpr long long kVgKnnMaxCells = 1LL << 22;     // the search grid of a cloud is dense
 constexpr int kVgKnnMaxDim = 2048;                  // cells per axis of the search grid (the walk's rounding slack is sized for this)
 
 // ---- NaN points are no points: the finite records, in input order ---------------------------------------------------------------
@@ -190,14 +189,15 @@ struct VgBuild {
     const int*      vstart;     // [n_vox + 1]
     int             n_vox;
     long long       n_cells;
-    double*         stats;      // [n_vox][kVgRec]
+    double*         stats;      // [n_vox][kVoxelRec]
     int*            cell;       // [n_vox]
     int*            table;      // [n_cells], -1 on entry
+    template <bool WAVE> static __device__ void voxel(const VgBuild& B, int v, int lane);
 };
 
 // WAVE: the 64 lanes of a wavefront share voxel v (every lane ends up with the same sums: the butterfly adds the same pairs everywhere)
 template <bool WAVE>
-__device__ __forceinline__ void vg_voxel(const VgBuild& B, int v, int lane)
+__device__ __forceinline__ void VgBuild::voxel(const VgBuild& B, int v, int lane)
 {
     const int a = B.vstart[v], b = B.vstart[v + 1];
     const int step = WAVE ? 64 : 1;
@@ -214,38 +214,22 @@ __device__ __forceinline__ void vg_voxel(const VgBuild& B, int v, int lane)
     }
     if (WAVE) {
 #pragma unroll
-        for (int e = 0; e < 9; ++e) s[e] = vg_wave_sum(s[e]);
+        for (int e = 0; e < 9; ++e) s[e] = wave_sum(s[e]);
     }
     if (lane != 0) return;
     const double cnt = (double)(b - a);
     const uint32_t cid = B.sidx[a];
 #pragma unroll
-    for (int e = 0; e < 9; ++e) B.stats[(size_t)v * kVgRec + e] = s[e] / cnt;
-    B.stats[(size_t)v * kVgRec + 9] = cnt;
+    for (int e = 0; e < 9; ++e) B.stats[(size_t)v * kVoxelRec + e] = s[e] / cnt;
+    B.stats[(size_t)v * kVoxelRec + 9] = cnt;
     B.cell[v] = (int)cid;
     if ((long long)cid < B.n_cells) B.table[cid] = v;
-}
-
-__global__ __launch_bounds__(256) void k_vg_stats_small(VgBuild B)
-{
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    if (v >= B.n_vox) return;
-    if (B.vstart[v + 1] - B.vstart[v] > kVgBig) return;        // k_vg_stats_big
-    vg_voxel<false>(B, v, 0);
-}
-
-__global__ __launch_bounds__(64) void k_vg_stats_big(VgBuild B)
-{
-    const int v = blockIdx.x;
-    if (v >= B.n_vox) return;
-    if (B.vstart[v + 1] - B.vstart[v] <= kVgBig) return;       // the whole wavefront leaves together
-    vg_voxel<true>(B, v, (int)threadIdx.x);
 }
 
 // ---- one linearisation ------------------------------------------------------------------------------------------------------------
 // one lane per source point (vg_linearize_lane of lisreg_vgicp_lane.hpp), one wavefront per workgroup, one partial record per workgroup
 template <bool HESS>
-__global__ __launch_bounds__(64) void k_vgicp_linearize(const float4* __restrict__ src, const double* __restrict__ cov, int n, VgGrid G,
+__global__ __launch_bounds__(64) void k_vgicp_linearize(const float4* __restrict__ src, const double* __restrict__ cov, int n, VoxelView G,
                                                         VgPose P, double* __restrict__ part)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -259,20 +243,14 @@ __global__ __launch_bounds__(64) void k_vgicp_linearize(const float4* __restrict
     }
 }
 
-// the partial records added in a fixed order: lane l takes records l, l + 64, ..., then the butterfly
-__global__ __launch_bounds__(64) void k_vgicp_total(const double* __restrict__ part, int n_part, double* __restrict__ out)
+// the partial records of one evaluation added in a fixed order (sum_records), for the three verifiers
+__global__ __launch_bounds__(64) void k_eval_total(const double* __restrict__ part, int n_part, double* __restrict__ out)
 {
-    double acc[kOut];
-#pragma unroll
-    for (int k = 0; k < kOut; ++k) acc[k] = 0.0;
-    for (int b = (int)threadIdx.x; b < n_part; b += 64)
-#pragma unroll
-        for (int k = 0; k < kOut; ++k) acc[k] += part[(size_t)b * kOut + k];
-#pragma unroll
-    for (int k = 0; k < kOut; ++k) acc[k] = vg_wave_sum(acc[k]);
+    double acc[kEvalOut];
+    sum_records<kEvalOut>(part, n_part, acc);
     if (threadIdx.x == 0)
 #pragma unroll
-        for (int k = 0; k < kOut; ++k) out[k] = acc[k];
+        for (int k = 0; k < kEvalOut; ++k) out[k] = acc[k];
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
@@ -304,16 +282,6 @@ int lisreg::vg_check_params(lisreg_ctx* c, const lisreg_vgicp_params* P, const c
 int lisreg::vg_find_target(lisreg_ctx* c, int slot, const lisreg_vgicp_params* P, const char* who, VgicpTarget** out)
 {
     return find_target(c, slot, P, who, out);
-}
-
-VgGrid lisreg::vg_grid_view(const VgicpTarget& T)
-{
-    VgGrid G;
-    G.stats = T.stats.as<double>(); G.table = T.table.as<int>();
-    G.d0 = T.dims[0]; G.d1 = T.dims[1]; G.d2 = T.dims[2];
-    G.m0 = T.min_b[0]; G.m1 = T.min_b[1]; G.m2 = T.min_b[2];
-    G.inv_res = 1.0 / T.resolution;
-    return G;
 }
 
 // The distributions of one cloud of n device records: afterwards c->vg_pts holds its *m_out finite points in input order, c->vg_idx
@@ -386,9 +354,9 @@ int lisreg::vg_distributions(lisreg_ctx* c, const char* who, const float4* raw, 
     return LISREG_OK;
 }
 
-void lisreg::launch_vgicp_total(const double* part, int n_part, double* out, hipStream_t st)
+void lisreg::launch_eval_total(const double* part, int n_part, double* out, hipStream_t st)
 {
-    k_vgicp_total<<<1, 64, 0, st>>>(part, n_part, out);
+    k_eval_total<<<1, 64, 0, st>>>(part, n_part, out);
 }
 
 namespace {
@@ -411,24 +379,16 @@ struct VgRun {
 int evaluate(VgRun& r, const double T[16], bool hess, double out[kOut])
 {
     lisreg_ctx* c = r.c;
-    hipStream_t st = c->stream;
     const VgPose P = pose_of<VgPose>(T);
-    const VgGrid G = vg_grid_view(*r.T);
+    const VoxelView G = voxel_table_view(*r.T);
     const int nb = (r.n + 63) / 64;
-    HIPCHK(c, c->vg_part.ensure(sizeof(double) * kOut * (size_t)nb));
-    HIPCHK(c, c->vg_out.ensure(sizeof(double) * kOut));
-    HIPCHK(c, c->vg_host.ensure(sizeof(double) * kOut, sizeof(double) * 64));
-    ctx_prof_mark(c, 0);                                           // "assoc" = the linearisations (both launches), one interval each
-    if (hess) k_vgicp_linearize<true><<<nb, 64, 0, st>>>(r.src, r.cov, r.n, G, P, c->vg_part.as<double>());
-    else      k_vgicp_linearize<false><<<nb, 64, 0, st>>>(r.src, r.cov, r.n, G, P, c->vg_part.as<double>());
-    k_vgicp_total<<<1, 64, 0, st>>>(c->vg_part.as<double>(), nb, c->vg_out.as<double>());
-    ctx_prof_mark(c, -1);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->vg_host.p, c->vg_out.p, sizeof(double) * kOut, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    memcpy(out, c->vg_host.p, sizeof(double) * kOut);
-    ++r.n_evals;
-    return LISREG_OK;
+    const int rc = eval_totals(c, nb, [&](double* part) {
+        ctx_prof_mark(c, 0);                                       // "assoc" = the linearisations (both launches), one interval each
+        if (hess) k_vgicp_linearize<true><<<nb, 64, 0, c->stream>>>(r.src, r.cov, r.n, G, P, part);
+        else      k_vgicp_linearize<false><<<nb, 64, 0, c->stream>>>(r.src, r.cov, r.n, G, P, part);
+    }, true, out);
+    if (!rc) ++r.n_evals;
+    return rc;
 }
 
 // the checks and the staging every entry point with a source shares: its distributions end up in c->vg_pts / c->vg_cov
@@ -494,60 +454,21 @@ int lisreg_vgicp_set_target(lisreg_ctx* c, int slot, const void* cloud, int n, i
     HIPCHK(c, hipMemcpyAsync(T.cells.p, c->vg_cells.p, sizeof(int) * (n_grid_cells + 1), hipMemcpyDeviceToDevice, st));
     T.grid = g; T.grid.pts = T.sorted.as<float4>(); T.grid.cell_start = T.cells.as<int>();
     for (int k = 0; k < 6; ++k) T.bb[k] = bb[k];
-    // ---- the voxel geometry (pcl::VoxelGrid's, as the NDT target's) ------------------------------------------------------------------
-    const float inv = 1.0f / (float)P->resolution;
-    VoxelDesc d;
-    long long div_b[3];
-    const double lim = 2.0e9;
-    for (int k = 0; k < 3; ++k) {
-        const double lo = floor((double)(bb[k] * inv)), hi = floor((double)(bb[3 + k] * inv));
-        if (!(fabs(lo) < lim && fabs(hi) < lim)) return bad(c, "vgicp_set_target: the grid has more than 2^26 cells (resolution too small for this cloud)");
-        T.min_b[k] = (int)floorf(bb[k] * inv);
-        div_b[k] = (long long)floorf(bb[3 + k] * inv) - T.min_b[k] + 1;
-    }
-    if (div_b[0] > kVgMaxCells || div_b[1] > kVgMaxCells || div_b[2] > kVgMaxCells || div_b[0] * div_b[1] > kVgMaxCells ||
-        div_b[0] * div_b[1] * div_b[2] > kVgMaxCells)
-        return bad(c, "vgicp_set_target: the grid has more than 2^26 cells (the voxel table is dense; resolution too small for this cloud)");
-    const long long total = div_b[0] * div_b[1] * div_b[2];
-    for (int k = 0; k < 3; ++k) T.dims[k] = (int)div_b[k];
-    d.inv_leaf = inv; d.min_b0 = T.min_b[0]; d.min_b1 = T.min_b[1]; d.min_b2 = T.min_b[2];
-    d.mul1 = T.dims[0]; d.mul2 = T.dims[0] * T.dims[1];
-    const long long max_buckets = 1LL << 22;
-    d.span = (uint32_t)std::max(1LL, (total + max_buckets - 1) / max_buckets);
-    const int n_buckets = (int)((total + d.span - 1) / d.span);
-    // ---- sort by voxel, voxel starts (the launches of lisreg_voxel_downsample) -------------------------------------------------------
-    rc = ensure_sort_scratch(c, (size_t)m, (size_t)std::max(n_buckets, m) + 1);
+    // ---- the voxel table (pcl::VoxelGrid's geometry and sort, as the NDT target's) and its statistics --------------------------------------
+    // "solve" = the voxel sort and statistics (with the wait for the voxel count)
+    rc = voxel_table_build(c, "vgicp_set_target", "voxel table", c->vg_pts.as<float4>(), m, bb, P->resolution, 1, T);
     if (rc) return rc;
-    HIPCHK(c, c->vox_order.ensure(sizeof(int) * (size_t)m));
-    HIPCHK(c, c->vox_sidx.ensure(sizeof(uint32_t) * (size_t)m));
-    HIPCHK(c, c->vox_head.ensure(sizeof(int) * ((size_t)m + 1)));
-    HIPCHK(c, c->vox_slot.ensure(sizeof(int) * ((size_t)m + 2)));
-    ctx_prof_mark(c, 1);                                           // "solve" = the voxel sort and statistics (with the wait for the voxel count)
-    launch_voxel_sort(c->vg_pts.as<float4>(), m, d, n_buckets, sort_buffers(c), c->vox_order.as<int>(), c->vox_sidx.as<uint32_t>(),
-                      c->vox_head.as<int>(), c->vox_slot.as<int>(), st);
-    int n_vox = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_vox, c->vox_slot.as<int>() + m, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (n_vox < 1 || n_vox > m) return ctx_fail(c, LISREG_ERR_HIP, "vgicp_set_target: the voxel sort returned an impossible voxel count");
-    HIPCHK(c, c->vox_start.ensure(sizeof(int) * ((size_t)n_vox + 2)));
-    launch_voxel_starts(m, c->vox_head.as<int>(), c->vox_slot.as<int>(), c->vox_start.as<int>(), st);
-    // ---- the statistics -----------------------------------------------------------------------------------------------------------------
-    HIPCHK(c, T.stats.ensure(sizeof(double) * kVgRec * (size_t)n_vox));
-    HIPCHK(c, T.cell.ensure(sizeof(int) * (size_t)n_vox));
-    HIPCHK(c, T.table.ensure(sizeof(int) * (size_t)total));
-    HIPCHK(c, hipMemsetAsync(T.table.p, 0xFF, sizeof(int) * (size_t)total, st));
     VgBuild B;
     B.pts = c->vg_pts.as<float4>(); B.cov = c->vg_cov.as<double>(); B.order = c->vox_order.as<int>(); B.sidx = c->vox_sidx.as<uint32_t>();
-    B.vstart = c->vox_start.as<int>(); B.n_vox = n_vox; B.n_cells = total;
+    B.vstart = c->vox_start.as<int>(); B.n_vox = T.n_voxels; B.n_cells = (long long)T.dims[0] * T.dims[1] * T.dims[2];
     B.stats = T.stats.as<double>(); B.cell = T.cell.as<int>(); B.table = T.table.as<int>();
-    k_vg_stats_small<<<(n_vox + 255) / 256, 256, 0, st>>>(B);
-    k_vg_stats_big<<<n_vox, 64, 0, st>>>(B);
+    launch_voxel_stats(B, st);
     ctx_prof_mark(c, -1);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(st));
     ctx_prof_collect(c);
-    T.n_voxels = n_vox; T.n_points = m; T.resolution = P->resolution;
-    if (info) { for (int k = 0; k < 3; ++k) info->dims[k] = T.dims[k]; info->n_voxels = n_vox; info->n_points = m; }
+    T.n_points = m;
+    if (info) { for (int k = 0; k < 3; ++k) info->dims[k] = T.dims[k]; info->n_voxels = T.n_voxels; info->n_points = m; }
     T.valid = true;
     return LISREG_OK;
 }
@@ -594,18 +515,7 @@ int lisreg_vgicp_get_voxels(lisreg_ctx* c, int slot, int* cell_ids, int* counts,
     *n_out = T->n_voxels;
     if (T->n_voxels > capacity) return LISREG_OK;
     if (!cell_ids || !counts || !means || !cov6) return bad(c, "vgicp_get_voxels: NULL output");
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<double> st((size_t)T->n_voxels * kVgRec);
-    HIPCHK(c, hipMemcpyAsync(st.data(), T->stats.p, sizeof(double) * st.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cell_ids, T->cell.p, sizeof(int) * (size_t)T->n_voxels, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int v = 0; v < T->n_voxels; ++v) {
-        const double* r = &st[(size_t)v * kVgRec];
-        counts[v] = (int)r[9];
-        memcpy(means + 3 * (size_t)v, r, sizeof(double) * 3);
-        memcpy(cov6 + 6 * (size_t)v, r + 3, sizeof(double) * 6);
-    }
-    return LISREG_OK;
+    return voxel_table_read(c, *T, nullptr, cell_ids, counts, means, cov6, capacity);
 }
 
 int lisreg_vgicp_linearize(lisreg_ctx* c, int slot, const void* source, int n, int stride, int fmt, const lisreg_vgicp_params* P,

@@ -4,7 +4,7 @@
 // (select_registration_method("FAST_VGICP"), :2771).  The definition is tests/vgicp_batch_ref.py: the loop of single alignments plus the
 // fitness score and the `best` rule of §7m.  Every item of a batch gets the bits lisreg_vgicp_align returns for it alone: the lanes run
 // the same body (lisreg_vgicp_lane.hpp) over the same partition of the source into wavefronts, the partial records are added in
-// k_vgicp_total's order (lisreg_batch_rounds.hpp), and the Levenberg-Marquardt loop is the single aligner's (lisreg_lm_stepper.hpp).
+// the single call's order (sum_records of lisreg_fp64_sums.hpp), and the Levenberg-Marquardt loop is the single aligner's (lisreg_lm_stepper.hpp).
 // What the batch saves: a source's distributions are made once per call, and the outstanding evaluations of ALL unfinished items are
 // answered by one round of launches and one synchronisation.  VGICP derives its pairs again at every evaluation, so an item owns no
 // device memory.  The fitness score searches the grid lisreg_vgicp_set_target keeps with the slot, with FastGICP's search
@@ -22,7 +22,7 @@ namespace {
 // One evaluation of one item.  The entries of a round sit in one array, the linearising ones first; wg_start[e] is the first workgroup
 // of entry e over the whole round (wg_start[n_entries] = their number), so a workgroup's number is also the number of its partial record.
 struct VgWork {
-    VgGrid    G;
+    VoxelView    G;
     VgPose    P;
     long long src_off;     // the source's first finite point in the batch's point / covariance buffers
     int       n;           // finite points of the source
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(64) void k_vgicp_linearize_batch(const VgWork* __re
     const VgWork* __restrict__ w = work + e;
     const int n = w->n;
     const int i = (g - wg_start[e]) * 64 + (int)threadIdx.x;
-    const VgGrid G = w->G;
+    const VoxelView G = w->G;
     const VgPose P = w->P;
     const size_t s = (size_t)w->src_off + (size_t)i;
     double acc[28], pairs;
@@ -84,7 +84,7 @@ struct VgBatch {
 
     static void fill(const Target& T, const double Tm[16], long long src_off, long long, int n, Work* w)
     {
-        w->G = vg_grid_view(T);
+        w->G = voxel_table_view(T);
         w->P = vgicp_host::pose_of<VgPose>(Tm);
         w->src_off = src_off; w->n = n; w->reserved = 0;
     }

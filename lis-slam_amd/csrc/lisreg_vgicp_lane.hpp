@@ -1,37 +1,25 @@
 // lisreg_vgicp_lane.hpp — what one lane of a VGICP linearisation computes, shared by the single alignment
 // (lisreg_vgicp.hip) and the batch (lisreg_vgicp_batch.hip, §7n): the transform of one source point, its voxel, the matrix of the pair,
-// the 28 terms and the wavefront butterfly.  Both units are built with -ffp-contract=off and inline this body, so a lane of either
-// computes the same bits from the same input.  Also the few host helpers of lisreg_vgicp.hip that the batch shares.  Not installed.
+// the 28 terms and the wavefront sums (lisreg_fp64_sums.hpp).  Both units are built with -ffp-contract=off and inline this body, so a
+// lane of either computes the same bits from the same input.  Also the few host helpers of lisreg_vgicp.hip that the batch shares.  Not
+// installed.
 #pragma once
-#include "lisreg_ctx.hpp"
+#include "lisreg_fp64_sums.hpp"
 #include "lisreg_vgicp_host.hpp"
 
 #include <string>
 
 namespace lisreg {
 
-constexpr int kVgRec = 10;             // doubles per voxel: mean [3], upper triangle of the mean covariance [6], points
+static_assert(vgicp_host::kOut == kEvalOut, "one evaluation is 29 doubles in every family");
 
-struct VgGrid {
-    const double* stats;
-    const int*    table;
-    int    d0, d1, d2, m0, m1, m2;
-    double inv_res;
-};
 struct VgPose { double R[9], t[3]; };
-
-__device__ __forceinline__ double vg_wave_sum(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 // One source point per lane: the 28 terms of its pair at P (zeros without one, and on a lane past the source's end: !live) and its 1.0
 // or 0.0 for the pair count.  src_i / ca: the lane's point and the six entries of its covariance (read only if live).  The wavefront's
 // sums of them are left in acc[28] and pairs on every lane.
 template <bool HESS>
-__device__ __forceinline__ void vg_linearize_lane(bool live, const float4* __restrict__ src_i, const double* __restrict__ ca, const VgGrid& G,
+__device__ __forceinline__ void vg_linearize_lane(bool live, const float4* __restrict__ src_i, const double* __restrict__ ca, const VoxelView& G,
                                                   const VgPose& P, double acc[28], double& pairs)
 {
 #pragma unroll
@@ -50,7 +38,7 @@ __device__ __forceinline__ void vg_linearize_lane(bool live, const float4* __res
         if (f0 >= 0.0 && f0 < (double)G.d0 && f1 >= 0.0 && f1 < (double)G.d1 && f2 >= 0.0 && f2 < (double)G.d2)
             v = G.table[(long long)f0 + (long long)f1 * G.d0 + (long long)f2 * (long long)G.d0 * G.d1];
         if (v >= 0) {
-            const double* __restrict__ rec = G.stats + (size_t)v * kVgRec;
+            const double* __restrict__ rec = G.stats + (size_t)v * kVoxelRec;
             const double d[3] = { rec[0] - x0, rec[1] - x1, rec[2] - x2 };
             const double C[3][3] = { { ca[0], ca[1], ca[2] }, { ca[1], ca[3], ca[4] }, { ca[2], ca[4], ca[5] } };
             double RC[3][3];
@@ -93,15 +81,13 @@ __device__ __forceinline__ void vg_linearize_lane(bool live, const float4* __res
         }
     }
 #pragma unroll
-    for (int k = 0; k < 28; ++k) acc[k] = vg_wave_sum(acc[k]);
-    pairs = vg_wave_sum(pairs);
+    for (int k = 0; k < 28; ++k) acc[k] = wave_sum(acc[k]);
+    pairs = wave_sum(pairs);
 }
 
 // ---- lisreg_vgicp.hip: the host checks of every VGICP entry point (one copy) -----------------------------------------------------------
 // P may be null in vg_find_target: the slot's resolution is then not compared
 int vg_check_params(lisreg_ctx* c, const lisreg_vgicp_params* P, const char* who);
 int vg_find_target(lisreg_ctx* c, int slot, const lisreg_vgicp_params* P, const char* who, VgicpTarget** out);
-// the linearisation's view of a slot's target
-VgGrid vg_grid_view(const VgicpTarget& T);
 
 }  // namespace lisreg

@@ -540,35 +540,28 @@ def lib():
     return _lib
 
 
-def fgicp_default_params(kind: int = 0, **overrides) -> FgicpParams:
-    p = FgicpParams()
-    if lib().lisreg_fgicp_default_params(kind, C.byref(p)):
-        raise LisregError(ERR_ARG, "lisreg_fgicp_default_params")
+def _default_params(struct, fn_name: str, kind: int, overrides: dict):
+    """the library's defaults of one verifier's parameter struct, then the caller's overrides (an unknown name raises AttributeError)"""
+    p = struct()
+    if getattr(lib(), fn_name)(kind, C.byref(p)):
+        raise LisregError(ERR_ARG, fn_name)
     for k, v in overrides.items():
         if not hasattr(p, k):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def fgicp_default_params(kind: int = 0, **overrides) -> FgicpParams:
+    return _default_params(FgicpParams, "lisreg_fgicp_default_params", kind, overrides)
 
 
 def vgicp_default_params(kind: int = 0, **overrides) -> VgicpParams:
-    p = VgicpParams()
-    if lib().lisreg_vgicp_default_params(kind, C.byref(p)):
-        raise LisregError(ERR_ARG, "lisreg_vgicp_default_params")
-    for k, v in overrides.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _default_params(VgicpParams, "lisreg_vgicp_default_params", kind, overrides)
 
 
 def ndt_default_params(kind: int = 0, **overrides) -> NdtParams:
-    p = NdtParams()
-    if lib().lisreg_ndt_default_params(kind, C.byref(p)):
-        raise LisregError(ERR_ARG, "lisreg_ndt_default_params")
-    for k, v in overrides.items():
-        setattr(p, k, v)
-    return p
+    return _default_params(NdtParams, "lisreg_ndt_default_params", kind, overrides)
 
 
 def localmap_default_params() -> LocalMapParams:
@@ -1592,53 +1585,8 @@ class Context:
         self._chk(self._L.lisreg_ndt_set_target(self._h, slot, ptr, n, stride, fmt, C.byref(params), C.byref(info)))
         return dict(dims=list(info.dims), n_voxels=info.n_voxels, n_valid=info.n_valid)
 
-    def ndt_align(self, slot: int, source, params: "NdtParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
-        """pcl::NormalDistributionsTransform::align against the NDT target in `slot`; returns the result dict (+ 'aligned')."""
-        ptr, n, stride, fmt, keep = self._cloud_args(source)
-        res = NdtResult()
-        g = None if guess is None else np.ascontiguousarray(guess, np.float32).ravel().ctypes.data_as(C.POINTER(C.c_float))
-        out = np.zeros_like(keep) if (want_aligned and keep is not None) else None
-        o = C.c_void_p(out_ptr) if out_ptr else (_vp(out) if out is not None else None)
-        self._chk(self._L.lisreg_ndt_align(self._h, slot, ptr, n, stride, fmt, C.byref(params), g, C.byref(res), o))
-        d = res.as_dict()
-        if out is not None:
-            d["aligned"] = out
-        return d
-
-    def ndt_get_voxels(self, slot: int) -> dict:
-        """the valid voxels of an NDT target in ascending cell order: cell_ids, counts, means [m, 3], icov6 [m, 6]"""
-        m = C.c_int(0)
-        self._chk(self._L.lisreg_ndt_get_voxels(self._h, slot, None, None, None, None, 0, C.byref(m)))
-        cap = max(m.value, 1)
-        ids, cnt = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
-        means, ic = np.zeros((cap, 3)), np.zeros((cap, 6))
-        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
-        self._chk(self._L.lisreg_ndt_get_voxels(self._h, slot, ids.ctypes.data_as(ip), cnt.ctypes.data_as(ip), means.ctypes.data_as(dp),
-                                                ic.ctypes.data_as(dp), cap, C.byref(m)))
-        k = m.value
-        return dict(cell_ids=ids[:k], counts=cnt[:k], means=means[:k], icov6=ic[:k])
-
-    def ndt_derivatives(self, slot: int, source, params: "NdtParams", p, with_hessian: bool = True):
-        """one evaluation at p = (tx, ty, tz, a, b, c): (out [28] = score, gradient, Hessian upper triangle; pairs)"""
-        ptr, n, stride, fmt, _keep = self._cloud_args(source)
-        p = np.ascontiguousarray(p, np.float64)
-        out = np.zeros(28)
-        pairs = C.c_longlong(0)
-        dp = C.POINTER(C.c_double)
-        self._chk(self._L.lisreg_ndt_derivatives(self._h, slot, ptr, n, stride, fmt, C.byref(params), p.ctypes.data_as(dp),
-                                                 1 if with_hessian else 0, out.ctypes.data_as(dp), C.byref(pairs)))
-        return out, pairs.value
-
-    # -- §7k: VGICP registration -------------------------------------------------------------------------
-    def vgicp_set_target(self, slot: int, cloud, params: "VgicpParams") -> dict:
-        """distributions + voxel statistics of the target; cloud = host PCL-struct array or (device_ptr, n)"""
-        ptr, n, stride, fmt, _keep = self._cloud_args(cloud)
-        info = VgicpInfo()
-        self._chk(self._L.lisreg_vgicp_set_target(self._h, slot, ptr, n, stride, fmt, C.byref(params), C.byref(info)))
-        return dict(dims=list(info.dims), n_voxels=info.n_voxels, n_points=info.n_points)
-
-    def _gicp_align(self, fn, result_type, slot, source, params, guess, want_aligned, out_ptr) -> dict:
-        """one alignment of the fast_gicp family through `fn`; returns the result dict (+ 'aligned')."""
+    def _align(self, fn, result_type, slot, source, params, guess, want_aligned, out_ptr) -> dict:
+        """one alignment of a verifier through `fn`; returns the result dict (+ 'aligned')."""
         ptr, n, stride, fmt, keep = self._cloud_args(source)
         res = result_type()
         g = None if guess is None else np.ascontiguousarray(guess, np.float32).ravel().ctypes.data_as(C.POINTER(C.c_float))
@@ -1650,9 +1598,53 @@ class Context:
             d["aligned"] = out
         return d
 
+    def _get_voxels(self, fn, slot: int, last_key: str) -> dict:
+        """the voxels `fn` reports for a slot: cell_ids, counts, means [m, 3] and the [m, 6] array named last_key"""
+        m = C.c_int(0)
+        self._chk(fn(self._h, slot, None, None, None, None, 0, C.byref(m)))
+        cap = max(m.value, 1)
+        ids, cnt = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        means, sym = np.zeros((cap, 3)), np.zeros((cap, 6))
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        self._chk(fn(self._h, slot, ids.ctypes.data_as(ip), cnt.ctypes.data_as(ip), means.ctypes.data_as(dp), sym.ctypes.data_as(dp), cap,
+                     C.byref(m)))
+        k = m.value
+        return {"cell_ids": ids[:k], "counts": cnt[:k], "means": means[:k], last_key: sym[:k]}
+
+    def _sums_at(self, fn, slot, source, params, poses, with_hessian):
+        """one evaluation through `fn` at `poses` (float64 arrays, None: a NULL pointer): (out [28]; pairs)"""
+        ptr, n, stride, fmt, _keep = self._cloud_args(source)
+        dp = C.POINTER(C.c_double)
+        poses = [None if a is None else np.ascontiguousarray(a, np.float64).ravel() for a in poses]
+        out = np.zeros(28)
+        pairs = C.c_longlong(0)
+        self._chk(fn(self._h, slot, ptr, n, stride, fmt, C.byref(params), *[None if a is None else a.ctypes.data_as(dp) for a in poses],
+                     1 if with_hessian else 0, out.ctypes.data_as(dp), C.byref(pairs)))
+        return out, pairs.value
+
+    def ndt_align(self, slot: int, source, params: "NdtParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
+        """pcl::NormalDistributionsTransform::align against the NDT target in `slot`; returns the result dict (+ 'aligned')."""
+        return self._align(self._L.lisreg_ndt_align, NdtResult, slot, source, params, guess, want_aligned, out_ptr)
+
+    def ndt_get_voxels(self, slot: int) -> dict:
+        """the valid voxels of an NDT target in ascending cell order: cell_ids, counts, means [m, 3], icov6 [m, 6]"""
+        return self._get_voxels(self._L.lisreg_ndt_get_voxels, slot, "icov6")
+
+    def ndt_derivatives(self, slot: int, source, params: "NdtParams", p, with_hessian: bool = True):
+        """one evaluation at p = (tx, ty, tz, a, b, c): (out [28] = score, gradient, Hessian upper triangle; pairs)"""
+        return self._sums_at(self._L.lisreg_ndt_derivatives, slot, source, params, [p], with_hessian)
+
+    # -- §7k: VGICP registration -------------------------------------------------------------------------
+    def vgicp_set_target(self, slot: int, cloud, params: "VgicpParams") -> dict:
+        """distributions + voxel statistics of the target; cloud = host PCL-struct array or (device_ptr, n)"""
+        ptr, n, stride, fmt, _keep = self._cloud_args(cloud)
+        info = VgicpInfo()
+        self._chk(self._L.lisreg_vgicp_set_target(self._h, slot, ptr, n, stride, fmt, C.byref(params), C.byref(info)))
+        return dict(dims=list(info.dims), n_voxels=info.n_voxels, n_points=info.n_points)
+
     def vgicp_align(self, slot: int, source, params: "VgicpParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
         """FastVGICP::align against the VGICP target in `slot`; returns the result dict (+ 'aligned')."""
-        return self._gicp_align(self._L.lisreg_vgicp_align, VgicpResult, slot, source, params, guess, want_aligned, out_ptr)
+        return self._align(self._L.lisreg_vgicp_align, VgicpResult, slot, source, params, guess, want_aligned, out_ptr)
 
     def vgicp_covariances(self, cloud, k: int = 20, want_neighbours: bool = True, cell_edge: float = 0.0):
         """(cov6 [n, 6] with NaN rows for NaN points, neighbours [n, k] or None) of every point's distribution"""
@@ -1665,27 +1657,11 @@ class Context:
 
     def vgicp_get_voxels(self, slot: int) -> dict:
         """the voxels of a VGICP target in ascending cell order: cell_ids, counts, means [m, 3], cov6 [m, 6]"""
-        m = C.c_int(0)
-        self._chk(self._L.lisreg_vgicp_get_voxels(self._h, slot, None, None, None, None, 0, C.byref(m)))
-        cap = max(m.value, 1)
-        ids, cnt = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
-        means, cv = np.zeros((cap, 3)), np.zeros((cap, 6))
-        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
-        self._chk(self._L.lisreg_vgicp_get_voxels(self._h, slot, ids.ctypes.data_as(ip), cnt.ctypes.data_as(ip), means.ctypes.data_as(dp),
-                                                  cv.ctypes.data_as(dp), cap, C.byref(m)))
-        k = m.value
-        return dict(cell_ids=ids[:k], counts=cnt[:k], means=means[:k], cov6=cv[:k])
+        return self._get_voxels(self._L.lisreg_vgicp_get_voxels, slot, "cov6")
 
     def vgicp_linearize(self, slot: int, source, params: "VgicpParams", T, with_hessian: bool = True):
         """one linearisation at T (4x4): (out [28] = error, b, H upper triangle; pairs)"""
-        ptr, n, stride, fmt, _keep = self._cloud_args(source)
-        T = np.ascontiguousarray(T, np.float64).reshape(16)
-        out = np.zeros(28)
-        pairs = C.c_longlong(0)
-        dp = C.POINTER(C.c_double)
-        self._chk(self._L.lisreg_vgicp_linearize(self._h, slot, ptr, n, stride, fmt, C.byref(params), T.ctypes.data_as(dp),
-                                                 1 if with_hessian else 0, out.ctypes.data_as(dp), C.byref(pairs)))
-        return out, pairs.value
+        return self._sums_at(self._L.lisreg_vgicp_linearize, slot, source, params, [np.reshape(T, 16)], with_hessian)
 
     # -- §7l: FastGICP registration ----------------------------------------------------------------------
     def fgicp_set_target(self, slot: int, cloud, params: "FgicpParams", cell_edge: float = 0.0) -> dict:
@@ -1697,7 +1673,7 @@ class Context:
 
     def fgicp_align(self, slot: int, source, params: "FgicpParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
         """FastGICP::align against the FastGICP target in `slot`; returns the result dict (+ 'aligned')."""
-        return self._gicp_align(self._L.lisreg_fgicp_align, FgicpResult, slot, source, params, guess, want_aligned, out_ptr)
+        return self._align(self._L.lisreg_fgicp_align, FgicpResult, slot, source, params, guess, want_aligned, out_ptr)
 
     def fgicp_correspondences(self, slot: int, source, params: "FgicpParams", T, want_sqdist: bool = True):
         """the search at T (4x4): (index [n] in the caller's target cloud, -1 none; squared distance [n], NaN where -1, or None)"""
@@ -1712,16 +1688,8 @@ class Context:
 
     def fgicp_linearize(self, slot: int, source, params: "FgicpParams", T_pairs, with_hessian: bool = True, T_eval=None):
         """pairs and M from a search at T_pairs, the sums at T_eval (None: T_pairs): (out [28] = error, b, H upper triangle; pairs)"""
-        ptr, n, stride, fmt, _keep = self._cloud_args(source)
-        T = np.ascontiguousarray(T_pairs, np.float64).reshape(16)
-        Te = None if T_eval is None else np.ascontiguousarray(T_eval, np.float64).reshape(16)
-        out = np.zeros(28)
-        pairs = C.c_longlong(0)
-        dp = C.POINTER(C.c_double)
-        self._chk(self._L.lisreg_fgicp_linearize(self._h, slot, ptr, n, stride, fmt, C.byref(params), T.ctypes.data_as(dp),
-                                                 None if Te is None else Te.ctypes.data_as(dp), 1 if with_hessian else 0,
-                                                 out.ctypes.data_as(dp), C.byref(pairs)))
-        return out, pairs.value
+        return self._sums_at(self._L.lisreg_fgicp_linearize, slot, source, params,
+                             [np.reshape(T_pairs, 16), None if T_eval is None else np.reshape(T_eval, 16)], with_hessian)
 
     # -- §7m, §7n: FastGICP / VGICP verification of a candidate list -----------------------------------------
     def _gicp_align_batch(self, fn, item_type, result_type, info_type, who, sources, items, params, want_fitness):

@@ -122,10 +122,24 @@ def test_the_restatement_is_fgicp_batch_refs_reading():
 def test_both_units_share_one_copy_of_the_lane_body_and_of_the_round_helpers():
     """the per-lane arithmetic and the totals exist once in the sources, and every unit that inlines them is built without contraction"""
     text = {f: open(os.path.join(CSRC, f)).read() for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))}
-    for needle, home in (("void vg_linearize_lane(", "lisreg_vgicp_lane.hpp"), ("struct VgGrid {", "lisreg_vgicp_lane.hpp"),
+    for needle, home in (("void vg_linearize_lane(", "lisreg_vgicp_lane.hpp"), ("struct VoxelView {", "lisreg_ctx.hpp"),
                          ("struct VgPose {", "lisreg_vgicp_lane.hpp"), ("int fg_entry_of(", "lisreg_batch_rounds.hpp"),
-                         ("void k_fgicp_total_batch(", "lisreg_batch_rounds.hpp")):
+                         ("void k_fgicp_total_batch(", "lisreg_batch_rounds.hpp"),
+                         # the fp64 butterfly, the strided total and the lane / wavefront threshold of the voxel statistics
+                         ("for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);", "lisreg_fp64_sums.hpp"),
+                         ("for (int k = 0; k < W; ++k) acc[k] += part[(size_t)b * W + k];", "lisreg_fp64_sums.hpp"),
+                         ("kVoxelBig = 48", "lisreg_fp64_sums.hpp"),
+                         # the dense-table limit and the read-back of the voxel count (the multi form reads its counts another way)
+                         ("max_cells = 1LL << 26", "lisreg_api_cloud.hip"), ("vox_slot.as<int>() + ", "lisreg_api_cloud.hip")):
         assert [f for f, t in text.items() if needle in t] == [home], needle
+    sums = text["lisreg_fp64_sums.hpp"]
+    assert re.search(r"double wave_sum\(double v\)\s*\{\s*#pragma unroll\s*for \(int d = 32; d > 0; d >>= 1\) v \+= __shfl_xor\(v, d\);", sums)
+    # no other butterfly in the verifiers' units: they call the header's; and none of them builds a dense table of its own
+    for unit in ("lisreg_ndt.hip", "lisreg_vgicp.hip", "lisreg_fgicp.hip", "lisreg_vgicp_lane.hpp", "lisreg_fgicp_lane.hpp", "lisreg_batch_rounds.hpp",
+                 "lisreg_fgicp_batch.hip", "lisreg_vgicp_batch.hip", "lisreg_batch_driver.hpp"):
+        assert "__shfl_xor" not in text[unit] and "<< 26" not in text[unit] and "Big = " not in text[unit], unit
+    assert "sum_records<W>(part + (size_t)p0 * W, n_part, acc);" in text["lisreg_batch_rounds.hpp"]
+    assert "sum_records<kEvalOut>(part, n_part, acc);" in text["lisreg_vgicp.hip"]
     # VGICP's 28 terms are written once: the weight of a pair (the square root of the voxel's point count) occurs in the lane header only
     assert [f for f, t in text.items() if "sqrt(rec[9])" in t] == ["lisreg_vgicp_lane.hpp"]
     for unit in ("lisreg_vgicp.hip", "lisreg_vgicp_batch.hip"):
