@@ -357,6 +357,26 @@ int  lisreg_get_map_grid(lisreg_ctx* ctx, int slot, int* dims, float* geom);
 int  lisreg_test_nn1(lisreg_ctx* ctx, int slot, const float* queries, int n, float max_dist, int form, const int* seeds,
                      int* idx_out, float* sqd_out);
 
+/* Test hook: the exclusive scan under every bucket sort, compaction and cell-row build (lisreg_index.hip), dispatched exactly as production
+ * dispatches it — no forced form, the thresholds as they stand: n <= 16 384 one workgroup (k_scan_small), up to 4 096 tiles of 2 048 the
+ * fused two-launch form, beyond that three launches.
+ *   in1 == NULL   single form: out0[n0 + 1] = exclusive scan of in0[n0], out0[n0] = the total.  n0 = 0 is valid: out0[0] = 0.
+ *   in1 != NULL   pair form: the two scans of a slot's corner and surf row counts in one launch pair (the tiled kernels at any size, one
+ *                 tile included; either half beyond 4 096 tiles sends both through the single form).  A half with n = 0 is off, as in
+ *                 production: its output is neither written nor returned (its pointers may be anything).
+ *   in_offset, out_offset   0 to 3, in ints, added to 16-byte aligned device allocations: the tiled kernels move full tiles as int4 only
+ *                 when both pointers are aligned, so (0, 0) takes the vector path and anything else the scalar path (the feature
+ *                 extractor scans into such an address on purpose).  k_scan_small has one path.
+ *   in_place      != 0: out = in (the offsets must be equal).  Every form reads a thread's items before it writes them, so all three
+ *                 support it.
+ * Inputs and outputs are host arrays; the device buffers are the call's own, the scratch of each half is n / 2048 + 4 ints (the smallest
+ * a production call site allocates).  16 guard words behind out[n], the words in front of a shifted out and 16 behind the scratch are
+ * checked after the run: LISREG_ERR_HIP with a text that names the word if one changed.  Runs on the context's stream and returns with
+ * the outputs complete.  LISREG_ERR_ARG: a NULL pointer of a half that runs, a negative size, n1 > 0 without in1, an offset outside
+ * 0 to 3, in_place with differing offsets. */
+int  lisreg_test_scan(lisreg_ctx* ctx, const int* in0, int n0, const int* in1, int n1, int in_offset, int out_offset, int in_place,
+                      int* out0, int* out1);
+
 /* Diagnostics (tests): the search index of target `slot`, kind 0 = corner / 1 = surf, as it stands in HBM after the work queued on
  * the context's stream: dims = {n, nx, ny, nz, n_cells}, geom = {ox, oy, oz, cell edge}, the cell-sorted records
  * (x, y, z, bit-cast original index; ordered by cell (ix * ny + iy) * nz + iz, then original index) and cell_start[n_cells + 1].

@@ -336,6 +336,82 @@ int lisreg_test_nn1(lisreg_ctx* c, int slot, const float* queries, int n, float 
     return LISREG_OK;
 }
 
+// Test hook: exclusive_scan (in1 == NULL) or the pair of scans of launch_crow_rows_pair (in1 != NULL) exactly as production dispatches
+// them, in buffers of the call's own.  Every buffer is filled with a pattern first; the words in front of a shifted output, the 16 behind
+// out[n] and the 16 behind tmp (sized by the smallest formula of a production call site, n / 2048 + 4 ints) must still hold it afterwards.
+int lisreg_test_scan(lisreg_ctx* c, const int* in0, int n0, const int* in1, int n1, int in_offset, int out_offset, int in_place,
+                     int* out0, int* out1)
+{
+    if (!c) return LISREG_ERR_ARG;
+    const bool pair = in1 != nullptr;
+    if (n0 < 0 || n1 < 0) return bad(c, "test_scan: negative size");
+    if (!pair && n1 != 0) return bad(c, "test_scan: n1 > 0 without in1");
+    if (in_offset < 0 || in_offset > 3 || out_offset < 0 || out_offset > 3) return bad(c, "test_scan: offsets are 0 to 3 ints");
+    if (in_place && in_offset != out_offset) return bad(c, "test_scan: in place needs in_offset == out_offset");
+    const int* hin[2] = { in0, in1 };
+    int* hout[2] = { out0, out1 };
+    const int n[2] = { n0, n1 };
+    bool on[2];
+    for (int k = 0; k < 2; ++k) {
+        on[k] = pair ? n[k] > 0 : k == 0;           // (the single form runs n0 = 0 too: out0[0] = 0; an empty half of the pair is off)
+        if (on[k] && ((n[k] > 0 && !hin[k]) || !hout[k])) return bad(c, "test_scan: NULL input / output");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    constexpr int kGuard = 16;
+    constexpr unsigned kFill = 0xA5A5A5A5u;         // (what hipMemsetAsync(0xA5) leaves in a word)
+    DevBuf din[2], dout[2], dtmp[2];
+    const int* pin[2] = { nullptr, nullptr };
+    int* pout[2] = { nullptr, nullptr };
+    int* ptmp[2] = { nullptr, nullptr };
+    size_t out_words[2] = { 0, 0 }, tmp_words[2] = { 0, 0 };
+    for (int k = 0; k < 2; ++k) {
+        if (!on[k]) continue;
+        out_words[k] = (size_t)out_offset + (size_t)n[k] + 1 + kGuard;
+        tmp_words[k] = (size_t)n[k] / 2048 + 4;
+        HIPCHK(c, dout[k].ensure(sizeof(int) * out_words[k]));
+        HIPCHK(c, dtmp[k].ensure(sizeof(int) * (tmp_words[k] + kGuard)));
+        HIPCHK(c, hipMemsetAsync(dout[k].p, 0xA5, sizeof(int) * out_words[k], st));
+        HIPCHK(c, hipMemsetAsync(dtmp[k].p, 0xA5, sizeof(int) * (tmp_words[k] + kGuard), st));
+        pout[k] = dout[k].as<int>() + out_offset;
+        ptmp[k] = dtmp[k].as<int>();
+        int* dst = pout[k];
+        if (!in_place) {
+            HIPCHK(c, din[k].ensure(sizeof(int) * ((size_t)in_offset + (size_t)std::max(n[k], 1))));
+            dst = din[k].as<int>() + in_offset;
+        }
+        if (n[k] > 0) HIPCHK(c, hipMemcpyAsync(dst, hin[k], sizeof(int) * (size_t)n[k], hipMemcpyHostToDevice, st));
+        pin[k] = dst;
+    }
+    if (pair) {
+        const int np[2] = { on[0] ? n[0] : 0, on[1] ? n[1] : 0 };
+        launch_exclusive_scan_pair(pin, pout, ptmp, np, st);
+    } else launch_exclusive_scan(pin[0], pout[0], ptmp[0], n[0], st);
+    HIPCHK(c, hipGetLastError());
+    std::vector<unsigned> guard[2], tguard[2];
+    for (int k = 0; k < 2; ++k) {
+        if (!on[k]) continue;
+        guard[k].assign((size_t)out_offset + kGuard, 0u); tguard[k].assign(kGuard, 0u);
+        HIPCHK(c, hipMemcpyAsync(hout[k], pout[k], sizeof(int) * ((size_t)n[k] + 1), hipMemcpyDeviceToHost, st));
+        if (out_offset) HIPCHK(c, hipMemcpyAsync(guard[k].data(), dout[k].p, sizeof(int) * (size_t)out_offset, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(guard[k].data() + out_offset, pout[k] + n[k] + 1, sizeof(int) * kGuard, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(tguard[k].data(), ptmp[k] + tmp_words[k], sizeof(int) * kGuard, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(c, hipStreamSynchronize(st));           // (the guards are locals; the buffers are freed on return)
+    for (int k = 0; k < 2; ++k) {
+        if (!on[k]) continue;
+        for (size_t i = 0; i < guard[k].size(); ++i)
+            if (guard[k][i] != kFill)
+                return ctx_fail(c, LISREG_ERR_HIP, "test_scan: the scan of half " + std::to_string(k) + " wrote outside out[0, n]: guard word " +
+                                std::to_string((long long)i - out_offset) + (i < (size_t)out_offset ? " (in front of out)" : " (behind out[n])") + " changed");
+        for (size_t i = 0; i < tguard[k].size(); ++i)
+            if (tguard[k][i] != kFill)
+                return ctx_fail(c, LISREG_ERR_HIP, "test_scan: the scan of half " + std::to_string(k) + " wrote behind tmp[n / 2048 + 4]: guard word " +
+                                std::to_string(i) + " changed");
+    }
+    return LISREG_OK;
+}
+
 int lisreg_dynamic_filter(lisreg_ctx* c, int slot, const void* cloud, int n, int stride, int fmt, float center_radius,
                           float dist_thre_min, float dist_thre_max, float near_dist_thre, void* out, int* n_out)
 {

@@ -213,6 +213,23 @@ void exclusive_scan(const int* in, int* out /* [n+1] */, int* tmp, int n, hipStr
     k_scan_add<<<nb, kScanBlock, 0, st>>>(out, tmp, n, nb);
 }
 
+// two scans in two launches (the tiled form whatever the size, one tile included); n[k] = 0: half k is off and nothing of it is touched.
+// A half beyond the fused form's 4 096 tiles sends both through exclusive_scan, one after the other.
+void exclusive_scan_pair(const int* const in[2], int* const out[2], int* const tmp[2], const int n[2], hipStream_t st)
+{
+    ScanPair sp = {};
+    for (int k = 0; k < 2; ++k) {
+        sp.in[k] = in[k]; sp.out[k] = out[k]; sp.tmp[k] = tmp[k]; sp.n[k] = n[k] > 0 ? n[k] : 0;
+        sp.nb[k] = (sp.n[k] + kScanTile - 1) / kScanTile;
+    }
+    if (sp.nb[0] + sp.nb[1] == 0) return;
+    if (sp.nb[0] <= kScanFusedMaxTiles && sp.nb[1] <= kScanFusedMaxTiles) {
+        k_scan_local_pair<<<sp.nb[0] + sp.nb[1], kScanBlock, 0, st>>>(sp);
+        k_scan_add_sum_pair<<<sp.nb[0] + sp.nb[1], kScanBlock, 0, st>>>(sp);
+    } else
+        for (int k = 0; k < 2; ++k) if (sp.n[k] > 0) exclusive_scan(in[k], out[k], tmp[k], sp.n[k], st);
+}
+
 // ---- bounding box ------------------------------------------------------------------------------------------
 __device__ __forceinline__ void k_bbox_block(const float4* __restrict__ pts, int n, float* __restrict__ part)
 {
@@ -1826,16 +1843,11 @@ void launch_crow_rows_pair(const GridIndex g[2], const int n_cells[2], const Cro
     }
     // row counts -> first rows: both scans in two launches (tiled form whatever the size)
     {
-        ScanPair sp = {};
-        for (int k = 0; k < 2; ++k) {
-            sp.in[k] = cb[k].need; sp.out[k] = cb[k].scan; sp.tmp[k] = cb[k].scan_tmp; sp.n[k] = on[k] ? n_cells[k] : 0;
-            sp.nb[k] = on[k] ? (n_cells[k] + kScanTile - 1) / kScanTile : 0;
-        }
-        if (sp.nb[0] <= kScanFusedMaxTiles && sp.nb[1] <= kScanFusedMaxTiles) {
-            k_scan_local_pair<<<sp.nb[0] + sp.nb[1], kScanBlock, 0, st>>>(sp);
-            k_scan_add_sum_pair<<<sp.nb[0] + sp.nb[1], kScanBlock, 0, st>>>(sp);
-        } else
-            for (int k = 0; k < 2; ++k) if (on[k]) exclusive_scan(cb[k].need, cb[k].scan, cb[k].scan_tmp, n_cells[k], st);
+        const int* in[2] = { cb[0].need, cb[1].need };
+        int* out[2] = { cb[0].scan, cb[1].scan };
+        int* tmp[2] = { cb[0].scan_tmp, cb[1].scan_tmp };
+        const int n[2] = { on[0] ? n_cells[0] : 0, on[1] ? n_cells[1] : 0 };
+        exclusive_scan_pair(in, out, tmp, n, st);
     }
     // rows
     {
@@ -1990,6 +2002,7 @@ void launch_count_jumps(const BlockDesc* blocks, int n_blocks, const Segment* se
 }
 
 void launch_exclusive_scan(const int* in, int* out, int* tmp, int n, hipStream_t st) { exclusive_scan(in, out, tmp, n, st); }
+void launch_exclusive_scan_pair(const int* const in[2], int* const out[2], int* const tmp[2], const int n[2], hipStream_t st) { exclusive_scan_pair(in, out, tmp, n, st); }
 
 void launch_pack_cloud(const void* raw_dev, size_t n, int stride, int has_label, float4* out, hipStream_t st)
 {

@@ -285,6 +285,8 @@ void launch_transform_cloud_m(const float4* in, int n, const float M12_host[12],
 void launch_count_jumps(const BlockDesc* blocks, int n_blocks, const Segment* segs, float thr, int* jumps, hipStream_t st);
 // out[n+1] = exclusive scan of in[n] (out[n] = total); tmp: n/2048 + 4 ints
 void launch_exclusive_scan(const int* in, int* out, int* tmp, int n, hipStream_t st);
+// the two scans of launch_crow_rows_pair (the row counts of a slot's corner and surf target) in one launch pair; n[k] = 0: half k is off
+void launch_exclusive_scan_pair(const int* const in[2], int* const out[2], int* const tmp[2], const int n[2], hipStream_t st);
 
 // §8 f-2 (lisreg_features.hip): range-image projection + LOAM feature extraction for one scan
 struct FeatureBuffers {

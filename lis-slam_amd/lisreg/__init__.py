@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "lisreg_device_count", "lisreg_create", "lisreg_destroy", "lisreg_last_error", "lisreg_set_stream",
     "lisreg_get_stream", "lisreg_default_params", "lisreg_set_target", "lisreg_set_target_slot",
     "lisreg_target_from_classes", "lisreg_align", "lisreg_align_batch", "lisreg_batch_prepare", "lisreg_batch_run",
-    "lisreg_batch_fetch", "lisreg_stage_host_items", "lisreg_upload_cloud", "lisreg_concat_device", "lisreg_batch_result_device", "lisreg_set_option", "lisreg_get_option", "lisreg_get_counters", "lisreg_get_neighbors", "lisreg_test_fit_models", "lisreg_test_solve_steps", "lisreg_test_nn1", "lisreg_get_map_grid", "lisreg_get_target_index", "lisreg_get_target_graph", "lisreg_get_target_cell_rows", "lisreg_keyframes_reset", "lisreg_keyframes_push", "lisreg_keyframes_target", "lisreg_get_trace",
+    "lisreg_batch_fetch", "lisreg_stage_host_items", "lisreg_upload_cloud", "lisreg_concat_device", "lisreg_batch_result_device", "lisreg_set_option", "lisreg_get_option", "lisreg_get_counters", "lisreg_get_neighbors", "lisreg_test_fit_models", "lisreg_test_solve_steps", "lisreg_test_nn1", "lisreg_test_scan", "lisreg_get_map_grid", "lisreg_get_target_index", "lisreg_get_target_graph", "lisreg_get_target_cell_rows", "lisreg_keyframes_reset", "lisreg_keyframes_push", "lisreg_keyframes_target", "lisreg_get_trace",
     "lisreg_set_profiling", "lisreg_get_timing", "lisreg_pose_to_matrix", "lisreg_transform_update",
     "lisreg_comm_unique_id", "lisreg_comm_init", "lisreg_gather_results", "lisreg_comm_destroy",
     "lisreg_voxel_downsample", "lisreg_voxel_downsample_multi", "lisreg_transform_cloud",
@@ -467,6 +467,7 @@ def lib():
         L.lisreg_nearest.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]
         L.lisreg_get_map_grid.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_float)]
         L.lisreg_test_nn1.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int, ip, ip, C.POINTER(C.c_float)]
+        L.lisreg_test_scan.argtypes = [vp, ip, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]
         L.lisreg_dynamic_filter.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                             C.c_float, vp, ip]
         L.lisreg_bbx_filter.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, dp, C.c_int, vp, ip]
@@ -1346,6 +1347,22 @@ class Context:
         self._chk(self._L.lisreg_test_nn1(self._h, int(slot), q.ctypes.data_as(fp), n, float(max_dist), int(form),
                                           None if sd is None else sd.ctypes.data_as(ip), idx.ctypes.data_as(ip), sqd.ctypes.data_as(fp)))
         return idx, sqd
+
+    def test_scan(self, in0, in1=None, in_offset: int = 0, out_offset: int = 0, in_place: bool = False):
+        """Test hook (lisreg_test_scan): the exclusive scan as production dispatches it.  in1 None: out0 [n0 + 1] int32 of in0 (out0[n0] =
+        the total).  Otherwise the pair form of the cell rows: (out0, out1), None for a half with n = 0 (off, as in production).  The
+        offsets (0 to 3 ints off a 16-byte aligned device address) choose the vector or the scalar path; in_place: out = in."""
+        a = [np.ascontiguousarray(in0, np.int32).ravel(), None if in1 is None else np.ascontiguousarray(in1, np.int32).ravel()]
+        ip = C.POINTER(C.c_int)
+        # (an empty array still hands over a pointer: in1 != NULL is what selects the pair form)
+        src = [None if v is None else (v if len(v) else np.zeros(1, np.int32)) for v in a]
+        out = [None if v is None else np.full(len(v) + 1, -1, np.int32) for v in a]
+        self._chk(self._L.lisreg_test_scan(self._h, src[0].ctypes.data_as(ip), len(a[0]), None if a[1] is None else src[1].ctypes.data_as(ip),
+                                           0 if a[1] is None else len(a[1]), int(in_offset), int(out_offset), 1 if in_place else 0,
+                                           out[0].ctypes.data_as(ip), None if a[1] is None else out[1].ctypes.data_as(ip)))
+        if in1 is None:
+            return out[0]
+        return tuple(o if len(v) else None for o, v in zip(out, a))
 
     def nearest_device(self, slot: int, q_ptr: int, n: int, max_dist: float, idx_ptr: int, sqd_ptr: int):
         self._chk(self._L.lisreg_nearest(self._h, slot, C.c_void_p(q_ptr), n, 16, FMT_DEVICE, max_dist,
