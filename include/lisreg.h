@@ -413,7 +413,9 @@ int  lisreg_get_trace(lisreg_ctx* ctx, float* buf, int max_iters);
  * out[4] = the distributions (search grid, k-nearest search, covariances); after lisreg_vgicp_align_batch out[0] / out[1] = the
  * rounds' linearisation and total launches (one interval per round) and their number, out[2] / out[3] = the fitness search, out[4] =
  * the distributions of every staged source.  After a lisreg_fgicp_* call: out[0] / out[1] = the sum
- * launches and their number, out[2] / out[3] = the search launches and their number, out[4] = the distributions. */
+ * launches and their number, out[2] / out[3] = the search launches and their number, out[4] = the distributions.  After
+ * lisreg_ndt_align_batch: out[0] / out[1] = the rounds' evaluation and total launches (one interval per round) and their number,
+ * out[2] / out[3] = the fitness search. */
 int  lisreg_set_profiling(lisreg_ctx* ctx, int enable);
 int  lisreg_get_timing(lisreg_ctx* ctx, double out[5]);
 
@@ -960,7 +962,9 @@ int  lisreg_ndt_default_params(int kind, lisreg_ndt_params* p);
 /* setInputTarget + setResolution: the Gaussians of `cloud` into NDT slot `slot` (0 .. 65535; NDT slots are apart from the map-index
  * slots).  Uses resolution, min_points_per_voxel and min_covar_eigvalue_mult of `params`.  NaN points belong to no voxel.  Refused
  * (LISREG_ERR_ARG): n <= 0, resolution <= 0, an infinite coordinate, a grid of more than 2^26 cells (the cell table is dense),
- * a target without a valid voxel.  info may be NULL. */
+ * a target without a valid voxel.  info may be NULL.  Besides the Gaussians the slot keeps a search grid over the target's finite
+ * points, for the fitness score of lisreg_ndt_align_batch (§7o): 16 bytes per finite point and 4 per grid cell (3.2 MB for a target
+ * of 200 000 points); the voxels and every alignment do not depend on it. */
 int  lisreg_ndt_set_target(lisreg_ctx* ctx, int slot, const void* cloud, int n, int stride_bytes, int fmt,
                            const lisreg_ndt_params* params, lisreg_ndt_info* info);
 /* align(): guess = row-major 4x4 or NULL for identity; aligned_out: NULL, or room for n points of the input layout.  Host PCL
@@ -976,6 +980,48 @@ int  lisreg_ndt_get_voxels(lisreg_ctx* ctx, int slot, int* cell_ids, int* counts
 int  lisreg_ndt_derivatives(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
                             const lisreg_ndt_params* params, const double p[6], int with_hessian, double out[28],
                             long long* n_pairs);
+
+/* ---- §7o: NDT verification of a candidate list as one call ----------------------------------------------------------------------
+ * The candidate loop of detectLoopClosureForSubMap (src/node/subMapOptmizationNode.cpp:2779-2846) with the verifier the reference
+ * names first (select_registration_method("NDT"), src/core/registration.cpp:147-155): lisreg_ndt_align_batch is
+ * lisreg_vgicp_align_batch (§7n, below) read for NDT.  Item k aligns sources[items[k].source] against the target of NDT slot
+ * items[k].slot from items[k].guess, and results[k] is what lisreg_ndt_align returns for the same arguments alone, to the bit, in
+ * every field; trans_probability keeps dividing by the source's record count, NaN records included.  A source is staged (uploaded)
+ * once per call however many items name it; a source no item names is neither checked nor read, and its pointer may be NULL.  The
+ * Newton loops of all items, each with its More-Thuente line search, advance in lockstep rounds: every unfinished item has exactly
+ * one evaluation outstanding, and one round answers them all with two evaluation launches (the items that want the Hessian, those
+ * that do not), one launch of fixed-order totals, one copy and one synchronisation; info->n_rounds is the largest n_evals of the items.
+ * fitness (may be NULL: no fitness pass, best = -1): fitness[k] = the mean, over the FINITE points of the source, of the squared
+ * distance to the nearest finite target point at the pose of results[k] — x' = ((R0 a0 + R1 a1) + R2 a2) + t and
+ * ((dx dx + dy dy) + dz dz) in double from the float coordinates as §7l's search defines it, ties to the lower index, without a
+ * cut-off (PCL's getFitnessScore() default), for every item, converged or not; two calls give the same bits.  The transform is the one
+ * the evaluations use, R and t of the pose results[k].p in double (x' = Rx(a) Ry(b) Rz(c) x + t, true trigonometry), NOT the float
+ * final_transform.  A source without a finite point has the score 0 / 0.  The search runs over the grid lisreg_ndt_set_target keeps
+ * with the slot.
+ * info->best: the best score starts at DBL_MAX; the items are walked in order, an item with converged == 0 or fitness > the best so
+ * far is skipped, any other one is taken (:2834-2840; equal scores go to the later item); -1 if none converged.  The DEFINITION is
+ * tests/ndt_batch_ref.py.
+ * Refused (LISREG_ERR_ARG) for the whole batch, with `results` and `fitness` untouched: NULL items / results / sources / n with
+ * n_items > 0, a source index outside 0 .. n_sources - 1, a slot without an NDT target, params lisreg_ndt_align refuses (among them
+ * a params->resolution that differs from ANY named slot's), a NAMED source it refuses (n <= 0, a NULL cloud, a short stride), and a
+ * batch of more than INT_MAX / 29 wavefronts (items x source records / 64).  Nothing a single call accepts is refused: a source may
+ * hold NaN records and needs no minimum point count.  n_items == 0 is LISREG_OK with best = -1.  All sources of a call share
+ * stride_bytes and fmt (host PCL structs or LISREG_FMT_DEVICE records).  Device memory the batch keeps (grow-only): 16 bytes per
+ * source record, 232 per (item, 64 source records), about 0.8 KB per item.  No per-item aligned_out and no per-item params. */
+typedef struct lisreg_ndt_item {
+    int          source;   /* index into sources[] */
+    int          slot;     /* lisreg_ndt_set_target(slot) */
+    const float* guess;    /* row-major 4x4, NULL = identity */
+} lisreg_ndt_item;
+typedef struct lisreg_ndt_batch_info {
+    int best;              /* -1 if no item converged (or fitness == NULL) */
+    int n_rounds;          /* host round trips of the alignment phase = the largest n_evals of the items */
+    int n_sources_staged;  /* sources actually uploaded */
+    int reserved;
+} lisreg_ndt_batch_info;
+int  lisreg_ndt_align_batch(lisreg_ctx* ctx, const void* const* sources, const int* n, int n_sources, int stride_bytes, int fmt,
+                            const lisreg_ndt_item* items, int n_items, const lisreg_ndt_params* params,
+                            lisreg_ndt_result* results, double* fitness, lisreg_ndt_batch_info* info);
 
 /* ---- §7k: voxelised GICP registration (loop-closure verification) ----------------------------------------------------
  * select_registration_method("FAST_VGICP") is the verifier detectLoopClosureForSubMap's authors chose last

@@ -1,14 +1,21 @@
-// lisreg_batch_driver.hpp — what the two batch verifiers share on the host (lisreg_fgicp_batch.hip, DESIGN.md §7m, and
-// lisreg_vgicp_batch.hip, §7n): the refusals, the staging of every named source's distributions, the work table of a round and its
-// upload, the lockstep rounds of the Levenberg-Marquardt steppers (lisreg_lm_stepper.hpp), the fitness pass, the `best` rule and the
+// lisreg_batch_driver.hpp — what the three batch verifiers share on the host (lisreg_fgicp_batch.hip, DESIGN.md §7m,
+// lisreg_vgicp_batch.hip, §7n, and lisreg_ndt_batch.hip, §7o): the refusals, the staging of every named source, the work table of a
+// round and its upload, the lockstep rounds of the items' resumable loops (the Levenberg-Marquardt stepper of lisreg_lm_stepper.hpp for
+// the fast_gicp family, the Newton / More-Thuente stepper of lisreg_ndt_stepper.hpp for NDT), the fitness pass, the `best` rule and the
 // copy-out.  A family F (a struct of static members, no virtual call) supplies
 //   kWho, Params / ItemC / Result / Info (its types of include/lisreg.h), Target (what a slot holds), Work (one entry of a round's table);
 //   bufs(c): its BatchBufs;  check_params(c, P);  find_target(c, slot, P, &T);
-//   ensure_lanes(c, lanes): the storage its items own per (item, finite source point), if any;
-//   fill(target, T[16], src_off, lane_off, n, Work*): one entry;  fit_view(target): the grid the fitness search reads;
+//   Stepper: one item's loop (start / finished / req_hessian / feed / res);  start(stepper, guess, P, n_records);
+//   ensure_sources(B, records): the batch's source buffers for that many records;
+//   stage_source(c, who, P, cloud, n, stride, fmt, B, off, want_finite, &m, &n_finite): one named source into the batch's buffers at `off`;
+//   m = the lanes of one evaluation of it (the finite points of the fast_gicp family, the records of NDT), n_finite = the points the
+//   fitness mean divides by (computed only if want_finite where that costs anything);
+//   ensure_lanes(c, lanes): the storage its items own per (item, lane), if any;
+//   fill(target, P, stepper, src_off, lane_off, m, Work*): one entry for the stepper's request;  fit_view(target): the grid the fitness
+//   search reads;  fit_pose(res): the pose it runs at;  result_to(res, Result*);
 //   launch_round(c, P, BatchRound<Work>): the evaluations of a round into r.part, with their profiling marks (the driver adds the totals
 //   and closes the interval);  kFitnessTotalsApart: the fitness pass's totals are an interval of their own.
-// One source for both units, like lisreg_batch_rounds.hpp.  Not installed.
+// One source for the three units, like lisreg_batch_rounds.hpp.  Not installed.
 #pragma once
 #include "lisreg_batch_rounds.hpp"
 #include "lisreg_lm_stepper.hpp"
@@ -34,14 +41,52 @@ struct BatchRound {
     hipStream_t   st;
 };
 
+// What the two families of the fast_gicp kind supply alike: the Levenberg-Marquardt stepper started from the guess matrix, a source
+// staged as the distributions of its finite points (points and covariances, one lane per finite point), the pose and the result of
+// an LmResult
+template <class Params, class Result>
+struct LmBatchFamily {
+    using Stepper = vgicp_host::LmStepper;
+
+    static void start(Stepper& lm, const float* guess, const Params& P, int)
+    {
+        double T0[16];
+        vgicp_host::guess_to_T0(guess, T0);
+        lm.start(T0, vgicp_host::lm_params_of(P));
+    }
+    static hipError_t ensure_sources(BatchBufs& B, size_t records)
+    {
+        const hipError_t e = B.src.ensure(sizeof(float4) * records);
+        return e != hipSuccess ? e : B.cov.ensure(sizeof(double) * 6 * records);
+    }
+    static int stage_source(lisreg_ctx* c, const char* who, const Params& P, const void* cloud, int n, int stride, int fmt, BatchBufs& B, long long off,
+                            bool, int* m_out, int* n_finite)
+    {
+        hipStream_t st = c->stream;
+        const float4* raw = nullptr;
+        int rc = stage_records(c, cloud, n, stride, fmt, c->vg_raw, &raw);
+        if (rc) return rc;
+        float bb[6];
+        int m = 0;
+        rc = vg_distributions(c, who, raw, n, P.k_correspondences, P.plane_epsilon, 0.f, bb, &m, nullptr, nullptr);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(B.src.as<float4>() + off, c->vg_pts.p, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(B.cov.as<double>() + 6 * off, c->vg_cov.p, sizeof(double) * 6 * (size_t)m, hipMemcpyDeviceToDevice, st));
+        *m_out = *n_finite = m;
+        return LISREG_OK;
+    }
+    static FgPose fit_pose(const vgicp_host::LmResult& lr) { return vgicp_host::pose_of<FgPose>(lr.T); }
+    static void result_to(const vgicp_host::LmResult& lr, Result* res) { vgicp_host::lm_result_to(lr, res); }
+};
+
 template <class F>
 int batch_align(lisreg_ctx* c, const void* const* sources, const int* n, int n_sources, int stride, int fmt, const typename F::ItemC* items,
                 int n_items, const typename F::Params* P, typename F::Result* results, double* fitness, typename F::Info* info)
 {
     using namespace vgicp_host;
     using Work = typename F::Work;
-    struct Source { bool used = false; int m = 0; long long off = 0; };
-    struct Item { LmStepper lm; const typename F::Target* T = nullptr; long long lane_off = 0; int src = 0, nb = 0; };
+    struct Source { bool used = false; int m = 0, n_finite = 0; long long off = 0; };
+    struct Item { typename F::Stepper lm; const typename F::Target* T = nullptr; long long lane_off = 0; int src = 0, nb = 0; };
     constexpr const char* kWho = F::kWho;
     if (!c) return LISREG_ERR_ARG;
     if (n_items < 0 || n_sources < 0) return bad(c, std::string(kWho) + ": n_items < 0 or n_sources < 0");
@@ -68,27 +113,21 @@ int batch_align(lisreg_ctx* c, const void* const* sources, const int* n, int n_s
         if (rc) return rc;
         cap += (size_t)n[s];
     }
-    // ---- the sources' distributions, once each; a cloud they refuse (too few finite points, an infinite coordinate) ends the call
-    // before any alignment work, with `results` untouched.  The context's scratch is overwritten by the next source: the batch keeps copies
+    // ---- the sources, once each; a cloud the staging refuses (for the fast_gicp family: too few finite points, an infinite coordinate)
+    // ends the call before any alignment work, with `results` untouched.  The context's scratch is overwritten by the next source: the
+    // batch keeps copies
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     BatchBufs& B = F::bufs(c);
-    HIPCHK(c, B.src.ensure(sizeof(float4) * cap));
-    HIPCHK(c, B.cov.ensure(sizeof(double) * 6 * cap));
+    HIPCHK(c, F::ensure_sources(B, cap));
     long long off = 0;
     int n_staged = 0;
     for (int s = 0; s < n_sources; ++s) {
         if (!S[s].used) continue;
-        const float4* raw = nullptr;
-        rc = stage_records(c, sources[s], n[s], stride, fmt, c->vg_raw, &raw);
+        int m = 0, n_finite = 0;
+        rc = F::stage_source(c, kWho, *P, sources[s], n[s], stride, fmt, B, off, fitness != nullptr, &m, &n_finite);
         if (rc) return rc;
-        float bb[6];
-        int m = 0;
-        rc = vg_distributions(c, kWho, raw, n[s], P->k_correspondences, P->plane_epsilon, 0.f, bb, &m, nullptr, nullptr);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(B.src.as<float4>() + off, c->vg_pts.p, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(B.cov.as<double>() + 6 * off, c->vg_cov.p, sizeof(double) * 6 * (size_t)m, hipMemcpyDeviceToDevice, st));
-        S[s].m = m; S[s].off = off;
+        S[s].m = m; S[s].n_finite = n_finite; S[s].off = off;
         off += m;
         ++n_staged;
     }
@@ -118,13 +157,8 @@ int batch_align(lisreg_ctx* c, const void* const* sources, const int* n, int n_s
         if (e != hipSuccess) return e;
         return hipMemcpyAsync(const_cast<int*>(d_start), h_start, sizeof(int) * ((size_t)ne + 1), hipMemcpyHostToDevice, st);
     };
-    // ---- the LM phase, in lockstep rounds: every unfinished item has one request outstanding -----------------------------------------
-    const LmParams lp = lm_params_of(*P);
-    for (int k = 0; k < n_items; ++k) {
-        double T0[16];
-        guess_to_T0(items[k].guess, T0);
-        I[k].lm.start(T0, lp);
-    }
+    // ---- the alignment phase, in lockstep rounds: every unfinished item has one request outstanding ----------------------------------
+    for (int k = 0; k < n_items; ++k) F::start(I[k].lm, items[k].guess, *P, n[I[k].src]);
     Work* const h_work = B.host_work.as<Work>();
     std::vector<int> order((size_t)n_items);
     int n_rounds = 0;
@@ -137,7 +171,7 @@ int batch_align(lisreg_ctx* c, const void* const* sources, const int* n, int n_s
         int g = 0;
         for (int e = 0; e < ne; ++e) {
             const Item& it = I[order[e]];
-            F::fill(*it.T, it.lm.req_T, S[it.src].off, it.lane_off, S[it.src].m, h_work + e);
+            F::fill(*it.T, *P, it.lm, S[it.src].off, it.lane_off, S[it.src].m, h_work + e);
             h_start[e] = g; g += it.nb;
         }
         h_start[ne] = g;
@@ -161,7 +195,7 @@ int batch_align(lisreg_ctx* c, const void* const* sources, const int* n, int n_s
         for (int k = 0; k < n_items; ++k) {
             FgFitWork* w = h_fit + k;
             w->A = F::fit_view(*I[k].T);
-            w->P = pose_of<FgPose>(I[k].lm.res.T);
+            w->P = F::fit_pose(I[k].lm.res);
             w->src_off = S[I[k].src].off; w->n = S[I[k].src].m; w->reserved = 0;
             h_start[k] = g; g += I[k].nb;
         }
@@ -176,7 +210,7 @@ int batch_align(lisreg_ctx* c, const void* const* sources, const int* n, int n_s
         HIPCHK(c, hipMemcpyAsync(B.host_out.p, B.out.p, sizeof(double) * (size_t)n_items, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         fit.assign(B.host_out.as<double>(), B.host_out.as<double>() + n_items);
-        for (int k = 0; k < n_items; ++k) fit[k] /= (double)S[I[k].src].m;
+        for (int k = 0; k < n_items; ++k) fit[k] /= (double)S[I[k].src].n_finite;
     } else {
         HIPCHK(c, hipStreamSynchronize(st));                       // (a batch whose items all end at once has made no round)
     }
@@ -185,8 +219,8 @@ int batch_align(lisreg_ctx* c, const void* const* sources, const int* n, int n_s
     int best = -1;
     double best_score = DBL_MAX;
     for (int k = 0; k < n_items; ++k) {
-        const LmResult& lr = I[k].lm.res;
-        lm_result_to(lr, results + k);
+        const auto& lr = I[k].lm.res;
+        F::result_to(lr, results + k);
         if (!fitness) continue;
         fitness[k] = fit[k];
         if (lr.converged == 0 || fit[k] > best_score) continue;

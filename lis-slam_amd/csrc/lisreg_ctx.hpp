@@ -138,11 +138,17 @@ struct VoxelView {
 };
 
 // the Gaussians of one NDT target (lisreg_ndt.hip: lisreg_ndt_set_target): stats = mean, upper triangle of the inverse covariance, finite
-// points; the table names the voxels that became a Gaussian only
+// points; the table names the voxels that became a Gaussian only; and a search grid over the target's finite points, its own copy (the
+// fitness score of lisreg_ndt_align_batch searches it)
 struct NdtTarget : VoxelTable {
     bool      valid = false;
     int       n_occupied = 0, n_valid = 0;
     DevBuf    vflag;               // [n_voxels] ints: became a Gaussian
+    int       n_points = 0;        // finite points
+    GridIndex grid;                // the search grid (pts = sorted, cell_start = cells)
+    float     bb[6] = { 0, 0, 0, 0, 0, 0 };   // the finite bounding box
+    DevBuf    sorted;              // [n_points] float4 by grid cell, .w = index among the finite points
+    DevBuf    cells;               // [nx * ny * nz + 1] ints
 };
 
 // the voxel statistics of one VGICP target (lisreg_vgicp.hip: lisreg_vgicp_set_target): stats = mean, upper triangle of the mean
@@ -292,9 +298,10 @@ struct lisreg_ctx {
     // correspondence rows of the test hook by the caller's index
     std::map<int, lisreg::FgicpTarget> fgicp;
     lisreg::DevBuf fg_pair, fg_M, fg_d2, fg_rows_i, fg_rows_d;
-    // lisreg_fgicp_align_batch (lisreg_fgicp_batch.hip) and lisreg_vgicp_align_batch (lisreg_vgicp_batch.hip): a set of buffers each
-    // (a call of one family leaves the other's alone), and the pairs and M FastGICP's items keep from a search to the sums after it
-    lisreg::BatchBufs fgb, vgb;
+    // lisreg_fgicp_align_batch (lisreg_fgicp_batch.hip), lisreg_vgicp_align_batch (lisreg_vgicp_batch.hip) and lisreg_ndt_align_batch
+    // (lisreg_ndt_batch.hip): a set of buffers each (a call of one family leaves the others' alone; NDT's has no covariances), and the
+    // pairs and M FastGICP's items keep from a search to the sums after it
+    lisreg::BatchBufs fgb, vgb, ndb;
     lisreg::DevBuf fgb_pair, fgb_M;
     lisreg::PinnedBuf done_host;            // one int
     lisreg::PinnedBuf stage_host;           // pinned staging of the per-batch tables
@@ -433,6 +440,11 @@ int  ensure_sort_scratch(lisreg_ctx* c, size_t n_elems, size_t n_buckets);
 // is the context's scratch: the next call overwrites it.
 int  vg_distributions(lisreg_ctx* c, const char* who, const float4* raw, int n, int k, double plane_eps, float edge, float bb[6], int* m_out,
                       int* nbr_dev, GridIndex* grid_out);
+// Its grid half, which lisreg_ndt_set_target calls too: the *m_out finite points of n device records with the finite bounding box bb into
+// c->vg_pts (with c->vg_idx, c->vg_flag, c->vg_pos as above) and by search-grid cell into c->vg_sorted / c->vg_cells; fewer than
+// min_points is refused.  mark >= 0: that profiling interval is opened in front of the gather.  *g: the grid, on the context's scratch.
+int  vg_search_grid(lisreg_ctx* c, const char* who, const float4* raw, int n, const float bb[6], float edge, int min_points, int mark,
+                    int* m_out, GridIndex* g);
 // out[29] = the n_part partial records of 29 doubles added in a fixed order (one wavefront: sum_records of lisreg_fp64_sums.hpp)
 void launch_eval_total(const double* part, int n_part, double* out, hipStream_t st);
 // ---- lisreg_api_cloud.hip: the voxel sort of one cloud and the voxel table of a target ---------------------------------------------------

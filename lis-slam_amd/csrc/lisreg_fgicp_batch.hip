@@ -6,7 +6,7 @@
 // added in the single call's order (sum_records of lisreg_fp64_sums.hpp), and the Levenberg-Marquardt loop is the single aligner's (lisreg_lm_stepper.hpp).  What the batch
 // saves: a source's distributions are made once per call, and the outstanding evaluations of ALL unfinished items are answered by one
 // round of launches and one synchronisation.  This unit holds the search and sum kernels and what they are launched with per round; the
-// host side of a call is the driver both batch units share (lisreg_batch_driver.hpp).  No LDS, no atomics, no CPU fallback.
+// host side of a call is the driver the batch units share (lisreg_batch_driver.hpp).  No LDS, no atomics, no CPU fallback.
 #include "lisreg_batch_rounds.hpp"
 #include "lisreg_batch_driver.hpp"
 
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(64) void k_fgicp_sums_batch(const FgWork* __restric
 }
 
 // ---- host: what FastGICP supplies to the driver of lisreg_batch_driver.hpp ---------------------------------------------------------------
-struct FgBatch {
+struct FgBatch : LmBatchFamily<lisreg_fgicp_params, lisreg_fgicp_result> {
     static constexpr const char* kWho = "fgicp_align_batch";
     using Params = lisreg_fgicp_params;
     using ItemC  = lisreg_fgicp_item;
@@ -91,10 +91,10 @@ struct FgBatch {
         return e != hipSuccess ? e : c->fgb_M.ensure(sizeof(double) * 6 * (size_t)lanes);
     }
 
-    static void fill(const Target& T, const double Tm[16], long long src_off, long long lane_off, int n, Work* w)
+    static void fill(const Target& T, const Params&, const Stepper& lm, long long src_off, long long lane_off, int n, Work* w)
     {
         w->A = fg_target_view(T);
-        w->P = vgicp_host::pose_of<FgPose>(Tm);
+        w->P = vgicp_host::pose_of<FgPose>(lm.req_T);
         w->src_off = src_off; w->lane_off = lane_off; w->n = n; w->reserved = 0;
     }
 

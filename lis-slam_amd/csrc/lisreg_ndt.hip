@@ -3,10 +3,13 @@
 // The definition is tests/ndt_ref.py.  GPU: the target's per-voxel Gaussians (the voxel table of voxel_table_build, lisreg_api_cloud.hip,
 // then one lane or one wavefront per voxel, fp64) and one evaluation of score / gradient / Hessian per call (one lane per source point,
 // fp64, sums in a fixed order: no floating-point atomics, the same input gives the same bits).  Host: the 6 x 6 solve and the
-// More-Thuente line search in double, one 29-double read-back per evaluation (eval_totals).  The butterfly, the total, the round trip
-// and the statistics' launch shell are the ones VGICP and FastGICP use (lisreg_fp64_sums.hpp).  No CPU fallback.
+// More-Thuente line search in double (the resumable loop of lisreg_ndt_stepper.hpp, answered one request at a time), one 29-double
+// read-back per evaluation (eval_totals).  The butterfly, the total, the round trip and the statistics' launch shell are the ones VGICP
+// and FastGICP use (lisreg_fp64_sums.hpp); the lane's body of an evaluation is shared with the batch form (lisreg_ndt_lane.hpp,
+// lisreg_ndt_batch.hip).  No CPU fallback.
 #include "lisreg_fp64_sums.hpp"
-#include "lisreg_ndt_host.hpp"
+#include "lisreg_ndt_lane.hpp"
+#include "lisreg_ndt_stepper.hpp"
 #include "lisreg_jacobi3.hpp"
 
 #include <algorithm>
@@ -119,100 +122,14 @@ __device__ __forceinline__ void NdtBuild::voxel(const NdtBuild& B, int v, int la
 }
 
 // ---- one evaluation --------------------------------------------------------------------------------------------------------------
-struct NdtGauss { double r2, g1, g2; };                         // resolution^2, the Gaussian constants d1, d2
-
-// one lane per source point, one wavefront per workgroup, one partial record per workgroup
+// one lane per source record, one wavefront per workgroup, one partial record per workgroup (the lane's body: lisreg_ndt_lane.hpp)
 template <bool HESS>
 __global__ __launch_bounds__(64) void k_ndt_eval(const float4* __restrict__ src, int n, VoxelView G, NdtGauss K, NdtPose P, double* __restrict__ part)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
-    double acc[28];
-#pragma unroll
-    for (int k = 0; k < 28; ++k) acc[k] = 0.0;
-    double pairs = 0.0;
-    bool live = i < n;
-    double x0 = 0, x1 = 0, x2 = 0;
-    if (live) { const float4 s = src[i]; x0 = (double)s.x; x1 = (double)s.y; x2 = (double)s.z; }
-    const double t0 = ((P.R[0] * x0 + P.R[1] * x1) + P.R[2] * x2) + P.t[0];
-    const double t1 = ((P.R[3] * x0 + P.R[4] * x1) + P.R[5] * x2) + P.t[1];
-    const double t2 = ((P.R[6] * x0 + P.R[7] * x1) + P.R[8] * x2) + P.t[2];
-    live = live && t0 == t0 && t1 == t1 && t2 == t2;
-    if (live) {
-        double J[6][3] = { { 1, 0, 0 }, { 0, 1, 0 }, { 0, 0, 1 }, { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
-        double Hv[6][3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int r = 0; r < 3; ++r) J[3 + k][r] = (P.dR[9 * k + 3 * r] * x0 + P.dR[9 * k + 3 * r + 1] * x1) + P.dR[9 * k + 3 * r + 2] * x2;
-        if (HESS) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-#pragma unroll
-                for (int r = 0; r < 3; ++r) Hv[k][r] = (P.ddR[9 * k + 3 * r] * x0 + P.ddR[9 * k + 3 * r + 1] * x1) + P.ddR[9 * k + 3 * r + 2] * x2;
-        }
-        const long long c0 = (long long)fmin(fmax(floor(t0 * G.inv_res), -2.0e9), 2.0e9) - G.m0;
-        const long long c1 = (long long)fmin(fmax(floor(t1 * G.inv_res), -2.0e9), 2.0e9) - G.m1;
-        const long long c2 = (long long)fmin(fmax(floor(t2 * G.inv_res), -2.0e9), 2.0e9) - G.m2;
-        for (int dz = -1; dz <= 1; ++dz) {
-            const long long z = c2 + dz;
-            if (z < 0 || z >= G.d2) continue;
-            for (int dy = -1; dy <= 1; ++dy) {
-                const long long y = c1 + dy;
-                if (y < 0 || y >= G.d1) continue;
-                for (int dx = -1; dx <= 1; ++dx) {
-                    const long long x = c0 + dx;
-                    if (x < 0 || x >= G.d0) continue;
-                    const int v = G.table[x + y * G.d0 + z * (long long)G.d0 * G.d1];
-                    if (v < 0) continue;
-                    const double* __restrict__ rec = G.stats + (size_t)v * kVoxelRec;
-                    const double q0 = t0 - rec[0], q1 = t1 - rec[1], q2 = t2 - rec[2];
-                    if (!((q0 * q0 + q1 * q1) + q2 * q2 <= K.r2)) continue;
-                    const double C[3][3] = { { rec[3], rec[4], rec[5] }, { rec[4], rec[6], rec[7] }, { rec[5], rec[7], rec[8] } };
-                    double cq[3];
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) cq[r] = (C[r][0] * q0 + C[r][1] * q1) + C[r][2] * q2;
-                    const double e = exp(-K.g2 * ((q0 * cq[0] + q1 * cq[1]) + q2 * cq[2]) / 2.0);
-                    pairs += 1.0;
-                    acc[0] += -K.g1 * e;
-                    double w = K.g2 * e;
-                    if (w > 1.0 || w < 0.0 || w != w) continue;
-                    w *= K.g1;
-                    double cJ[6];
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) cJ[a] = (cq[0] * J[a][0] + cq[1] * J[a][1]) + cq[2] * J[a][2];
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) acc[1 + a] += w * cJ[a];
-                    if (HESS) {
-                        double CJ[6][3];
-#pragma unroll
-                        for (int a = 0; a < 6; ++a)
-#pragma unroll
-                            for (int r = 0; r < 3; ++r) CJ[a][r] = (C[r][0] * J[a][0] + C[r][1] * J[a][1]) + C[r][2] * J[a][2];
-#pragma unroll
-                        for (int a = 0; a < 6; ++a)
-#pragma unroll
-                            for (int b = a; b < 6; ++b) {
-                                double t = -K.g2 * cJ[a] * cJ[b] + ((J[b][0] * CJ[a][0] + J[b][1] * CJ[a][1]) + J[b][2] * CJ[a][2]);
-                                if (a >= 3) {
-                                    const int h = a == 3 ? b - 3 : (a == 4 ? b - 1 : 5);          // aa ab ac | bb bc | cc
-                                    t += (cq[0] * Hv[h][0] + cq[1] * Hv[h][1]) + cq[2] * Hv[h][2];
-                                }
-                                acc[7 + a * 6 - a * (a - 1) / 2 + (b - a)] += w * t;
-                            }
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 28; ++k) acc[k] = wave_sum(acc[k]);
-    pairs = wave_sum(pairs);
-    if (threadIdx.x == 0) {
-        double* o = part + (size_t)blockIdx.x * kEvalOut;
-#pragma unroll
-        for (int k = 0; k < 28; ++k) o[k] = acc[k];
-        o[28] = pairs;
-    }
+    double acc[28], pairs;
+    ndt_eval_lane<HESS>(i < n, src + i, G, K, P, acc, pairs);
+    ndt_store_partial(acc, pairs, part + (size_t)blockIdx.x * kEvalOut);
 }
 
 struct NdtRun {
@@ -222,7 +139,6 @@ struct NdtRun {
     int              n;
     double           g1, g2;
     double           out[kEvalOut];
-    int              n_evals = 0;
 };
 
 int evaluate(NdtRun& r, const double p[6], bool hess)
@@ -233,26 +149,10 @@ int evaluate(NdtRun& r, const double p[6], bool hess)
     const VoxelView G = voxel_table_view(*r.T);
     const NdtGauss K = { r.T->resolution * r.T->resolution, r.g1, r.g2 };
     const int nb = (r.n + 63) / 64;
-    const int rc = eval_totals(c, nb, [&](double* part) {
+    return eval_totals(c, nb, [&](double* part) {
         if (hess) k_ndt_eval<true><<<nb, 64, 0, c->stream>>>(r.src, r.n, G, K, P, part);
         else      k_ndt_eval<false><<<nb, 64, 0, c->stream>>>(r.src, r.n, G, K, P, part);
     }, false, r.out);
-    if (!rc) ++r.n_evals;
-    return rc;
-}
-
-// phi(a), phi'(a) along `dir` from `base`
-int eval_along(NdtRun& r, const double base[6], const double dir[6], double a, bool hess, double* phi, double* dphi)
-{
-    double p[6];
-    for (int k = 0; k < 6; ++k) p[k] = base[k] + a * dir[k];
-    const int rc = evaluate(r, p, hess);
-    if (rc) return rc;
-    *phi = -r.out[0];
-    double d = 0;
-    for (int k = 0; k < 6; ++k) d += r.out[1 + k] * dir[k];
-    *dphi = -d;
-    return LISREG_OK;
 }
 
 int find_target(lisreg_ctx* c, int slot, const lisreg_ndt_params* P, const char* who, NdtTarget** out)
@@ -276,6 +176,25 @@ int check_params(lisreg_ctx* c, const lisreg_ndt_params* P, const char* who)
 }
 
 }  // namespace
+
+// the one copy of the checks and of the result's conversion, for lisreg_ndt_batch.hip
+int lisreg::ndt_check_params(lisreg_ctx* c, const lisreg_ndt_params* P, const char* who) { return check_params(c, P, who); }
+int lisreg::ndt_find_target(lisreg_ctx* c, int slot, const lisreg_ndt_params* P, const char* who, NdtTarget** out)
+{
+    return find_target(c, slot, P, who, out);
+}
+void lisreg::ndt_result_to(const NdtLoopResult& lr, lisreg_ndt_result* res)
+{
+    NdtPose Pm;
+    pose_matrices(lr.p, &Pm);
+    float* F = res->final_transform;
+    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) F[4 * i + j] = (float)Pm.R[3 * i + j]; F[4 * i + 3] = (float)lr.p[i]; }
+    F[12] = F[13] = F[14] = 0.f; F[15] = 1.f;
+    memcpy(res->p, lr.p, sizeof lr.p);
+    res->converged = lr.converged; res->iters = lr.iters; res->n_evals = lr.n_evals; res->reserved = 0;
+    res->n_pairs_last = lr.n_pairs_last;
+    res->score = lr.score; res->trans_probability = lr.trans_probability;
+}
 
 extern "C" {
 
@@ -309,6 +228,20 @@ int lisreg_ndt_set_target(lisreg_ctx* c, int slot, const void* cloud, int n, int
     for (int k = 0; k < 6; ++k)
         if (!std::isfinite(bb[k])) return bad(c, "ndt_set_target: the cloud has infinite coordinates");
     if (!(bb[0] <= bb[3] && bb[1] <= bb[4] && bb[2] <= bb[5])) return bad(c, "ndt_set_target: the cloud has no finite point: no valid voxel");
+    // ---- the search grid over the finite points (the fitness score of lisreg_ndt_align_batch searches it): the grid half of the fast_gicp
+    // family's distributions, and the slot's own copies of it, made before the voxel sort reuses any scratch ---------------------------
+    GridIndex g;
+    int m = 0;
+    rc = vg_search_grid(c, "ndt_set_target", raw, n, bb, 0.f, 1, -1, &m, &g);
+    if (rc) return rc;
+    const size_t n_grid_cells = (size_t)g.nx * (size_t)g.ny * (size_t)g.nz;
+    HIPCHK(c, T.sorted.ensure(sizeof(float4) * (size_t)m));
+    HIPCHK(c, T.cells.ensure(sizeof(int) * (n_grid_cells + 1)));
+    HIPCHK(c, hipMemcpyAsync(T.sorted.p, c->vg_sorted.p, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(T.cells.p, c->vg_cells.p, sizeof(int) * (n_grid_cells + 1), hipMemcpyDeviceToDevice, st));
+    T.grid = g; T.grid.pts = T.sorted.as<float4>(); T.grid.cell_start = T.cells.as<int>();
+    T.n_points = m;
+    for (int k = 0; k < 6; ++k) T.bb[k] = bb[k];
     // ---- NaN points aside, then the voxel table (the sort of lisreg_voxel_downsample) ------------------------------------------------
     HIPCHK(c, c->ndt_pts.ensure(sizeof(float4) * (size_t)n));
     k_ndt_clean<<<(n + 255) / 256, 256, 0, st>>>(raw, n, bb[0], bb[1], bb[2], c->ndt_pts.as<float4>());
@@ -390,65 +323,19 @@ int lisreg_ndt_align(lisreg_ctx* c, int slot, const void* source, int n, int str
     rc = stage_records(c, source, n, stride, fmt, c->ndt_src, &r.src);
     if (rc) return rc;
     gauss_constants(P->outlier_ratio, P->resolution, &r.g1, &r.g2);
-    double p[6];
-    p_from_matrix(guess, p);
-    const double eps = P->transformation_epsilon;
-    rc = evaluate(r, p, true);
+    // the Newton loop with its line search, one evaluation at a time
+    double p0[6];
+    p_from_matrix(guess, p0);
+    NdtLoopResult lr;
+    rc = ndt_optimise([&](const double p[6], bool hess, double out[kNdtOut]) {
+        const int e = evaluate(r, p, hess);
+        memcpy(out, r.out, sizeof r.out);
+        return e;
+    }, p0, ndt_loop_params_of(*P), n, &lr);
     if (rc) return rc;
-    int iters = 0;
-    bool converged = false;
-    while (!converged) {
-        double Hm[36], g[6], delta[6];
-        for (int k = 0; k < 6; ++k) g[k] = r.out[1 + k];
-        for (int i = 0, k = 7; i < 6; ++i)
-            for (int j = i; j < 6; ++j, ++k) Hm[6 * i + j] = Hm[6 * j + i] = r.out[k];
-        solve_step(Hm, g, delta);
-        double nrm = 0;
-        for (int k = 0; k < 6; ++k) nrm += delta[k] * delta[k];
-        nrm = sqrt(nrm);
-        if (nrm == 0 || std::isnan(nrm)) { converged = !std::isnan(nrm); break; }
-        for (int k = 0; k < 6; ++k) delta[k] /= nrm;
-        const double phi_0 = -r.out[0];
-        double d_phi_0 = 0;
-        for (int k = 0; k < 6; ++k) d_phi_0 += g[k] * delta[k];
-        d_phi_0 = -d_phi_0;
-        double a_t = 0.0;
-        if (d_phi_0 != 0) {
-            if (d_phi_0 > 0) { d_phi_0 = -d_phi_0; for (int k = 0; k < 6; ++k) delta[k] = -delta[k]; }
-            double base[6];
-            memcpy(base, p, sizeof base);
-            if (P->line_search) {
-                int trials = 0;
-                rc = line_search_mt([&](double a, bool hess, double* f, double* gd) { return eval_along(r, base, delta, a, hess, f, gd); },
-                                    phi_0, d_phi_0, nrm, P->step_size, eps / 2, &a_t, &trials);
-                if (rc) return rc;
-                if (trials) {                               // one Hessian pass at the accepted step
-                    double f, gd;
-                    rc = eval_along(r, base, delta, a_t, true, &f, &gd);
-                    if (rc) return rc;
-                }
-            } else {
-                a_t = std::min(std::max(nrm, eps / 2), P->step_size);
-                double f, gd;
-                rc = eval_along(r, base, delta, a_t, true, &f, &gd);
-                if (rc) return rc;
-            }
-            for (int k = 0; k < 6; ++k) p[k] = base[k] + a_t * delta[k];
-        }
-        if (iters > P->max_iters || (iters && fabs(a_t) < eps)) converged = true;
-        ++iters;
-    }
-    NdtPose Pm;
-    pose_matrices(p, &Pm);
-    float* F = res->final_transform;
-    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) F[4 * i + j] = (float)Pm.R[3 * i + j]; F[4 * i + 3] = (float)p[i]; }
-    F[12] = F[13] = F[14] = 0.f; F[15] = 1.f;
-    memcpy(res->p, p, sizeof p);
-    res->converged = converged ? 1 : 0; res->iters = iters; res->n_evals = r.n_evals; res->reserved = 0;
-    res->n_pairs_last = (long long)r.out[28];
-    res->score = r.out[0]; res->trans_probability = r.out[0] / (double)n;
+    ndt_result_to(lr, res);
     // `output` of align(): the source under the final transformation
-    if (aligned_out) return emit_aligned(c, r.src, n, F, source, stride, fmt, c->ndt_pts, aligned_out);
+    if (aligned_out) return emit_aligned(c, r.src, n, res->final_transform, source, stride, fmt, c->ndt_pts, aligned_out);
     return LISREG_OK;
 }
 

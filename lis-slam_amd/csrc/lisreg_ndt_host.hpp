@@ -1,6 +1,7 @@
 // lisreg_ndt_host.hpp — the host half of the NDT registration (lisreg_ndt.hip): pose matrices, the 6 x 6 pseudo-inverse solve and the
-// More-Thuente line search, in double, statement by statement what tests/ndt_ref.py defines.  Plain C++ (no HIP), so that it can be
-// compiled and checked on its own.  Not installed.
+// pieces of the More-Thuente line search that hold no state (the trial value, the interval update), in double, statement by statement
+// what tests/ndt_ref.py defines; the loop that drives them is lisreg_ndt_stepper.hpp.  Plain C++ (no HIP), so that it can be compiled
+// and checked on its own.  Not installed.
 #pragma once
 #include <algorithm>
 #include <cfloat>
@@ -161,42 +162,6 @@ inline void gauss_constants(double o, double res, double* g1, double* g2)
     const double d3 = -log(c2);
     *g1 = -log(c1 + c2) - d3;
     *g2 = -2.0 * log((-log(c1 * exp(-0.5) + c2) - d3) / *g1);
-}
-
-
-// eval(a, with_hessian, &phi, &dphi) -> 0 or an error code (returned at once).  The first trial carries the Hessian, those inside the
-// loop do not.  *a_out = the step, *trials_out = trials made inside the loop.
-template <class Eval>
-int line_search_mt(Eval&& eval, double phi_0, double d_phi_0, double step_init, double step_max, double step_min, double* a_out,
-                   int* trials_out)
-{
-    double I[6] = { 0.0, 0.0, d_phi_0 - kMu * d_phi_0, 0.0, 0.0, d_phi_0 - kMu * d_phi_0 };
-    auto clamp = [&](double a) { if (a > step_max) a = step_max; if (a < step_min) a = step_min; return a; };
-    double a_t = clamp(step_init), phi_t, d_phi_t;
-    int rc = eval(a_t, true, &phi_t, &d_phi_t);
-    if (rc) return rc;
-    double psi_t = phi_t - phi_0 - kMu * d_phi_0 * a_t, d_psi_t = d_phi_t - kMu * d_phi_0;
-    bool open_interval = true, converged = false;
-    int trials = 0;
-    while (!converged && trials < kMaxTrials && !(psi_t <= 0.0 && fabs(d_phi_t) <= kNu * fabs(d_phi_0))) {
-        if (open_interval && psi_t <= 0.0 && d_psi_t >= 0.0) {
-            open_interval = false;
-            I[1] += phi_0 - kMu * d_phi_0 * I[0]; I[2] += kMu * d_phi_0;
-            I[4] += phi_0 - kMu * d_phi_0 * I[3]; I[5] += kMu * d_phi_0;
-        }
-        const double f_t = open_interval ? psi_t : phi_t, g_t = open_interval ? d_psi_t : d_phi_t;
-        if (a_t == I[0]) break;                                              // the trial coincides with a_l: it is the step
-        double a_next;
-        if (!trial_value(I, a_t, f_t, g_t, &a_next) || !std::isfinite(a_next)) break;
-        converged = update_interval(I, a_t, f_t, g_t);
-        a_t = clamp(a_next);
-        rc = eval(a_t, false, &phi_t, &d_phi_t);
-        if (rc) return rc;
-        psi_t = phi_t - phi_0 - kMu * d_phi_0 * a_t; d_psi_t = d_phi_t - kMu * d_phi_0;
-        ++trials;
-    }
-    *a_out = a_t; *trials_out = trials;
-    return 0;
 }
 
 }  // namespace ndt_host

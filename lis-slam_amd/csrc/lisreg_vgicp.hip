@@ -297,6 +297,33 @@ int lisreg::vg_distributions(lisreg_ctx* c, const char* who, const float4* raw, 
     if (rc) return rc;
     for (int e = 0; e < 6; ++e)
         if (std::isinf(bb[e])) return bad(c, std::string(who) + ": the cloud has infinite coordinates");
+    GridIndex g;
+    rc = vg_search_grid(c, who, raw, n, bb, edge, k, 2, m_out, &g);           // (2: the "index" interval opens in front of the gather)
+    if (rc) return rc;
+    const int m = *m_out;
+    HIPCHK(c, c->vg_cov.ensure(sizeof(double) * 6 * (size_t)m));
+    VgKnn A;
+    A.sorted = c->vg_sorted.as<float4>(); A.cell_start = c->vg_cells.as<int>(); A.pts = c->vg_pts.as<float4>(); A.orig = c->vg_idx.as<int>();
+    A.m = m; A.k = k; A.ox = g.ox; A.oy = g.oy; A.oz = g.oz; A.cell = g.cell; A.inv_cell = g.inv_cell; A.nx = g.nx; A.ny = g.ny; A.nz = g.nz;
+    A.plane_eps = plane_eps; A.cov = c->vg_cov.as<double>(); A.nbr = nbr_dev;
+    if (k <= 20) k_vg_knn<20><<<(m + 63) / 64, 64, 0, st>>>(A);
+    else         k_vg_knn<32><<<(m + 63) / 64, 64, 0, st>>>(A);
+    ctx_prof_mark(c, -1);
+    HIPCHK(c, hipGetLastError());
+    if (grid_out) *grid_out = g;
+    return LISREG_OK;
+}
+
+// The grid half of the distributions, which the NDT target shares (lisreg_ndt_set_target keeps the grid for the batch's fitness score):
+// the finite points of n device records with the finite bounding box bb, compacted in input order into c->vg_pts (c->vg_idx their
+// indices in the cloud, c->vg_flag / c->vg_pos the finite flags and their exclusive scan), and the same points by search-grid cell in
+// c->vg_sorted / c->vg_cells.  *m_out = their number, read back and waited for; fewer than min_points (or an empty box) is refused.
+// edge as vg_distributions'.  mark >= 0: that profiling interval is opened in front of the gather.  *g = the grid, on the scratch.
+int lisreg::vg_search_grid(lisreg_ctx* c, const char* who, const float4* raw, int n, const float bb[6], float edge, int min_points, int mark,
+                           int* m_out, GridIndex* g_out)
+{
+    hipStream_t st = c->stream;
+    int rc;
     HIPCHK(c, c->vg_flag.ensure(sizeof(int) * ((size_t)n + 1)));
     HIPCHK(c, c->vg_pos.ensure(sizeof(int) * ((size_t)n + 2)));
     HIPCHK(c, c->vg_idx.ensure(sizeof(int) * ((size_t)n + 1)));
@@ -309,11 +336,11 @@ int lisreg::vg_distributions(lisreg_ctx* c, const char* who, const float4* raw, 
     HIPCHK(c, hipMemcpyAsync(&m, c->vg_cnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     if (m < 0 || m > n) return ctx_fail(c, LISREG_ERR_HIP, std::string(who) + ": the compaction returned an impossible count");
-    if (m < k || !(bb[0] <= bb[3] && bb[1] <= bb[4] && bb[2] <= bb[5]))
+    if (m < min_points || !(bb[0] <= bb[3] && bb[1] <= bb[4] && bb[2] <= bb[5]))
         return bad(c, std::string(who) + ": the cloud has fewer finite points than k_correspondences");
     *m_out = m;
     HIPCHK(c, c->vg_pts.ensure(sizeof(float4) * (size_t)m));
-    ctx_prof_mark(c, 2);                                           // lisreg_get_timing: "index" = the search grid, the search, the covariances
+    if (mark >= 0) ctx_prof_mark(c, mark);                         // lisreg_get_timing: "index" = the search grid, the search, the covariances
     launch_gather_points(raw, c->vg_idx.as<int>(), m, c->vg_pts.as<float4>(), st);
     // ---- the search grid ---------------------------------------------------------------------------------------------------------
     const double ex[3] = { (double)bb[3] - bb[0], (double)bb[4] - bb[1], (double)bb[5] - bb[2] };
@@ -340,17 +367,9 @@ int lisreg::vg_distributions(lisreg_ctx* c, const char* who, const float4* raw, 
     if (rc) return rc;
     HIPCHK(c, c->vg_sorted.ensure(sizeof(float4) * (size_t)m));
     HIPCHK(c, c->vg_cells.ensure(sizeof(int) * ((size_t)n_cells + 2)));
-    HIPCHK(c, c->vg_cov.ensure(sizeof(double) * 6 * (size_t)m));
     launch_build_target(c->vg_pts.as<float4>(), m, g, c->vg_sorted.as<float4>(), c->vg_cells.as<int>(), n_cells, sort_buffers(c), st);
-    VgKnn A;
-    A.sorted = c->vg_sorted.as<float4>(); A.cell_start = c->vg_cells.as<int>(); A.pts = c->vg_pts.as<float4>(); A.orig = c->vg_idx.as<int>();
-    A.m = m; A.k = k; A.ox = g.ox; A.oy = g.oy; A.oz = g.oz; A.cell = g.cell; A.inv_cell = g.inv_cell; A.nx = g.nx; A.ny = g.ny; A.nz = g.nz;
-    A.plane_eps = plane_eps; A.cov = c->vg_cov.as<double>(); A.nbr = nbr_dev;
-    if (k <= 20) k_vg_knn<20><<<(m + 63) / 64, 64, 0, st>>>(A);
-    else         k_vg_knn<32><<<(m + 63) / 64, 64, 0, st>>>(A);
-    ctx_prof_mark(c, -1);
     HIPCHK(c, hipGetLastError());
-    if (grid_out) { *grid_out = g; grid_out->pts = c->vg_sorted.as<float4>(); grid_out->cell_start = c->vg_cells.as<int>(); }
+    *g_out = g; g_out->pts = c->vg_sorted.as<float4>(); g_out->cell_start = c->vg_cells.as<int>();
     return LISREG_OK;
 }
 

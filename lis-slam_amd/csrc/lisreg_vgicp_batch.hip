@@ -9,7 +9,7 @@
 // answered by one round of launches and one synchronisation.  VGICP derives its pairs again at every evaluation, so an item owns no
 // device memory.  The fitness score searches the grid lisreg_vgicp_set_target keeps with the slot, with FastGICP's search
 // (lisreg_fgicp_lane.hpp).  This unit holds the linearising kernel and what it launches per round; the host side of a call is the
-// driver both batch units share (lisreg_batch_driver.hpp).  No LDS, no atomics, no CPU fallback.
+// driver the batch units share (lisreg_batch_driver.hpp).  No LDS, no atomics, no CPU fallback.
 #include "lisreg_batch_rounds.hpp"
 #include "lisreg_vgicp_lane.hpp"
 #include "lisreg_batch_driver.hpp"
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(64) void k_vgicp_linearize_batch(const VgWork* __re
 }
 
 // ---- host: what VGICP supplies to the driver of lisreg_batch_driver.hpp -------------------------------------------------------------------
-struct VgBatch {
+struct VgBatch : LmBatchFamily<lisreg_vgicp_params, lisreg_vgicp_result> {
     static constexpr const char* kWho = "vgicp_align_batch";
     using Params = lisreg_vgicp_params;
     using ItemC  = lisreg_vgicp_item;
@@ -82,10 +82,10 @@ struct VgBatch {
         return A;
     }
 
-    static void fill(const Target& T, const double Tm[16], long long src_off, long long, int n, Work* w)
+    static void fill(const Target& T, const Params&, const Stepper& lm, long long src_off, long long, int n, Work* w)
     {
         w->G = voxel_table_view(T);
-        w->P = vgicp_host::pose_of<VgPose>(Tm);
+        w->P = vgicp_host::pose_of<VgPose>(lm.req_T);
         w->src_off = src_off; w->n = n; w->reserved = 0;
     }
 

@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "lisreg_rangenet_label_batch",
     "lisreg_default_rangenet_knn_params", "lisreg_rangenet_knn_weights", "lisreg_rangenet_label_knn", "lisreg_rangenet_label_knn_batch",
     "lisreg_ndt_default_params", "lisreg_ndt_set_target", "lisreg_ndt_align", "lisreg_ndt_get_voxels", "lisreg_ndt_derivatives",
+    "lisreg_ndt_align_batch",
     "lisreg_vgicp_default_params", "lisreg_vgicp_set_target", "lisreg_vgicp_align", "lisreg_vgicp_covariances", "lisreg_vgicp_get_voxels",
     "lisreg_vgicp_linearize", "lisreg_vgicp_align_batch",
     "lisreg_fgicp_default_params", "lisreg_fgicp_set_target", "lisreg_fgicp_align", "lisreg_fgicp_correspondences", "lisreg_fgicp_linearize",
@@ -155,6 +156,18 @@ class VgicpBatchInfo(FgicpBatchInfo):
 
 class VgicpItem(FgicpItem):
     """one alignment of a batch: sources[source] against the VGICP target in `slot` from `guess` (4x4 or None = identity)"""
+
+
+class NdtItemC(FgicpItemC):
+    """lisreg_ndt_item: the fields of lisreg_fgicp_item, in the same order"""
+
+
+class NdtBatchInfo(FgicpBatchInfo):
+    """lisreg_ndt_batch_info: the fields of lisreg_fgicp_batch_info, in the same order"""
+
+
+class NdtItem(FgicpItem):
+    """one alignment of a batch: sources[source] against the NDT target in `slot` from `guess` (4x4 or None = identity)"""
 
 
 class GuessInput(C.Structure):
@@ -520,6 +533,8 @@ def lib():
         L.lisreg_ndt_get_voxels.argtypes = [vp, C.c_int, ip, ip, dbl, dbl, C.c_int, ip]
         L.lisreg_ndt_derivatives.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(NdtParams), dbl, C.c_int, dbl,
                                              C.POINTER(C.c_longlong)]
+        L.lisreg_ndt_align_batch.argtypes = [vp, C.POINTER(vp), ip, C.c_int, C.c_int, C.c_int, C.POINTER(NdtItemC), C.c_int,
+                                             C.POINTER(NdtParams), C.POINTER(NdtResult), dbl, C.POINTER(NdtBatchInfo)]
         L.lisreg_vgicp_default_params.argtypes = [C.c_int, C.POINTER(VgicpParams)]
         L.lisreg_vgicp_set_target.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VgicpParams), C.POINTER(VgicpInfo)]
         L.lisreg_vgicp_align.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(VgicpParams), fp, C.POINTER(VgicpResult), vp]
@@ -1710,12 +1725,13 @@ class Context:
 
     # -- §7m, §7n: FastGICP / VGICP verification of a candidate list -----------------------------------------
     def _gicp_align_batch(self, fn, item_type, result_type, info_type, who, sources, items, params, want_fitness):
-        """one batch call of the fast_gicp family through `fn`; returns (results: a list of the single call's dicts, fitness [n_items] or
-        None, info dict)."""
-        args = [self._cloud_args(s) for s in sources]
-        if len({(a[2], a[3]) for a in args}) > 1:
+        """one batch call of a verifier through `fn`; returns (results: a list of the single call's dicts, fitness [n_items] or None,
+        info dict).  A source given as None goes down as a NULL pointer of no points (for a source no item names)."""
+        args = [(None, 0, None, None, None) if s is None else self._cloud_args(s) for s in sources]
+        layouts = {(a[2], a[3]) for a in args if a[2] is not None}
+        if len(layouts) > 1:
             raise ValueError(who + ": the sources of one call share one layout")
-        stride, fmt = (args[0][2], args[0][3]) if args else (16, FMT_DEVICE)
+        stride, fmt = layouts.pop() if layouts else (16, FMT_DEVICE)
         ptrs = (C.c_void_p * max(len(args), 1))(*[a[0] for a in args])
         ns = (C.c_int * max(len(args), 1))(*[a[1] for a in args])
         its = (item_type * max(len(items), 1))()
@@ -1740,6 +1756,13 @@ class Context:
         """lisreg_vgicp_align_batch: sources = a list of clouds (all host PCL-struct arrays of one dtype, or all (device_ptr, n)),
         items = a list of VgicpItem.  Returns (results: a list of vgicp_align's dicts, fitness [n_items] or None, info dict)."""
         return self._gicp_align_batch(self._L.lisreg_vgicp_align_batch, VgicpItemC, VgicpResult, VgicpBatchInfo, "vgicp_align_batch",
+                                      sources, items, params, want_fitness)
+
+    def ndt_align_batch(self, sources, items, params: "NdtParams", want_fitness: bool = True):
+        """lisreg_ndt_align_batch (§7o): sources = a list of clouds (all host PCL-struct arrays of one dtype, or all (device_ptr, n); None
+        for a source no item names), items = a list of NdtItem.  Returns (results: a list of ndt_align's dicts, fitness [n_items] or
+        None, info dict)."""
+        return self._gicp_align_batch(self._L.lisreg_ndt_align_batch, NdtItemC, NdtResult, NdtBatchInfo, "ndt_align_batch",
                                       sources, items, params, want_fitness)
 
     def set_profiling(self, on: bool):
