@@ -184,7 +184,7 @@ int lisreg_map_index_set_batch(lisreg_ctx* c, int n_maps, const int* slots, cons
         ts.grid_id = k;
         // strip form of the build (the one a prepared batch's targets take, lisreg_batch_prepare): same layout rule
         ts.strip_base = tstrip;
-        ts.ystrip = std::max(1, std::min(ts.ny, ((c->strip_cells > 0 ? c->strip_cells : 2048) + ts.nz / 2) / std::max(ts.nz, 1)));      // (map batches: many maps, the big strips)
+        ts.ystrip = std::max(1, std::min(ts.ny, ((c->opt.strip_cells > 0 ? c->opt.strip_cells : 2048) + ts.nz / 2) / std::max(ts.nz, 1)));      // (map batches: many maps, the big strips)
         if (ts.nx > 0 && ts.nx <= kMaxStrips) {
             const int max_nstrips = std::max(1, kMaxStrips / ts.nx);
             ts.ystrip = std::max(ts.ystrip, (ts.ny + max_nstrips - 1) / max_nstrips);
@@ -202,14 +202,14 @@ int lisreg_map_index_set_batch(lisreg_ctx* c, int n_maps, const int* slots, cons
     // Two or more maps whose grids fit it take the strip form (4.9 -> 1.2 ms for the 256 targets of 200 k points of bench.py --workload
     // cfg4_icp: LDS histograms instead of one random global atomic per point, profiles/r05_kernel_experiments.md section 12); same records,
     // same tables (tests/test_index_build.py, tests/test_mapfilter.py).  index_build 0 keeps the bucket sort.
-    strips_fit = strips_fit && ((size_t)max_ucells + 1) * 4 + (size_t)c->strip_cap * 6 + 8192 <= kStripLdsLarge;
-    const bool strips = strips_fit && c->index_build != 0 && n_maps >= 2 && tstrip > 0;
+    strips_fit = strips_fit && ((size_t)max_ucells + 1) * 4 + (size_t)c->opt.strip_cap * 6 + 8192 <= kStripLdsLarge;
+    const bool strips = strips_fit && c->opt.index_build != 0 && n_maps >= 2 && tstrip > 0;
     int rc = ensure_sort_scratch(c, (size_t)std::max(tflat, 1), strips ? 1 : (size_t)std::max<long long>(total_cells, 1));
     if (rc) return rc;
     const std::vector<BlockDesc>& tb = strips ? tchunks : tblocks;
     HIPCHK(c, c->map_tsegs.ensure(sizeof(TargetSeg) * (size_t)n_maps));
     HIPCHK(c, c->map_tblocks.ensure(sizeof(BlockDesc) * std::max<size_t>(tb.size(), 1)));
-    if (strips) { HIPCHK(c, c->strip_tab.ensure(sizeof(int) * (3 * ((size_t)tstrip + 4) + (size_t)tstrip / 2048 + 8))); c->strip_zero_ints = 0; }      // (this build leaves the counters as they are)
+    if (strips) { HIPCHK(c, c->strip_tab.ensure(sizeof(int) * (3 * ((size_t)tstrip + 4) + (size_t)tstrip / 2048 + 8))); c->mem.strip_zero_ints = 0; }      // (this build leaves the counters as they are)
     HIPCHK(c, hipMemcpyAsync(c->map_tsegs.p, tsegs.data(), sizeof(TargetSeg) * (size_t)n_maps, hipMemcpyHostToDevice, st));
     if (!tb.empty()) HIPCHK(c, hipMemcpyAsync(c->map_tblocks.p, tb.data(), sizeof(BlockDesc) * tb.size(), hipMemcpyHostToDevice, st));
     for (int k = 0; k < n_maps; ++k)
@@ -224,7 +224,7 @@ int lisreg_map_index_set_batch(lisreg_ctx* c, int n_maps, const int* slots, cons
         for (int k = 0; k < n_maps; ++k)          // an empty cloud has no strip: its one-cell table is [0, 0]
             if (counts[k] <= 0) HIPCHK(c, hipMemsetAsync(ms[(size_t)k]->cell_start.p, 0, sizeof(int) * ((size_t)ms[(size_t)k]->n_cells + 1), st));
         if (launch_build_targets_strips(c->map_tblocks.as<BlockDesc>(), (int)tchunks.size(), c->map_tsegs.as<TargetSeg>(), n_maps, tstrip,
-                                        max_units, max_ucells, c->strip_cap, sl, st))
+                                        max_units, max_ucells, c->opt.strip_cap, sl, st))
             return ctx_fail(c, LISREG_ERR_HIP, "map_index_set_batch: strip index build: LDS configuration refused");
     } else
         launch_build_targets_batched(c->map_tblocks.as<BlockDesc>(), (int)tblocks.size(), c->map_tsegs.as<TargetSeg>(), n_maps, tflat,

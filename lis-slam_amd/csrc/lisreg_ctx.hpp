@@ -217,6 +217,96 @@ struct RcclApi {
     int (*CommDestroy)(void*) = nullptr;
 };
 
+// ---- the batch pipeline's host state (lisreg_batch_prepare / run_impl / lisreg_batch_fetch), grouped by who may write it --------------------
+// Options: written only by lisreg_set_option (and, for the length of one call, lisreg_align's trace_cap / fetch_trace_records).  They
+// survive every call; prepare, run and fetch read them through a const reference.
+struct BatchOptions {
+    int       early_stop_chunk = -1;        // iterations between host looks at the finished-counter; -1 auto, 0 never
+    int       fetch_trace_records = 0;      // lisreg_align: trace records copied out together with the results
+    int       trace_cap = 0;
+    int       index_build = 2;                          // 0 bucket sort, 1 strip form (error if a grid does not fit it), 2 strip form whenever it fits
+    int       strip_cells = 0, strip_cap = 2048;        // cells per strip aimed at (0: 1024 for a batch of one or two targets, else 2048); points per strip of the small-workgroup variant
+    int         row_reach = 2;                          // option "row_reach": rows only for the cells the batch's queries come within a metre of (runs that rebuild their targets);
+                                                        // 2: of those, only the cells a query starts in or that lie within half a metre of a target point
+    bool      count_searches = false;
+    bool      dump_neighbors = false;   // tests: keep the five neighbour ids of every query of the last iteration run
+    int       search_mode = 4;           // 1 per-lane cell walk, 3 k-NN graph scan, 5 cell rows,
+                                         // 4 auto: 3 when the prepared batch asks enough queries per target point to pay for the graph, else 1
+    bool      lanes_per_query_auto = true;
+    int       cell_min_ratio = 110;      // auto: query-iterations per target point from which the cell rows pay (they cost more than the graph to build and
+                                         // halve the first iterations of a batch).  Round 6, rows filtered by the query marks: 16 scans against 200 k points
+                                         // (92) draw, 24 (138) win 1.5 %, 32 (184) win 7 % (170 in rounds 4-5: 24 scans lost 4 %, 32 won 2 %)
+    int       cell_rows_max_mb = 16384;  // auto: cell rows only while the targets' rows are expected to fit this (about 5 KB per target point)
+    int       graph_min_ratio = 60;      // auto: query-iterations per target point from which the graph build pays (measured break-even ~55, DESIGN.md)
+    int       interleave = 0;            // "interleave": big batches that run a fixed number of iterations are cut in two halves iterating on two
+                                         // streams, each half's solves underneath the other half's correspondence launch (run_impl).  0 off (default),
+                                         // 1 the halves' launches alternate through events, 2 free-running.  Measured on configs[1] (round 5):
+                                         // 24.09 k reg/s off, 21.7 k alternating (a cross-stream hand-off costs more than the solve it hides),
+                                         // 24.5 k free-running (+1.7 %, but two launches then share the chip and their durations stop being a
+                                         // launch's own: 122 us per half against 98) — bit-identical results either way (tests)
+    int       interleave_min_blocks = 8192;   // workgroups from which a run is interleaved (each half should still fill the chip; tests lower it)
+    int       xcd_order = 2;             // XCD-aware dispatch order of the correspondence launches: 0 off, 1 on (graph front-end), 2 auto (graph front-end, >= 32 registrations, >= 2048 blocks)
+    int       cell_anchor_until = 1;     // graph front-end: GN iterations 1 .. this also try an anchor out of the query's own grid column
+    bool      canonical_ties = false;    // "canonical_ties" (always on with exact_arithmetic)
+    bool      exact = false;             // "exact_arithmetic": the correspondence launches and the pose cache run the reference's arithmetic (lisreg_assoc.hip)
+    int       sort_sources = 2;          // 0: keep the caller order, 1: 2-D column sort, 2: auto (probe the order at prepare time)
+    float     first_pass_r = 0.45f;
+    bool      rebuild_targets_each_run = false;
+};
+
+// The prepared batch: what lisreg_batch_prepare decided.  Constant until the next prepare, except `live`; prepare fills it field by field
+// (the host vectors keep their capacity: a single-frame lisreg_align prepares once per frame).
+struct PreparedBatch {
+    lisreg_params params;
+    DevParams prm;                       // (a run hands the kernels a copy with its own reach_miss and cell_anchor_until)
+    int       n_items = 0, n_blocks = 0, n_segs = 0, n_elems = 0, n_buckets = 0;
+    int       mode_now = 1;              // front-end of the prepared batch
+    int       lanes_q = 1;               // lanes per query of the prepared batch (8 for small walk-mode batches)
+    bool      sort_now = false;          // the sort verdict
+    bool      strip_now = false;         // the strip-form verdict
+    std::vector<int> batch_slots;           // target slots used by the prepared batch
+    std::vector<BlockDesc> h_blocks;      // 256-query workgroups: partial rows, sorts, probes
+    std::vector<BlockDesc> h_blocks_q;    // lanes_q > 1: kBlockQ / lanes_q queries per workgroup of the search kernel
+    std::vector<Segment>   h_segs;
+    std::vector<ItemState> h_items;
+    std::vector<TargetSeg> h_tsegs;
+    std::vector<BlockDesc> h_tblocks;
+    std::vector<BlockDesc> h_tchunks;          // the same targets in chunks of kPartChunkHost points (strip form of the build)
+    int       t_strips = 0, t_max_units = 0, t_max_ucells = 0;
+    int       t_elems = 0, t_buckets = 0;
+    // ---- what changes while the batch stays prepared, each with its writers --------------------------------------------------------------
+    struct Live {
+        bool  prepared = false;          // prepare sets it; dropped by set_target, the options that change what prepare decides, ensure_crows
+                                         // (a grid re-made with the rows' margin) and lisreg_align
+        bool  reach_ready = false;       // prepare made the reach words of this batch's targets; cleared by a fetch that saw too many misses
+        bool  xcd_cached = false;        // prepare made the dispatch-order table of this batch (runs reuse it); cleared by an interleaved run,
+                                         // which overwrites the table with one per half, and by option "xcd_order"
+        bool  items_reset = false;       // the device registrations are in their start-of-run state (prepare, or the run before: launch_finalize); a run clears it while it runs
+        int   reach_miss_seen = 0;       // the cumulative miss count the last fetch read (prepare: 0)
+        int   runs_since_fetch = 0;      // run counts, prepare and fetch clear
+    } live;
+};
+
+// What the last run did: written by run_impl and lisreg_batch_fetch, read by lisreg_get_option
+struct LastRun {
+    bool      xcd_now = false;           // the XCD-aware dispatch order was used
+    bool      reach_now = false;         // its rows were built for the reached cells only ("row_reach")
+    bool      interleaved_now = false;   // it ran as two halves
+    int       reach_miss_last = 0;       // query-iterations of the last fetched run that found their cell without rows
+    std::vector<float> h_results;        // the last fetch's result records
+};
+
+// What the context remembers from one batch to the next
+struct BatchMemory {
+    int       probe_items = -1, probe_elems = -1, probe_age = 0; bool probe_verdict = false;   // the batch shape the order was last probed on (auto): batches of a stream are alike ("sort_sources" forgets it)
+    int       reach_backoff = 0;         // batches still to be prepared without the marks after a run that missed too often ("row_reach" clears it)
+    int       strip_zero_ints = 0;       // leading ints of strip_tab known to be zero (a strip build hands its counters back clean)
+    int       last_launches = 0;         // Gauss-Newton iterations the last fetched batch ran (its slowest item): where run_impl looks first
+    int       degenerate = 0;            // isDegenerate member (odomEstimationNode.cpp:67)
+    std::vector<float> last_trace;       // last align trace (host copy)
+    int       last_trace_n = 0;
+};
+
 }  // namespace lisreg
 
 struct lisreg_ctx {
@@ -307,82 +397,22 @@ struct lisreg_ctx {
     lisreg::PinnedBuf stage_host;           // pinned staging of the per-batch tables
     lisreg::Event stage_done;
     lisreg::PinnedBuf fetch_host;           // pinned landing area of results (+ trace)
-    int       early_stop_chunk = -1;        // iterations between host looks at the finished-counter; -1 auto, 0 never
-    int       fetch_trace_records = 0;      // lisreg_align: trace records copied out together with the results
-    std::vector<lisreg::TargetSeg> h_tsegs;
-    std::vector<lisreg::BlockDesc> h_tblocks;
-    std::vector<lisreg::BlockDesc> h_tchunks;          // the same targets in chunks of kPartChunkHost points (strip form of the build)
-    int       t_strips = 0, t_max_units = 0, t_max_ucells = 0;
-    int       index_build = 2;                          // 0 bucket sort, 1 strip form (error if a grid does not fit it), 2 strip form whenever it fits
-    int       strip_cells = 0, strip_cap = 2048;        // cells per strip aimed at (0: 1024 for a batch of one or two targets, else 2048); points per strip of the small-workgroup variant
-    bool      strip_now = false;
-    int         row_reach = 2;                          // option "row_reach": rows only for the cells the batch's queries come within a metre of (runs that rebuild their targets);
-                                                        // 2: of those, only the cells a query starts in or that lie within half a metre of a target point
-    bool        reach_ready = false;                    // lisreg_batch_prepare made the reach words of this batch's targets
-    bool        xcd_cached = false;                     // lisreg_batch_prepare made the dispatch-order table of this batch (runs reuse it)
-    int         reach_backoff = 0;                      // batches still to be prepared without the marks after a run that missed too often
-    int         strip_zero_ints = 0;                    // leading ints of strip_tab known to be zero (a strip build hands its counters back clean)
-    bool        items_reset = false;                    // the device registrations are in their start-of-run state (prepare, or the run before: launch_finalize)
-    int         reach_miss_seen = 0, runs_since_fetch = 0;
-    int         reach_miss_last = 0;                    // query-iterations of the last fetched run that found their cell without rows
-    bool        reach_now = false;                      // the last run built its rows that way
     lisreg::Stream side_stream;                         // strip build: the big-strip kernel runs here, forked from / joined to `stream`
     lisreg::Event ev_fork, ev_join;
     lisreg::Event ev_ab, ev_ba;                         // interleaved runs: "half A's / half B's correspondence launch is through"
-    int       t_elems = 0, t_buckets = 0;
-    bool      count_searches = false;
-    bool      dump_neighbors = false;   // tests: keep the five neighbour ids of every query of the last iteration run
-    int       search_mode = 4;           // 1 per-lane cell walk, 3 k-NN graph scan, 5 cell rows,
-                                         // 4 auto: 3 when the prepared batch asks enough queries per target point to pay for the graph, else 1
-    int       mode_now = 1;              // front-end of the prepared batch
-    int       lanes_q = 1;               // lanes per query of the prepared batch (8 for small walk-mode batches)
-    bool      lanes_per_query_auto = true;
-    int       cell_min_ratio = 110;      // auto: query-iterations per target point from which the cell rows pay (they cost more than the graph to build and
-                                         // halve the first iterations of a batch).  Round 6, rows filtered by the query marks: 16 scans against 200 k points
-                                         // (92) draw, 24 (138) win 1.5 %, 32 (184) win 7 % (170 in rounds 4-5: 24 scans lost 4 %, 32 won 2 %)
-    int       cell_rows_max_mb = 16384;  // auto: cell rows only while the targets' rows are expected to fit this (about 5 KB per target point)
-    int       graph_min_ratio = 60;      // auto: query-iterations per target point from which the graph build pays (measured break-even ~55, DESIGN.md)
-    int       interleave = 0;            // "interleave": big batches that run a fixed number of iterations are cut in two halves iterating on two
-                                         // streams, each half's solves underneath the other half's correspondence launch (run_impl).  0 off (default),
-                                         // 1 the halves' launches alternate through events, 2 free-running.  Measured on configs[1] (round 5):
-                                         // 24.09 k reg/s off, 21.7 k alternating (a cross-stream hand-off costs more than the solve it hides),
-                                         // 24.5 k free-running (+1.7 %, but two launches then share the chip and their durations stop being a
-                                         // launch's own: 122 us per half against 98) — bit-identical results either way (tests)
-    bool      interleaved_now = false;   // what the last run did
-    int       interleave_min_blocks = 8192;   // workgroups from which a run is interleaved (each half should still fill the chip; tests lower it)
-    int       xcd_order = 2;             // XCD-aware dispatch order of the correspondence launches: 0 off, 1 on (graph front-end), 2 auto (graph front-end, >= 32 registrations, >= 2048 blocks)
-    bool      xcd_now = false;           // what the last run used
     int       feeder_numa = 1;           // packing threads bound to the CPUs of the device's NUMA node (those this process owns)
     int       feeder_node = -1, feeder_cpus = 0;       // what that found: the node, the CPUs bound to
-    int       cell_anchor_until = 1;     // graph front-end: GN iterations 1 .. this also try an anchor out of the query's own grid column
-    bool      canonical_ties = false;    // "canonical_ties" (always on with exact_arithmetic)
-    bool      exact = false;             // "exact_arithmetic": the correspondence launches and the pose cache run the reference's arithmetic (lisreg_assoc.hip)
-    int       sort_sources = 2;          // 0: keep the caller order, 1: 2-D column sort, 2: auto (probe the order at prepare time)
-    bool      sort_now = false;          // decision for the prepared batch
-    int       probe_items = -1, probe_elems = -1, probe_age = 0; bool probe_verdict = false;   // the batch shape the order was last probed on (auto): batches of a stream are alike
-    float     first_pass_r = 0.45f;
-    int       last_launches = 0;         // Gauss-Newton iterations the last fetched batch ran (its slowest item): where run_impl looks first
-    std::vector<lisreg::BlockDesc> h_blocks;      // 256-query workgroups: partial rows, sorts, probes
-    std::vector<lisreg::BlockDesc> h_blocks_q;    // lanes_q > 1: kBlockQ / lanes_q queries per workgroup of the search kernel
-    std::vector<lisreg::Segment>   h_segs;
-    std::vector<lisreg::ItemState> h_items;
-    std::vector<float>     h_results;
-    int       n_items = 0, n_blocks = 0, n_segs = 0, n_elems = 0, n_buckets = 0, trace_cap = 0;
-    lisreg::DevParams prm;
-    lisreg_params params;
-    bool      prepared = false;
-    bool      rebuild_targets_each_run = false;
-    std::vector<int> batch_slots;           // target slots used by the prepared batch
-    int       degenerate = 0;               // isDegenerate member (odomEstimationNode.cpp:67)
+    // the batch pipeline's host state (lisreg_api_batch.hip), by who may write it: see the four structs above
+    lisreg::BatchOptions  opt;
+    lisreg::PreparedBatch batch;
+    lisreg::LastRun       last;
+    lisreg::BatchMemory   mem;
     // profiling
     bool      profiling = false;
     std::vector<lisreg::Event> ev;
     std::vector<int>        ev_kind;        // kind of the interval STARTING at event i: 0 assoc, 1 solve, 2 index, -1 none
     std::vector<int>        ev_sidx;        // stream the event was recorded on: 0 the context's, 1 the side stream (interleaved runs)
     double    timing[5] = { 0, 0, 0, 0, 0 };
-    // last align trace (host copy)
-    std::vector<float> last_trace;
-    int       last_trace_n = 0;
     // RCCL
     lisreg::RcclApi   rccl;
     void*     comm = nullptr;
@@ -462,8 +492,16 @@ VoxelView voxel_table_view(const VoxelTable& T);
 // cell ids, point counts, means [3] and the six doubles behind them
 int  voxel_table_read(lisreg_ctx* c, const VoxelTable& T, const DevBuf* flag, int* cell_ids, int* counts, double* means, double* sym6, int capacity);
 // ---- lisreg_api.hip -------------------------------------------------------------------------------------------------------------------
-void ctx_prof_mark(lisreg_ctx* c, int kind_of_next_interval);      // 0 correspondence kernel, 1 solve, 2 index build, -1 nothing
+// (sidx 1: the mark goes on the side stream — the second half of an interleaved run; an interval runs from a mark to the next on the SAME stream)
+void ctx_prof_mark(lisreg_ctx* c, int kind_of_next_interval, int sidx = 0);      // 0 correspondence kernel, 1 solve, 2 index build, -1 nothing
 void ctx_prof_collect(lisreg_ctx* c);
+DevParams make_dev_params(const lisreg_params& p);                  // the literals of lisreg_params as the kernels want them
+// the target indices a batch asks for (lisreg_api_batch.hip); the index itself must already be enqueued on the stream
+int  ensure_graph(lisreg_ctx* c, Target& t, int k, bool launch);
+int  ensure_crows(lisreg_ctx* c, Target& t, int k, bool may_decline = false, long long* rows_left = nullptr);
+int  ensure_reach(lisreg_ctx* c, Target& t, int k, bool on);
+CrowBuffers crow_buffers(Target& t, int k, bool with_reach = false, bool near_only = false);
+int  upload_grids(lisreg_ctx* c);
 }  // namespace lisreg
 
 #define HIPCHK(c, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \

@@ -621,6 +621,73 @@ def test_row_reach_walk_and_back_off():
 
 
 @pytest.mark.gpu
+def test_other_batches_between_leave_a_batch_its_bits():
+    """One context, three batches prepared, run and fetched in turn under the auto front-end: A (the nine scans against the shared
+    submap), B (two registrations with small scattered targets of their own in slots 1 and 2 and "cell_rows_max_mb" = 1: auto takes the
+    cell rows, finds that they do not fit together, releases them and takes the graph scan), A again with the bound put back.  What one
+    batch leaves in the context — decisions, tables, probe and back-off memory, released rows — must not reach the next: all three
+    results equal fresh contexts' byte for byte, and the second A engages as the fresh one does."""
+    import lisreg
+    from lisreg import synth
+    b = Batch()
+    rng = np.random.default_rng(31)
+    own = [[synth.to_pcl(rng.uniform(-10, 10, (50, 3)).astype(np.float32)) for _ in range(2)] for _ in range(2)]     # 200 target points in all
+    items_b = [dict(b.items[i], target=1 + i) for i in range(2)]
+    readouts = ("front_end", "lanes_per_query", "index_build_now", "row_reach_now")
+
+    def context(max_mb=None):
+        c = lisreg.Context(0)
+        c.set_option("canonical_ties", 1); c.set_option("sort_sources", 0); c.set_option("rebuild_targets_each_run", 1)
+        c.set_option("search_mode", 4)
+        if max_mb is not None:
+            c.set_option("cell_rows_max_mb", max_mb)
+        return c
+
+    def run_a(c):
+        c.batch_prepare_device(b.items, b.T0, b.p_fixed)
+        return _step(c), {k: c.get_option(k) for k in readouts}
+
+    def run_b(c):
+        c.batch_prepare_device(items_b, b.T0[:2], b.p_fixed)
+        return _step(c), {k: c.get_option(k) for k in readouts}
+
+    def set_own(c):
+        for i, (tc, ts) in enumerate(own):
+            c.set_target(tc, ts, slot=1 + i)
+
+    c = context()
+    try:
+        c.set_target(b.tc, b.ts)
+        fresh_a, fresh_a_state = run_a(c)
+    finally:
+        c.close()
+    c = context(1)
+    try:
+        set_own(c)
+        fresh_b, fresh_b_state = run_b(c)
+    finally:
+        c.close()
+    assert fresh_b_state["front_end"] == 3, fresh_b_state          # (5: the rows fitted, nothing was declined)
+    c = context()
+    try:
+        c.set_target(b.tc, b.ts)
+        set_own(c)
+        max_mb = c.get_option("cell_rows_max_mb")
+        first_a, first_a_state = run_a(c)
+        c.set_option("cell_rows_max_mb", 1)
+        got_b, got_b_state = run_b(c)
+        c.set_option("cell_rows_max_mb", max_mb)
+        second_a, second_a_state = run_a(c)
+    finally:
+        c.close()
+    print(f"[batches between] A {fresh_a_state}, B {fresh_b_state}")
+    for what, got, want in (("first A", first_a, fresh_a), ("B", got_b, fresh_b), ("second A", second_a, fresh_a)):
+        assert got[0].tobytes() == want[0].tobytes() and got[1] == want[1], f"{what}: items {_diff(got, want)} differ from a fresh context"
+    assert first_a_state == fresh_a_state and got_b_state == fresh_b_state
+    assert second_a_state == fresh_a_state, (second_a_state, fresh_a_state)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("seed", [2234, 2240])
 def test_exact_build_through_neutral_options_equals_oracle(oracle, seed):
     """The exact build through the class-(a) options it does not switch off: per-iteration correspondence counts equal the CPU
