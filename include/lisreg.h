@@ -156,7 +156,13 @@ int  lisreg_default_params(int variant, lisreg_params* p);
  * option "rebuild_targets_each_run" every lisreg_batch_run re-reads them).  The index persists until the next call for
  * that slot, so a target shared by many registrations is built once.  Slot 0 is what lisreg_align uses.  A cloud with an
  * infinite coordinate, or with no finite point at all, is refused (LISREG_ERR_ARG); NaN points are simply never neighbours.
- * A cloud is limited to 2^28 - 1 points (the kernels address its 16-byte records by 32-bit byte offsets). */
+ * A cloud is limited to 2^28 - 1 points (the kernels address its 16-byte records by 32-bit byte offsets).
+ * Supported coordinate range: every finite coordinate of the target, and of the transformed source points searched against it, below
+ * 8192 m in magnitude.  The 5-NN front-ends (walk, graph scan, cell rows) prove their exactness with one millimetre of absolute slack,
+ * which has to absorb the rounding of the cell faces they recompute (ox + ix * cell, and + cell): one float step of the coordinate in
+ * all, 0.49 mm below 8192 m and 0.98 mm — the whole millimetre, with the 0.02 mm the cell assignment needs — from there on.  Beyond
+ * the range the searches still run and still return true neighbours in all but face-grazing cases; they are no longer proven exact.
+ * Keep the map frame's origin near the work (tests/test_far_frame.py runs at 8000 m). */
 int  lisreg_set_target(lisreg_ctx* ctx, const void* corner, int n_corner,
                        const void* surf, int n_surf, int stride_bytes, int fmt);
 int  lisreg_set_target_slot(lisreg_ctx* ctx, int slot, const void* corner, int n_corner,
@@ -642,6 +648,15 @@ int  lisreg_concat_device(lisreg_ctx* ctx, int k, const void* const* in, const i
 int  lisreg_upload_cloud(lisreg_ctx* ctx, const void* cloud, int n, int stride_bytes, int fmt, void* dev_out);
 
 /* ---- §8 f-3: local-map maintenance (src/include/subMap.h) -------------------------------------------------- */
+/* Supported coordinate range of this section: |coordinate| < 8192 m for the map cloud of a k = 1 index and for its queries
+ * (lisreg_map_index_set*, lisreg_nearest, lisreg_dynamic_filter, the ICP rows that search it).  The k = 1 walk carries the same
+ * millimetre of absolute slack as the 5-NN front-ends (see lisreg_set_target): it absorbs one rounding each of ox + ix * cell and of
+ * xl + cell — together one float step of the coordinate, 0.49 mm in [4096, 8192) m — plus about 0.02 mm from the float cell
+ * assignment at any offset; at 0.98 mm per step, from 8192 m on, it is spent.  lisreg_bbx_filter, lisreg_cloud_bounds,
+ * lisreg_voxel_downsample* and lisreg_transform_cloud carry no slack at all: they restate the reference's arithmetic operation for
+ * operation and equal it bit for bit at any offset at which floorf(x / leaf) fits an int (tests/test_far_frame.py: 8000 m, leaf
+ * 0.05 m).  The fp64 verifiers (lisreg_ndt_*, lisreg_vgicp_*, lisreg_fgicp_*) form their cell faces in double with a slack of
+ * 1e-3 of the cell edge and are not limited by this range. */
 /* A k = 1 search index over one cloud, kept in HBM under `slot` (its own slot space, separate from the registration
  * targets).  Replaces pcl::search::KdTree<PointT>::setInputCloud (subMap.h:889 `local_map->tree_dynamic`,
  * subMapOptmizationNode.cpp:2779 icp.setInputTarget).  LISREG_FMT_DEVICE clouds are referenced, not copied. */

@@ -6,7 +6,9 @@ predicate of SubMapManager::map_scan_feature_pts_distance_removal (subMap.h:1076
 make_grid (csrc/lisreg_api_ctx.hip), so that a test can say on the CPU which path of the walk its inputs take.
 
 Every `*_case()` returns dict(map=float32[n, 3], queries=float32[k, 3], groups=name -> indices it planted); `case(name)` makes each
-once per process and `brute(name)` its reference, so the CPU and the GPU tests read one definition."""
+once per process and `brute(name)` its reference, so the CPU and the GPU tests read one definition.  `case(name, frame)` is the same case
+moved into one of the map frames of tests/far_frame.py (None: as planted, around the origin): the float32 sum of every coordinate and
+the frame's offset IS the moved cloud; a case that is built from the grid's geometry is rebuilt from the moved map's geometry."""
 import numpy as np
 
 f32 = np.float32
@@ -276,10 +278,10 @@ def nan_map_case():
     return dict(map=m, queries=q, groups=dict(nan=planted, beside=np.arange(6)))
 
 
-def edges_case():
+def edges_case(frame=None):
     """On the scene map: queries 1, 30 and 500 m outside the grid on each of its six sides and past a corner, a query exactly on a
-    cell face and one on the grid's origin, and NaN queries (NaN x, NaN z, all NaN)."""
-    m = scene_case()["map"]
+    cell face and one on the grid's origin, and NaN queries (NaN x, NaN z, all NaN).  In a frame: the same, from the moved map's grid."""
+    m = case("scene", frame)["map"]
     geom = grid_geometry(m)
     lo = geom["o"].astype(np.float64)
     hi = lo + np.array(geom["dims"]) * float(geom["cell"])            # the grid's far faces (up to a cell past the cloud)
@@ -302,9 +304,9 @@ def edges_case():
                                               nan=np.arange(n_out + 2, n_out + 5)))
 
 
-def count_case(k):
+def count_case(k, frame=None):
     """the first k scene queries (k = 1, 63, 64, 65, 257: the last wavefront and workgroup are partial for every lane count)"""
-    s = case("scene")
+    s = case("scene", frame)
     return dict(map=s["map"], queries=s["queries"][:k], groups={})
 
 
@@ -343,27 +345,42 @@ THRESHOLDS = dict(center_radius=40.0, near=0.25, dmin=0.5, dmax=1.0)
 _MAKERS = dict(scene=scene_case, lattice=lattice_case, lattice2=lambda: lattice_case(True), duplicates=duplicates_case,
                one=lambda: degenerate_case("one"), ident25=lambda: degenerate_case("ident25"), plane=lambda: degenerate_case("plane"),
                line=lambda: degenerate_case("line"), corners=lambda: degenerate_case("corners"), nan_map=nan_map_case, edges=edges_case,
-               count1=lambda: count_case(1), count63=lambda: count_case(63), count64=lambda: count_case(64),
-               count65=lambda: count_case(65), count257=lambda: count_case(257), thresholds=threshold_case)
+               count1=lambda f=None: count_case(1, f), count63=lambda f=None: count_case(63, f), count64=lambda f=None: count_case(64, f),
+               count65=lambda f=None: count_case(65, f), count257=lambda f=None: count_case(257, f), thresholds=threshold_case)
+_FROM_GEOMETRY = ("edges", "count1", "count63", "count64", "count65", "count257")     # makers that take the frame themselves
 CASE_NAMES = tuple(k for k in _MAKERS if k != "thresholds")
 _CASES, _BRUTE = {}, {}
 
 
-def case(name):
-    if name not in _CASES:
-        _CASES[name] = _MAKERS[name]()
-    return _CASES[name]
+def case(name, frame=None):
+    """the named case as planted (frame None) or moved into a frame of far_frame.FRAMES"""
+    key = (name, frame)
+    if key not in _CASES:
+        if frame is None:
+            _CASES[key] = _MAKERS[name]()
+        elif name in _FROM_GEOMETRY:
+            _CASES[key] = _MAKERS[name](frame)
+        else:
+            from far_frame import offset, shift
+            c = case(name)
+            m, q = c["map"], c["queries"]
+            if name == "corners":                 # 200 m wide: hung on the INNER side of a positive offset, so that it stays within range
+                back = np.where(offset(frame) > 0, f32(-200.0), f32(0.0)).astype(f32)
+                m, q = m + back, q + back
+            _CASES[key] = dict(map=shift(m, frame), queries=shift(q, frame), groups=c["groups"])
+    return _CASES[key]
 
 
-def brute(name):
-    """brute_force of a named case, computed once and never written to"""
-    if name not in _BRUTE:
-        c = case(name)
+def brute(name, frame=None):
+    """brute_force of a named case (in a frame: of the moved clouds), computed once and never written to"""
+    key = (name, frame)
+    if key not in _BRUTE:
+        c = case(name, frame)
         if name.startswith("count"):
             k = len(c["queries"])
-            _BRUTE[name] = tuple(a[:k] for a in brute("scene"))
+            _BRUTE[key] = tuple(a[:k] for a in brute("scene", frame))
         else:
-            _BRUTE[name] = brute_force(c["map"], c["queries"])
-        for a in _BRUTE[name]:
+            _BRUTE[key] = brute_force(c["map"], c["queries"])
+        for a in _BRUTE[key]:
             a.setflags(write=False)
-    return _BRUTE[name]
+    return _BRUTE[key]

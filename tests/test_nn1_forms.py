@@ -40,11 +40,11 @@ def _same_found(got, want, what):
 
 
 # ---------------------------------------------------------------- planted properties, from nn1_ref alone (CPU)
-def check_planted(name):
+def check_planted(name, frame=None):
     """the property case `name` was planted for still holds — asserted from nn1_ref's outputs, so that a GPU test whose inputs lost
-    it fails instead of passing empty"""
-    c = R.case(name)
-    idx, d2, cnt, last = R.brute(name)
+    it fails instead of passing empty (frame: the case moved into a map frame of tests/far_frame.py)"""
+    c = R.case(name, frame)
+    idx, d2, cnt, last = R.brute(name, frame)
     m, q, g = c["map"], c["queries"], c["groups"]
     assert len(m) <= 20000 and len(q) <= 4096
     geom = R.grid_geometry(m)
@@ -217,18 +217,18 @@ def test_seed_partners_are_real():
 
 
 # ---------------------------------------------------------------- GPU
-def _same_grid(gpu_ctx, m):
+def _same_grid(gpu_ctx, m, slot=SLOT):
     """the grid the library built IS the one nn1_ref.grid_geometry restates (the planted-property assertions rest on it)"""
-    got, want = gpu_ctx.map_grid(SLOT), R.grid_geometry(m)
+    got, want = gpu_ctx.map_grid(slot), R.grid_geometry(m)
     assert got["n"] == len(m) and got["dims"] == want["dims"] and got["n_cells"] == int(np.prod(want["dims"])), (got, want)
     assert np.array_equal(got["o"], want["o"]) and got["cell"] == want["cell"], (got, want)
 
 
-def _seed_choices(name):
+def _seed_choices(name, frame=None):
     """name -> seeds[k] (original indices; -1 none, -2 the cell seed).  The answer is by definition the LOWEST index of its tied set, so
     'a tied point with a lower index' is the answer itself; the partner with a higher index is the tied set's highest."""
-    c = R.case(name)
-    idx, d2, cnt, last = R.brute(name)
+    c = R.case(name, frame)
+    idx, d2, cnt, last = R.brute(name, frame)
     m, q = c["map"], c["queries"]
     k, n = len(q), len(m)
     if "far" in c["groups"] and name != "scene":

@@ -203,13 +203,8 @@ def test_multi_cloud_grid_equals_single_calls_bitwise(gpu_ctx):
         x.free()
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("labelled", [True, False])
-@pytest.mark.parametrize("seed", [31, 32, 33])
-def test_hip_voxel_grid_crowded_voxels(oracle, gpu_ctx, labelled, seed):
-    """Voxels that hold tens to thousands of points (the cells next to the sensor, a key-frame ring's overlap): the wavefront-per-voxel
-    path sums them 64 at a time through LDS, in input order — centroid, intensity average and label vote equal the oracle's bit for bit,
-    for voxel populations around every chunk boundary (24 / 25, 63 / 64 / 65, 128, several thousand)."""
+def crowded_cloud(seed):
+    """(cloud, populations): voxel k holds pops[k] points inside one 0.5 m cell of a 3-D lattice, 14 possible labels, input order shuffled"""
     from lisreg import synth
     rng = np.random.default_rng(seed)
     pops = [1, 2, 23, 24, 25, 26, 63, 64, 65, 127, 128, 129, 500, 4097] + [int(v) for v in rng.integers(1, 300, 40)]
@@ -222,6 +217,17 @@ def test_hip_voxel_grid_crowded_voxels(oracle, gpu_ctx, labelled, seed):
     perm = rng.permutation(len(xyz))                   # input order is not voxel order
     cloud = synth.to_pcl(xyz[perm], lab[perm])
     cloud["intensity"] = rng.uniform(0, 255, len(cloud)).astype(np.float32)
+    return cloud, pops
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("labelled", [True, False])
+@pytest.mark.parametrize("seed", [31, 32, 33])
+def test_hip_voxel_grid_crowded_voxels(oracle, gpu_ctx, labelled, seed):
+    """Voxels that hold tens to thousands of points (the cells next to the sensor, a key-frame ring's overlap): the wavefront-per-voxel
+    path sums them 64 at a time through LDS, in input order — centroid, intensity average and label vote equal the oracle's bit for bit,
+    for voxel populations around every chunk boundary (24 / 25, 63 / 64 / 65, 128, several thousand)."""
+    cloud, pops = crowded_cloud(seed)
     st_o, want = oracle.voxel_grid(cloud, 0.5, fmt=1 if labelled else 0)
     st_g, got = gpu_ctx.voxel_downsample(cloud, 0.5) if labelled else gpu_ctx.voxel_downsample(_as_xyzi(cloud), 0.5)
     assert st_o == st_g == 0 and len(got) == len(want) == len(pops)
