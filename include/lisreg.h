@@ -1247,6 +1247,62 @@ int  lisreg_fgicp_align_batch(lisreg_ctx* ctx, const void* const* sources, const
                               const lisreg_fgicp_item* items, int n_items, const lisreg_fgicp_params* params,
                               lisreg_fgicp_result* results, double* fitness, lisreg_fgicp_batch_info* info);
 
+/* ---- §7q: PCL's GICP registration (loop-closure verification) ---------------------------------------------------------------
+ * select_registration_method("GICP") (src/core/registration.cpp:137-146: pcl::GeneralizedIterativeClosestPoint, max correspondence
+ * distance 10, 30 iterations, transformation epsilon 1e-6, Euclidean fitness epsilon 1e-3, RANSAC 0) is the fifth verifier the
+ * reference names.  The method: the distributions and the nearest-neighbour pairs of §7l (a GICP target IS a FastGICP slot:
+ * lisreg_fgicp_set_target with plane_epsilon = gicp_epsilon); per OUTER iteration the pairs and their M = (C_b + R C_a R^T)^-1 are
+ * fixed at T_k = X(x_k) guess and a BFGS with Fletcher's line search (PCL's BFGS<> = GSL's vector_bfgs2) minimises
+ * f(x) = (1/m) sum (X(x) p - q)^T M (X(x) p - q) over x = (tx, ty, tz, roll, pitch, yaw), X(x) = [Rz(yaw) Ry(pitch) Rx(roll) | t].
+ * With the pairs fixed f is an exact quadratic in the 12 entries of X(x): the GPU makes ONE search-and-moments launch and one launch
+ * of fixed-order totals per outer iteration (74 doubles: c0, g [12], S [60], the pair count; two evaluations of the same input give
+ * the same bits), and the whole inner BFGS runs on the host over those 74 doubles.  The DEFINITION is tests/gicp_ref.py (PCL's source
+ * is not available to this project); DESIGN.md §7q lists the readings it picks.  Fewer than 4 pairs is PCL's "need at least 4 points":
+ * converged = 0 and the pose at which that round searched.  Both ends of the outer loop (max_iters reached, delta < 1) set
+ * converged = 1, as PCL 1.8 does.  No fitness score (aligned_out and lisreg_nearest give one) and no batch form yet. */
+typedef struct lisreg_gicp_params {
+    double max_correspondence_distance; /* a nearest point this far away or further is no pair */
+    double transformation_epsilon;      /* delta scales the translation entries of X(x_k) - X(x_k+1) by 1 / this ... */
+    double rotation_epsilon;            /* ... and the rotation entries by 1 / this; the outer loop ends when delta < 1 */
+    double gicp_epsilon;                /* the smallest eigenvalue of a regularised covariance (the slot's plane_epsilon) */
+    double rho, sigma;                  /* Fletcher's two tests */
+    double tau1, tau2, tau3;            /* the bracket's growth and the section's two margins */
+    double step_size;                   /* the first trial step of an inner minimisation */
+    double gradient_tol;                /* an inner minimisation ends when |grad f| is below this */
+    int    k_correspondences;           /* points per distribution, 4 .. 32 */
+    int    max_iters;                   /* outer iterations, >= 1 */
+    int    max_inner_iters;             /* BFGS steps per outer iteration, >= 1 */
+    int    order;                       /* of the line search's interpolation: 3 (cubic) or 2 */
+} lisreg_gicp_params;
+typedef struct lisreg_gicp_result {
+    double final_transform[16];         /* row-major 4x4, in double: X(x) guess */
+    int    converged;
+    int    iters;                       /* outer iterations (inner minimisations run) */
+    int    inner_iters;                 /* BFGS steps, all outer iterations together */
+    int    n_evals;                     /* host evaluations of f or its gradient from the moments */
+    int    n_rounds;                    /* GPU round trips: == iters, or iters + 1 when the loop ended on fewer than 4 pairs */
+    int    inner_exit;                  /* how the last inner loop ended: 0 gradient_tol, 1 max_inner_iters, 2 no progress; -1: none ran */
+    long long n_pairs_last;             /* pairs of the last round */
+    double error;                       /* f at final_transform over the pairs of the last round */
+    double last_delta;                  /* delta of the last outer iteration */
+} lisreg_gicp_result;
+/* kind 0 (the reference's GICP block + PCL's defaults): {10, 1e-6, 2e-3, 1e-3, 0.01, 0.01, 9, 0.05, 0.5, 0.01, 1e-2, 20, 30, 20, 3};
+ * kind 1: the settings of src/node/subMapOptmizationNode.cpp:2765-2769 read for GICP: transformation_epsilon 1e-4 */
+int  lisreg_gicp_default_params(int kind, lisreg_gicp_params* p);
+/* `slot` is a FastGICP slot (lisreg_fgicp_set_target): there is no GICP slot family.  guess, aligned_out, the source formats and the
+ * refusals are lisreg_fgicp_align's; also refused: max_iters < 1, max_inner_iters < 1, rho / sigma / tau2 / tau3 outside (0, 1),
+ * tau1 <= 1, step_size or gradient_tol <= 0, order outside 2 .. 3.  A refused call leaves `result` untouched. */
+int  lisreg_gicp_align(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
+                       const lisreg_gicp_params* params, const float* guess, lisreg_gicp_result* result, void* aligned_out);
+/* test hooks.  _moments: one round at T (row-major 4x4): the search, the moments about the centre of the slot's bounding box and
+ * their total, out[74] in the order tests/gicp_ref.py lists.  _inner: the inner minimisation alone, from moments[74], that centre
+ * and the outer iterate x0 — no device, no context, callable without a GPU; counts (may be NULL) = BFGS steps, evaluations of f,
+ * evaluations of the gradient alone, inner_exit; f_out (may be NULL) = f at x_out.  Refused: a NULL pointer, fewer than 1 pair. */
+int  lisreg_gicp_moments(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
+                         const lisreg_gicp_params* params, const double T[16], double out[74]);
+int  lisreg_gicp_inner(const double moments[74], const double centre[3], const double x0[6], const lisreg_gicp_params* params,
+                       double x_out[6], int counts[4], double* f_out);
+
 /* ---- loop-closure candidate detection: FEPSC (src/core/epscGeneration.cpp) -------------------------------------------
  * EPSCGeneration::loopDetection (:663-992) with UsingFEPSCFlag (config/params.yaml:22-28), as loopClosureThread calls it for every
  * key frame (subMapOptmizationNode.cpp:2328-2362): its matched_frame_id / matched_frame_transform become loopKeyPre and the EPSC

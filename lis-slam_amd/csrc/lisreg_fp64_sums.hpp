@@ -1,5 +1,5 @@
 // lisreg_fp64_sums.hpp — the fp64 reductions the NDT, VGICP and FastGICP verifiers and their batch forms share: the
-// wavefront butterfly, the fixed-order total of partial records, the round trip of one evaluation, and the launch shell of the voxel
+// wavefront butterfly, the fixed-order total of partial records, the round trip of one total, and the launch shell of the voxel
 // statistics.  Each exists once: "an item of a batch gets the bits of the single call" rests on every unit adding in THIS order.  Every
 // unit that includes the header is built with -ffp-contract=off.  Not installed.
 #pragma once
@@ -34,24 +34,32 @@ __device__ __forceinline__ void sum_records(const double* __restrict__ part, int
     for (int k = 0; k < W; ++k) acc[k] = wave_sum(acc[k]);
 }
 
-// One evaluation's round trip: launch(part) writes nb partial records of kEvalOut doubles on the context's stream (and opens its
-// profiling interval, if it has one; close_mark: the interval ends behind the total), launch_eval_total adds them, out = the total,
-// waited for.  One set of buffers serves the three families: a context is single-threaded and every evaluation ends in the wait.
+// One round trip of fixed-order totals: launch(part) writes nb partial records of W doubles on the context's stream (and opens its
+// profiling interval, if it has one; close_mark: the interval ends behind the total), total(part, nb, out, stream) adds them with
+// sum_records<W>, out = the total, waited for.  One set of buffers serves every family (an evaluation of the NDT, VGICP and FastGICP
+// verifiers is W = kEvalOut, PCL's GICP takes W = 74 moments): a context is single-threaded and every round trip ends in the wait.
+template <int W, class Launch, class Total>
+int record_totals(lisreg_ctx* c, int nb, Launch launch, Total total, bool close_mark, double out[W])
+{
+    hipStream_t st = c->stream;
+    HIPCHK(c, c->eval_part.ensure(sizeof(double) * W * (size_t)nb));
+    HIPCHK(c, c->eval_out.ensure(sizeof(double) * W));
+    HIPCHK(c, c->eval_host.ensure(sizeof(double) * W, sizeof(double) * (W > 64 ? W : 64)));
+    launch(c->eval_part.as<double>());
+    total(c->eval_part.as<double>(), nb, c->eval_out.as<double>(), st);
+    if (close_mark) ctx_prof_mark(c, -1);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->eval_host.p, c->eval_out.p, sizeof(double) * W, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(out, c->eval_host.p, sizeof(double) * W);
+    return LISREG_OK;
+}
+
+// one evaluation's round trip: records of kEvalOut doubles, added by launch_eval_total
 template <class Launch>
 int eval_totals(lisreg_ctx* c, int nb, Launch launch, bool close_mark, double out[kEvalOut])
 {
-    hipStream_t st = c->stream;
-    HIPCHK(c, c->eval_part.ensure(sizeof(double) * kEvalOut * (size_t)nb));
-    HIPCHK(c, c->eval_out.ensure(sizeof(double) * kEvalOut));
-    HIPCHK(c, c->eval_host.ensure(sizeof(double) * kEvalOut, sizeof(double) * 64));
-    launch(c->eval_part.as<double>());
-    launch_eval_total(c->eval_part.as<double>(), nb, c->eval_out.as<double>(), st);
-    if (close_mark) ctx_prof_mark(c, -1);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->eval_host.p, c->eval_out.p, sizeof(double) * kEvalOut, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    memcpy(out, c->eval_host.p, sizeof(double) * kEvalOut);
-    return LISREG_OK;
+    return record_totals<kEvalOut>(c, nb, launch, launch_eval_total, close_mark, out);
 }
 
 // The statistics of the n_vox voxels of a sorted cloud: a lane per voxel up to kVoxelBig points, a wavefront per voxel above.  Build is

@@ -604,6 +604,71 @@ private:
     double fitness_ = 1.7976931348623157e308;
 };
 
+// ---- pcl::GeneralizedIterativeClosestPoint as select_registration_method("GICP") sets it up -----------------------------
+// (src/core/registration.cpp:137-146: max correspondence distance 10, 30 iterations, transformation epsilon 1e-6, Euclidean fitness
+// epsilon 1e-3, RANSAC 0 — the one verifier of the five that is NOT commented out there), with the pcl::Registration surface the
+// loop-closure code uses.  The target lives in a FastGICP slot (a GICP target is a FastGICP target); map_slot: a map-index slot of the
+// same target for getFitnessScore, as FastGicpRegistration's.  setEuclideanFitnessEpsilon and setRANSACIterations are kept and unused:
+// PCL's GICP reads neither in its loop.
+template <class PointT>
+class GicpRegistration {
+public:
+    GicpRegistration(lisreg_ctx* ctx, int fgicp_slot, int map_slot) : tree_(ctx, map_slot), fgicp_slot_(fgicp_slot) { lisreg_gicp_default_params(0, &prm_); }
+    void setMaxCorrespondenceDistance(double d) { prm_.max_correspondence_distance = d; }
+    void setMaximumIterations(int n) { prm_.max_iters = n; }
+    void setTransformationEpsilon(double e) { prm_.transformation_epsilon = e; }
+    void setRotationEpsilon(double e) { prm_.rotation_epsilon = e; }
+    void setEuclideanFitnessEpsilon(double e) { euclidean_fitness_epsilon_ = e; }
+    void setRANSACIterations(int n) { ransac_iterations_ = n; }
+    void setCorrespondenceRandomness(int k) { prm_.k_correspondences = k; if (target_) setInputTarget(*target_); }
+    void setMaximumOptimizerIterations(int n) { prm_.max_inner_iters = n; }
+    void setInputTarget(const PointCloud<PointT>& cloud) {
+        target_ = &cloud;
+        lisreg_fgicp_params tp;
+        lisreg_fgicp_default_params(0, &tp);
+        tp.max_correspondence_distance = prm_.max_correspondence_distance;
+        tp.k_correspondences = prm_.k_correspondences;
+        tp.plane_epsilon = prm_.gicp_epsilon;
+        check(lisreg_fgicp_set_target(tree_.ctx(), fgicp_slot_, cloud.points.data(), (int)cloud.size(), (int)sizeof(PointT), SearchTree<PointT>::fmt(), &tp, &info_, 0.f));
+        tree_.setInputCloud(cloud);
+    }
+    void setInputSource(const PointCloud<PointT>* cloud) { source_ = cloud; }
+    void align(PointCloud<PointT>& output, const float* guess = nullptr) {
+        if (!source_) throw RegistrationError(LISREG_ERR_ARG, "GICP: no input source");
+        output.points.resize(source_->size());
+        check(lisreg_gicp_align(tree_.ctx(), fgicp_slot_, source_->points.data(), (int)source_->size(), (int)sizeof(PointT),
+                                SearchTree<PointT>::fmt(), &prm_, guess, &res_, output.points.data()));
+        for (int k = 0; k < 16; ++k) final_[k] = (float)res_.final_transform[k];
+        std::vector<int> idx(output.size());
+        std::vector<float> d2(output.size());
+        check(lisreg_nearest(tree_.ctx(), tree_.slot(), output.points.data(), (int)output.size(), (int)sizeof(PointT), SearchTree<PointT>::fmt(),
+                             1e18f, idx.data(), d2.data()));
+        double sum = 0; size_t nr = 0;
+        for (size_t i = 0; i < d2.size(); ++i) if (idx[i] >= 0) { sum += d2[i]; ++nr; }
+        fitness_ = nr ? sum / (double)nr : 1.7976931348623157e308;
+    }
+    bool hasConverged() const { return res_.converged != 0; }
+    double getFitnessScore() const { return fitness_; }
+    const float* getFinalTransformation() const { return final_; }                  // row-major 4x4 (result().final_transform holds it in double)
+    int getFinalNumIteration() const { return res_.iters; }
+    const lisreg_fgicp_info& info() const { return info_; }
+    const lisreg_gicp_result& result() const { return res_; }
+    const lisreg_gicp_params& params() const { return prm_; }
+private:
+    void check(int rc) { if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(tree_.ctx())); }
+    SearchTree<PointT> tree_;
+    int fgicp_slot_;
+    const PointCloud<PointT>* target_ = nullptr;
+    const PointCloud<PointT>* source_ = nullptr;
+    lisreg_gicp_params prm_{};
+    lisreg_fgicp_info  info_{};
+    lisreg_gicp_result res_{};
+    double euclidean_fitness_epsilon_ = 0.0;
+    int    ransac_iterations_ = 0;
+    float  final_[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    double fitness_ = 1.7976931348623157e308;
+};
+
 // ---- the candidate loop of detectLoopClosureForSubMap (src/node/subMapOptmizationNode.cpp:2779-2846) as one call ------
 // Every candidate submap is a FastGICP slot with its initial pose; alignAll(source) aligns the key-frame cloud against all of them
 // (lisreg_fgicp_align_batch: the source's distributions once, the LM loops in lockstep rounds) and best() is the candidate the loop's

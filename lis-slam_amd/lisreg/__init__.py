@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "lisreg_vgicp_linearize", "lisreg_vgicp_align_batch",
     "lisreg_fgicp_default_params", "lisreg_fgicp_set_target", "lisreg_fgicp_align", "lisreg_fgicp_correspondences", "lisreg_fgicp_linearize",
     "lisreg_fgicp_align_batch",
+    "lisreg_gicp_default_params", "lisreg_gicp_align", "lisreg_gicp_moments", "lisreg_gicp_inner",
 ]
 
 
@@ -127,6 +128,26 @@ class FgicpInfo(C.Structure):
 
 class FgicpResult(VgicpResult):
     """the fields of VgicpResult, in the same order"""
+
+
+class GicpParams(C.Structure):
+    """lisreg_gicp_params"""
+    _fields_ = [("max_correspondence_distance", C.c_double), ("transformation_epsilon", C.c_double), ("rotation_epsilon", C.c_double),
+                ("gicp_epsilon", C.c_double), ("rho", C.c_double), ("sigma", C.c_double), ("tau1", C.c_double), ("tau2", C.c_double),
+                ("tau3", C.c_double), ("step_size", C.c_double), ("gradient_tol", C.c_double), ("k_correspondences", C.c_int),
+                ("max_iters", C.c_int), ("max_inner_iters", C.c_int), ("order", C.c_int)]
+
+
+class GicpResult(C.Structure):
+    """lisreg_gicp_result"""
+    _fields_ = [("final_transform", C.c_double * 16), ("converged", C.c_int), ("iters", C.c_int), ("inner_iters", C.c_int),
+                ("n_evals", C.c_int), ("n_rounds", C.c_int), ("inner_exit", C.c_int), ("n_pairs_last", C.c_longlong),
+                ("error", C.c_double), ("last_delta", C.c_double)]
+
+    def as_dict(self):
+        return dict(T=np.array(list(self.final_transform), np.float64).reshape(4, 4), converged=bool(self.converged), iters=self.iters,
+                    inner_iters=self.inner_iters, n_evals=self.n_evals, n_rounds=self.n_rounds, inner_exit=self.inner_exit,
+                    n_pairs_last=self.n_pairs_last, error=self.error, last_delta=self.last_delta)
 
 
 class FgicpItemC(C.Structure):
@@ -552,6 +573,10 @@ def lib():
                                                C.POINTER(FgicpParams), C.POINTER(FgicpResult), dbl, C.POINTER(FgicpBatchInfo)]
         L.lisreg_fgicp_linearize.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), dbl, dbl, C.c_int, dbl,
                                              C.POINTER(C.c_longlong)]
+        L.lisreg_gicp_default_params.argtypes = [C.c_int, C.POINTER(GicpParams)]
+        L.lisreg_gicp_align.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(GicpParams), fp, C.POINTER(GicpResult), vp]
+        L.lisreg_gicp_moments.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(GicpParams), dbl, dbl]
+        L.lisreg_gicp_inner.argtypes = [dbl, dbl, dbl, C.POINTER(GicpParams), dbl, ip, dbl]
         _lib = L
     return _lib
 
@@ -570,6 +595,25 @@ def _default_params(struct, fn_name: str, kind: int, overrides: dict):
 
 def fgicp_default_params(kind: int = 0, **overrides) -> FgicpParams:
     return _default_params(FgicpParams, "lisreg_fgicp_default_params", kind, overrides)
+
+
+def gicp_default_params(kind: int = 0, **overrides) -> GicpParams:
+    return _default_params(GicpParams, "lisreg_gicp_default_params", kind, overrides)
+
+
+def gicp_inner(moments, centre, x0, params: GicpParams) -> dict:
+    """lisreg_gicp_inner: the inner BFGS of one outer iteration of PCL's GICP from its 74 moments, the centre they are taken about and
+    the outer iterate x0 = (tx, ty, tz, roll, pitch, yaw).  Needs no GPU.  Returns dict(x [6], f, iters, n_f, n_df, exit)."""
+    dp = C.POINTER(C.c_double)
+    m, c, x0 = (np.ascontiguousarray(a, np.float64).ravel() for a in (moments, centre, x0))
+    if m.size != 74 or c.size != 3 or x0.size != 6:
+        raise ValueError("gicp_inner: moments [74], centre [3], x0 [6]")
+    x, cnt, f = np.zeros(6), np.zeros(4, np.int32), C.c_double(0.0)
+    rc = lib().lisreg_gicp_inner(m.ctypes.data_as(dp), c.ctypes.data_as(dp), x0.ctypes.data_as(dp), C.byref(params), x.ctypes.data_as(dp),
+                                 cnt.ctypes.data_as(C.POINTER(C.c_int)), C.byref(f))
+    if rc:
+        raise LisregError(rc, "lisreg_gicp_inner")
+    return dict(x=x, f=f.value, iters=int(cnt[0]), n_f=int(cnt[1]), n_df=int(cnt[2]), exit=int(cnt[3]))
 
 
 def vgicp_default_params(kind: int = 0, **overrides) -> VgicpParams:
@@ -1723,7 +1767,20 @@ class Context:
         return self._sums_at(self._L.lisreg_fgicp_linearize, slot, source, params,
                              [np.reshape(T_pairs, 16), None if T_eval is None else np.reshape(T_eval, 16)], with_hessian)
 
-    # -- §7m, §7n: FastGICP / VGICP verification of a candidate list -----------------------------------------
+    # -- §7q: PCL's GICP registration (the target is a FastGICP slot) ------------------------------------------
+    def gicp_align(self, slot: int, source, params: "GicpParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
+        """pcl::GeneralizedIterativeClosestPoint::align against the FastGICP target in `slot`; returns the result dict (+ 'aligned')."""
+        return self._align(self._L.lisreg_gicp_align, GicpResult, slot, source, params, guess, want_aligned, out_ptr)
+
+    def gicp_moments(self, slot: int, source, params: "GicpParams", T):
+        """one round at T (4x4): the 74 moments of the pairs found at T (c0, g [12], S [60], pairs)"""
+        ptr, n, stride, fmt, _keep = self._cloud_args(source)
+        T = np.ascontiguousarray(T, np.float64).reshape(16)
+        out = np.zeros(74)
+        dp = C.POINTER(C.c_double)
+        self._chk(self._L.lisreg_gicp_moments(self._h, slot, ptr, n, stride, fmt, C.byref(params), T.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+        return out
+
     def _gicp_align_batch(self, fn, item_type, result_type, info_type, who, sources, items, params, want_fitness):
         """one batch call of a verifier through `fn`; returns (results: a list of the single call's dicts, fitness [n_items] or None,
         info dict).  A source given as None goes down as a NULL pointer of no points (for a source no item names)."""
