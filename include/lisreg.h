@@ -421,7 +421,10 @@ int  lisreg_get_trace(lisreg_ctx* ctx, float* buf, int max_iters);
  * the distributions of every staged source.  After a lisreg_fgicp_* call: out[0] / out[1] = the sum
  * launches and their number, out[2] / out[3] = the search launches and their number, out[4] = the distributions.  After
  * lisreg_ndt_align_batch: out[0] / out[1] = the rounds' evaluation and total launches (one interval per round) and their number,
- * out[2] / out[3] = the fitness search. */
+ * out[2] / out[3] = the fitness search.  After a lisreg_gicp_* call: out[2] / out[3] = the search-and-moments launches and their
+ * number, out[0] / out[1] = their fixed-order totals, out[4] = the distributions; after lisreg_gicp_align_batch the same per round
+ * (one moments interval and one totals interval per round), plus the fitness search in out[2] / out[3] and its totals in out[0] /
+ * out[1], and out[4] = the distributions of every staged source. */
 int  lisreg_set_profiling(lisreg_ctx* ctx, int enable);
 int  lisreg_get_timing(lisreg_ctx* ctx, double out[5]);
 
@@ -1259,7 +1262,8 @@ int  lisreg_fgicp_align_batch(lisreg_ctx* ctx, const void* const* sources, const
  * the same bits), and the whole inner BFGS runs on the host over those 74 doubles.  The DEFINITION is tests/gicp_ref.py (PCL's source
  * is not available to this project); DESIGN.md §7q lists the readings it picks.  Fewer than 4 pairs is PCL's "need at least 4 points":
  * converged = 0 and the pose at which that round searched.  Both ends of the outer loop (max_iters reached, delta < 1) set
- * converged = 1, as PCL 1.8 does.  No fitness score (aligned_out and lisreg_nearest give one) and no batch form yet. */
+ * converged = 1, as PCL 1.8 does.  No fitness score of its own (aligned_out and lisreg_nearest give one); the batch form below (§7r)
+ * computes one per item. */
 typedef struct lisreg_gicp_params {
     double max_correspondence_distance; /* a nearest point this far away or further is no pair */
     double transformation_epsilon;      /* delta scales the translation entries of X(x_k) - X(x_k+1) by 1 / this ... */
@@ -1302,6 +1306,45 @@ int  lisreg_gicp_moments(lisreg_ctx* ctx, int slot, const void* source, int n, i
                          const lisreg_gicp_params* params, const double T[16], double out[74]);
 int  lisreg_gicp_inner(const double moments[74], const double centre[3], const double x0[6], const lisreg_gicp_params* params,
                        double x_out[6], int counts[4], double* f_out);
+
+/* ---- §7r: PCL's GICP verification of a candidate list as one call ------------------------------------------------------------
+ * The candidate loop of detectLoopClosureForSubMap (src/node/subMapOptmizationNode.cpp:2779-2846) with the one verifier whose block
+ * is live in select_registration_method ("GICP", src/core/registration.cpp:137-146): lisreg_gicp_align_batch is
+ * lisreg_fgicp_align_batch (§7m, above) read for GICP.  Item k aligns sources[items[k].source] against the target of FastGICP slot
+ * items[k].slot (a GICP target IS a FastGICP slot, §7q) from items[k].guess, and results[k] is what lisreg_gicp_align returns for the
+ * same arguments alone, to the bit, in all 176 bytes.  The distributions of a source are made once per call however many items name
+ * it; a source no item names is neither checked nor staged.  The outer loops of all items advance in lockstep rounds: one round
+ * answers the outstanding outer iteration of every unfinished item with one search-and-moments launch, one launch of fixed-order
+ * totals, one copy of 592 bytes per item and one synchronisation, and then runs the items' inner BFGS minimisations on the host one
+ * after the other; info->n_rounds is the largest n_rounds of the items.
+ * fitness (may be NULL: no fitness pass, best = -1): fitness[k] = the mean, over the finite source points, of the squared distance to
+ * the nearest finite target point at results[k].final_transform (the double T = X(x) guess) — in double from the float coordinates as
+ * §7l's search defines it, without a cut-off (PCL's getFitnessScore() default), for every item, converged or not; two calls give the
+ * same bits.  info->best: the items are walked in order, an item with converged == 0 or fitness > the best so far is skipped, any
+ * other one is taken (:2834-2840; equal scores go to the later item); -1 if none converged.  An item that ends on fewer than 4 pairs
+ * (a guess far off) has converged = 0: `best` skips it, and it still gets a score.  The DEFINITION is tests/gicp_batch_ref.py.
+ * Refused (LISREG_ERR_ARG) for the whole batch, with `results`, `fitness` and best untouched: NULL items / results / sources / n with
+ * n_items > 0, n_items < 0, a source index outside 0 .. n_sources - 1, a slot without a FastGICP target, params lisreg_gicp_align
+ * refuses, a NAMED source it refuses (n <= 0, a NULL cloud, a short stride, an infinite coordinate, fewer finite points than
+ * k_correspondences; the last two are found while the distributions are made, before any alignment work), and a batch of more than
+ * INT_MAX / 74 wavefronts (items x ceil(finite source points / 64)).  n_items == 0 is LISREG_OK with best = -1.  All sources of a
+ * call share stride_bytes and fmt (host PCL structs or LISREG_FMT_DEVICE records).  Device memory the batch keeps (grow-only): 592
+ * bytes per (item, wavefront of its source) for the partial records, 64 per finite source point; an item owns nothing per point.  No
+ * per-item aligned_out and no per-item params. */
+typedef struct lisreg_gicp_item {
+    int          source;   /* index into sources[] */
+    int          slot;     /* lisreg_fgicp_set_target(slot) */
+    const float* guess;    /* row-major 4x4, NULL = identity */
+} lisreg_gicp_item;
+typedef struct lisreg_gicp_batch_info {
+    int best;              /* see above; -1 if no item converged */
+    int n_rounds;          /* host round trips of the alignment phase */
+    int n_sources_staged;  /* distributions actually computed */
+    int reserved;
+} lisreg_gicp_batch_info;
+int  lisreg_gicp_align_batch(lisreg_ctx* ctx, const void* const* sources, const int* n, int n_sources, int stride_bytes, int fmt,
+                             const lisreg_gicp_item* items, int n_items, const lisreg_gicp_params* params,
+                             lisreg_gicp_result* results, double* fitness, lisreg_gicp_batch_info* info);
 
 /* ---- loop-closure candidate detection: FEPSC (src/core/epscGeneration.cpp) -------------------------------------------
  * EPSCGeneration::loopDetection (:663-992) with UsingFEPSCFlag (config/params.yaml:22-28), as loopClosureThread calls it for every

@@ -1,11 +1,13 @@
-// lisreg_batch_driver.hpp — what the three batch verifiers share on the host (lisreg_fgicp_batch.hip, DESIGN.md §7m,
-// lisreg_vgicp_batch.hip, §7n, and lisreg_ndt_batch.hip, §7o): the refusals, the staging of every named source, the work table of a
-// round and its upload, the lockstep rounds of the items' resumable loops (the Levenberg-Marquardt stepper of lisreg_lm_stepper.hpp for
-// the fast_gicp family, the Newton / More-Thuente stepper of lisreg_ndt_stepper.hpp for NDT), the fitness pass, the `best` rule and the
-// copy-out.  A family F (a struct of static members, no virtual call) supplies
+// lisreg_batch_driver.hpp — what the four batch verifiers share on the host (lisreg_fgicp_batch.hip, DESIGN.md §7m,
+// lisreg_vgicp_batch.hip, §7n, lisreg_ndt_batch.hip, §7o, and lisreg_gicp_batch.hip, §7r): the refusals, the staging of every named
+// source, the work table of a round and its upload, the lockstep rounds of the items' resumable loops (the Levenberg-Marquardt stepper of
+// lisreg_lm_stepper.hpp for the fast_gicp family, the Newton / More-Thuente stepper of lisreg_ndt_stepper.hpp for NDT, the outer loop
+// of lisreg_gicp_stepper.hpp for PCL's GICP), the fitness pass, the `best` rule and the copy-out.  A family F (a struct of static
+// members, no virtual call) supplies
 //   kWho, Params / ItemC / Result / Info (its types of include/lisreg.h), Target (what a slot holds), Work (one entry of a round's table);
+//   kRec: the doubles of one evaluation's record (29 for the fast_gicp family and NDT, 74 for GICP's moments);
 //   bufs(c): its BatchBufs;  check_params(c, P);  find_target(c, slot, P, &T);
-//   Stepper: one item's loop (start / finished / req_hessian / feed / res);  start(stepper, guess, P, n_records);
+//   Stepper: one item's loop (start / finished / req_hessian / feed / res);  start(stepper, target, guess, P, n_records);
 //   ensure_sources(B, records): the batch's source buffers for that many records;
 //   stage_source(c, who, P, cloud, n, stride, fmt, B, off, want_finite, &m, &n_finite): one named source into the batch's buffers at `off`;
 //   m = the lanes of one evaluation of it (the finite points of the fast_gicp family, the records of NDT), n_finite = the points the
@@ -15,7 +17,7 @@
 //   search reads;  fit_pose(res): the pose it runs at;  result_to(res, Result*);
 //   launch_round(c, P, BatchRound<Work>): the evaluations of a round into r.part, with their profiling marks (the driver adds the totals
 //   and closes the interval);  kFitnessTotalsApart: the fitness pass's totals are an interval of their own.
-// One source for the three units, like lisreg_batch_rounds.hpp.  Not installed.
+// One source for the four units, like lisreg_batch_rounds.hpp.  Not installed.
 #pragma once
 #include "lisreg_batch_rounds.hpp"
 #include "lisreg_lm_stepper.hpp"
@@ -41,26 +43,17 @@ struct BatchRound {
     hipStream_t   st;
 };
 
-// What the two families of the fast_gicp kind supply alike: the Levenberg-Marquardt stepper started from the guess matrix, a source
-// staged as the distributions of its finite points (points and covariances, one lane per finite point), the pose and the result of
-// an LmResult
-template <class Params, class Result>
-struct LmBatchFamily {
-    using Stepper = vgicp_host::LmStepper;
-
-    static void start(Stepper& lm, const float* guess, const Params& P, int)
-    {
-        double T0[16];
-        vgicp_host::guess_to_T0(guess, T0);
-        lm.start(T0, vgicp_host::lm_params_of(P));
-    }
+// A source staged as the distributions of its finite points (points and covariances, one lane per finite point), for every family
+// whose lanes read them: the fast_gicp kind and PCL's GICP.  epsilon: the family's regularisation of a covariance (plane_epsilon,
+// gicp_epsilon)
+struct DistributionSources {
     static hipError_t ensure_sources(BatchBufs& B, size_t records)
     {
         const hipError_t e = B.src.ensure(sizeof(float4) * records);
         return e != hipSuccess ? e : B.cov.ensure(sizeof(double) * 6 * records);
     }
-    static int stage_source(lisreg_ctx* c, const char* who, const Params& P, const void* cloud, int n, int stride, int fmt, BatchBufs& B, long long off,
-                            bool, int* m_out, int* n_finite)
+    static int stage_distributions(lisreg_ctx* c, const char* who, int k_correspondences, double epsilon, const void* cloud, int n, int stride, int fmt,
+                                   BatchBufs& B, long long off, int* m_out, int* n_finite)
     {
         hipStream_t st = c->stream;
         const float4* raw = nullptr;
@@ -68,12 +61,33 @@ struct LmBatchFamily {
         if (rc) return rc;
         float bb[6];
         int m = 0;
-        rc = vg_distributions(c, who, raw, n, P.k_correspondences, P.plane_epsilon, 0.f, bb, &m, nullptr, nullptr);
+        rc = vg_distributions(c, who, raw, n, k_correspondences, epsilon, 0.f, bb, &m, nullptr, nullptr);
         if (rc) return rc;
         HIPCHK(c, hipMemcpyAsync(B.src.as<float4>() + off, c->vg_pts.p, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, st));
         HIPCHK(c, hipMemcpyAsync(B.cov.as<double>() + 6 * off, c->vg_cov.p, sizeof(double) * 6 * (size_t)m, hipMemcpyDeviceToDevice, st));
         *m_out = *n_finite = m;
         return LISREG_OK;
+    }
+};
+
+// What the two families of the fast_gicp kind supply alike: the Levenberg-Marquardt stepper started from the guess matrix, a source
+// staged as its distributions, the pose and the result of an LmResult
+template <class Params, class Result>
+struct LmBatchFamily : DistributionSources {
+    using Stepper = vgicp_host::LmStepper;
+    static constexpr int kRec = vgicp_host::kOut;
+
+    template <class Target>
+    static void start(Stepper& lm, const Target&, const float* guess, const Params& P, int)
+    {
+        double T0[16];
+        vgicp_host::guess_to_T0(guess, T0);
+        lm.start(T0, vgicp_host::lm_params_of(P));
+    }
+    static int stage_source(lisreg_ctx* c, const char* who, const Params& P, const void* cloud, int n, int stride, int fmt, BatchBufs& B, long long off,
+                            bool, int* m_out, int* n_finite)
+    {
+        return stage_distributions(c, who, P.k_correspondences, P.plane_epsilon, cloud, n, stride, fmt, B, off, m_out, n_finite);
     }
     static FgPose fit_pose(const vgicp_host::LmResult& lr) { return vgicp_host::pose_of<FgPose>(lr.T); }
     static void result_to(const vgicp_host::LmResult& lr, Result* res) { vgicp_host::lm_result_to(lr, res); }
@@ -85,6 +99,7 @@ int batch_align(lisreg_ctx* c, const void* const* sources, const int* n, int n_s
 {
     using namespace vgicp_host;
     using Work = typename F::Work;
+    constexpr int kOut = F::kRec;                                  // the doubles of one record: the family's, not vgicp_host's
     struct Source { bool used = false; int m = 0, n_finite = 0; long long off = 0; };
     struct Item { typename F::Stepper lm; const typename F::Target* T = nullptr; long long lane_off = 0; int src = 0, nb = 0; };
     constexpr const char* kWho = F::kWho;
@@ -158,7 +173,7 @@ int batch_align(lisreg_ctx* c, const void* const* sources, const int* n, int n_s
         return hipMemcpyAsync(const_cast<int*>(d_start), h_start, sizeof(int) * ((size_t)ne + 1), hipMemcpyHostToDevice, st);
     };
     // ---- the alignment phase, in lockstep rounds: every unfinished item has one request outstanding ----------------------------------
-    for (int k = 0; k < n_items; ++k) F::start(I[k].lm, items[k].guess, *P, n[I[k].src]);
+    for (int k = 0; k < n_items; ++k) F::start(I[k].lm, *I[k].T, items[k].guess, *P, n[I[k].src]);
     Work* const h_work = B.host_work.as<Work>();
     std::vector<int> order((size_t)n_items);
     int n_rounds = 0;

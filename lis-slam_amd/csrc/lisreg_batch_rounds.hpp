@@ -1,6 +1,6 @@
 // lisreg_batch_rounds.hpp — what the rounds of the batch verifiers share on the device (lisreg_fgicp_batch.hip, DESIGN.md §7m,
-// lisreg_vgicp_batch.hip, §7n, and lisreg_ndt_batch.hip, §7o): how a workgroup finds its entry in the round's work table, the fixed-order
-// totals of an entry's partial records, and the fitness search.  One source for the units; the anonymous namespace gives each unit a kernel of its own in
+// lisreg_vgicp_batch.hip, §7n, lisreg_ndt_batch.hip, §7o, and lisreg_gicp_batch.hip, §7r): how a workgroup finds its entry in the round's
+// work table, the fixed-order totals of an entry's partial records (of the family's width), and the fitness search.  One source for the units; the anonymous namespace gives each unit a kernel of its own in
 // its own code object.  The host side of the rounds is lisreg_batch_driver.hpp.  Not installed.
 #pragma once
 #include "lisreg_fgicp_lane.hpp"

@@ -388,10 +388,10 @@ struct lisreg_ctx {
     // correspondence rows of the test hook by the caller's index
     std::map<int, lisreg::FgicpTarget> fgicp;
     lisreg::DevBuf fg_pair, fg_M, fg_d2, fg_rows_i, fg_rows_d;
-    // lisreg_fgicp_align_batch (lisreg_fgicp_batch.hip), lisreg_vgicp_align_batch (lisreg_vgicp_batch.hip) and lisreg_ndt_align_batch
-    // (lisreg_ndt_batch.hip): a set of buffers each (a call of one family leaves the others' alone; NDT's has no covariances), and the
-    // pairs and M FastGICP's items keep from a search to the sums after it
-    lisreg::BatchBufs fgb, vgb, ndb;
+    // lisreg_fgicp_align_batch (lisreg_fgicp_batch.hip), lisreg_vgicp_align_batch (lisreg_vgicp_batch.hip), lisreg_ndt_align_batch
+    // (lisreg_ndt_batch.hip) and lisreg_gicp_align_batch (lisreg_gicp_batch.hip): a set of buffers each (a call of one family leaves the
+    // others' alone; NDT's has no covariances), and the pairs and M FastGICP's items keep from a search to the sums after it
+    lisreg::BatchBufs fgb, vgb, ndb, gcb;
     lisreg::DevBuf fgb_pair, fgb_M;
     lisreg::PinnedBuf done_host;            // one int
     lisreg::PinnedBuf stage_host;           // pinned staging of the per-batch tables

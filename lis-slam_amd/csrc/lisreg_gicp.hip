@@ -7,6 +7,7 @@
 // its line search runs on the host over 74 doubles (lisreg_gicp_host.hpp).  One round trip per outer iteration; the same input gives
 // the same bits.  No CPU fallback.
 #include "lisreg_gicp_lane.hpp"
+#include "lisreg_gicp_stepper.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -41,20 +42,6 @@ __global__ __launch_bounds__(64) void k_gicp_total(const double* __restrict__ pa
 void launch_gicp_total(const double* part, int n_part, double* out, hipStream_t st) { k_gicp_total<<<1, 64, 0, st>>>(part, n_part, out); }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-int check_params(lisreg_ctx* c, const lisreg_gicp_params* P, const char* who)
-{
-    if (!P) return bad(c, std::string(who) + ": NULL params");
-    if (!(P->max_correspondence_distance > 0)) return bad(c, std::string(who) + ": max_correspondence_distance <= 0");
-    if (P->k_correspondences < 4 || P->k_correspondences > 32) return bad(c, std::string(who) + ": k_correspondences outside 4 .. 32");
-    if (!(P->transformation_epsilon > 0) || !(P->rotation_epsilon > 0) || P->max_iters < 1 || P->max_inner_iters < 1 ||
-        !(P->gicp_epsilon > 0 && P->gicp_epsilon <= 1))
-        return bad(c, std::string(who) + ": bad transformation_epsilon / rotation_epsilon / max_iters / max_inner_iters / gicp_epsilon");
-    if (!(P->rho > 0 && P->rho < 1) || !(P->sigma > 0 && P->sigma < 1) || !(P->tau1 > 1) || !(P->tau2 > 0 && P->tau2 < 1) ||
-        !(P->tau3 > 0 && P->tau3 < 1) || !(P->step_size > 0) || !std::isfinite(P->step_size) || !(P->gradient_tol > 0) || P->order < 2 || P->order > 3)
-        return bad(c, std::string(who) + ": bad rho / sigma / tau1 / tau2 / tau3 / step_size / gradient_tol / order");
-    return LISREG_OK;
-}
-
 struct GicpRun {
     lisreg_ctx*        c;
     const FgicpTarget* T;
@@ -70,7 +57,7 @@ struct GicpRun {
 int stage_source(lisreg_ctx* c, const char* who, int slot, const void* source, int n, int stride, int fmt, const lisreg_gicp_params* P,
                  GicpRun* r, const float4** raw)
 {
-    int rc = check_params(c, P, who);
+    int rc = gc_check_params(c, P, who);
     if (rc) return rc;
     FgicpTarget* T = nullptr;
     rc = fg_find_target(c, slot, who, &T);
@@ -86,7 +73,7 @@ int stage_source(lisreg_ctx* c, const char* who, int slot, const void* source, i
     if (rc) return rc;
     r->c = c; r->T = T; r->src = c->vg_pts.as<float4>(); r->cov = c->vg_cov.as<double>(); r->n = m;
     r->max_d = P->max_correspondence_distance;
-    for (int k = 0; k < 3; ++k) r->C.c[k] = ((double)T->bb[k] + (double)T->bb[3 + k]) / 2.0;
+    r->C = gicp_centre_of(*T);
     return LISREG_OK;
 }
 
@@ -105,6 +92,21 @@ int moments_at(GicpRun& r, const double T[16], double rec[kGicpRec])
 }
 
 }  // namespace
+
+// the parameter checks of every GICP entry point, the batch's among them (declared in lisreg_gicp_lane.hpp)
+int lisreg::gc_check_params(lisreg_ctx* c, const lisreg_gicp_params* P, const char* who)
+{
+    if (!P) return bad(c, std::string(who) + ": NULL params");
+    if (!(P->max_correspondence_distance > 0)) return bad(c, std::string(who) + ": max_correspondence_distance <= 0");
+    if (P->k_correspondences < 4 || P->k_correspondences > 32) return bad(c, std::string(who) + ": k_correspondences outside 4 .. 32");
+    if (!(P->transformation_epsilon > 0) || !(P->rotation_epsilon > 0) || P->max_iters < 1 || P->max_inner_iters < 1 ||
+        !(P->gicp_epsilon > 0 && P->gicp_epsilon <= 1))
+        return bad(c, std::string(who) + ": bad transformation_epsilon / rotation_epsilon / max_iters / max_inner_iters / gicp_epsilon");
+    if (!(P->rho > 0 && P->rho < 1) || !(P->sigma > 0 && P->sigma < 1) || !(P->tau1 > 1) || !(P->tau2 > 0 && P->tau2 < 1) ||
+        !(P->tau3 > 0 && P->tau3 < 1) || !(P->step_size > 0) || !std::isfinite(P->step_size) || !(P->gradient_tol > 0) || P->order < 2 || P->order > 3)
+        return bad(c, std::string(who) + ": bad rho / sigma / tau1 / tau2 / tau3 / step_size / gradient_tol / order");
+    return LISREG_OK;
+}
 
 extern "C" {
 
@@ -155,40 +157,14 @@ int lisreg_gicp_align(lisreg_ctx* c, int slot, const void* source, int n, int st
     const float4* raw = nullptr;
     int rc = stage_source(c, "gicp_align", slot, source, n, stride, fmt, P, &r, &raw);
     if (rc) return rc;
-    double G[16], T[16], rec[kGicpRec];
+    double G[16];
     guess_to_T0(guess, G);
-    const BfgsParams B = bfgs_params_of(*P);
-    double x[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
-    lisreg_gicp_result out;
-    memset(&out, 0, sizeof out);
-    out.inner_exit = -1;
-    for (;;) {                                                      // computeTransformation: one round per outer iteration
-        pose_of_state(x, G, T);
-        rc = moments_at(r, T, rec);
-        if (rc) return rc;
-        ++out.n_rounds;
-        out.n_pairs_last = (long long)rec[73];
-        if (rec[73] < 4.0) {                                        // PCL's "need at least 4 points": not converged, the pose of this round
-            out.error = rec[73] > 0.0 ? rec[0] / rec[73] : 0.0;
-            break;
-        }
-        double xn[6];
-        memcpy(xn, x, sizeof x);
-        InnerCounts cnt;
-        const double f = inner(rec, r.C.c, xn, B, &cnt);
-        const double delta = outer_delta(x, xn, P->rotation_epsilon, P->transformation_epsilon);
-        memcpy(x, xn, sizeof x);
-        ++out.iters;
-        out.inner_iters += cnt.iters;
-        out.n_evals += cnt.n_f + cnt.n_df;
-        out.error = f; out.last_delta = delta; out.inner_exit = cnt.exit;
-        if (out.iters >= P->max_iters || delta < 1.0) {             // both ends count as converged (PCL 1.8)
-            out.converged = 1;
-            break;
-        }
-    }
+    GicpLoopResult lr;                                              // computeTransformation: one round per outer iteration (GicpStepper)
+    rc = gicp_closed_loop([&](const double T[16], double rec[kGicpRec]) { return moments_at(r, T, rec); }, G, gicp_loop_params_of(*P), r.C.c, &lr);
+    if (rc) return rc;
     ctx_prof_collect(c);
-    pose_of_state(x, G, out.final_transform);
+    lisreg_gicp_result out;
+    gicp_result_to(lr, &out);
     *res = out;
     if (aligned_out) {                                    // the source under the final transformation (in float, like lisreg_transform_cloud)
         float F[12];

@@ -60,4 +60,15 @@ __device__ __forceinline__ void gicp_moments_lane(bool live, const float4 s, con
     if (writer) out[73] = v;
 }
 
+// ---- what the single call (lisreg_gicp.hip) and the batch (lisreg_gicp_batch.hip) share on the host, one copy each ----------------------
+// the parameter checks of every GICP entry point (defined in lisreg_gicp.hip)
+int gc_check_params(lisreg_ctx* c, const lisreg_gicp_params* P, const char* who);
+// the centre of a slot's finite bounding box
+inline GicpCentre gicp_centre_of(const FgicpTarget& T)
+{
+    GicpCentre C;
+    for (int k = 0; k < 3; ++k) C.c[k] = ((double)T.bb[k] + (double)T.bb[3 + k]) / 2.0;
+    return C;
+}
+
 }  // namespace lisreg

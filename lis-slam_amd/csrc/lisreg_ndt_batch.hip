@@ -70,6 +70,7 @@ struct NdBatch {
     using Target  = NdtTarget;
     using Work    = NdtWork;
     using Stepper = NdtStepper;
+    static constexpr int  kRec = kNdtOut;
     static constexpr bool kFitnessTotalsApart = false;             // the fitness pass: "solve" = the search with its totals, one interval
 
     static BatchBufs& bufs(lisreg_ctx* c) { return c->ndb; }
@@ -82,7 +83,7 @@ struct NdBatch {
     }
     static hipError_t ensure_lanes(lisreg_ctx*, long long) { return hipSuccess; }      // an item owns no device memory
 
-    static void start(Stepper& s, const float* guess, const Params& P, int n_records)
+    static void start(Stepper& s, const Target&, const float* guess, const Params& P, int n_records)
     {
         double p0[6];
         p_from_matrix(guess, p0);

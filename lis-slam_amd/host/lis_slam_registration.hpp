@@ -836,6 +836,68 @@ private:
     lisreg_ndt_batch_info info_{ -1, 0, 0, 0 };
 };
 
+// ---- the same candidate loop with the one verifier whose block is live (GICP, registration.cpp:137-146) --------------------
+// Every candidate submap is a FastGICP slot (a GICP target is a FastGICP target, set with plane_epsilon = gicp_epsilon) with its initial
+// pose; alignAll(source) aligns the key-frame cloud against all of them (lisreg_gicp_align_batch: the source's distributions once, the
+// outer loops in lockstep rounds of one moments launch each, the inner BFGS on the host) and best() is the candidate the loop's
+// `hasConverged() == false || score > bestScore` test would have kept (-1: none), with result(i) / fitness(i) per candidate.
+template <class PointT>
+class GicpVerifier {
+public:
+    explicit GicpVerifier(lisreg_ctx* ctx) : ctx_(ctx) { lisreg_gicp_default_params(0, &prm_); }
+    void setMaxCorrespondenceDistance(double d) { prm_.max_correspondence_distance = d; }
+    void setCorrespondenceRandomness(int k) { prm_.k_correspondences = k; }
+    void setTransformationEpsilon(double e) { prm_.transformation_epsilon = e; }
+    void setRotationEpsilon(double e) { prm_.rotation_epsilon = e; }
+    void setMaximumIterations(int n) { prm_.max_iters = n; }
+    void setMaximumOptimizerIterations(int n) { prm_.max_inner_iters = n; }
+    const lisreg_gicp_params& params() const { return prm_; }
+    // the submap of a candidate into its slot (a submap that stays resident between key frames is set once)
+    void setCandidateTarget(int slot, const PointCloud<PointT>& cloud) {
+        lisreg_fgicp_params tp;
+        lisreg_fgicp_default_params(0, &tp);
+        tp.max_correspondence_distance = prm_.max_correspondence_distance;
+        tp.k_correspondences = prm_.k_correspondences;
+        tp.plane_epsilon = prm_.gicp_epsilon;
+        check(lisreg_fgicp_set_target(ctx_, slot, cloud.points.data(), (int)cloud.size(), (int)sizeof(PointT), SearchTree<PointT>::fmt(), &tp, nullptr, 0.f));
+    }
+    void clearCandidates() { slots_.clear(); guesses_.clear(); }
+    // guess: row-major 4x4 (key2PreSubMapTrans), nullptr = identity; returns the candidate's index
+    int addCandidate(int slot, const float* guess = nullptr) {
+        slots_.push_back(slot);
+        std::vector<float> g;
+        if (guess) g.assign(guess, guess + 16);
+        guesses_.push_back(g);
+        return (int)slots_.size() - 1;
+    }
+    size_t size() const { return slots_.size(); }
+    void alignAll(const PointCloud<PointT>& source) {
+        const size_t n = slots_.size();
+        std::vector<lisreg_gicp_item> items(n);
+        for (size_t i = 0; i < n; ++i) items[i] = lisreg_gicp_item{ 0, slots_[i], guesses_[i].empty() ? nullptr : guesses_[i].data() };
+        res_.assign(n, lisreg_gicp_result{});
+        fit_.assign(n, 1.7976931348623157e308);
+        const void* src = source.points.data();
+        const int ns = (int)source.size();
+        check(lisreg_gicp_align_batch(ctx_, &src, &ns, 1, (int)sizeof(PointT), SearchTree<PointT>::fmt(), items.data(), (int)n, &prm_,
+                                      res_.data(), fit_.data(), &info_));
+    }
+    int best() const { return info_.best; }
+    bool hasConverged(int i) const { return res_.at((size_t)i).converged != 0; }
+    double fitness(int i) const { return fit_.at((size_t)i); }
+    const lisreg_gicp_result& result(int i) const { return res_.at((size_t)i); }
+    const lisreg_gicp_batch_info& info() const { return info_; }
+private:
+    void check(int rc) { if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_)); }
+    lisreg_ctx* ctx_;
+    lisreg_gicp_params prm_{};
+    std::vector<int> slots_;
+    std::vector<std::vector<float>> guesses_;
+    std::vector<lisreg_gicp_result> res_;
+    std::vector<double> fit_;
+    lisreg_gicp_batch_info info_{ -1, 0, 0, 0 };
+};
+
 // OptimizedICPGN (src/include/registration.h:44-70, src/core/registration.cpp:8-115): same constructor and calls
 template <class PointT>
 class OptimizedICPGN {

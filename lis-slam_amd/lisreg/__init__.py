@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "lisreg_vgicp_linearize", "lisreg_vgicp_align_batch",
     "lisreg_fgicp_default_params", "lisreg_fgicp_set_target", "lisreg_fgicp_align", "lisreg_fgicp_correspondences", "lisreg_fgicp_linearize",
     "lisreg_fgicp_align_batch",
-    "lisreg_gicp_default_params", "lisreg_gicp_align", "lisreg_gicp_moments", "lisreg_gicp_inner",
+    "lisreg_gicp_default_params", "lisreg_gicp_align", "lisreg_gicp_moments", "lisreg_gicp_inner", "lisreg_gicp_align_batch",
 ]
 
 
@@ -189,6 +189,18 @@ class NdtBatchInfo(FgicpBatchInfo):
 
 class NdtItem(FgicpItem):
     """one alignment of a batch: sources[source] against the NDT target in `slot` from `guess` (4x4 or None = identity)"""
+
+
+class GicpItemC(FgicpItemC):
+    """lisreg_gicp_item: the fields of lisreg_fgicp_item, in the same order"""
+
+
+class GicpBatchInfo(FgicpBatchInfo):
+    """lisreg_gicp_batch_info: the fields of lisreg_fgicp_batch_info, in the same order"""
+
+
+class GicpItem(FgicpItem):
+    """one alignment of a batch: sources[source] against the FastGICP target in `slot` (PCL's GICP, §7r) from `guess` (4x4 or None = identity)"""
 
 
 class GuessInput(C.Structure):
@@ -577,6 +589,8 @@ def lib():
         L.lisreg_gicp_align.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(GicpParams), fp, C.POINTER(GicpResult), vp]
         L.lisreg_gicp_moments.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(GicpParams), dbl, dbl]
         L.lisreg_gicp_inner.argtypes = [dbl, dbl, dbl, C.POINTER(GicpParams), dbl, ip, dbl]
+        L.lisreg_gicp_align_batch.argtypes = [vp, C.POINTER(vp), ip, C.c_int, C.c_int, C.c_int, C.POINTER(GicpItemC), C.c_int,
+                                              C.POINTER(GicpParams), C.POINTER(GicpResult), dbl, C.POINTER(GicpBatchInfo)]
         _lib = L
     return _lib
 
@@ -1820,6 +1834,13 @@ class Context:
         for a source no item names), items = a list of NdtItem.  Returns (results: a list of ndt_align's dicts, fitness [n_items] or
         None, info dict)."""
         return self._gicp_align_batch(self._L.lisreg_ndt_align_batch, NdtItemC, NdtResult, NdtBatchInfo, "ndt_align_batch",
+                                      sources, items, params, want_fitness)
+
+    def gicp_align_batch(self, sources, items, params: "GicpParams", want_fitness: bool = True):
+        """lisreg_gicp_align_batch (§7r): sources = a list of clouds (all host PCL-struct arrays of one dtype, or all (device_ptr, n); None
+        for a source no item names), items = a list of GicpItem naming FastGICP slots.  Returns (results: a list of gicp_align's dicts,
+        fitness [n_items] or None, info dict)."""
+        return self._gicp_align_batch(self._L.lisreg_gicp_align_batch, GicpItemC, GicpResult, GicpBatchInfo, "gicp_align_batch",
                                       sources, items, params, want_fitness)
 
     def set_profiling(self, on: bool):
