@@ -928,6 +928,46 @@ int  lisreg_icp_gn_match(lisreg_ctx* ctx, int slot, const void* source, int n, i
                          unsigned max_iterations, float max_correspond_distance, const float predict_pose[16],
                          lisreg_icpgn_result* result, void* transformed_out);
 
+/* The candidate loop of detectLoopClosureForSubMapICP (src/node/subMapOptmizationNode.cpp:2496-2621: a static OptimizedICPGN
+ * myICP(30, 10) and, per candidate, SetTargetCloud / Match / GetFitnessScore / HasConverged, then the `best` rule) as ONE call (DESIGN.md
+ * section 7s).  Item k matches sources[items[k].source] against the map index of items[k].slot from items[k].predict_pose.
+ * Batch equals single: results[k] is what lisreg_icp_gn_match(ctx, items[k].slot, sources[items[k].source], ..., max_iterations,
+ *   max_correspond_distance, predict_pose or identity, &r, NULL) writes, in all bytes of lisreg_icpgn_result, whatever else is in the
+ *   batch: the quirk of :49-50 (squared distance against the un-squared threshold), a negative max_correspond_distance does no
+ *   iteration work, max_iterations == 0 gives the pose untouched plus a fitness, the pcl::isFinite filter, a singular Hessian skips the
+ *   step.  (An item keeps the lanes per query, the partial rows and the order of sums of its single call.)
+ * Sources: host PCL structs or LISREG_FMT_DEVICE records, one stride and one format for the call; a source is staged once however
+ *   many items name it; a source no item names is neither checked nor staged (its pointer may be NULL, its n anything).
+ * info->best: bestScore starts at DBL_MAX and the items are walked in order; an item with (double)fitness > bestScore is skipped, any
+ *   other is taken — equal scores go to the later item and a NaN score is taken, as the comparison of :2551-2558 is written
+ *   (HasConverged() is always true and drops out).  -1 only for n_items == 0.
+ * Refused for the whole batch, results untouched (LISREG_ERR_ARG / LISREG_ERR_NO_TARGET as the single call chooses): NULL items /
+ *   results / sources / n with n_items > 0, n_items < 0, a source index out of range, a slot without a map index, max_iterations >
+ *   100000, a named source the single call refuses, a batch whose workgroups or partial rows do not fit 32-bit counts (nor may the
+ *   source points summed over the items: the neighbours are kept per item).
+ *   n_items == 0 is LISREG_OK with best = -1.  There is no per-item transformed_out and there are no per-item parameters.
+ * Synchronisation: every iteration is one correspondence launch per lanes-per-query class present (at most three, one in practice)
+ *   and one solve launch over all items; the host waits only every 64 iterations (as the single call does, to bound the queue) and for
+ *   the read-back: n_syncs = max_iterations / 64 + 1 (1 when a negative max_correspond_distance leaves nothing to iterate).  Ordered
+ *   on the context's stream (lisreg_set_stream).
+ * Memory (grow-only, the batch's own: lisreg_icp_align_batch's and lisreg_icp_gn_match's scratch is left alone): per item a state of
+ *   192 bytes and a table entry of 48, per workgroup of 256 lanes a partial row of 176 bytes, per (item, source point) 4 bytes for the
+ *   neighbour kept as the next iteration's seed, and the host sources staged as 16-byte records. */
+typedef struct lisreg_icpgn_item {
+    int          source;                /* index into sources[] */
+    int          slot;                  /* SetTargetCloud: lisreg_map_index_set(slot) */
+    const float* predict_pose;          /* row-major 4x4, NULL = identity */
+} lisreg_icpgn_item;                    /* 16 bytes */
+typedef struct lisreg_icpgn_batch_info {
+    int best;                           /* see above; -1 only for n_items == 0 */
+    int n_sources_staged;               /* named sources actually staged */
+    int n_syncs;                        /* host synchronisations of the call, read-back included */
+    int reserved;
+} lisreg_icpgn_batch_info;              /* 16 bytes */
+int  lisreg_icp_gn_match_batch(lisreg_ctx* ctx, const void* const* sources, const int* n, int n_sources, int stride_bytes, int fmt,
+                               const lisreg_icpgn_item* items, int n_items, unsigned max_iterations, float max_correspond_distance,
+                               lisreg_icpgn_result* results, lisreg_icpgn_batch_info* info /* may be NULL */);
+
 /* ---- §7j: Normal Distributions Transform registration (loop-closure verification) ------------------------------------
  * select_registration_method("NDT") (src/core/registration.cpp:147-155) returns a pcl::NormalDistributionsTransform with
  * epsilon 0.01, step size 0.1, resolution 1.0 and 35 iterations; detectLoopClosureForSubMap carries the same four settings as its

@@ -369,6 +369,11 @@ struct lisreg_ctx {
     int               gm_flip = 0;
     lisreg::DevBuf map_stage;                          // lisreg_map_index_set_batch: host clouds of a batch, packed, in one upload
     lisreg::DevBuf mp_pts, mp_flag, mp_pos, mp_idx, mp_cnt, mp_d2, mp_out, icp_state, icp_partials, icp_cur, icp_items, map_tab, map_tsegs, map_tblocks;
+    // lisreg_icp_gn_match_batch (lisreg_api_icpgn.hip), its own (icp_state / icp_partials / icp_cur stay the single calls' and
+    // lisreg_icp_align_batch's): [states | block table | packed host sources] in pinned memory and on the device, the partial rows, the
+    // neighbour of every (item, source point)
+    lisreg::PinnedBuf gnb_host;
+    lisreg::DevBuf gnb_tab, gnb_part, gnb_nn;
     // one evaluation of the NDT, VGICP and FastGICP verifiers (eval_totals in lisreg_fp64_sums.hpp): per-workgroup partial sums, their
     // total and its pinned landing area
     lisreg::DevBuf eval_part, eval_out;

@@ -362,6 +362,27 @@ void launch_icp_fitness_batch(const IcpItem* items, int n_items, int total_block
 void launch_icpgn_iteration(const float4* src, int n, const GridIndex* grid_dev, IcpState* st, float cap2, double* partials,
                             hipStream_t stream);
 void launch_icp_fitness(const float4* src, int n, const GridIndex* grid_dev, IcpState* st, double* partials, hipStream_t stream);
+// lisreg_icp_gn_match_batch: one alignment of the batch (device).  The table is ordered by lane class (icp_lanes(n) = 1, 4, 8); blocks
+// blk0 .. blk0 + nblk of its CLASS's launch work on it, nblk = icp_blocks(n); its partial rows are row0 .. row0 + nblk of the batch
+struct IcpGnItem {
+    const float4*    src;    // source records
+    int*             nn;     // last iteration's neighbour of every source point (position in the sorted target, -1 none): the next search's seed
+    const GridIndex* grid;   // its target's k = 1 index
+    int n, blk0, nblk, row0;
+    int state;               // its IcpState (= its index in the caller's items)
+    int pad_;
+};
+struct IcpGnClasses {
+    int first[4];            // table entries first[c] .. first[c + 1] have lane class c (1, 4, 8 lanes per query)
+    int blocks[3];           // workgroups of the class's launch
+};
+int  icp_lanes(int n);
+// one iteration of every item (partials: 22 doubles per row; first: no neighbours kept yet), and the fitness scores into fit_sum / fit_n
+// (partials: 2 doubles per row; seeded: an iteration has run)
+void launch_icpgn_batch_iteration(const IcpGnItem* items, int n_items, const IcpGnClasses& cls, IcpState* states, float cap2, bool first,
+                                  double* partials, hipStream_t stream);
+void launch_icpgn_batch_fitness(const IcpGnItem* items, int n_items, const IcpGnClasses& cls, IcpState* states, bool seeded, double* partials,
+                                hipStream_t stream);
 void launch_bbx_flags(const float4* pts, int n, const double b[6], int delete_box, int* flag, hipStream_t st);
 // stable compaction: idx_out[0..count) = indices i with flag[i] != 0, ascending; pos [n+1]
 void launch_compact(int n, const int* flag, int* pos, int* scan_tmp, int* idx_out, int* count_out, hipStream_t st);

@@ -353,8 +353,9 @@ __device__ __forceinline__ double wave_sum_up(double v)
     return v;
 }
 
-// the block -> item table of a batch: items[k].blk0 ascending, items[n_items].blk0 = total
-__device__ __forceinline__ int icp_find_item(const IcpItem* __restrict__ items, int n_items, int blk)
+// the block -> item table of a batch: items[k].blk0 ascending, items[n_items].blk0 = total  (Item: IcpItem, IcpGnItem)
+template <class Item>
+__device__ __forceinline__ int icp_find_item(const Item* __restrict__ items, int n_items, int blk)
 {
     int lo = 0, hi = n_items - 1;
     while (lo < hi) {
@@ -367,7 +368,8 @@ __device__ __forceinline__ int icp_find_item(const IcpItem* __restrict__ items, 
 // Which alignment, and which of its blocks, a workgroup of a batch launch works on: workgroup p = block p of the batch.  (An XCD-aware order —
 // XCD x working through the alignments x, x + 8, ... so that an L2 holds the one target its CUs are searching — measured 4 % SLOWER on
 // configs[3] in round 5: the search is not bound by L2 misses; profiles/r05_kernel_experiments.md section 6, r05_xp_icp_xcd_order.patch.)
-__device__ __forceinline__ int icp_locate(const IcpItem* __restrict__ items, int n_items, int* b)
+template <class Item>
+__device__ __forceinline__ int icp_locate(const Item* __restrict__ items, int n_items, int* b)
 {
     const int item = icp_find_item(items, n_items, blockIdx.x);
     *b = (int)blockIdx.x - items[item].blk0;
@@ -515,26 +517,36 @@ __global__ __launch_bounds__(1024) void k_icp_solve(const double* __restrict__ a
     if (st->done && n_done) atomicAdd(n_done, 1);
 }
 
-// getFitnessScore(): unbounded k = 1 of the source under the final transformation
+// getFitnessScore(): unbounded k = 1 of the source under the final transformation.  One workgroup's row of (sum d2, count) for the
+// queries (blk * 256 + thread) / Q of a cloud of n points: wave_sum per wavefront, (w0 + w1) + (w2 + w3) across them.  `nn` (may be
+// null): a seed per query for the search, which returns the same neighbour and distance with it as without.
+// (the single call and an item of lisreg_icp_gn_match_batch both come through here: the same bits)
 template <int Q>
-__global__ __launch_bounds__(256) void k_icp_fitness(const float4* __restrict__ src, int n, const GridIndex* __restrict__ gp,
-                                                     const IcpState* __restrict__ stp, double* __restrict__ partials)
+__device__ __forceinline__ void icp_fitness_row(const float4* __restrict__ src, int n, const GridIndex* __restrict__ gp, const float* F,
+                                                const int* __restrict__ nn, unsigned blk, double (*red)[2], double* __restrict__ row)
 {
-    __shared__ double red[4][2];
-    const int i = (blockIdx.x * 256 + threadIdx.x) / Q;
+    const int i = (blk * 256 + threadIdx.x) / Q;
     double sum = 0, cnt = 0;
     if (i < n) {
         const GridIndex g = *gp;
         const float4 s = src[i];
         float px, py, pz, d2;
-        apply4(stp->F, s.x, s.y, s.z, px, py, pz);
-        if (nn1_search<Q>(px, py, pz, g, 3.0e38f, &d2) >= 0 && (threadIdx.x & (Q - 1)) == 0) { sum = d2; cnt = 1; }
+        apply4(F, s.x, s.y, s.z, px, py, pz);
+        if (nn1_search<Q>(px, py, pz, g, 3.0e38f, &d2, nn ? nn[i] : -1) >= 0 && (threadIdx.x & (Q - 1)) == 0) { sum = d2; cnt = 1; }
     }
     sum = wave_sum(sum); cnt = wave_sum(cnt);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { red[wave][0] = sum; red[wave][1] = cnt; }
     __syncthreads();
-    if (threadIdx.x < 2) partials[(size_t)blockIdx.x * 2 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    if (threadIdx.x < 2) row[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+template <int Q>
+__global__ __launch_bounds__(256) void k_icp_fitness(const float4* __restrict__ src, int n, const GridIndex* __restrict__ gp,
+                                                     const IcpState* __restrict__ stp, double* __restrict__ partials)
+{
+    __shared__ double red[4][2];
+    icp_fitness_row<Q>(src, n, gp, stp->F, nullptr, blockIdx.x, red, partials + (size_t)blockIdx.x * 2);
 }
 
 // the batch forms of the two kernels above: block -> item table, rows of 256 / Q queries summed by the Q-independent tree
@@ -585,9 +597,9 @@ __global__ __launch_bounds__(256) void k_icp_fit_reduce_b(const double* __restri
     if (threadIdx.x == 0) { states[blockIdx.x].fit_sum = red[0][0]; states[blockIdx.x].fit_n = (int)red[0][1]; }
 }
 
-__global__ __launch_bounds__(256) void k_icp_fit_reduce(const double* __restrict__ partials, int n_blocks, IcpState* __restrict__ st)
+// the n_blocks rows of icp_fitness_row added by a workgroup of 256 threads: thread t takes rows t, t + 256, ... in order, then a halving tree
+__device__ __forceinline__ void icp_fit_total(const double* __restrict__ partials, int n_blocks, IcpState* __restrict__ st, double (*red)[2])
 {
-    __shared__ double red[256][2];
     double s = 0, c = 0;
     for (int b = threadIdx.x; b < n_blocks; b += 256) { s += partials[(size_t)b * 2]; c += partials[(size_t)b * 2 + 1]; }
     red[threadIdx.x][0] = s; red[threadIdx.x][1] = c;
@@ -599,56 +611,61 @@ __global__ __launch_bounds__(256) void k_icp_fit_reduce(const double* __restrict
     if (threadIdx.x == 0) { st->fit_sum = red[0][0]; st->fit_n = (int)red[0][1]; }
 }
 
+__global__ __launch_bounds__(256) void k_icp_fit_reduce(const double* __restrict__ partials, int n_blocks, IcpState* __restrict__ st)
+{
+    __shared__ double red[256][2];
+    icp_fit_total(partials, n_blocks, st, red);
+}
+
 // ---- §8 f-4, second half: OptimizedICPGN (src/core/registration.cpp:19-115) ------------------------------------------------
 // J = [I | A] with A = -R hat(p), so J^T J = [[n I, sum A], [sum A^T, sum A^T A]] and J^T e = [sum e; sum A^T e]:
 // count, sum e (3), sum A (9), sum A^T A (6 unique), sum A^T e (3) = 22 sums instead of 21 + 6 + 1 generic ones.
 constexpr int kGnAcc = 22;
 
+// The per-lane body, the ONE copy of the arithmetic of a correspondence: source point p of a query under T = F, its neighbour within
+// cap2 and, in the query's lead lane, the 22 terms into acc (zeros come in).  All Q lanes of a query call it together.  seed: a
+// position in the sorted target for the search to start from, -1 none, -2 nn1_cell_seed of the transformed point; the neighbour does
+// not depend on it (tests/test_nn1_forms.py).  Returns the neighbour's position, -1 none (or p not finite).
 template <int Q>
-__global__ __launch_bounds__(256) void k_icpgn_assoc(const float4* __restrict__ src, int n, const GridIndex* __restrict__ gp,
-                                                     const IcpState* __restrict__ stp, float cap2, double* __restrict__ partials)
+__device__ __forceinline__ int icpgn_lane(const float4 p, const float* F, const GridIndex& g, float cap2, bool lead, int seed,
+                                          double (&acc)[kGnAcc])
 {
-    __shared__ double red[4][kGnAcc];
-    const int i = (blockIdx.x * 256 + threadIdx.x) / Q;
-    const bool lead = (threadIdx.x & (Q - 1)) == 0;
-    double acc[kGnAcc];
+    if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) return -1;              // pcl::isFinite(origin_point), :37
+    float tx, ty, tz, d2;
+    apply4(F, p.x, p.y, p.z, tx, ty, tz);
+    if (seed == -2) seed = nn1_cell_seed(tx, ty, tz, g);
+    const int bi = nn1_search<Q>(tx, ty, tz, g, cap2, &d2, seed);
+    if (bi >= 0 && lead) {
+        const float4 q = g.pts[bi];
+        const float e[3] = { tx - q.x, ty - q.y, tz - q.z };
+        float A[3][3];
 #pragma unroll
-    for (int k = 0; k < kGnAcc; ++k) acc[k] = 0.0;
-    if (i < n) {
-        const GridIndex g = *gp;
-        const float4 p = src[i];
-        const float* F = stp->F;
-        if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {                      // pcl::isFinite(origin_point), :37
-            float tx, ty, tz, d2;
-            apply4(F, p.x, p.y, p.z, tx, ty, tz);
-            const int bi = nn1_search<Q>(tx, ty, tz, g, cap2, &d2);
-            if (bi >= 0 && lead) {
-                const float4 q = g.pts[bi];
-                const float e[3] = { tx - q.x, ty - q.y, tz - q.z };
-                float A[3][3];
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const float R0 = F[4 * r], R1 = F[4 * r + 1], R2 = F[4 * r + 2];
-                    A[r][0] = -(R1 * p.z - R2 * p.y);
-                    A[r][1] = -(R2 * p.x - R0 * p.z);
-                    A[r][2] = -(R0 * p.y - R1 * p.x);
-                }
-                acc[0] = 1.0;
-                acc[1] = e[0]; acc[2] = e[1]; acc[3] = e[2];
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) acc[4 + 3 * r + c] = A[r][c];
-                int k = 13;
-#pragma unroll
-                for (int a = 0; a < 3; ++a)
-#pragma unroll
-                    for (int b = a; b < 3; ++b) acc[k++] = (A[0][a] * A[0][b] + A[1][a] * A[1][b]) + A[2][a] * A[2][b];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) acc[19 + a] = (A[0][a] * e[0] + A[1][a] * e[1]) + A[2][a] * e[2];
-            }
+        for (int r = 0; r < 3; ++r) {
+            const float R0 = F[4 * r], R1 = F[4 * r + 1], R2 = F[4 * r + 2];
+            A[r][0] = -(R1 * p.z - R2 * p.y);
+            A[r][1] = -(R2 * p.x - R0 * p.z);
+            A[r][2] = -(R0 * p.y - R1 * p.x);
         }
+        acc[0] = 1.0;
+        acc[1] = e[0]; acc[2] = e[1]; acc[3] = e[2];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[4 + 3 * r + c] = A[r][c];
+        int k = 13;
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = a; b < 3; ++b) acc[k++] = (A[0][a] * A[0][b] + A[1][a] * A[1][b]) + A[2][a] * A[2][b];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) acc[19 + a] = (A[0][a] * e[0] + A[1][a] * e[1]) + A[2][a] * e[2];
     }
+    return bi;
+}
+
+// one workgroup's row of the 22 sums: wave_sum per wavefront, (w0 + w1) + (w2 + w3) across the four (every thread of the workgroup calls)
+__device__ __forceinline__ void icpgn_row(const double (&acc)[kGnAcc], double (*red)[kGnAcc], double* __restrict__ row)
+{
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < kGnAcc; ++k) {
@@ -656,16 +673,58 @@ __global__ __launch_bounds__(256) void k_icpgn_assoc(const float4* __restrict__ 
         if (lane == 0) red[wave][k] = v;
     }
     __syncthreads();
-    if (threadIdx.x < kGnAcc)
-        partials[(size_t)blockIdx.x * kGnAcc + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    if (threadIdx.x < kGnAcc) row[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+template <int Q>
+__global__ __launch_bounds__(256) void k_icpgn_assoc(const float4* __restrict__ src, int n, const GridIndex* __restrict__ gp,
+                                                     const IcpState* __restrict__ stp, float cap2, double* __restrict__ partials)
+{
+    __shared__ double red[4][kGnAcc];
+    const int i = (blockIdx.x * 256 + threadIdx.x) / Q;
+    double acc[kGnAcc];
+#pragma unroll
+    for (int k = 0; k < kGnAcc; ++k) acc[k] = 0.0;
+    if (i < n) {
+        const GridIndex g = *gp;
+        icpgn_lane<Q>(src[i], stp->F, g, cap2, (threadIdx.x & (Q - 1)) == 0, -1, acc);
+    }
+    icpgn_row(acc, red, partials + (size_t)blockIdx.x * kGnAcc);
+}
+
+// The batch form (lisreg_icp_gn_match_batch): workgroup p works on block p - blk0 of the item the block table names, and writes that
+// item's row row0 + block.  Every item of a launch has Q lanes per query — those of its OWN size, icp_lanes(n) — and goes through
+// icpgn_lane / icpgn_row like the single kernel above: the same rows, to the bit.  nn: last iteration's neighbour of every source point
+// as the next search's seed (first: none yet, the query's grid column gives one).
+template <int Q>
+__global__ __launch_bounds__(256) void k_icpgn_assoc_b(const IcpGnItem* __restrict__ items, int n_items, const IcpState* __restrict__ states,
+                                                       float cap2, int first, double* __restrict__ partials)
+{
+    __shared__ double red[4][kGnAcc];
+    int blk;
+    int item = icp_locate(items, n_items, &blk);
+    item = __builtin_amdgcn_readfirstlane(item); blk = __builtin_amdgcn_readfirstlane(blk);
+    const IcpGnItem I = items[item];
+    const int i = ((unsigned)blk * 256 + threadIdx.x) / Q;
+    const bool lead = (threadIdx.x & (Q - 1)) == 0;
+    double acc[kGnAcc];
+#pragma unroll
+    for (int k = 0; k < kGnAcc; ++k) acc[k] = 0.0;
+    if (i < I.n) {
+        const GridIndex g = *I.grid;
+        const int bi = icpgn_lane<Q>(I.src[i], states[I.state].F, g, cap2, lead, first ? -2 : I.nn[i], acc);
+        if (lead) I.nn[i] = bi;          // (all Q lanes have read the seed: they did before the search, and the search ends in a butterfly)
+    }
+    icpgn_row(acc, red, partials + (size_t)(I.row0 + blk) * kGnAcc);
 }
 
 // Hessian.determinant() == 0 -> skip; delta = Hessian.inverse() * B (Eigen PartialPivLU in float); t += delta[0:3];
 // R = R * Sophus::SO3f::exp(delta[3:6]).matrix()  (src/sophus/so3.hpp:279-312, small-angle branch as written there)
-__global__ __launch_bounds__(1024) void k_icpgn_solve(const double* __restrict__ partials, int n_blocks, IcpState* __restrict__ st)
+// The ONE copy of the step, for a workgroup of 1024 threads: the n_blocks rows of an alignment are added in an order that depends on
+// n_blocks alone (32 row groups with four running sums each, then the groups in order), thread 0 solves and updates st->F.
+__device__ __forceinline__ void icpgn_solve_step(const double* __restrict__ partials, int n_blocks, IcpState* __restrict__ st,
+                                                 double (*red)[32], double* tot)
 {
-    __shared__ double red[32][32];
-    __shared__ double tot[kGnAcc];
     const int k = threadIdx.x & 31, grp = threadIdx.x >> 5;
     double v0 = 0, v1 = 0, v2 = 0, v3 = 0;
     if (k < kGnAcc) {
@@ -744,6 +803,45 @@ __global__ __launch_bounds__(1024) void k_icpgn_solve(const double* __restrict__
     st->iters += 1;
 }
 
+__global__ __launch_bounds__(1024) void k_icpgn_solve(const double* __restrict__ partials, int n_blocks, IcpState* __restrict__ st)
+{
+    __shared__ double red[32][32];
+    __shared__ double tot[kGnAcc];
+    icpgn_solve_step(partials, n_blocks, st, red, tot);
+}
+
+// one workgroup per item of a batch: its own icp_blocks(n) rows, added in the single call's order
+__global__ __launch_bounds__(1024) void k_icpgn_solve_b(const double* __restrict__ partials, const IcpGnItem* __restrict__ items,
+                                                        IcpState* __restrict__ states)
+{
+    __shared__ double red[32][32];
+    __shared__ double tot[kGnAcc];
+    const IcpGnItem I = items[blockIdx.x];
+    icpgn_solve_step(partials + (size_t)I.row0 * kGnAcc, I.nblk, &states[I.state], red, tot);
+}
+
+// getFitnessScore() of every item: icp_fitness_row over the block table (rows of 2 doubles at row0 + block), seeded with the last
+// iteration's neighbours where one ran (seeded), and one workgroup per item for its total
+template <int Q>
+__global__ __launch_bounds__(256) void k_icpgn_fit_b(const IcpGnItem* __restrict__ items, int n_items, const IcpState* __restrict__ states,
+                                                     int seeded, double* __restrict__ partials)
+{
+    __shared__ double red[4][2];
+    int blk;
+    int item = icp_locate(items, n_items, &blk);
+    item = __builtin_amdgcn_readfirstlane(item); blk = __builtin_amdgcn_readfirstlane(blk);
+    const IcpGnItem I = items[item];
+    icp_fitness_row<Q>(I.src, I.n, I.grid, states[I.state].F, seeded ? I.nn : nullptr, (unsigned)blk, red, partials + (size_t)(I.row0 + blk) * 2);
+}
+
+__global__ __launch_bounds__(256) void k_icpgn_fit_reduce_b(const double* __restrict__ partials, const IcpGnItem* __restrict__ items,
+                                                            IcpState* __restrict__ states)
+{
+    __shared__ double red[256][2];
+    const IcpGnItem I = items[blockIdx.x];
+    icp_fit_total(partials + (size_t)I.row0 * 2, I.nblk, &states[I.state], red);
+}
+
 }  // namespace
 
 // lanes per query: a scan-sized query set (~1e5) fills the chip only when each query is spread over several lanes
@@ -806,6 +904,38 @@ void launch_icp_fitness(const float4* src, int n, const GridIndex* grid_dev, Icp
                              (k_icp_fitness<4><<<nb, 256, 0, stream>>>(src, n, grid_dev, st, partials)),
                              (k_icp_fitness<8><<<nb, 256, 0, stream>>>(src, n, grid_dev, st, partials)));
     k_icp_fit_reduce<<<1, 256, 0, stream>>>(partials, nb, st);
+}
+
+// lisreg_icp_gn_match_batch: one correspondence launch per lane class present (the table is ordered by class, blk0 counts within the
+// class), then one solve workgroup per item
+void launch_icpgn_batch_iteration(const IcpGnItem* items, int n_items, const IcpGnClasses& cls, IcpState* states, float cap2, bool first,
+                                  double* partials, hipStream_t stream)
+{
+    if (n_items <= 0) return;
+    for (int c = 0; c < 3; ++c) {
+        const int m = cls.first[c + 1] - cls.first[c], nb = cls.blocks[c];
+        if (m <= 0 || nb <= 0) continue;
+        const IcpGnItem* t = items + cls.first[c];
+        LISREG_DISPATCH_Q(c == 0 ? 1 : (c == 1 ? 4 : 8), (k_icpgn_assoc_b<1><<<nb, 256, 0, stream>>>(t, m, states, cap2, first ? 1 : 0, partials)),
+                          (k_icpgn_assoc_b<4><<<nb, 256, 0, stream>>>(t, m, states, cap2, first ? 1 : 0, partials)),
+                          (k_icpgn_assoc_b<8><<<nb, 256, 0, stream>>>(t, m, states, cap2, first ? 1 : 0, partials)));
+    }
+    k_icpgn_solve_b<<<n_items, 1024, 0, stream>>>(partials, items, states);
+}
+
+void launch_icpgn_batch_fitness(const IcpGnItem* items, int n_items, const IcpGnClasses& cls, IcpState* states, bool seeded, double* partials,
+                                hipStream_t stream)
+{
+    if (n_items <= 0) return;
+    for (int c = 0; c < 3; ++c) {
+        const int m = cls.first[c + 1] - cls.first[c], nb = cls.blocks[c];
+        if (m <= 0 || nb <= 0) continue;
+        const IcpGnItem* t = items + cls.first[c];
+        LISREG_DISPATCH_Q(c == 0 ? 1 : (c == 1 ? 4 : 8), (k_icpgn_fit_b<1><<<nb, 256, 0, stream>>>(t, m, states, seeded ? 1 : 0, partials)),
+                          (k_icpgn_fit_b<4><<<nb, 256, 0, stream>>>(t, m, states, seeded ? 1 : 0, partials)),
+                          (k_icpgn_fit_b<8><<<nb, 256, 0, stream>>>(t, m, states, seeded ? 1 : 0, partials)));
+    }
+    k_icpgn_fit_reduce_b<<<n_items, 256, 0, stream>>>(partials, items, states);
 }
 
 void launch_dynamic_flags(const float4* pts, int n, const GridIndex* grid_dev, float center_radius, float near_thre,

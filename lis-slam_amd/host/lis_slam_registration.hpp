@@ -923,6 +923,58 @@ private:
     lisreg_icpgn_result res_{};
 };
 
+// ---- the candidate loop of detectLoopClosureForSubMapICP (src/node/subMapOptmizationNode.cpp:2496-2621) as one call -------
+// `static OptimizedICPGN myICP(30, 10)` and, per candidate, SetTargetCloud / Match / GetFitnessScore / HasConverged.  Every candidate
+// submap is a map-index slot with its predict_pose (the caller composes the loop's correctionKey2PreSubMap carry into it); matchAll(source)
+// matches the key-frame cloud against all of them (lisreg_icp_gn_match_batch: the source staged once, every iteration one launch
+// sequence over all candidates) and best() is the candidate the loop's `score > bestScore` test keeps (-1: none), with result(i) /
+// fitness(i) per candidate — what an OptimizedICPGN gives each of them alone, byte for byte.
+template <class PointT>
+class IcpGnVerifier {
+public:
+    explicit IcpGnVerifier(lisreg_ctx* ctx, unsigned max_iterations = 30, float max_correspond_distance = 10.f)
+        : ctx_(ctx), max_iterations_(max_iterations), max_correspond_distance_(max_correspond_distance) {}
+    // the submap of a candidate into its slot (a submap that stays resident between key frames is set once)
+    void setCandidateTarget(int slot, const PointCloud<PointT>& cloud) {
+        check(lisreg_map_index_set(ctx_, slot, cloud.points.data(), (int)cloud.size(), (int)sizeof(PointT), SearchTree<PointT>::fmt()));
+    }
+    void clearCandidates() { slots_.clear(); poses_.clear(); }
+    // predict_pose: row-major 4x4, nullptr = identity; returns the candidate's index
+    int addCandidate(int slot, const float* predict_pose = nullptr) {
+        slots_.push_back(slot);
+        std::vector<float> g;
+        if (predict_pose) g.assign(predict_pose, predict_pose + 16);
+        poses_.push_back(g);
+        return (int)slots_.size() - 1;
+    }
+    size_t size() const { return slots_.size(); }
+    void matchAll(const PointCloud<PointT>& source) {
+        const size_t n = slots_.size();
+        std::vector<lisreg_icpgn_item> items(n);
+        for (size_t i = 0; i < n; ++i) items[i] = lisreg_icpgn_item{ 0, slots_[i], poses_[i].empty() ? nullptr : poses_[i].data() };
+        res_.assign(n, lisreg_icpgn_result{});
+        info_ = lisreg_icpgn_batch_info{ -1, 0, 0, 0 };
+        const void* src = source.points.data();
+        const int ns = (int)source.size();
+        check(lisreg_icp_gn_match_batch(ctx_, &src, &ns, 1, (int)sizeof(PointT), SearchTree<PointT>::fmt(), items.data(), (int)n,
+                                        max_iterations_, max_correspond_distance_, res_.data(), &info_));
+    }
+    int best() const { return info_.best; }
+    bool hasConverged(int) const { return true; }                   // registration.cpp:110-113
+    float fitness(int i) const { return res_.at((size_t)i).fitness; }
+    const lisreg_icpgn_result& result(int i) const { return res_.at((size_t)i); }
+    const lisreg_icpgn_batch_info& info() const { return info_; }
+private:
+    void check(int rc) { if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_)); }
+    lisreg_ctx* ctx_;
+    unsigned max_iterations_;
+    float max_correspond_distance_;
+    std::vector<int> slots_;
+    std::vector<std::vector<float>> poses_;
+    std::vector<lisreg_icpgn_result> res_;
+    lisreg_icpgn_batch_info info_{ -1, 0, 0, 0 };
+};
+
 // ---- SURVEY.md §8 f-3 composite: the sliding local map kept in HBM -------------------------------------------------------
 // localMap_t + SubMapManager::insert_local_map (src/include/subMap.h:979-1059) + SubMapOptmizationNode::extractSlidingCloud
 // (src/node/subMapOptmizationNode.cpp:1369-1432).  Class order of the arrays: dynamic, pole, ground, building, outlier

@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     "lisreg_localmap_default_params", "lisreg_localmap_reset", "lisreg_localmap_insert", "lisreg_localmap_extract",
     "lisreg_localmap_get", "lisreg_predict_pose", "lisreg_guess_state_init", "lisreg_update_initial_guess", "lisreg_submap_insert", "lisreg_submap_extract", "lisreg_submap_crop_boxes",
     "lisreg_default_gather_params", "lisreg_submap_gather_count", "lisreg_submap_gather",
-    "lisreg_icp_default_params", "lisreg_icp_align", "lisreg_icp_align_batch", "lisreg_icp_gn_match",
+    "lisreg_icp_default_params", "lisreg_icp_align", "lisreg_icp_align_batch", "lisreg_icp_gn_match", "lisreg_icp_gn_match_batch",
     "lisreg_loopdet_default_params", "lisreg_loopdet_reset", "lisreg_loopdet_detect", "lisreg_loopdet_candidates",
     "lisreg_loopdet_get", "lisreg_loop_descriptor",
     "lisreg_loopdet_configure", "lisreg_loopdet_matches", "lisreg_loopdet_candidate_scores", "lisreg_loopdet_get_descriptor",
@@ -311,6 +311,25 @@ class IcpGnResult(C.Structure):
     _fields_ = [("final_transform", C.c_float * 16), ("steps_applied", C.c_int), ("n_corr_last", C.c_int),
                 ("fitness", C.c_float), ("reserved", C.c_int)]
 
+    def as_dict(self):
+        return dict(T=np.array(list(self.final_transform), np.float32).reshape(4, 4), steps_applied=self.steps_applied,
+                    n_corr_last=self.n_corr_last, fitness=self.fitness)
+
+
+class IcpGnItemC(C.Structure):
+    _fields_ = [("source", C.c_int), ("slot", C.c_int), ("predict_pose", C.POINTER(C.c_float))]
+
+
+class IcpGnBatchInfo(C.Structure):
+    _fields_ = [("best", C.c_int), ("n_sources_staged", C.c_int), ("n_syncs", C.c_int), ("reserved", C.c_int)]
+
+
+class IcpGnItem:
+    """one candidate of icp_gn_match_batch: the index of its source, its map-index slot and its predict_pose (None: identity)"""
+
+    def __init__(self, source: int, slot: int, predict_pose=None):
+        self.source, self.slot, self.predict_pose = source, slot, predict_pose
+
 
 class Params(C.Structure):
     _fields_ = [("max_iters", C.c_int), ("fixed_iters", C.c_int), ("knn_sq_thresh", C.c_float),
@@ -544,6 +563,8 @@ def lib():
         L.lisreg_update_initial_guess.restype = None
         L.lisreg_icp_default_params.argtypes = [C.c_int, C.POINTER(IcpParams)]
         L.lisreg_icp_gn_match.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_float, fp, C.POINTER(IcpGnResult), vp]
+        L.lisreg_icp_gn_match_batch.argtypes = [vp, C.POINTER(vp), ip, C.c_int, C.c_int, C.c_int, C.POINTER(IcpGnItemC), C.c_int, C.c_uint, C.c_float,
+                                                C.POINTER(IcpGnResult), C.POINTER(IcpGnBatchInfo)]
         L.lisreg_icp_align.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams), fp, C.POINTER(IcpResult), vp]
         L.lisreg_icp_align_batch.argtypes = [vp, C.POINTER(IcpItem), C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams), C.c_int, C.POINTER(IcpResult)]
         u8p = C.POINTER(C.c_uint8)
@@ -1651,6 +1672,32 @@ class Context:
         if want_transformed:
             d["transformed"] = out
         return d
+
+    def icp_gn_match_batch(self, sources, items, max_iterations: int, max_correspond_distance: float):
+        """lisreg_icp_gn_match_batch: sources = a list of clouds (all host PCL-struct arrays of one dtype, or all (device_ptr, n); None
+        for a source no item names), items = a list of IcpGnItem.  Returns (results, info): per item icp_gn_match's dict plus
+        'bytes', the 80 bytes of its lisreg_icpgn_result; info = dict(best, n_sources_staged, n_syncs)."""
+        args = [(None, 0, None, None, None) if s is None else self._cloud_args(s) for s in sources]
+        layouts = {(a[2], a[3]) for a in args if a[2] is not None}
+        if len(layouts) > 1:
+            raise ValueError("icp_gn_match_batch: the sources of one call share one layout")
+        stride, fmt = layouts.pop() if layouts else (16, FMT_DEVICE)
+        ptrs = (C.c_void_p * max(len(args), 1))(*[a[0] for a in args])
+        ns = (C.c_int * max(len(args), 1))(*[a[1] for a in args])
+        its = (IcpGnItemC * max(len(items), 1))()
+        keep = []
+        for k, it in enumerate(items):
+            its[k].source, its[k].slot = it.source, it.slot
+            if it.predict_pose is not None:
+                g = np.ascontiguousarray(it.predict_pose, np.float32).ravel()
+                keep.append(g)
+                its[k].predict_pose = g.ctypes.data_as(C.POINTER(C.c_float))
+        res = (IcpGnResult * max(len(items), 1))()
+        info = IcpGnBatchInfo()
+        self._chk(self._L.lisreg_icp_gn_match_batch(self._h, ptrs, ns, len(args), stride, fmt, its, len(items), max_iterations,
+                                                    max_correspond_distance, res, C.byref(info)))
+        return ([dict(res[k].as_dict(), bytes=bytes(res[k])) for k in range(len(items))],
+                dict(best=info.best, n_sources_staged=info.n_sources_staged, n_syncs=info.n_syncs))
 
     def icp_align_device(self, slot: int, src_ptr: int, n: int, params: "IcpParams", guess=None, out_ptr: int = 0):
         res = IcpResult()
