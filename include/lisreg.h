@@ -506,6 +506,17 @@ int  lisreg_extract_features_deskew(lisreg_ctx* ctx, const void* cloud, int n, i
  * n_sweeps x n_scan <= 32768 per call. */
 int  lisreg_extract_features_batch(lisreg_ctx* ctx, int n_sweeps, const void* const* sweeps, const int* n,
                                    const lisreg_feature_params* params, lisreg_feature_out* outs);
+/* lisreg_extract_features_batch with the IMU de-skew of lisreg_extract_features_deskew (deskewPoint / findRotation,
+ * laserProcessing.cpp:368-399, 427-462, called at :501) applied per sweep: deskews[s] is that sweep's own lisreg_deskew — its own host
+ * tables of any length the single call accepts, its own time_scan_cur and its own time_device (required when enabled;
+ * lisreg_pretreat_batch's time_device output goes in directly).  The five clouds of every sweep are byte for byte what
+ * lisreg_extract_features_deskew gives for that sweep alone; a sweep with enabled == 0, and every sweep when deskews == NULL, gets
+ * lisreg_extract_features_batch's bytes, and a call without an enabled sweep issues exactly that call's launches.  The de-skew adds
+ * one table upload and three launches, whatever n_sweeps is.  Every argument is checked before the first launch (the single call's
+ * rules per sweep): on LISREG_ERR_ARG for an argument no output buffer has been written. */
+int  lisreg_extract_features_deskew_batch(lisreg_ctx* ctx, int n_sweeps, const void* const* sweeps, const int* n,
+                                          const lisreg_feature_params* params, const lisreg_deskew* deskews /* [n_sweeps] or NULL */,
+                                          lisreg_feature_out* outs);
 
 /* ---- laser pretreatment: ring and per-point time of a raw sweep ------------------------------------------------- */
 /* Replaces LaserPretreatment::Pretreatment (src/core/laserPretreatment.cpp:4-81, :84-161; inline in src/node/laserPretreatmentNode.cpp:
@@ -544,6 +555,38 @@ int  lisreg_pretreat(lisreg_ctx* ctx, const void* cloud, int n, int stride_bytes
  * outs[s] is identical to what a single call on sweeps[s] gives and feeds lisreg_extract_features_batch directly. */
 int  lisreg_pretreat_batch(lisreg_ctx* ctx, int n_sweeps, const void* const* sweeps, const int* n,
                            const lisreg_pretreat_params* params, lisreg_pretreat_out* outs);
+
+/* ---- constant-velocity motion compensation of a sweep --------------------------------------------------------------- */
+/* Replaces DistortionAdjust::SetMotionInfo, AdjustCloud and UpdateMatrix (src/core/distortionAdjust.cpp:412-417, 419-469, 471-480), the
+ * middle stage of dataPretreatNode's LaserPretreatment -> DistortionAdjust -> FeatureExtraction: point 0 is dropped (the loop starts at
+ * point_index = 1, :437), and every other point, in input order, becomes R(angular_velocity * real_time) * p + linear_velocity * real_time
+ * with real_time = time - scan_period / 2 (:447) and R the float matrix of AngleAxisf t_V = t_Vz * t_Vy * t_Vx (:474-479); intensity,
+ * ring and time are copied bit for bit.  The float / double steps, and the reading of Eigen they rest on, are listed in
+ * tests/adjust_ref.py and at the top of lis-slam_amd/csrc/lisreg_motion.hip.  Which velocity to pass is the caller's choice (the
+ * reference's deskewInfo takes vel_data_.front() of a deque it never pops, :245). */
+typedef struct lisreg_motion {
+    float  scan_period;           /* SetMotionInfo's first argument; the reference passes 0.1 (distortionAdjust.cpp:246) */
+    double linear_velocity[3];    /* VelocityData, cast to float as SetMotionInfo's << does (:415-416) */
+    double angular_velocity[3];
+} lisreg_motion;
+typedef struct lisreg_adjust_out {
+    void*  cloud;         /* host input: structs of the input's stride; device input: lisreg_dpoint records  */
+    int    capacity;      /* points; n - 1 is always enough                                                   */
+    int    n;             /* written back: max(n - 1, 0)                                                      */
+    float* time_device;   /* device input only: per-point time [capacity], shifted by one like the cloud      */
+} lisreg_adjust_out;
+int  lisreg_default_motion(lisreg_motion* m);                            /* 0.1f, zeros */
+/* One sweep.  fmt: LISREG_FMT_XYZIRT — host PointXYZIRT structs in and out (stride >= 28; a record is copied whole, then its x y z are
+ * replaced), time_device is not read; LISREG_FMT_DEVICE — device records with the ring in the payload plus the device time array
+ * `time_device` [n], device records and times out (what lisreg_pretreat* writes goes in as it is, and what comes out goes into
+ * lisreg_extract_features* as it is).  One launch.  capacity < n - 1: nothing is written, out->n receives the count, LISREG_ERR_ARG.
+ * An output that overlaps the input: LISREG_ERR_ARG (the shift by one makes in-place a race).  n == 0 or 1: LISREG_OK, out->n = 0. */
+int  lisreg_adjust_cloud(lisreg_ctx* ctx, const void* cloud, int n, int stride_bytes, int fmt, const float* time_device,
+                         const lisreg_motion* motion, lisreg_adjust_out* out);
+/* n_sweeps (<= 256) sweeps of device records (LISREG_FMT_DEVICE), each with its own motion, in ONE launch behind one upload of the job
+ * table; every outs[s] is identical to what a single call on sweeps[s] gives.  A refused argument (LISREG_ERR_ARG) writes no buffer. */
+int  lisreg_adjust_cloud_batch(lisreg_ctx* ctx, int n_sweeps, const void* const* sweeps, const int* n,
+                               const float* const* time_device, const lisreg_motion* motions, lisreg_adjust_out* outs);
 
 /* ---- RangeNet++ around the network: range-image projection and point labelling --------------------------------- */
 /* The host code the reference wraps around its segmentation network, without the network (the model is the

@@ -1,5 +1,5 @@
 // lisreg_api_features.hip — host side of the C-ABI entry points of SURVEY.md §8 f-2: range-image projection + feature extraction (one sweep,
-// with IMU de-skew, or a batch of sweeps) and the semantic split.  Kernels: lisreg_features.hip.  Host code only.
+// with IMU de-skew, or a batch of sweeps with a de-skew per sweep) and the semantic split.  Kernels: lisreg_features.hip.  Host code only.
 #include "lisreg_ctx.hpp"
 
 #include <algorithm>
@@ -154,10 +154,14 @@ int lisreg_extract_features_deskew(lisreg_ctx* c, const void* cloud, int n, int 
 // rings), every flat pass of the single-sweep pipeline runs once over the stack with per-sweep end guards, and one gather per
 // output list hands every sweep its slice.  Device records in, device records out; the only host round trip is the (S + 1) x 5
 // list boundaries the caller needs anyway.  Results are identical to S single calls (tests/test_features.py).
-int lisreg_extract_features_batch(lisreg_ctx* c, int n_sweeps, const void* const* sweeps, const int* n, const lisreg_feature_params* P,
-                                  lisreg_feature_out* outs)
+//
+// deskews (NULL: none): the IMU de-skew of the enabled sweeps, between the extraction passes and the gathers — by then every pass has
+// read the raw coordinates (ranges, columns and the selection use the raw points), so the library's concatenated copy is de-skewed in
+// place.  Every sweep's tables and the per-sweep descriptors are packed on the host and cross the link in ONE copy; three launches
+// (launch_deskew_batch) whatever n_sweeps is.  Without an enabled sweep nothing is added to the plain call.
+static int extract_features_batch(lisreg_ctx* c, int n_sweeps, const void* const* sweeps, const int* n, const lisreg_feature_params* P,
+                                  const lisreg_deskew* deskews, lisreg_feature_out* outs)
 {
-    if (!c) return LISREG_ERR_ARG;
     if (n_sweeps < 0 || (n_sweeps > 0 && (!sweeps || !n || !outs)) || !P) return bad(c, "extract_features_batch: bad arguments");
     if (n_sweeps == 0) return LISREG_OK;
     if (P->n_scan < 1 || P->n_scan > 1024 || P->horizon_scan < 16 || P->horizon_scan > 4096 || P->downsample_rate < 1)
@@ -170,6 +174,29 @@ int lisreg_extract_features_batch(lisreg_ctx* c, int n_sweeps, const void* const
         off[(size_t)s + 1] = off[(size_t)s] + n[s];
     }
     const int N = off[(size_t)n_sweeps];
+    // ---- the de-skew arguments, by the single call's rules per sweep; packed: [n_sweeps] descriptors, then every enabled sweep's tables ----
+    std::vector<DeskewSweep> dsk;
+    std::vector<double> dsk_tab;
+    bool any_deskew = false;
+    if (deskews) {
+        dsk.assign((size_t)n_sweeps, DeskewSweep{ nullptr, 0.0, 0, 0, 0, 0 });
+        for (int s = 0; s < n_sweeps; ++s) {
+            const lisreg_deskew& dk = deskews[s];
+            if (!dk.enabled || n[s] == 0) continue;
+            if (dk.imu_pointer_cur < 0 || dk.imu_pointer_cur > (1 << 20) || !dk.imu_time || !dk.imu_rot_x || !dk.imu_rot_y || !dk.imu_rot_z)
+                return bad(c, "extract_features_batch: de-skew needs IMU tables with imu_pointer_cur >= 0");
+            if (!dk.time_device) return bad(c, "extract_features_batch: de-skew of device records needs time_device");
+        }
+        for (int s = 0; s < n_sweeps; ++s) {
+            const lisreg_deskew& dk = deskews[s];
+            if (!dk.enabled || n[s] == 0) continue;
+            const size_t m = (size_t)dk.imu_pointer_cur + 1;
+            if (dsk_tab.size() + 4 * m > 0x7fffffffu) return bad(c, "extract_features_batch: the IMU tables of the call are too long");
+            dsk[(size_t)s] = DeskewSweep{ dk.time_device, dk.time_scan_cur, (int)dsk_tab.size(), dk.imu_pointer_cur, off[(size_t)s], 1 };
+            for (const double* src : { dk.imu_time, dk.imu_rot_x, dk.imu_rot_y, dk.imu_rot_z }) dsk_tab.insert(dsk_tab.end(), src, src + m);
+            any_deskew = true;
+        }
+    }
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const int Hs = P->n_scan, W = P->horizon_scan, H = Hs * n_sweeps, hw = H * W, hw_sweep = Hs * W;
@@ -202,6 +229,21 @@ int lisreg_extract_features_batch(lisreg_ctx* c, int n_sweeps, const void* const
     int* Bdev = c->ft_bounds.as<int>();
     launch_feature_batch_bounds(n_sweeps, Hs, hw_sweep, fb, hw, Bdev, st);
     HIPCHK(c, hipGetLastError());
+    std::vector<unsigned char> dsk_pack;                               // lives until the wait below
+    if (any_deskew) {
+        static_assert(sizeof(DeskewSweep) == 32, "descriptors of 32 bytes: the tables behind them stay 8-byte aligned");
+        const size_t desc_bytes = sizeof(DeskewSweep) * (size_t)n_sweeps, tab_bytes = sizeof(double) * dsk_tab.size();
+        dsk_pack.resize(desc_bytes + tab_bytes);
+        memcpy(dsk_pack.data(), dsk.data(), desc_bytes);
+        memcpy(dsk_pack.data() + desc_bytes, dsk_tab.data(), tab_bytes);
+        HIPCHK(c, c->ft_dsk_tab.ensure(dsk_pack.size()));
+        HIPCHK(c, c->ft_dsk_misc.ensure((sizeof(int) + 9 * sizeof(float)) * (size_t)n_sweeps + 64));
+        HIPCHK(c, hipMemcpyAsync(c->ft_dsk_tab.p, dsk_pack.data(), dsk_pack.size(), hipMemcpyHostToDevice, st));
+        const unsigned char* base = c->ft_dsk_tab.as<unsigned char>();
+        launch_deskew_batch(fb.owner, hw_sweep, n_sweeps, reinterpret_cast<const DeskewSweep*>(base), reinterpret_cast<const double*>(base + desc_bytes),
+                            c->ft_dsk_misc.as<int>(), c->ft_dsk_misc.as<float>() + n_sweeps, cat, st);
+        HIPCHK(c, hipGetLastError());
+    }
     std::vector<int> B(5 * ((size_t)n_sweeps + 1));
     HIPCHK(c, hipMemcpyAsync(B.data(), Bdev, sizeof(int) * B.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -233,6 +275,20 @@ int lisreg_extract_features_batch(lisreg_ctx* c, int n_sweeps, const void* const
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(st));           // `jobs` is a local
     return LISREG_OK;
+}
+
+int lisreg_extract_features_batch(lisreg_ctx* c, int n_sweeps, const void* const* sweeps, const int* n, const lisreg_feature_params* P,
+                                  lisreg_feature_out* outs)
+{
+    if (!c) return LISREG_ERR_ARG;
+    return extract_features_batch(c, n_sweeps, sweeps, n, P, nullptr, outs);
+}
+
+int lisreg_extract_features_deskew_batch(lisreg_ctx* c, int n_sweeps, const void* const* sweeps, const int* n, const lisreg_feature_params* P,
+                                         const lisreg_deskew* deskews, lisreg_feature_out* outs)
+{
+    if (!c) return LISREG_ERR_ARG;
+    return extract_features_batch(c, n_sweeps, sweeps, n, P, deskews, outs);
 }
 
 int lisreg_semantic_split(lisreg_ctx* c, const void* cloud, int n, int stride, int fmt, const uint32_t* using_label,

@@ -331,6 +331,8 @@ struct lisreg_ctx {
     // sweep table of a batch; staging of a host sweep and of its results
     lisreg::DevBuf pt_ends, pt_ring, pt_ori, pt_blk, pt_hdr, pt_tab, pt_in, pt_out, pt_time;
     lisreg::PinnedBuf pt_hdr_host;
+    // motion compensation (lisreg_api_motion.hip): the job table of a batch; staging of a host sweep, of its times and of its result
+    lisreg::DevBuf mo_tab, mo_in, mo_time, mo_out;
     // RangeNet++ projection and labelling (lisreg_rangenet.hip): the pixel keys (all empty between calls: rn_keys_clean), per-workgroup
     // valid-pixel counts, per-sweep counts, the sweep table of a batch, staging of a host sweep, the label image when the caller wants none,
     // the per-pixel range image of the kNN clean-up (written in full by every call that reads it: no state between calls)

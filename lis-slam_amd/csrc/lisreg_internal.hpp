@@ -322,7 +322,32 @@ struct DeskewTables {
 // rotate every pixel-owning point of pts_copy (a private copy of the sweep) into the first owner's frame
 void launch_deskew(const int* owner, int hw, const float* times_dev, DeskewTables T, int* first_dev, float* rsi_dev, float4* pts_copy,
                    hipStream_t st);
+// The de-skew of a batch (lisreg_extract_features_deskew_batch): one descriptor per sweep; `tab` of launch_deskew_batch holds, at
+// tab_off doubles, the sweep's four tables back to back (time, rot x, rot y, rot z: imu_pointer_cur + 1 entries each)
+struct DeskewSweep {
+    const float* times;           // the sweep's per-point time (device), indexed by the point's index WITHIN the sweep
+    double time_scan_cur;
+    int    tab_off, imu_pointer_cur;
+    int    pt_off;                // the sweep's first point in the concatenated cloud
+    int    enabled;
+};
+// Three launches for any number of sweeps: each sweep's first pixel owner (the minimum of `owner` over its hw_sweep pixels of the
+// stack), each sweep's transStartInverse, and the rotation of every pixel owner of every enabled sweep, in place in `cat`.
+// first_dev: [n_sweeps] ints, rsi_dev: [n_sweeps][9] floats.
+void launch_deskew_batch(const int* owner, int hw_sweep, int n_sweeps, const DeskewSweep* sweeps_dev, const double* tab, int* first_dev,
+                         float* rsi_dev, float4* cat, hipStream_t st);
 void launch_gather_points(const float4* pts, const int* idx, int n, float4* out, hipStream_t st);
+// lisreg_motion.hip: one sweep of lisreg_adjust_cloud[_batch] — output point i is input point i + 1 under the sweep's motion
+struct AdjustJob {
+    const float4* src; const float* time;      // [n_out + 1]
+    float4* dst; float* dst_time;              // [n_out]; dst_time may be null
+    int    n_out, blk0;                        // blk0: the sweep's first workgroup (adjust_blocks)
+    float  scan_period, vel[3], rate[3];
+    int    pad;
+};
+int  adjust_blocks(AdjustJob* jobs, int n_jobs);                    // fills blk0; returns the grid size (0: nothing to launch)
+// one launch; tab_dev == null: the one job travels as the kernel argument
+void launch_adjust_cloud(const AdjustJob& one, const AdjustJob* tab_dev, int n_jobs, int blocks, hipStream_t st);
 // §8 f-3 / f-4 building blocks (lisreg_nn1.hip): exact k = 1 queries on a GridIndex that lives in device memory
 void launch_nn1(const float4* q, int n, const GridIndex* grid_dev, float max_dist, int* idx_out, float* d2_out, hipStream_t st);
 void launch_dynamic_flags(const float4* pts, int n, const GridIndex* grid_dev, float center_radius, float near_thre, float dmin,

@@ -250,6 +250,12 @@ public:
         for (int k = 0; k < 5; ++k) clouds[k]->points.resize((size_t)n[k]);
         return f;
     }
+    // the throughput form: n_sweeps sweeps of device records, each with its own de-skew (deskews[s].time_device: the sweep's device
+    // times, e.g. lisreg_pretreat_batch's; deskews == nullptr: none), into the caller's device buffers; the counts come back in outs
+    void processBatch(int n_sweeps, const void* const* sweeps, const int* n, const lisreg_deskew* deskews, lisreg_feature_out* outs) {
+        const int rc = lisreg_extract_features_deskew_batch(ctx_, n_sweeps, sweeps, n, &params, deskews, outs);
+        if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_));
+    }
 private:
     lisreg_ctx* ctx_;
 };
@@ -283,6 +289,42 @@ private:
         startOri = o.start_ori; endOri = o.end_ori; halfIndex = o.half_index;
         return out;
     }
+    lisreg_ctx* ctx_;
+};
+
+// ---- motion compensation: the stage between LaserPretreatment and FeatureExtraction ----------------------------------------------------
+// DistortionAdjust (src/core/distortionAdjust.cpp:412-480): SetMotionInfo keeps the scan period and the velocity, AdjustCloud drops point
+// 0 and moves every other point by the constant-velocity model at its own time.  The deques and their synchronisation (SyncData,
+// TransformCoordinate, NED2ENU) stay with the node; which velocity to pass is the caller's choice (the reference's deskewInfo takes
+// vel_data_.front() of a deque it never pops, :245).
+struct VelocityData { double linear_velocity[3] = { 0, 0, 0 }, angular_velocity[3] = { 0, 0, 0 }; };
+class DistortionAdjust {
+public:
+    lisreg_motion motion;
+    explicit DistortionAdjust(lisreg_ctx* ctx) : ctx_(ctx) { lisreg_default_motion(&motion); }
+    void SetMotionInfo(float scan_period, const VelocityData& velocity_data) {
+        motion.scan_period = scan_period;
+        for (int k = 0; k < 3; ++k) { motion.linear_velocity[k] = velocity_data.linear_velocity[k]; motion.angular_velocity[k] = velocity_data.angular_velocity[k]; }
+    }
+    PointCloud<PointXYZIRT> AdjustCloud(const PointCloud<PointXYZIRT>& cloudIn) {
+        PointCloud<PointXYZIRT> out;
+        const int n = (int)cloudIn.size();
+        out.points.resize((size_t)(n > 1 ? n - 1 : 0));
+        lisreg_adjust_out o{};
+        o.cloud = out.points.data(); o.capacity = (int)out.points.size();
+        const int rc = lisreg_adjust_cloud(ctx_, cloudIn.points.data(), n, (int)sizeof(PointXYZIRT), LISREG_FMT_XYZIRT, nullptr, &motion, &o);
+        if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_));
+        out.points.resize((size_t)o.n);
+        return out;
+    }
+    // n_sweeps sweeps of device records with their device times (lisreg_pretreat_batch's outputs), one motion each, in one launch;
+    // outs[s].cloud / time_device / capacity are the caller's device buffers, outs[s].n comes back
+    void AdjustCloudBatch(int n_sweeps, const void* const* sweeps, const int* n, const float* const* time_device, const lisreg_motion* motions,
+                          lisreg_adjust_out* outs) {
+        const int rc = lisreg_adjust_cloud_batch(ctx_, n_sweeps, sweeps, n, time_device, motions, outs);
+        if (rc != LISREG_OK) throw RegistrationError(rc, lisreg_last_error(ctx_));
+    }
+private:
     lisreg_ctx* ctx_;
 };
 

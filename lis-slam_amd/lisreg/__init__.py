@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "lisreg_loopdet_configure", "lisreg_loopdet_matches", "lisreg_loopdet_candidate_scores", "lisreg_loopdet_get_descriptor",
     "lisreg_loop_descriptor_kind",
     "lisreg_default_pretreat_params", "lisreg_pretreat", "lisreg_pretreat_batch",
+    "lisreg_extract_features_deskew_batch", "lisreg_default_motion", "lisreg_adjust_cloud", "lisreg_adjust_cloud_batch",
     "lisreg_default_rangenet_params", "lisreg_rangenet_project", "lisreg_rangenet_project_batch", "lisreg_rangenet_label",
     "lisreg_rangenet_label_batch",
     "lisreg_default_rangenet_knn_params", "lisreg_rangenet_knn_weights", "lisreg_rangenet_label_knn", "lisreg_rangenet_label_knn_batch",
@@ -410,6 +411,28 @@ class PretreatOut(C.Structure):
         return dict(n=self.n, start_ori=np.float32(self.start_ori), end_ori=np.float32(self.end_ori), half_index=self.half_index)
 
 
+class Motion(C.Structure):
+    """lisreg_motion: DistortionAdjust::SetMotionInfo's arguments"""
+    _fields_ = [("scan_period", C.c_float), ("linear_velocity", C.c_double * 3), ("angular_velocity", C.c_double * 3)]
+
+
+class AdjustOut(C.Structure):
+    _fields_ = [("cloud", C.c_void_p), ("capacity", C.c_int), ("n", C.c_int), ("time_device", C.c_void_p)]
+
+
+def make_motion(linear_velocity=(0.0, 0.0, 0.0), angular_velocity=(0.0, 0.0, 0.0), scan_period: float | None = None) -> Motion:
+    """lisreg_default_motion (scan period 0.1f, zero rates) with the given velocities"""
+    m = Motion()
+    rc = lib().lisreg_default_motion(C.byref(m))
+    if rc:
+        raise LisregError(rc, "lisreg_default_motion")
+    if scan_period is not None:
+        m.scan_period = scan_period
+    m.linear_velocity[:] = [float(v) for v in linear_velocity]
+    m.angular_velocity[:] = [float(v) for v in angular_velocity]
+    return m
+
+
 class RangenetParams(C.Structure):
     _fields_ = [("img_h", C.c_int), ("img_w", C.c_int), ("fov_up", C.c_double), ("fov_down", C.c_double), ("means", C.c_float * 5),
                 ("stds", C.c_float * 5), ("n_classes", C.c_int)]
@@ -510,6 +533,12 @@ def lib():
         L.lisreg_pretreat.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PretreatParams), C.POINTER(PretreatOut)]
         L.lisreg_pretreat_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(PretreatParams),
                                             C.POINTER(PretreatOut)]
+        L.lisreg_extract_features_deskew_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(FeatureParams),
+                                                           C.POINTER(Deskew), C.POINTER(FeatureOut)]
+        L.lisreg_default_motion.argtypes = [C.POINTER(Motion)]
+        L.lisreg_adjust_cloud.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(Motion), C.POINTER(AdjustOut)]
+        L.lisreg_adjust_cloud_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(Motion),
+                                                C.POINTER(AdjustOut)]
         L.lisreg_default_rangenet_params.argtypes = [C.POINTER(RangenetParams)]
         L.lisreg_rangenet_project.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(RangenetParams), C.POINTER(RangenetOut)]
         L.lisreg_rangenet_project_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(RangenetParams),
@@ -1060,6 +1089,63 @@ class Context:
                 setattr(fos[s], k, C.c_void_p(ptr)); setattr(fos[s], "cap_" + k, cap)
         self._chk(self._L.lisreg_extract_features_batch(self._h, S, ptrs, ns, C.byref(params), fos))
         return [{k: getattr(fos[s], "n_" + k) for k in ("deskewed", "corner", "surface", "corner_sharp", "surface_sharp")} for s in range(S)]
+
+    def extract_features_deskew_batch_device(self, in_ptrs, counts, params: "FeatureParams", deskews, out_ptrs: list, cap: int) -> list:
+        """lisreg_extract_features_deskew_batch: as extract_features_batch_device, with one Deskew (make_deskew with time_device_ptr; or
+        None: that sweep is not de-skewed) per sweep, or deskews = None for the plain batch.  Returns the per-sweep count dicts."""
+        S = len(in_ptrs)
+        ptrs = (C.c_void_p * S)(*[C.c_void_p(int(p)) if n else None for p, n in zip(in_ptrs, counts)])
+        ns = (C.c_int * S)(*[int(x) for x in counts])
+        fos = (FeatureOut * S)()
+        for s in range(S):
+            for k, ptr in out_ptrs[s].items():
+                setattr(fos[s], k, C.c_void_p(ptr)); setattr(fos[s], "cap_" + k, cap)
+        dks = None
+        if deskews is not None:
+            assert len(deskews) == S
+            dks = (Deskew * S)()
+            for s, d in enumerate(deskews):
+                if d is not None:
+                    C.memmove(C.byref(dks[s]), C.byref(d), C.sizeof(Deskew))          # the tables stay alive with the caller's Deskew
+        self._chk(self._L.lisreg_extract_features_deskew_batch(self._h, S, ptrs, ns, C.byref(params), dks, fos))
+        return [{k: getattr(fos[s], "n_" + k) for k in ("deskewed", "corner", "surface", "corner_sharp", "surface_sharp")} for s in range(S)]
+
+    # -- constant-velocity motion compensation (DistortionAdjust) -------------------------------------------
+    def adjust_cloud(self, cloud: np.ndarray, motion: "Motion", capacity: int | None = None) -> np.ndarray:
+        """DistortionAdjust::AdjustCloud on a PointXYZIRT struct array: points 1 .. n - 1 under the motion, as structs of the same dtype."""
+        cloud = np.ascontiguousarray(cloud)
+        n = len(cloud)
+        cap = max(n - 1, 0) if capacity is None else capacity
+        out = np.zeros(max(cap, 1), cloud.dtype)
+        ao = AdjustOut()
+        ao.cloud, ao.capacity = out.ctypes.data_as(C.c_void_p), cap
+        self._chk(self._L.lisreg_adjust_cloud(self._h, _vp(cloud) if n else None, n, cloud.dtype.itemsize, FMT_XYZIRT, None, C.byref(motion),
+                                              C.byref(ao)))
+        return out[: ao.n]
+
+    def adjust_cloud_device(self, in_ptr: int, n: int, time_ptr: int, motion: "Motion", out_ptr: int, out_time_ptr: int, cap: int) -> int:
+        """lisreg_adjust_cloud on device records (ring in the payload) and their device times; returns the number of points written."""
+        ao = AdjustOut()
+        ao.cloud, ao.capacity, ao.time_device = C.c_void_p(out_ptr), cap, C.c_void_p(out_time_ptr)
+        self._chk(self._L.lisreg_adjust_cloud(self._h, C.c_void_p(in_ptr) if n else None, n, 16, FMT_DEVICE, C.c_void_p(time_ptr) if n else None,
+                                              C.byref(motion), C.byref(ao)))
+        return ao.n
+
+    def adjust_cloud_batch_device(self, in_ptrs, counts, time_ptrs, motions, out_ptrs, out_time_ptrs, cap) -> list:
+        """lisreg_adjust_cloud_batch: per sweep device records, device times, a Motion and two output buffers of `cap` points (an int, or
+        one per sweep).  Returns the per-sweep counts."""
+        S = len(in_ptrs)
+        caps = [int(cap)] * S if np.isscalar(cap) else [int(x) for x in cap]
+        ptrs = (C.c_void_p * S)(*[C.c_void_p(int(p)) if n else None for p, n in zip(in_ptrs, counts)])
+        tps = (C.c_void_p * S)(*[C.c_void_p(int(p)) if n else None for p, n in zip(time_ptrs, counts)])
+        ns = (C.c_int * S)(*[int(x) for x in counts])
+        ms = (Motion * S)()
+        aos = (AdjustOut * S)()
+        for s in range(S):
+            C.memmove(C.byref(ms[s]), C.byref(motions[s]), C.sizeof(Motion))
+            aos[s].cloud, aos[s].capacity, aos[s].time_device = C.c_void_p(int(out_ptrs[s])), caps[s], C.c_void_p(int(out_time_ptrs[s]))
+        self._chk(self._L.lisreg_adjust_cloud_batch(self._h, S, ptrs, ns, tps, ms, aos))
+        return [aos[s].n for s in range(S)]
 
     # -- laser pretreatment: ring and time of a raw sweep ---------------------------------------------------
     def pretreat(self, raw: np.ndarray, params: "PretreatParams", capacity: int | None = None, info: dict | None = None) -> np.ndarray:
