@@ -445,6 +445,26 @@ int  lisreg_voxel_downsample(lisreg_ctx* ctx, const void* in, int n, int stride_
  * that do not fit the joint sort (a leaf too small for its cloud, > 8 clouds) are done one by one. */
 int  lisreg_voxel_downsample_multi(lisreg_ctx* ctx, int k, const void* const* in, const int* n, const float* leaf, int fmt,
                                    void* const* out, const int* out_capacity, int* n_out);
+/* The same for up to LISREG_VOXEL_BATCH_MAX clouds of device records — the corner and surface clouds of a whole sweep batch
+ * (currentCloudInit, odomEstimationNode.cpp:260-281) or the class clouds of many key frames — in one launch sequence whose length does
+ * not depend on n_clouds, with ONE host synchronisation (the n_out / status table).  fmt: LISREG_FMT_DEVICE (label vote) or
+ * LISREG_FMT_DEVICE_XYZI (.w averaged), one per call.  Per job, out[0 .. n_out), n_out and status are byte for byte those of
+ * lisreg_voxel_downsample(ctx, in, n, 16, fmt, leaf, out, out_capacity, &n_out) on that cloud alone (clouds without NaN coordinates):
+ * LISREG_OK; LISREG_LEAF_TOO_SMALL with a copy of the input (needs out_capacity >= n); LISREG_ERR_ARG with n_out = the count needed
+ * and nothing written when the voxels exceed out_capacity; LISREG_ERR_ARG with n_out = 0 and nothing written for a cloud with an
+ * infinite coordinate.  A job's failure leaves the other jobs alone, and the call returns LISREG_OK when the batch ran.
+ * Refused with LISREG_ERR_ARG before anything is launched (lisreg_last_error names the job): a NULL pointer, n < 0, a leaf that is not
+ * > 0, n_clouds outside 0 .. LISREG_VOXEL_BATCH_MAX, a bad fmt, more than 2e9 points in all, an `out` range (out_capacity records) that
+ * overlaps any job's `in` range or another job's `out` range — the batch form does no in-place grids.  Outputs are complete on return. */
+#define LISREG_VOXEL_BATCH_MAX 1024
+typedef struct lisreg_voxel_job {
+    const void* in;  int n;          /* device lisreg_dpoint records */
+    float       leaf;
+    void*       out; int out_capacity;
+    int         n_out;               /* written back: voxels of this cloud (the count needed, when the capacity is too small) */
+    int         status;              /* written back: LISREG_OK, LISREG_LEAF_TOO_SMALL or LISREG_ERR_ARG */
+} lisreg_voxel_job;
+int  lisreg_voxel_downsample_batch(lisreg_ctx* ctx, int n_clouds, lisreg_voxel_job* jobs, int fmt);
 /* Replaces transformPointCloud(cloud, &pose6D) (src/core/common.cpp:112-173 and the PointXYZIL overload; callers
  * odomEstimationNode.cpp:457-458, 574-575): p' = R(T) p + t with T = {roll,pitch,yaw,x,y,z}; other fields copied.
  * Same formats as above; in == out is allowed. */

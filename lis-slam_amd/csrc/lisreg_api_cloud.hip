@@ -3,6 +3,7 @@
 // NDT and VGICP targets are built on (voxel_sort_cloud, voxel_table_build; declared in lisreg_ctx.hpp).  Kernels: lisreg_index.hip,
 // lisreg_features.hip.  Host code only.
 #include "lisreg_ctx.hpp"
+#include "lisreg_voxel_shared.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -10,38 +11,6 @@
 #include <vector>
 
 using namespace lisreg;
-
-namespace {
-
-// pcl::VoxelGrid's min_b_ and div_b_ (voxel_grid.hpp) of the box `bb` at the inverse leaf size `inv`
-void voxel_bounds(const float bb[6], float inv, int min_b[3], long long div_b[3])
-{
-    for (int k = 0; k < 3; ++k) {
-        min_b[k] = (int)floorf(bb[k] * inv);
-        div_b[k] = (long long)floorf(bb[3 + k] * inv) - min_b[k] + 1;
-    }
-}
-
-// pcl::VoxelGrid's geometry (voxel_grid.hpp) of a cloud with bounding box `bb`: the voxel index of a point and the number of voxels the
-// box spans.  d->span is left to the sort (it follows from how many buckets it may use).  false: "Leaf size is too small for the
-// input dataset" — the index would overflow int32.  Both voxel entry points take their geometry from here: that is what makes the multi
-// form's results those of K single calls.
-bool voxel_geometry(const float bb[6], float leaf, VoxelDesc* d, long long* total)
-{
-    const float inv = 1.0f / leaf;
-    const long long dx = (long long)((bb[3] - bb[0]) * inv) + 1, dy = (long long)((bb[4] - bb[1]) * inv) + 1,
-                    dz = (long long)((bb[5] - bb[2]) * inv) + 1;
-    if (dx * dy * dz > 2147483647LL) return false;
-    int min_b[3];
-    long long div_b[3];
-    voxel_bounds(bb, inv, min_b, div_b);
-    d->inv_leaf = inv; d->min_b0 = min_b[0]; d->min_b1 = min_b[1]; d->min_b2 = min_b[2];
-    d->mul1 = (int)div_b[0]; d->mul2 = (int)(div_b[0] * div_b[1]);
-    *total = div_b[0] * div_b[1] * div_b[2];
-    return true;
-}
-
-}  // namespace
 
 int lisreg::voxel_sort_cloud(lisreg_ctx* c, const char* who, const float4* pts, int n, VoxelDesc d, long long total, int mark, int* n_vox)
 {

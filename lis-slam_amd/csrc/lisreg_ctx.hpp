@@ -333,6 +333,11 @@ struct lisreg_ctx {
     lisreg::PinnedBuf pt_hdr_host;
     // motion compensation (lisreg_api_motion.hip): the job table of a batch; staging of a host sweep, of its times and of its result
     lisreg::DevBuf mo_tab, mo_in, mo_time, mo_out;
+    // lisreg_voxel_downsample_batch (lisreg_voxel_batch.hip): [cloud table | chunk table] uploaded per call followed by the per-cloud
+    // state and the result table the device writes; the chunks' bounding boxes, the list of big voxels and its counter; the pinned host
+    // sides of the upload and of the results.  The sort itself runs in the sort scratch and the vox_* buffers above.
+    lisreg::DevBuf vb_tab, vb_part, vb_big;
+    lisreg::PinnedBuf vb_host;
     // RangeNet++ projection and labelling (lisreg_rangenet.hip): the pixel keys (all empty between calls: rn_keys_clean), per-workgroup
     // valid-pixel counts, per-sweep counts, the sweep table of a batch, staging of a host sweep, the label image when the caller wants none,
     // the per-pixel range image of the kNN clean-up (written in full by every call that reads it: no state between calls)

@@ -11,6 +11,7 @@
 // bucket by (sub-key, original index).  The result is bit-reproducible run to run.  All passes are HBM
 // streaming/gather passes with coalesced 16-byte records; nothing here is GEMM-shaped.
 #include "lisreg_internal.hpp"
+#include "lisreg_voxel_shared.hpp"
 
 namespace lisreg {
 
@@ -1437,10 +1438,8 @@ __global__ __launch_bounds__(256) void k_voxel_starts(int n, const int* __restri
     if (p == n - 1) vstart[slot[p] + head[p]] = n;
 }
 
-constexpr int kVoteBig = 24;            // voxels with more points are summed and voted by one wavefront each (k_voxel_big)
-// CentroidPoint (common/impl/accumulators.hpp): xyz and intensity = sequential float sums / n, label = most frequent
-// (smallest on ties).  One thread per output voxel with a handful of points; the loads of four points are in flight together, the
-// sums stay strictly in input order (that order is part of the result).
+// CentroidPoint (common/impl/accumulators.hpp): one thread per output voxel with a handful of points (voxel_centroid_thread,
+// lisreg_voxel_shared.hpp: the batch form runs the same body).
 // w_mode 0: .w is an intensity (averaged), labels (if any) in `labels`; w_mode 1: .w is a lisreg_dpoint payload whose
 // low 16 bits are the label (majority-voted into the output payload).
 __global__ __launch_bounds__(256) void k_voxel_centroids(int n_vox, const float4* __restrict__ pts,
@@ -1452,64 +1451,12 @@ __global__ __launch_bounds__(256) void k_voxel_centroids(int n_vox, const float4
     if (v >= n_vox) return;
     const int a = vstart[v], b = vstart[v + 1];
     if (b - a > kVoteBig) return;                              // k_voxel_big
-    const bool vote = w_mode == 1 || labels;
-    float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
-    // AccumulatorLabel through up to 8 distinct (label, count) slots held in registers (compile-time indices); a voxel with more
-    // distinct labels than that falls back to the quadratic count below
-    uint32_t sl[8]; int sc[8]; int ns = 0; bool overflow = false;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) { sl[s] = 0xffffffffu; sc[s] = 0; }
-#define LISREG_VOX_ADD(q_, e_) do { \
-        sx += (q_).x; sy += (q_).y; sz += (q_).z; \
-        if (w_mode == 0) sw += (q_).w; \
-        if (vote && !overflow) { \
-            const uint32_t lp_ = (w_mode == 1 ? __float_as_uint((q_).w) : labels[e_]) & 0xffffu; \
-            bool hit_ = false; \
-            _Pragma("unroll") for (int s = 0; s < 8; ++s) if (sl[s] == lp_) { ++sc[s]; hit_ = true; } \
-            if (!hit_) { \
-                if (ns < 8) { _Pragma("unroll") for (int s = 0; s < 8; ++s) if (s == ns) { sl[s] = lp_; sc[s] = 1; } ++ns; } \
-                else overflow = true; \
-            } \
-        } } while (0)
-    int p = a;
-    for (; p + 4 <= b; p += 4) {
-        const int e0 = order[p], e1 = order[p + 1], e2 = order[p + 2], e3 = order[p + 3];
-        const float4 q0 = pts[e0], q1 = pts[e1], q2 = pts[e2], q3 = pts[e3];
-        LISREG_VOX_ADD(q0, e0); LISREG_VOX_ADD(q1, e1); LISREG_VOX_ADD(q2, e2); LISREG_VOX_ADD(q3, e3);
-    }
-    for (; p < b; ++p) { const int e = order[p]; const float4 q = pts[e]; LISREG_VOX_ADD(q, e); }
-#undef LISREG_VOX_ADD
-    const float cnt = (float)(b - a);
-    uint32_t best = 0u;
-    if (vote) {
-        int bestc = 0;
-        if (!overflow) {
-#pragma unroll
-            for (int s = 0; s < 8; ++s)
-                if (sc[s] > bestc || (sc[s] == bestc && sc[s] > 0 && sl[s] < best)) { bestc = sc[s]; best = sl[s]; }
-        } else {
-            for (int p2 = a; p2 < b; ++p2) {
-                const int e = order[p2];
-                const uint32_t lp = (w_mode == 1 ? __float_as_uint(pts[e].w) : labels[e]) & 0xffffu;
-                int c = 0;
-                for (int m = a; m < b; ++m) {
-                    const int em = order[m];
-                    c += (((w_mode == 1 ? __float_as_uint(pts[em].w) : labels[em]) & 0xffffu) == lp) ? 1 : 0;
-                }
-                if (c > bestc || (c == bestc && lp < best)) { bestc = c; best = lp; }
-            }
-        }
-    }
-    out_pts[v] = make_float4(sx / cnt, sy / cnt, sz / cnt, w_mode == 1 ? __uint_as_float(best) : sw / cnt);
+    uint32_t best;
+    out_pts[v] = voxel_centroid_thread(a, b, pts, labels, w_mode, order, &best);
     if (out_labels) out_labels[v] = best;
 }
 
-// The voxels k_voxel_centroids left out (more than kVoteBig points: the cells next to the sensor hold hundreds to thousands, and one
-// lane walking through them — a dependent gather per point — was most of a grid's time).  One wavefront per voxel.  Centroid: the lanes
-// fetch 64 points at a time into LDS and lane 0 adds them up in input order, so the float sums are the serial ones bit for bit.  Label:
-// one pass per DISTINCT label in ascending order; every pass counts the current label and finds the next larger one (lanes stride over
-// the points, wave reductions), so the most frequent label — the smallest among equals, as the serial vote keeps it — falls out
-// without any table.
+// The voxels k_voxel_centroids left out (more than kVoteBig points): one wavefront per voxel (voxel_centroid_wave).
 __global__ __launch_bounds__(64) void k_voxel_big(int n_vox, const float4* __restrict__ pts, const uint32_t* __restrict__ labels, int w_mode,
                                                   const int* __restrict__ order, const int* __restrict__ vstart,
                                                   float4* __restrict__ out_pts, uint32_t* __restrict__ out_labels)
@@ -1519,51 +1466,10 @@ __global__ __launch_bounds__(64) void k_voxel_big(int n_vox, const float4* __res
     if (v >= n_vox) return;
     const int a = vstart[v], b = vstart[v + 1];
     if (b - a <= kVoteBig) return;
-    const int lane = threadIdx.x;
-    const bool vote = w_mode == 1 || labels;
-    float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
-    unsigned cur = 0xffffffffu;
-    for (int p0 = a; p0 < b; p0 += 64) {
-        const int p = p0 + lane;
-        if (p < b) {
-            const int e = order[p];
-            const float4 q = pts[e];
-            s_q[lane] = q;
-            if (vote) cur = min(cur, (w_mode == 1 ? __float_as_uint(q.w) : labels[e]) & 0xffffu);
-        }
-        __builtin_amdgcn_wave_barrier();                       // one wavefront: its LDS operations execute in order
-        if (lane == 0) {
-            const int m = min(64, b - p0);
-            for (int i = 0; i < m; ++i) {
-                const float4 q = s_q[i];
-                sx += q.x; sy += q.y; sz += q.z;
-                if (w_mode == 0) sw += q.w;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    unsigned best = 0u;
-    if (vote) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) cur = min(cur, (unsigned)__shfl_xor((int)cur, d));
-        int bestc = 0;
-        while (cur != 0xffffffffu) {
-            int c = 0; unsigned nxt = 0xffffffffu;
-            for (int p = a + lane; p < b; p += 64) {
-                const int e = order[p];
-                const unsigned lp = (w_mode == 1 ? __float_as_uint(pts[e].w) : labels[e]) & 0xffffu;
-                c += lp == cur ? 1 : 0;
-                if (lp > cur) nxt = min(nxt, lp);
-            }
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) { c += __shfl_xor(c, d); nxt = min(nxt, (unsigned)__shfl_xor((int)nxt, d)); }
-            if (c > bestc) { bestc = c; best = cur; }              // ascending labels: a later equal count does not replace
-            cur = nxt;
-        }
-    }
-    if (lane == 0) {
-        const float cnt = (float)(b - a);
-        out_pts[v] = make_float4(sx / cnt, sy / cnt, sz / cnt, w_mode == 1 ? __uint_as_float(best) : sw / cnt);
+    uint32_t best;
+    const float4 o = voxel_centroid_wave(a, b, (int)threadIdx.x, s_q, pts, labels, w_mode, order, &best);
+    if (threadIdx.x == 0) {
+        out_pts[v] = o;
         if (out_labels) out_labels[v] = best;
     }
 }

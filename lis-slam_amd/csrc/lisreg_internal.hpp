@@ -126,7 +126,8 @@ struct ItemState {
     lisreg_imu imu;
 };
 
-// pcl::VoxelGrid geometry (filters/impl/voxel_grid.hpp): computed on the host from the bounding box
+// pcl::VoxelGrid geometry (filters/impl/voxel_grid.hpp): computed from the bounding box by voxel_geometry (lisreg_voxel_shared.hpp), on the
+// host for the single and the multi call, on the device for the batch call
 struct VoxelDesc {
     float    inv_leaf;             // inverse_leaf_size_ = 1 / leaf (float)
     int      min_b0, min_b1, min_b2;

@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "lisreg_batch_fetch", "lisreg_stage_host_items", "lisreg_upload_cloud", "lisreg_concat_device", "lisreg_batch_result_device", "lisreg_set_option", "lisreg_get_option", "lisreg_get_counters", "lisreg_get_neighbors", "lisreg_test_fit_models", "lisreg_test_solve_steps", "lisreg_test_nn1", "lisreg_test_scan", "lisreg_get_map_grid", "lisreg_get_target_index", "lisreg_get_target_graph", "lisreg_get_target_cell_rows", "lisreg_keyframes_reset", "lisreg_keyframes_push", "lisreg_keyframes_target", "lisreg_get_trace",
     "lisreg_set_profiling", "lisreg_get_timing", "lisreg_pose_to_matrix", "lisreg_transform_update",
     "lisreg_comm_unique_id", "lisreg_comm_init", "lisreg_gather_results", "lisreg_comm_destroy",
-    "lisreg_voxel_downsample", "lisreg_voxel_downsample_multi", "lisreg_transform_cloud",
+    "lisreg_voxel_downsample", "lisreg_voxel_downsample_multi", "lisreg_voxel_downsample_batch", "lisreg_transform_cloud",
     "lisreg_extract_features", "lisreg_extract_features_deskew", "lisreg_extract_features_batch", "lisreg_default_feature_params", "lisreg_semantic_split",
     "lisreg_map_index_set", "lisreg_map_index_set_batch", "lisreg_nearest", "lisreg_dynamic_filter", "lisreg_bbx_filter", "lisreg_cloud_bounds",
     "lisreg_localmap_default_params", "lisreg_localmap_reset", "lisreg_localmap_insert", "lisreg_localmap_extract",
@@ -399,6 +399,15 @@ class FeatureOut(C.Structure):
                 for f, t in ((name, C.c_void_p), ("cap_" + name, C.c_int), ("n_" + name, C.c_int))]
 
 
+VOXEL_BATCH_MAX = 1024
+
+
+class VoxelJob(C.Structure):
+    """lisreg_voxel_job: one cloud of lisreg_voxel_downsample_batch (n_out and status are written back)."""
+    _fields_ = [("in_", C.c_void_p), ("n", C.c_int), ("leaf", C.c_float), ("out", C.c_void_p), ("out_capacity", C.c_int),
+                ("n_out", C.c_int), ("status", C.c_int)]
+
+
 class PretreatParams(C.Structure):
     _fields_ = [("n_scan", C.c_int), ("min_range", C.c_float), ("max_range", C.c_float), ("scan_period", C.c_double)]
 
@@ -522,6 +531,7 @@ def lib():
         L.lisreg_voxel_downsample_multi.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int,
                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.lisreg_voxel_downsample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_int, ip]
+        L.lisreg_voxel_downsample_batch.argtypes = [vp, C.c_int, C.POINTER(VoxelJob), C.c_int]
         L.lisreg_transform_cloud.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, fp, vp]
         L.lisreg_extract_features.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FeatureParams), C.POINTER(FeatureOut)]
         L.lisreg_default_feature_params.argtypes = [C.POINTER(FeatureParams)]
@@ -1041,6 +1051,18 @@ class Context:
         lf = (C.c_float * k)(*[float(x) for x in leafs]); no = (C.c_int * k)()
         self._chk(self._L.lisreg_voxel_downsample_multi(self._h, k, ins, cnt, lf, FMT_DEVICE_XYZI if intensity else FMT_DEVICE, outs, cap, no))
         return [int(x) for x in no]
+
+    def voxel_downsample_batch_device(self, in_ptrs, counts, leafs, out_ptrs, capacities, intensity: bool = False):
+        """Up to VOXEL_BATCH_MAX device clouds through one launch sequence and one host synchronisation
+        (lisreg_voxel_downsample_batch).  Returns (n_out, status): two lists with, per cloud, what voxel_downsample_device gives for
+        it alone — status OK, LEAF_TOO_SMALL (the input was copied) or ERR_ARG (n_out = the count needed when the capacity was too
+        small, 0 for a cloud with an infinite coordinate; nothing written).  Bad arguments raise."""
+        k = len(in_ptrs)
+        jobs = (VoxelJob * max(k, 1))()
+        for s in range(k):
+            jobs[s] = VoxelJob(int(in_ptrs[s]) or None, int(counts[s]), float(leafs[s]), int(out_ptrs[s]) or None, int(capacities[s]), 0, 0)
+        self._chk(self._L.lisreg_voxel_downsample_batch(self._h, k, jobs, FMT_DEVICE_XYZI if intensity else FMT_DEVICE))
+        return [int(jobs[s].n_out) for s in range(k)], [int(jobs[s].status) for s in range(k)]
 
     def transform_cloud(self, cloud: np.ndarray, T):
         cloud = np.ascontiguousarray(cloud)
