@@ -707,6 +707,45 @@ int  lisreg_semantic_split(lisreg_ctx* ctx, const void* cloud, int n, int stride
  * the call does not wait, every later call of this context is ordered behind it.  *n_out = the total (may be NULL). */
 int  lisreg_concat_device(lisreg_ctx* ctx, int k, const void* const* in, const int* n, void* out, int* n_out);
 
+/* lisreg_semantic_split for the labelled device clouds of up to LISREG_SEMANTIC_BATCH_MAX key frames (what lisreg_rangenet_label*_batch
+ * writes) in one launch sequence whose length does not depend on n_frames — three launches — behind ONE upload of the job and tile
+ * tables, with ONE read-back (n[5] + status per frame) and ONE host synchronisation, all on the context's stream.  using_label: one map
+ * per call, [32] indexed by payload & 31, or NULL for label.yaml.  Per job, out.cloud[0..4][0 .. n[k]), out.n[0..4] and status are byte
+ * for byte what lisreg_semantic_split(ctx, in, n, 16, LISREG_FMT_DEVICE, using_label, &out) gives for that frame alone: the stable
+ * five-way partition in input order, records copied whole (all 16 bytes, whatever they hold), nothing written beyond n[k] records; a
+ * NULL cloud[k] is counted and not written.  A frame some non-NULL cloud[k] of which has cap[k] below the class count gets status
+ * LISREG_ERR_ARG, n[] = the five counts needed and nothing written in any of its buffers; every other frame is unaffected, and the
+ * call returns LISREG_OK when the batch ran.  n_frames == 0: LISREG_OK, no launch; a frame with n == 0: five zero counts, LISREG_OK.
+ * Refused with LISREG_ERR_ARG before anything is launched or written (lisreg_last_error names the job), in this order: n_frames outside
+ * 0 .. LISREG_SEMANTIC_BATCH_MAX; jobs == NULL with n_frames > 0; per job n < 0, in == NULL with n > 0, cap[k] < 0 on a non-NULL cloud;
+ * more than 2e9 points in all; an output range (cap[k] records) that meets any job's input range (its own included) or any other output
+ * range, another class of the same job included.  Inputs may meet each other: two jobs may split the same cloud.  Outputs are complete
+ * on return. */
+#define LISREG_SEMANTIC_BATCH_MAX 256
+typedef struct lisreg_semantic_job {
+    const void*         in;  int n;   /* device lisreg_dpoint records, label in the payload */
+    lisreg_semantic_out out;          /* cloud[5]: device buffers, NULL = that class is counted but not written; cap[5]; n[5] written back */
+    int                 status;       /* written back: LISREG_OK or LISREG_ERR_ARG */
+} lisreg_semantic_job;               /* LP64: in@0 n@8 out@16 (80 bytes) status@96, sizeof 104 */
+int  lisreg_semantic_split_batch(lisreg_ctx* ctx, int n_frames, lisreg_semantic_job* jobs,
+                                 const uint32_t* using_label /* [32] or NULL, one map per call */);
+
+/* lisreg_concat_device for up to LISREG_CONCAT_BATCH_MAX jobs — currentCloudInit's surf source (dynamic_down + building_down +
+ * ground_down) of every key frame of a batch — in ONE launch behind one upload of the job table, whatever n_jobs is, on the context's
+ * stream; the call returns when the table has been read (the outputs are complete by then).  Per job, out[0 .. n_out) is byte for byte
+ * what lisreg_concat_device(ctx, k, in, n, out, &n_out) writes, and n_out = the sum of n[0 .. k) (known on the host).  Refused with
+ * LISREG_ERR_ARG before the launch, nothing written (lisreg_last_error names the job), in this order: n_jobs outside
+ * 0 .. LISREG_CONCAT_BATCH_MAX; jobs == NULL with n_jobs > 0; per job k outside 0 .. 8, n < 0, a NULL input with n > 0, out_capacity
+ * below the sum, a NULL out with a sum > 0; an `out` range (out_capacity records) that meets any job's input range or another job's
+ * `out` range. */
+#define LISREG_CONCAT_BATCH_MAX 1024
+typedef struct lisreg_concat_job {
+    const void* in[8]; int n[8]; int k;      /* k <= 8 device clouds, end to end in this order; an empty one may be NULL */
+    void* out; int out_capacity;             /* device records */
+    int   n_out;                             /* written back: the sum */
+} lisreg_concat_job;
+int  lisreg_concat_device_batch(lisreg_ctx* ctx, int n_jobs, lisreg_concat_job* jobs);
+
 /* One host cloud (the reference's PCL structs: LISREG_FMT_XYZI, or LISREG_FMT_XYZIL whose uint16 at byte 20 — label, or the ring of a
  * raw sweep — becomes the payload) into a caller-owned device buffer of n 16-byte lisreg_dpoint records, through a pinned staging buffer
  * packed by the feeder threads; returns when the records are in HBM.  What a node's callback does first with a sensor_msgs cloud

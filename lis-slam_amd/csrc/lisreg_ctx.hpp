@@ -338,6 +338,11 @@ struct lisreg_ctx {
     // sides of the upload and of the results.  The sort itself runs in the sort scratch and the vox_* buffers above.
     lisreg::DevBuf vb_tab, vb_part, vb_big;
     lisreg::PinnedBuf vb_host;
+    // lisreg_semantic_split_batch (lisreg_semantic_batch.hip): [frame table | tile table] uploaded per call followed by the tiles' counts /
+    // bases and the result table the device writes; the pinned host sides of the upload and of the results.  lisreg_concat_device_batch:
+    // its job table.
+    lisreg::DevBuf sb_tab, cb_tab;
+    lisreg::PinnedBuf sb_host;
     // RangeNet++ projection and labelling (lisreg_rangenet.hip): the pixel keys (all empty between calls: rn_keys_clean), per-workgroup
     // valid-pixel counts, per-sweep counts, the sweep table of a batch, staging of a host sweep, the label image when the caller wants none,
     // the per-pixel range image of the kNN clean-up (written in full by every call that reads it: no state between calls)

@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "lisreg_comm_unique_id", "lisreg_comm_init", "lisreg_gather_results", "lisreg_comm_destroy",
     "lisreg_voxel_downsample", "lisreg_voxel_downsample_multi", "lisreg_voxel_downsample_batch", "lisreg_transform_cloud",
     "lisreg_extract_features", "lisreg_extract_features_deskew", "lisreg_extract_features_batch", "lisreg_default_feature_params", "lisreg_semantic_split",
+    "lisreg_semantic_split_batch", "lisreg_concat_device_batch",
     "lisreg_map_index_set", "lisreg_map_index_set_batch", "lisreg_nearest", "lisreg_dynamic_filter", "lisreg_bbx_filter", "lisreg_cloud_bounds",
     "lisreg_localmap_default_params", "lisreg_localmap_reset", "lisreg_localmap_insert", "lisreg_localmap_extract",
     "lisreg_localmap_get", "lisreg_predict_pose", "lisreg_guess_state_init", "lisreg_update_initial_guess", "lisreg_submap_insert", "lisreg_submap_extract", "lisreg_submap_crop_boxes",
@@ -459,6 +460,21 @@ class SemanticOut(C.Structure):
     _fields_ = [("cloud", C.c_void_p * 5), ("cap", C.c_int * 5), ("n", C.c_int * 5)]
 
 
+SEMANTIC_BATCH_MAX = 256
+CONCAT_BATCH_MAX = 1024
+SEMANTIC_BATCH_TILE = 1024         # kSbTile (csrc/lisreg_semantic_batch_plan.hpp): points of one tile of lisreg_semantic_split_batch
+
+
+class SemanticJob(C.Structure):
+    """lisreg_semantic_job: one frame of lisreg_semantic_split_batch (out.n and status are written back)."""
+    _fields_ = [("in_", C.c_void_p), ("n", C.c_int), ("out", SemanticOut), ("status", C.c_int)]
+
+
+class ConcatJob(C.Structure):
+    """lisreg_concat_job: one job of lisreg_concat_device_batch (n_out is written back)."""
+    _fields_ = [("in_", C.c_void_p * 8), ("n", C.c_int * 8), ("k", C.c_int), ("out", C.c_void_p), ("out_capacity", C.c_int), ("n_out", C.c_int)]
+
+
 class LisregError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"lisreg error {code}: {msg}")
@@ -565,6 +581,8 @@ def lib():
                                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(RangenetParams),
                                                       C.POINTER(RangenetKnnParams), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.lisreg_semantic_split.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(SemanticOut)]
+        L.lisreg_semantic_split_batch.argtypes = [vp, C.c_int, C.POINTER(SemanticJob), C.POINTER(C.c_uint32)]
+        L.lisreg_concat_device_batch.argtypes = [vp, C.c_int, C.POINTER(ConcatJob)]
         ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
         L.lisreg_map_index_set.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
         L.lisreg_map_index_set_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int]
@@ -1319,6 +1337,39 @@ class Context:
         m = (C.c_uint32 * 32)(*using_label) if using_label is not None else None
         self._chk(self._L.lisreg_semantic_split(self._h, C.c_void_p(in_ptr), n, 16, FMT_DEVICE, m, C.byref(so)))
         return [int(so.n[k]) for k in range(5)]
+
+    def semantic_split_batch_device(self, in_ptrs, counts, out_ptrs, caps, using_label=None):
+        """lisreg_semantic_split_batch: categoryMapping for up to SEMANTIC_BATCH_MAX labelled device clouds in three launches and one
+        host synchronisation.  out_ptrs[frame][5]: device buffers (dynamic, ground, building, pole, outlier), 0 = that class is counted
+        and not written; caps[frame][5] their capacities in records.  Returns (counts [frame][5], status [frame]): per frame what
+        semantic_split_device gives for it alone, status OK or ERR_ARG (a capacity below its class count: the counts needed, nothing
+        written).  Bad arguments raise."""
+        k = len(in_ptrs)
+        jobs = (SemanticJob * max(k, 1))()
+        for s in range(k):
+            jobs[s].in_ = int(in_ptrs[s]) or None
+            jobs[s].n = int(counts[s])
+            for q in range(5):
+                jobs[s].out.cloud[q] = int(out_ptrs[s][q]) or None
+                jobs[s].out.cap[q] = int(caps[s][q])
+        m = (C.c_uint32 * 32)(*using_label) if using_label is not None else None
+        self._chk(self._L.lisreg_semantic_split_batch(self._h, k, jobs, m))
+        return [[int(jobs[s].out.n[q]) for q in range(5)] for s in range(k)], [int(jobs[s].status) for s in range(k)]
+
+    def concat_device_batch(self, in_ptrs, counts, out_ptrs, capacities) -> list:
+        """lisreg_concat_device_batch: up to CONCAT_BATCH_MAX jobs in one launch.  in_ptrs[job] / counts[job]: up to 8 device clouds
+        (0 for an empty one) that go end to end into out_ptrs[job] (capacities[job] records).  Returns the totals."""
+        k = len(in_ptrs)
+        jobs = (ConcatJob * max(k, 1))()
+        for s in range(k):
+            jobs[s].k = len(in_ptrs[s])                      # more than 8: the library refuses the job by name
+            for q in range(min(len(in_ptrs[s]), 8)):
+                jobs[s].in_[q] = int(in_ptrs[s][q]) or None
+                jobs[s].n[q] = int(counts[s][q])
+            jobs[s].out = int(out_ptrs[s]) or None
+            jobs[s].out_capacity = int(capacities[s])
+        self._chk(self._L.lisreg_concat_device_batch(self._h, k, jobs))
+        return [int(jobs[s].n_out) for s in range(k)]
 
     def align_device(self, corner_ptr: int, n_corner: int, surf_ptr: int, n_surf: int, T_init, params: Params, imu: Imu | None = None):
         """lisreg_align on device-resident source records.  Returns (T, stats dict)."""
