@@ -255,6 +255,16 @@ void lisreg::ctx_prof_mark(lisreg_ctx* c, int kind_of_next_interval, int sidx) {
 void lisreg::ctx_prof_collect(lisreg_ctx* c) { if (!c->ev.empty()) prof_collect(c); }
 
 // =============================================================================================================
+// the context of this process that enqueued the last batch run (lisreg_ctx.hpp: batch_runner_alone)
+static std::atomic<const lisreg_ctx*> g_last_batch_runner{ nullptr };
+namespace lisreg {
+bool batch_runner_alone(const lisreg_ctx* c)
+{
+    const lisreg_ctx* before = g_last_batch_runner.exchange(c);
+    return before == nullptr || before == c;
+}
+}  // namespace lisreg
+
 extern "C" {
 
 int lisreg_device_count(void)
@@ -290,6 +300,7 @@ int lisreg_create(int device, lisreg_ctx** out)
 void lisreg_destroy(lisreg_ctx* c)
 {
     if (!c) return;
+    { const lisreg_ctx* self = c; g_last_batch_runner.compare_exchange_strong(self, nullptr); }
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     // everything the context owns goes with `delete c`, in no particular order; what has to be over BEFORE that is said here:

@@ -295,18 +295,37 @@ int make_reach_marks(lisreg_ctx* c)
 // Phase 12.  The dispatch order of the runs' correspondence launches (blocks ranked by the sector their queries fall into, one eighth per
 // XCD) is a function of the same inputs — block descriptors, sources, initial poses, grid geometry: made here once instead of by every run
 // (k_xcd_keys + a single-workgroup counting sort: 70 us per run on the side stream, which the shorter row build of "row_reach" had turned
-// into the tail of a run's index phase).  Runs that sort their sources or split the batch in halves keep making their own.  Decides
-// live.xcd_cached.
+// into the tail of a run's index phase).  Runs that sort their sources keep making their own; a run that splits the batch makes one table
+// per part and leaves them to the runs after it (dispatch_order_tables).  Decides live.xcd_cached and live.xcd_split_blk.
+// the dispatch-order table of the whole batch (split_blk 0), or one per part of a batch cut at workgroup split_blk: positions and ids
+// relative to the part
+void launch_order_tables(lisreg_ctx* c, int split_blk, const float4* sorted, hipStream_t st)
+{
+    const PreparedBatch& b = c->batch;
+    const bool by_target = many_targets(c->opt, b);
+    int* const pos = c->xcd_tab.as<int>();
+    int* const ids = pos + b.n_blocks;
+    const int nb0 = split_blk ? split_blk : b.n_blocks;
+    launch_xcd_order(c->blocks.as<BlockDesc>(), nb0, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(), c->items.as<ItemState>(),
+                     sorted, by_target, pos, ids, st);
+    if (split_blk)
+        launch_xcd_order(c->blocks.as<BlockDesc>() + split_blk, b.n_blocks - split_blk, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(),
+                         c->items.as<ItemState>(), sorted, by_target, pos + split_blk, ids + split_blk, st);
+}
+
 int cache_xcd_order(lisreg_ctx* c)
 {
     PreparedBatch& b = c->batch;
     b.live.xcd_cached = false;
     if (!xcd_order_wanted(c->opt, b) || b.sort_now || c->opt.exact || b.n_blocks <= 0) return LISREG_OK;
     HIPCHK(c, c->xcd_tab.ensure(sizeof(int) * 2 * (size_t)b.n_blocks));
-    launch_xcd_order(c->blocks.as<BlockDesc>(), b.n_blocks, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(), c->items.as<ItemState>(),
-                     nullptr, many_targets(c->opt, b), c->xcd_tab.as<int>(), c->xcd_tab.as<int>() + b.n_blocks, c->stream);
+    // the cut the batch's runs will take, as far as prepare can know it: a fixed iteration count never stops early from the host, whichever
+    // entry point runs it, and the context is taken to be the only one running batches; any other batch gets the whole-batch table (a run
+    // that cuts elsewhere makes its own, once)
+    const int split_blk = b.prm.fixed_iters > 0 ? plan_run_split(c->opt, b, false, !b.live.one_shot).blk : 0;
+    launch_order_tables(c, split_blk, nullptr, c->stream);
     HIPCHK(c, hipGetLastError());
-    b.live.xcd_cached = true;
+    b.live.xcd_cached = true; b.live.xcd_split_blk = split_blk;
     return LISREG_OK;
 }
 
@@ -350,19 +369,26 @@ constexpr int kGraphHops = 3;              // search_mode 3: neighbour lists sca
 
 // The split decision.  Two halves of the batch on two streams (round 5).  The 6x6 solves are one workgroup per registration and ~13 us of
 // dependent latency between two correspondence launches: the chip idles through ten of them per step.  Registrations are independent, so
-// the batch is cut in two at an item boundary near the middle of the workgroups: the first half iterates on the context's stream, the
+// the batch is cut in two at an item boundary (where: below): the first half iterates on the context's stream, the
 // second on the side stream, and each half's solve (and launch gaps, and the thinning tail of its correspondence launch) runs underneath
 // the other half's correspondence launch.  Same kernels on the same data in the same order per registration: same results to the bit.
 // Only for runs that do not stop early from the host (fixed iteration counts, lisreg_batch_run) and are big enough to fill the chip
 // twice.  Makes the side stream and the halves' events on first use; no split without them.
+// Whether, in which form and where: plan_run_split (lisreg_batch_plan.hpp: "interleave" = 1 cuts at the middle, 2 and the library's own
+// choice under the default 0 where plan_split_uneven says).
+// The library's own choice (the `alone` of split_form) is for a prepared batch run through lisreg_batch_run by the only context of the
+// process that runs batches: that is where it was measured to pay.  A synchronous lisreg_align_batch (prepare, one run, fetch; host clouds
+// staged in front) read 5 % lower with it in four pairs of bench.py's `pcie_inclusive` leg, within that leg's noise but never ahead.
 Split choose_split(lisreg_ctx* c, bool can_stop)
 {
     const auto [o, b] = view(c);
-    if (o.interleave == 0 || o.exact || can_stop || b.lanes_q != 1 || b.n_items < 2 || b.n_blocks < o.interleave_min_blocks) return Split();
+    const bool alone = batch_runner_alone(c);
+    const Split s = plan_run_split(o, b, can_stop, alone && !b.live.one_shot);
+    if (s.blk <= 0) return Split();
     ensure_side_stream(c);
     if (c->side_stream && !c->ev_ab && (c->ev_ab.create(hipEventDisableTiming) != hipSuccess ||
                                         c->ev_ba.create(hipEventDisableTiming) != hipSuccess)) { c->ev_ab.reset(); c->ev_ba.reset(); }
-    return c->side_stream ? plan_split(b.h_items, b.n_items, b.n_blocks) : Split();
+    return c->side_stream ? s : Split();
 }
 
 // The index of every target of the batch, rebuilt from the caller's points in one launch sequence ("rebuild_targets_each_run": the
@@ -410,28 +436,30 @@ int rebuild_targets(lisreg_ctx* c, hipStream_t st)
 void dispatch_order_tables(lisreg_ctx* c, Split split, hipStream_t st)
 {
     const auto [o, b] = view(c);
-    if (!c->last.xcd_now || (b.live.xcd_cached && split.blk == 0)) return;
-    const float4* sorted = b.sort_now ? c->sorted_all.as<float4>() : nullptr;
-    const bool by_target = many_targets(o, b);
-    int* const pos = c->xcd_tab.as<int>();
-    int* const ids = pos + b.n_blocks;
-    const int nb0 = split.blk ? split.blk : b.n_blocks;
-    launch_xcd_order(c->blocks.as<BlockDesc>(), nb0, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(), c->items.as<ItemState>(),
-                     sorted, by_target, pos, ids, st);
-    if (!split.blk) return;
-    launch_xcd_order(c->blocks.as<BlockDesc>() + split.blk, b.n_blocks - split.blk, c->segs.as<Segment>(), c->grids_dev.as<GridIndex>(),
-                     c->items.as<ItemState>(), sorted, by_target, pos + split.blk, ids + split.blk, st);
-    // the half tables have overwritten the batch's table from lisreg_batch_prepare: a later unsplit run of this batch (interleave
-    // switched off, interleave_min_blocks raised) must make its own instead of reading half-relative ids as whole-batch ones
-    c->batch.live.xcd_cached = false;
+    PreparedBatch::Live& live = c->batch.live;
+    if (!c->last.xcd_now || (live.xcd_cached && live.xcd_split_blk == split.blk)) return;
+    // the tables are a function of what lisreg_batch_prepare was given (cache_xcd_order) unless the run sorts its sources: the ones made
+    // here stay good for the later runs of this prepared batch that cut it at the same place (a split run made both of its tables anew
+    // in front of every Gauss-Newton loop: 41 us of a 2.1 ms step on configs[1], profiles/interleave_uneven.md)
+    live.xcd_cached = !b.sort_now && !o.exact;
+    live.xcd_split_blk = split.blk;
+    // (part tables overwrite the batch's table: live.xcd_split_blk says which the buffer holds, and a later run of this batch that is cut
+    // elsewhere or not at all — interleave switched off, interleave_min_blocks raised — makes its own instead of reading part-relative ids
+    // as whole-batch ones)
+    launch_order_tables(c, split.blk, b.sort_now ? c->sorted_all.as<float4>() : nullptr, st);
 }
 
 // the part of the batch one stream iterates on: the items [i0, i0 + ni) = the workgroups [b0, b0 + nb) on stream s (sidx: which stream the
 // profiling marks go on); after_assoc: an event recorded right behind the correspondence launch, for the alternation of an interleaved run
 struct RunHalf { int i0, ni, b0, nb; hipStream_t s; int sidx; hipEvent_t after_assoc; };
 
-// one Gauss-Newton iteration of a half: the correspondence launch and the solve
-void iteration(lisreg_ctx* c, const DevParams& prm, int it, const RunHalf& h)
+// Does the last solve of this run do the finalize as well (launch_solve's finalize_results)?  Runs whose last iteration is known when it
+// is enqueued and in which no registration finishes before it: a fixed iteration count, no early stop from the host.  One launch and one
+// kernel boundary less at the end of a step — per part in an interleaved run, whose parts then need nothing behind their join.
+bool finalize_in_last_solve(const DevParams& prm, bool can_stop) { return prm.fixed_iters > 0 && !can_stop; }
+
+// one Gauss-Newton iteration of a half: the correspondence launch and the solve (last_folded: and this half's finalize inside that solve)
+void iteration(lisreg_ctx* c, const DevParams& prm, int it, const RunHalf& h, bool last_folded)
 {
     const auto [o, b] = view(c);
     if (!h.after_assoc) ctx_prof_mark(c, 0, h.sidx);          // (an alternating run marks behind its wait for the other half)
@@ -447,7 +475,8 @@ void iteration(lisreg_ctx* c, const DevParams& prm, int it, const RunHalf& h)
     if (h.after_assoc) (void)hipEventRecord(h.after_assoc, h.s);
     ctx_prof_mark(c, 1, h.sidx);
     launch_solve(c->items.as<ItemState>() + h.i0, h.ni, prm, c->partials.as<double>(),
-                 o.trace_cap > 0 ? c->trace.as<float>() + (size_t)h.i0 * (size_t)o.trace_cap * kTraceStride : nullptr, o.trace_cap, c->done_dev.as<int>(), h.s);
+                 o.trace_cap > 0 ? c->trace.as<float>() + (size_t)h.i0 * (size_t)o.trace_cap * kTraceStride : nullptr, o.trace_cap, c->done_dev.as<int>(), h.s,
+                 last_folded ? c->results.as<float>() + (size_t)h.i0 * kResultSize : nullptr);
     ctx_prof_mark(c, -1, h.sidx);
 }
 
@@ -464,8 +493,9 @@ int run_plain(lisreg_ctx* c, const DevParams& prm, bool can_stop, hipStream_t st
     int next_check = chunk;
     if (o.early_stop_chunk <= 0 && c->mem.last_launches > 0) next_check = std::max(2, std::min(c->mem.last_launches, chunk));
     const RunHalf all{ 0, b.n_items, 0, b.n_blocks, st, 0, nullptr };
+    const bool fold = finalize_in_last_solve(prm, can_stop);
     for (int it = 0; it < prm.bound; ++it) {
-        iteration(c, prm, it, all);
+        iteration(c, prm, it, all, fold && it + 1 == prm.bound);
         if (o.exact && it + 1 < prm.bound) { int rc = exact_pose_caches(c); if (rc) return rc; }
         if (can_stop && it + 1 == next_check && it + 1 < prm.bound) {
             HIPCHK(c, hipMemcpyAsync(c->done_host.p, c->done_dev.p, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -491,16 +521,17 @@ int run_interleaved(lisreg_ctx* c, const DevParams& prm, Split split, hipStream_
     const bool alternate = o.interleave == 1 && c->ev_ab && c->ev_ba;
     const RunHalf A{ 0, split.item, 0, split.blk, st, 0, alternate ? (hipEvent_t)c->ev_ab : nullptr };
     const RunHalf B{ split.item, b.n_items - split.item, split.blk, b.n_blocks - split.blk, c->side_stream, 1, alternate ? (hipEvent_t)c->ev_ba : nullptr };
+    const bool fold = finalize_in_last_solve(prm, false);           // (a run that can stop early is never split)
     hipError_t ie = hipSuccess;
     for (int it = 0; it < prm.bound && ie == hipSuccess; ++it) {
         if (alternate && it > 0) ie = hipStreamWaitEvent(st, c->ev_ba, 0);                   // B's launch of the iteration before is through
         if (ie != hipSuccess) break;
         if (alternate) ctx_prof_mark(c, 0, 0);
-        iteration(c, prm, it, A);
+        iteration(c, prm, it, A, fold && it + 1 == prm.bound);
         if (alternate) ie = hipStreamWaitEvent(c->side_stream, c->ev_ab, 0);                 // A's launch of this iteration is through
         if (ie != hipSuccess) break;
         if (alternate) ctx_prof_mark(c, 0, 1);
-        iteration(c, prm, it, B);
+        iteration(c, prm, it, B, fold && it + 1 == prm.bound);
     }
     if (ie == hipSuccess) ie = hipEventRecord(c->ev_join, c->side_stream);
     if (ie == hipSuccess) ie = hipStreamWaitEvent(st, c->ev_join, 0);
@@ -510,10 +541,11 @@ int run_interleaved(lisreg_ctx* c, const DevParams& prm, Split split, hipStream_
     return ctx_fail(c, LISREG_ERR_HIP, std::string("interleaved run: ") + hipGetErrorString(ie));
 }
 
-// Finalize: the results, and the registrations reset for the next run; the staged source buffer may be overwritten once this run is through
-int finalize_run(lisreg_ctx* c, const DevParams& prm, hipStream_t st)
+// Finalize: the results, and the registrations reset for the next run (done: by the last solve already, finalize_in_last_solve); the
+// staged source buffer may be overwritten once this run is through
+int finalize_run(lisreg_ctx* c, const DevParams& prm, hipStream_t st, bool done)
 {
-    launch_finalize(c->items.as<ItemState>(), c->batch.n_items, prm, c->results.as<float>(), st, c->done_dev.as<int>());
+    if (!done) launch_finalize(c->items.as<ItemState>(), c->batch.n_items, prm, c->results.as<float>(), st, c->done_dev.as<int>());
     c->batch.live.items_reset = true; ++c->batch.live.runs_since_fetch;
     HIPCHK(c, hipGetLastError());
     if (c->pack_in_use >= 0 && c->pack_free[c->pack_in_use])
@@ -559,44 +591,17 @@ int run_impl(lisreg_ctx* c, bool early_stop)
         rc = run_interleaved(c, prm, split, st);
     else
         rc = run_plain(c, prm, can_stop, st);
-    return rc ? rc : finalize_run(c, prm, st);
+    return rc ? rc : finalize_run(c, prm, st, finalize_in_last_solve(prm, can_stop) && prm.bound > 0);
 }
 
-// lisreg_align_batch's tail, after the sources are on their way to the device: prepare, run with early stop, fetch.  A failure after
-// uploads have been enqueued must not return while the DMA still reads the caller's (possibly pinned) buffers: the stream is drained
-// first.  prof (null: no print): when the call came in and when its uploads were enqueued — where a synchronous call spends its host time.
-using HostClock = std::chrono::steady_clock;
-int prepare_run_fetch(lisreg_ctx* c, int n_items, const lisreg_item* dev_items, const lisreg_params* params, float* T, lisreg_stats* stats,
-                      const HostClock::time_point* prof)
-{
-    int rc = lisreg_batch_prepare(c, n_items, dev_items, params, T);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    const auto t1 = prof ? HostClock::now() : HostClock::time_point();
-    rc = run_impl(c, true);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    const auto t2 = prof ? HostClock::now() : HostClock::time_point();
-    rc = lisreg_batch_fetch(c, T, stats);
-    if (prof) {
-        auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-        fprintf(stderr, "[lisreg host] upload %.1f us, prepare %.1f us, enqueue %.1f us, fetch (incl. GPU wait) %.1f us\n",
-                us(prof[0], prof[1]), us(prof[1], t1), us(t1, t2), us(t2, HostClock::now()));
-    }
-    return rc;
-}
-
-}  // namespace
-
-// =============================================================================================================
-extern "C" {
-
-int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, const lisreg_params* params,
-                         const float* T_init)
+// lisreg_batch_prepare; one_shot: for a synchronous entry point, which enqueues the batch's one run right behind
+int prepare_impl(lisreg_ctx* c, int n_items, const lisreg_item* items, const lisreg_params* params, const float* T_init, bool one_shot)
 {
     if (!c) return LISREG_ERR_ARG;
     if (n_items < 0 || (n_items > 0 && (!items || !T_init)) || !params) return bad(c, "batch_prepare: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     PreparedBatch& b = c->batch;
-    b.live.prepared = false;
+    b.live.prepared = false; b.live.one_shot = one_shot;
     b.params = *params;
     b.prm = make_dev_params(*params);
     b.prm.exact = c->opt.exact ? 1 : 0;
@@ -619,6 +624,39 @@ int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, c
     if ((rc = cache_xcd_order(c))) return rc;                                                   // 12
     b.live.prepared = true;
     return LISREG_OK;
+}
+
+// lisreg_align_batch's tail, after the sources are on their way to the device: prepare, run with early stop, fetch.  A failure after
+// uploads have been enqueued must not return while the DMA still reads the caller's (possibly pinned) buffers: the stream is drained
+// first.  prof (null: no print): when the call came in and when its uploads were enqueued — where a synchronous call spends its host time.
+using HostClock = std::chrono::steady_clock;
+int prepare_run_fetch(lisreg_ctx* c, int n_items, const lisreg_item* dev_items, const lisreg_params* params, float* T, lisreg_stats* stats,
+                      const HostClock::time_point* prof)
+{
+    int rc = prepare_impl(c, n_items, dev_items, params, T, true);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    const auto t1 = prof ? HostClock::now() : HostClock::time_point();
+    rc = run_impl(c, true);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    const auto t2 = prof ? HostClock::now() : HostClock::time_point();
+    rc = lisreg_batch_fetch(c, T, stats);
+    if (prof) {
+        auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+        fprintf(stderr, "[lisreg host] upload %.1f us, prepare %.1f us, enqueue %.1f us, fetch (incl. GPU wait) %.1f us\n",
+                us(prof[0], prof[1]), us(prof[1], t1), us(t1, t2), us(t2, HostClock::now()));
+    }
+    return rc;
+}
+
+}  // namespace
+
+// =============================================================================================================
+extern "C" {
+
+int lisreg_batch_prepare(lisreg_ctx* c, int n_items, const lisreg_item* items, const lisreg_params* params,
+                         const float* T_init)
+{
+    return prepare_impl(c, n_items, items, params, T_init, false);
 }
 
 int lisreg_batch_run(lisreg_ctx* c)

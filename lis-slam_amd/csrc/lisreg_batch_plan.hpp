@@ -243,4 +243,49 @@ inline Split plan_split(const std::vector<ItemState>& items, int n_items, int n_
     return s;
 }
 
+// The cut of a FREE-RUNNING interleaved run ("interleave" = 2, and the runs the library splits by itself): the item boundary nearest to
+// `share_permille` thousandths of the workgroups (the earlier of two equally near ones) among the boundaries that leave neither part
+// under a quarter of the blocks; where no boundary qualifies, what plan_split returns — so this form engages on every batch the even
+// form engages on.  kFreeRunShare is measured, not derived (profiles/interleave_uneven.md): 64 scans against one submap gain 1.8-1.9 % over
+// the unsplit run with the first part at 0.30, 0.33 or 0.40 of the workgroups and 0.85 % with equal halves.  On the timeline the smaller
+// part's solves wait behind the larger part's resident workgroups, both parts keep one iteration period, and the larger part runs only
+// its last launch alone.
+constexpr int kFreeRunShare = 400;
+inline Split plan_split_uneven(const std::vector<ItemState>& items, int n_items, int n_blocks, int share_permille = kFreeRunShare)
+{
+    Split s;
+    long long best = -1;
+    for (int i = 1; i < n_items; ++i) {
+        const int blk = items[(size_t)i].blk_begin;
+        if ((long long)blk * 4 < n_blocks || ((long long)n_blocks - blk) * 4 < n_blocks) continue;
+        const long long d = std::llabs((long long)blk * 1000 - (long long)n_blocks * share_permille);
+        if (best < 0 || d < best) { best = d; s.item = i; s.blk = blk; }
+    }
+    return best < 0 ? plan_split(items, n_items, n_blocks) : s;
+}
+
+// May this run be cut in two parts on two streams, and in which form?  0: no; 1: halves whose launches alternate through events
+// ("interleave" = 1, cut by plan_split); 2: free-running parts (cut by plan_split_uneven).  Never: the exact-arithmetic build, a run that
+// can stop early from the host, eight lanes per query, a single registration, fewer workgroups than "interleave_min_blocks".
+// "interleave" = 0, the default, leaves the choice to the library: the free-running form for the shape it was measured to pay on
+// (profiles/interleave_uneven.md) — a fixed iteration count, at least kAutoSplitBlocks workgroups, at most kAutoSplitItems registrations
+// (64 x 1800 scans against one submap: 40 gain 3.7 %, 64 gain 1.9 %, 128 lose 0.6 % — their solve launches are no empty chip; 256
+// own-target registrations, configs[3], stay unsplit with them) and `alone`: no other context of the process ran a batch since this
+// one's last run (batch_runner_alone) — and every other batch unsplit.  Raising "interleave_min_blocks" past the batch switches it off
+// under every value of "interleave".
+constexpr int kAutoSplitBlocks = 16384, kAutoSplitItems = 64;
+inline int split_form(int n_blocks, int n_items, int lanes_q, int fixed_iters, bool can_stop, bool exact, int interleave, int min_blocks, bool alone)
+{
+    if (exact || can_stop || lanes_q != 1 || n_items < 2 || n_blocks < min_blocks) return 0;
+    if (interleave == 0) return alone && fixed_iters > 0 && n_blocks >= kAutoSplitBlocks && n_items <= kAutoSplitItems ? 2 : 0;
+    return interleave == 1 ? 1 : 2;
+}
+// ... and where: both zero for "not cut" (the form says no, or no item boundary qualifies)
+inline Split plan_run_split(const BatchOptions& o, const PreparedBatch& b, bool can_stop, bool alone)
+{
+    const int form = split_form(b.n_blocks, b.n_items, b.lanes_q, b.prm.fixed_iters, can_stop, o.exact, o.interleave, o.interleave_min_blocks, alone);
+    if (form == 0) return Split();
+    return form == 1 ? plan_split(b.h_items, b.n_items, b.n_blocks) : plan_split_uneven(b.h_items, b.n_items, b.n_blocks);
+}
+
 }  // namespace lisreg

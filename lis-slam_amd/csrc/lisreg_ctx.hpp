@@ -238,13 +238,17 @@ struct BatchOptions {
                                          // (92) draw, 24 (138) win 1.5 %, 32 (184) win 7 % (170 in rounds 4-5: 24 scans lost 4 %, 32 won 2 %)
     int       cell_rows_max_mb = 16384;  // auto: cell rows only while the targets' rows are expected to fit this (about 5 KB per target point)
     int       graph_min_ratio = 60;      // auto: query-iterations per target point from which the graph build pays (measured break-even ~55)
-    int       interleave = 0;            // "interleave": big batches that run a fixed number of iterations are cut in two halves iterating on two
-                                         // streams, each half's solves underneath the other half's correspondence launch (run_impl).  0 off (default),
-                                         // 1 the halves' launches alternate through events, 2 free-running.  Measured on configs[1] (round 5):
+    int       interleave = 0;            // "interleave": big batches that run a fixed number of iterations are cut in two parts iterating on two
+                                         // streams, each part's solves underneath the other part's correspondence launch (run_impl).  0 (default):
+                                         // the library's choice — free-running parts for the batches choose_split names (one lane per query, at
+                                         // least 16384 workgroups, at most 64 registrations, run by lisreg_batch_run, no other context running batches in between), unsplit otherwise; 1 two halves whose launches
+                                         // alternate through events; 2 free-running, cut by plan_split_uneven.  Measured on configs[1] (round 5):
                                          // 24.09 k reg/s off, 21.7 k alternating (a cross-stream hand-off costs more than the solve it hides),
-                                         // 24.5 k free-running (+1.7 %, but two launches then share the chip and their durations stop being a
-                                         // launch's own: 122 us per half against 98) — bit-identical results either way (tests)
-    int       interleave_min_blocks = 8192;   // workgroups from which a run is interleaved (each half should still fill the chip; tests lower it)
+                                         // 24.5 k free-running (two launches then share the chip and their durations stop being a launch's own:
+                                         // 122 us per half against 98); today's figures: profiles/interleave_uneven.md — bit-identical results
+                                         // either way (tests)
+    int       interleave_min_blocks = 8192;   // workgroups from which a run is interleaved (each part should still fill the chip; tests lower it;
+                                              // raised past a batch it keeps that batch unsplit under every value of "interleave")
     int       xcd_order = 2;             // XCD-aware dispatch order of the correspondence launches: 0 off, 1 on (graph front-end), 2 auto (graph front-end, >= 32 registrations, >= 2048 blocks)
     int       cell_anchor_until = 1;     // graph front-end: GN iterations 1 .. this also try an anchor out of the query's own grid column
     bool      canonical_ties = false;    // "canonical_ties" (always on with exact_arithmetic)
@@ -279,9 +283,11 @@ struct PreparedBatch {
         bool  prepared = false;          // prepare sets it; dropped by set_target, the options that change what prepare decides, ensure_crows
                                          // (a grid re-made with the rows' margin) and lisreg_align
         bool  reach_ready = false;       // prepare made the reach words of this batch's targets; cleared by a fetch that saw too many misses
-        bool  xcd_cached = false;        // prepare made the dispatch-order table of this batch (runs reuse it); cleared by an interleaved run,
-                                         // which overwrites the table with one per half, and by option "xcd_order"
+        bool  xcd_cached = false;        // the dispatch-order table of this batch is made (by prepare, or by the last run that needed another one:
+                                         // runs reuse it); cleared by option "xcd_order"
+        int   xcd_split_blk = 0;         // ... for a run cut at this workgroup (one table per part, ids relative to the part); 0: the whole batch's
         bool  items_reset = false;       // the device registrations are in their start-of-run state (prepare, or the run before: launch_finalize); a run clears it while it runs
+        bool  one_shot = false;          // prepared by a synchronous entry point (lisreg_align_batch, lisreg_align) for the one run it enqueues right behind
         int   reach_miss_seen = 0;       // the cumulative miss count the last fetch read (prepare: 0)
         int   runs_since_fetch = 0;      // run counts, prepare and fetch clear
     } live;
@@ -512,6 +518,11 @@ int  voxel_table_read(lisreg_ctx* c, const VoxelTable& T, const DevBuf* flag, in
 // (sidx 1: the mark goes on the side stream — the second half of an interleaved run; an interval runs from a mark to the next on the SAME stream)
 void ctx_prof_mark(lisreg_ctx* c, int kind_of_next_interval, int sidx = 0);      // 0 correspondence kernel, 1 solve, 2 index build, -1 nothing
 void ctx_prof_collect(lisreg_ctx* c);
+// Which context of the process enqueued the last batch run: true if it was `c` itself or nobody (`c` takes the place either way).  A process
+// that runs batches on several contexts in turn is overlapping them itself: the library then leaves its own split of a batch (the default
+// of option "interleave") alone — two batches in flight on two contexts, each cut in two, ran 5 % slower than uncut
+// (profiles/interleave_uneven.md).  lisreg_destroy forgets a context that goes.
+bool batch_runner_alone(const lisreg_ctx* c);
 DevParams make_dev_params(const lisreg_params& p);                  // the literals of lisreg_params as the kernels want them
 // the target indices a batch asks for (lisreg_api_batch.hip); the index itself must already be enqueued on the stream
 int  ensure_graph(lisreg_ctx* c, Target& t, int k, bool launch);

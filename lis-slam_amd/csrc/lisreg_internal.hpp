@@ -239,8 +239,10 @@ void launch_xcd_order(const BlockDesc* blocks, int n_blocks, const Segment* segs
 // exact build: poses to a dense [n][6] array / pose caches (M, sin-cos, Jacobian factors) rebuilt from host-computed trig values [n][6]
 void launch_pose_gather(const ItemState* items, int n_items, float* T_out, hipStream_t st);
 void launch_pose_cache_from_trig(ItemState* items, int n_items, const float* trig, hipStream_t st);
+// finalize_results (the record of items[0], or null): this is the last solve of a run with a fixed iteration count, and it also does
+// launch_finalize's work — results and the reset for the next run — for its registrations
 void launch_solve(ItemState* items, int n_items, DevParams prm, const double* partials, float* trace,
-                  int trace_cap, int* done_counter, hipStream_t st);
+                  int trace_cap, int* done_counter, hipStream_t st, float* finalize_results = nullptr);
 void launch_finalize(ItemState* items, int n_items, DevParams prm, float* results, hipStream_t st, int* reset_done_counter = nullptr);
 
 // §8 f-1 (lisreg_index.hip)

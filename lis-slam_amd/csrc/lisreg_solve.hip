@@ -242,10 +242,16 @@ __global__ __launch_bounds__(64) void k_reset_items(ItemState* __restrict__ item
 
 constexpr int kSolveThreads = 512;
 
+__device__ void finalize_item(ItemState* it, const DevParams& P, float* r, bool reset);
+
+// fin_results (null: no): this launch is the LAST solve of a run with a fixed iteration count — every registration is through after it
+// (or was from the start: the guard) — and each workgroup also does k_finalize's work for its registration: the result record and the
+// reset for the next run.  The done counter is left alone: in such a run no solve before the last one finishes a registration, so the
+// counter still holds the number of guard failures, which is the value a reset gives it.
 __global__ __launch_bounds__(kSolveThreads) void k_solve(ItemState* __restrict__ items, const DevParams P,
                                                          const double* __restrict__ partials,
                                                          float* __restrict__ trace, int trace_cap,
-                                                         int* __restrict__ done_counter)
+                                                         int* __restrict__ done_counter, float* __restrict__ fin_results)
 {
     __shared__ float s_AtA[36], s_AtB[6], s_X[6], s_A[36];
     __shared__ float s_E[6], s_V[36], s_V2[36], s_Vi[36];
@@ -253,9 +259,13 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve(ItemState* __restrict__
     __shared__ double s_part[kSolveThreads / 32][32];
     __shared__ double s_sum[kNumAcc];
     __shared__ double s_L[36];
+    __shared__ int    s_well;
 
     ItemState* it = &items[blockIdx.x];
-    if (it->done) return;
+    if (it->done) {
+        if (fin_results && threadIdx.x == 0) finalize_item(it, P, fin_results + (size_t)blockIdx.x * kResultSize, true);
+        return;
+    }
     // fixed-order fp64 sum of this registration's workgroup partials: 8 row groups x 28 columns in parallel,
     // group g takes rows g, g+8, ... ; groups are then combined in index order (deterministic).
     {
@@ -288,13 +298,13 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve(ItemState* __restrict__
     }
     __syncthreads();
     // the rest is one wavefront: lane-parallel where the arithmetic allows (the matrix fill, the QR solve, the three sine / cosine pairs of
-    // the pose cache), lane 0 for the strictly sequential pieces
-    if (threadIdx.x >= 64) return;
-    const int lane = threadIdx.x;
-    const bool l0 = lane == 0;
+    // the pose cache), lane 0 for the strictly sequential pieces — and, at iteration 0, one lane of the second wavefront beside it
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool l0 = threadIdx.x == 0;
 
     const int iter = it->iter;
     const int n_sel = (int)(s_sum[27] + 0.5);
+    const bool solving = n_sel >= P.min_corr;                    // :870-872 (uniform: n_sel comes out of LDS)
     float* tr = (trace && iter < trace_cap) ? trace + ((size_t)blockIdx.x * trace_cap + iter) * kTraceStride : nullptr;
     if (l0) {
         it->n_corr = n_sel;
@@ -304,8 +314,31 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve(ItemState* __restrict__
             for (int k = 0; k < 6; ++k) tr[49 + k] = it->T[k];
         }
     }
-    bool finished = false;
-    if (n_sel >= P.min_corr) {                                   // :870-872 (uniform: n_sel comes out of LDS)
+    // Iteration 0's conditioning certificate, the shortcut for the common, well-conditioned case: if AtA - shift * I is positive definite
+    // (6x6 Cholesky in double) every eigenvalue exceeds shift = eig_thresh + 2e-5 * trace, far enough above the threshold that cv::eigen's
+    // float Jacobi (absolute error ~ 1e-7 * norm) cannot report one below it: not degenerate, matP = V^-1 V = I.  Anything closer to the
+    // threshold takes the full restatement of cv::eigen below (78 us at this size).  Only its yes / no is used, and it is strictly
+    // sequential: it runs on the second wavefront, on the same float entries the first one puts into s_AtA, while that one fills the
+    // matrix and solves (on lane 0 behind the solve it made the first step of a run 14.5 us instead of 8.4).
+    // (the factor lives in LDS: as a private array under these data-dependent loops it went to scratch memory, and the first
+    //  iteration's step took 26 us instead of 10)
+    if (wave == 1 && lane == 0 && solving && iter == 0) {
+        auto ata = [&](int r_, int c_) { return (double)(float)s_sum[c_ * 6 - (c_ * (c_ - 1)) / 2 + (r_ - c_)]; };      // r_ >= c_
+        double* L = s_L;
+        double trace = 0.0;
+        for (int i = 0; i < 6; ++i) trace += ata(i, i);
+        const double shift = (double)P.eig_thresh + 2e-5 * trace;
+        bool well_conditioned = trace > 0.0;
+        for (int r = 0; r < 6 && well_conditioned; ++r)
+            for (int c = 0; c <= r; ++c) {
+                double v = ata(r, c) - (r == c ? shift : 0.0);
+                for (int k = 0; k < c; ++k) v -= L[r * 6 + k] * L[c * 6 + k];
+                if (r == c) { if (!(v > 0.0)) { well_conditioned = false; break; } L[r * 6 + r] = sqrt(v); }
+                else L[r * 6 + c] = v / L[c * 6 + c];
+            }
+        s_well = well_conditioned ? 1 : 0;
+    }
+    if (wave == 0 && solving) {
         // packed upper triangle -> the symmetric matrix: entry (r, c) of the 36 by lane, the right-hand side by the next six
         if (lane < 36) {
             const int r_ = lane / 6, c_ = lane % 6, lo = min(r_, c_), hi = max(r_, c_);
@@ -314,41 +347,24 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve(ItemState* __restrict__
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        {
-            float a[6], xs[6];
+        float a[6], xs[6];
 #pragma unroll
-            for (int i = 0; i < 6; ++i) a[i] = lane < 6 ? s_AtA[i * 6 + lane] : (lane == 6 ? s_AtB[i] : 0.f);
-            solve6_qr_lanes(a, lane, xs);                        // :921
-            if (l0) {
+        for (int i = 0; i < 6; ++i) a[i] = lane < 6 ? s_AtA[i * 6 + lane] : (lane == 6 ? s_AtB[i] : 0.f);
+        solve6_qr_lanes(a, lane, xs);                            // :921
+        if (l0) {
 #pragma unroll
-                for (int i = 0; i < 6; ++i) s_X[i] = xs[i];
-            }
+            for (int i = 0; i < 6; ++i) s_X[i] = xs[i];
         }
+    }
+    __syncthreads();                                             // (every wavefront: the certificate's verdict is in s_well)
+    if (threadIdx.x >= 64) return;
+    bool finished = false;
+    if (solving) {
         int isDeg = 0;
         float Tn[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
         if (l0) {
             isDeg = it->degenerate;
-            // Shortcut for the common, well-conditioned case: if AtA - shift * I is positive definite (6x6 Cholesky in double,
-            // < 1 us on one lane) every eigenvalue exceeds shift = eig_thresh + 2e-5 * trace, far enough above the threshold that
-            // cv::eigen's float Jacobi (absolute error ~ 1e-7 * norm) cannot report one below it: not degenerate, matP = V^-1 V = I.
-            // Anything closer to the threshold takes the full restatement of cv::eigen below (78 us at this size).
-            // (the factor lives in LDS: as a private array under these data-dependent loops it went to scratch memory, and the first
-            //  iteration's step took 26 us instead of 10)
-            bool well_conditioned = false;
-            if (iter == 0) {
-                double* L = s_L;
-                double trace = 0.0;
-                for (int i = 0; i < 6; ++i) trace += (double)s_AtA[i * 6 + i];
-                const double shift = (double)P.eig_thresh + 2e-5 * trace;
-                well_conditioned = trace > 0.0;
-                for (int r = 0; r < 6 && well_conditioned; ++r)
-                    for (int c = 0; c <= r; ++c) {
-                        double v = (double)s_AtA[r * 6 + c] - (r == c ? shift : 0.0);
-                        for (int k = 0; k < c; ++k) v -= L[r * 6 + k] * L[c * 6 + k];
-                        if (r == c) { if (!(v > 0.0)) { well_conditioned = false; break; } L[r * 6 + r] = sqrt(v); }
-                        else L[r * 6 + c] = v / L[c * 6 + c];
-                    }
-            }
+            const bool well_conditioned = iter == 0 && s_well != 0;      // (the second wavefront's verdict, above)
             if (iter == 0 && well_conditioned) {
                 isDeg = 0;
                 for (int i = 0; i < 36; ++i) it->P[i] = (i % 7 == 0) ? 1.f : 0.f;
@@ -408,7 +424,8 @@ __global__ __launch_bounds__(kSolveThreads) void k_solve(ItemState* __restrict__
     if (l0) {
         it->iter = iter + 1;
         if (!finished && iter + 1 >= P.bound) { it->iters_out = P.bound; finished = true; }
-        if (finished) { it->done = 1; atomicAdd(done_counter, 1); }     // host-side early stop of the launch loop
+        if (finished) { it->done = 1; if (!fin_results) atomicAdd(done_counter, 1); }     // host-side early stop of the launch loop
+        if (fin_results) finalize_item(it, P, fin_results + (size_t)blockIdx.x * kResultSize, true);
     }
 }
 
@@ -455,13 +472,10 @@ __device__ void q_get_rpy(Quat q, double& roll, double& pitch, double& yaw)
 }
 __device__ float clampf(float v, float lim) { v = v < -lim ? -lim : v; return v > lim ? lim : v; }
 
-__global__ __launch_bounds__(64) void k_finalize(ItemState* __restrict__ items, int n_items, const DevParams P,
-                                                 float* __restrict__ results, int* __restrict__ reset_done_counter)
+// one registration's result record (transformUpdate's IMU blend and constraintTransformation on the way), and with `reset` the registration
+// left reset for the next run of the prepared batch
+__device__ void finalize_item(ItemState* it, const DevParams& P, float* r, bool reset)
 {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i == 0 && reset_done_counter) *reset_done_counter = P.n_guard_failed;      // (no solve is in flight any more: nobody else touches the counter)
-    if (i >= n_items) return;
-    ItemState* it = &items[i];
     float T[6];
     for (int k = 0; k < 6; ++k) T[k] = it->T[k];
     int status = LISREG_OK;
@@ -469,10 +483,10 @@ __global__ __launch_bounds__(64) void k_finalize(ItemState* __restrict__ items, 
     else {
         if (P.use_imu && it->imu.imu_available && fabsf(it->imu.imu_pitch_init) < 1.4f) {
             const double w = (double)P.imu_w;
-            double r, p, y;
-            q_get_rpy(q_slerp(q_rpy((double)T[0], 0, 0), q_rpy((double)it->imu.imu_roll_init, 0, 0), w), r, p, y);
-            T[0] = (float)r;
-            q_get_rpy(q_slerp(q_rpy(0, (double)T[1], 0), q_rpy(0, (double)it->imu.imu_pitch_init, 0), w), r, p, y);
+            double r_, p, y;
+            q_get_rpy(q_slerp(q_rpy((double)T[0], 0, 0), q_rpy((double)it->imu.imu_roll_init, 0, 0), w), r_, p, y);
+            T[0] = (float)r_;
+            q_get_rpy(q_slerp(q_rpy(0, (double)T[1], 0), q_rpy(0, (double)it->imu.imu_pitch_init, 0), w), r_, p, y);
             T[1] = (float)p;
         }
         T[0] = clampf(T[0], P.rot_tol);                                   // constraintTransformation, common.cpp:285
@@ -480,13 +494,21 @@ __global__ __launch_bounds__(64) void k_finalize(ItemState* __restrict__ items, 
         T[5] = clampf(T[5], P.z_tol);
         if (!it->any_solved) status = LISREG_TOO_FEW_CORRESPONDENCES;
     }
-    float* r = results + (size_t)i * kResultSize;
     for (int k = 0; k < 6; ++k) r[k] = T[k];
     r[6] = (float)it->iters_out; r[7] = it->deltaR; r[8] = it->deltaT;
     r[9] = (float)it->degenerate; r[10] = (float)it->n_corr; r[11] = (float)status;
     // round 6: the run leaves its registrations reset for the next run of the prepared batch (what the head of every run used to do with a
     // memset and a launch of its own on the critical path of the index phase — or behind an event hop on a side stream)
-    if (reset_done_counter) reset_item(it, P);
+    if (reset) reset_item(it, P);
+}
+
+__global__ __launch_bounds__(64) void k_finalize(ItemState* __restrict__ items, int n_items, const DevParams P,
+                                                 float* __restrict__ results, int* __restrict__ reset_done_counter)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i == 0 && reset_done_counter) *reset_done_counter = P.n_guard_failed;      // (no solve is in flight any more: nobody else touches the counter)
+    if (i >= n_items) return;
+    finalize_item(&items[i], P, results + (size_t)i * kResultSize, reset_done_counter != nullptr);
 }
 
 // exact build: the poses out, and the pose caches rebuilt from trig values the host computed (six per registration)
@@ -520,9 +542,9 @@ void launch_reset_items(ItemState* items, int n_items, DevParams prm, int* done_
 }
 
 void launch_solve(ItemState* items, int n_items, DevParams prm, const double* partials, float* trace,
-                  int trace_cap, int* done_counter, hipStream_t st)
+                  int trace_cap, int* done_counter, hipStream_t st, float* finalize_results)
 {
-    if (n_items > 0) k_solve<<<n_items, kSolveThreads, 0, st>>>(items, prm, partials, trace, trace_cap, done_counter);
+    if (n_items > 0) k_solve<<<n_items, kSolveThreads, 0, st>>>(items, prm, partials, trace, trace_cap, done_counter, finalize_results);
 }
 
 void launch_finalize(ItemState* items, int n_items, DevParams prm, float* results, hipStream_t st, int* reset_done_counter)
