@@ -112,39 +112,11 @@ def test_graph_rows_cover_their_radius(gpu_ctx, m_points, kind):
     in ascending distance from the row's point (to 2^-16 relative), (2) the coordinates stored in the row are the listed points' own, bit for bit (the
     scan never gathers them), (3) EVERY target point closer than rho is listed — the guarantee the 5-NN certificate rests on —
     checked against a float64 kd-tree, (4) padded entries carry the point's own coordinates and id -1."""
-    from scipy.spatial import cKDTree
     from lisreg import synth
+    from row_checks import check_graph_rows
     tc, ts = synth.make_submap(m_points, 77)
     gpu_ctx.set_target(tc, ts)
-    idx = gpu_ctx.target_index(0, kind); g = gpu_ctx.target_graph(0, kind)
-    n, k = idx["n"], g["k"]
-    pts32 = idx["sorted"][:, :3]; pts = pts32.astype(np.float64)
-    assert g["ids"].shape == (n, k) and (g["count"] >= 0).all() and (g["count"] <= k).all()
-    col = np.arange(k)[None, :]
-    listed = col < g["count"][:, None]
-    assert ((g["ids"] >= 0) == listed).all()                                   # a prefix of real entries, then padding
-    own = np.broadcast_to(pts32[:, None, :], g["xyz"].shape)
-    assert np.array_equal(g["xyz"][~listed], own[~listed])                     # (4)
-    safe = np.where(listed, g["ids"], 0)
-    assert np.array_equal(g["xyz"][listed], pts32[safe][listed])               # (2)
-    assert (g["ids"][listed] != np.broadcast_to(np.arange(n)[:, None], (n, k))[listed]).all()
-    d = np.linalg.norm(g["xyz"].astype(np.float64) - pts[:, None, :], axis=2)
-    dd = np.where(listed, d, np.inf)
-    with np.errstate(invalid="ignore"):                                        # inf / inf in the padding
-        ratio = dd[:, 1:] / np.maximum(dd[:, :-1], 1e-12)
-    # (1) ascending up to the key quantisation: since round 5 the graph's rows go through the 32-bit-key sort of the cell rows (the squared
-    # distance's float bits with the low 7 bits replaced by the lane), exact to 2^-16 relative — inside the scan's millimetre of slack
-    assert (ratio[listed[:, 1:]] >= 1 - 2.0 ** -15).all()
-    # (a listed entry is inside rho up to the key quantisation: keys are compared with their low 7 mantissa bits cleared)
-    assert (dd[listed] <= np.sqrt(g["rho2"].astype(np.float64))[:, None].repeat(k, 1)[listed] * (1 + 2.0 ** -15)).all()
-    tree = cKDTree(pts)
-    rng = np.random.default_rng(1)
-    for s in rng.choice(n, min(n, 4000), replace=False):
-        rho = float(np.sqrt(g["rho2"][s]))
-        want = set(tree.query_ball_point(pts[s], rho * (1 - 1e-5))) - {int(s)}
-        have = set(g["ids"][s][:g["count"][s]].tolist())
-        assert len(have) == g["count"][s]                                      # each once
-        assert want <= have, (s, rho, sorted(want - have)[:4])                 # (3)
+    check_graph_rows(gpu_ctx, 0, kind, sample=4000)
 
 
 @pytest.mark.gpu
@@ -156,64 +128,48 @@ def test_cell_rows_cover_their_radius(gpu_ctx, m_points, kind):
     distance to 2^-16 relative (the build sorts quantised keys), (2) the stored coordinates are the listed points' own, bit for bit,
     (3) EVERY target point closer than rho is listed — the guarantee the certificate rests on — against a float64 kd-tree, (4) padded
     entries carry the centre's coordinates and id -1, (5) an octant with a target point inside its box has a row."""
-    from scipy.spatial import cKDTree
     from lisreg import synth
+    from row_checks import check_cell_rows
     tc, ts = synth.make_submap(m_points, 78)
     gpu_ctx.set_target(tc, ts)
-    g = gpu_ctx.target_cell_rows(0, kind); idx = gpu_ctx.target_index(0, kind)      # (building the rows gives the grid its two-cell margin)
-    n, k, R = idx["n"], g["k"], g["n_rows"]
-    nx, ny, nz, cell, org = idx["nx"], idx["ny"], idx["nz"], np.float32(idx["cell"]), idx["origin"].astype(np.float32)
-    pts32 = idx["sorted"][:, :3]; pts = pts32.astype(np.float64)
-    tab = g["table"]
-    assert tab.shape == (nx * ny * nz,) and ((tab >= 0) | (tab == -2)).all()      # (-1 only when the buffers are too small: not here)
-    # occupancy -> which cells may be -2
-    cs = idx["cell_start"]; occ = (np.diff(cs) > 0).reshape(nx, ny, nz)
-    from scipy.ndimage import maximum_filter
-    near = maximum_filter(occ.astype(np.uint8), size=5, mode="constant", cval=0).astype(bool).reshape(-1)
-    assert np.array_equal(tab >= 0, near)
-    have = np.flatnonzero(tab >= 0)
-    base = tab[have] >> 8; mask = tab[have] & 255
-    cnt = 1 + np.array([bin(int(m)).count("1") for m in mask])
-    order = np.argsort(base)
-    assert base[order][0] == 0 and np.array_equal(base[order][1:], np.cumsum(cnt[order])[:-1]) and base[order][-1] + cnt[order][-1] == R
-    # (5): cells that hold a point have the octant that point is in
-    pc = np.floor((pts32 - org) / cell).astype(np.int64)
-    pc = np.minimum(np.maximum(pc, 0), np.array([nx - 1, ny - 1, nz - 1]))
-    frac = (pts32 - org) / cell - pc
-    inner = ((frac > 0.01) & (frac < 0.49)) | ((frac > 0.51) & (frac < 0.99))   # clear of the octant faces (float rounding)
-    ok = inner.all(1)
-    octv = (frac[:, 0] >= 0.5).astype(int) + 2 * (frac[:, 1] >= 0.5) + 4 * (frac[:, 2] >= 0.5)
-    cid = (pc[:, 0] * ny + pc[:, 1]) * nz + pc[:, 2]
-    assert ((tab[cid[ok]] >> octv[ok]) & 1).all()
-    # rows -> centres
-    centre = np.zeros((R, 3), np.float32)
-    for c_, b_, m_ in zip(have, base, mask):
-        iz = c_ % nz; iy = (c_ // nz) % ny; ix = c_ // (nz * ny)
-        h = np.array([ix, iy, iz], np.float32)
-        centre[b_] = (org.astype(np.float64) + (h.astype(np.float64) + 0.5) * np.float64(cell)).astype(np.float32)
-        slot = 1
-        for o in range(8):
-            if (m_ >> o) & 1:
-                f = np.array([0.75 if o & 1 else 0.25, 0.75 if o & 2 else 0.25, 0.75 if o & 4 else 0.25], np.float32)
-                centre[b_ + slot] = (org.astype(np.float64) + (h.astype(np.float64) + f.astype(np.float64)) * np.float64(cell)).astype(np.float32)
-                slot += 1
-    col = np.arange(k)[None, :]
-    listed = col < g["count"][:, None]
-    assert (g["count"] >= 0).all() and (g["count"] <= k).all() and ((g["ids"] >= 0) == listed).all()
-    # (4) (the device forms a centre with one fused multiply-add; float64 here, rounded once: the same value up to double rounding)
-    assert np.abs(g["xyz"][~listed] - np.broadcast_to(centre[:, None, :], g["xyz"].shape)[~listed]).max(initial=0) <= 4e-6
-    safe = np.where(listed, g["ids"], 0)
-    assert np.array_equal(g["xyz"][listed], pts32[safe][listed])               # (2)
-    d = np.linalg.norm(g["xyz"].astype(np.float64) - centre.astype(np.float64)[:, None, :], axis=2)
-    dd = np.where(listed, d, np.inf)
-    with np.errstate(invalid="ignore"):
-        ratio = dd[:, 1:] / np.maximum(dd[:, :-1], 1e-12)
-    assert (ratio[listed[:, 1:]] >= 1 - 2.0 ** -15).all()                      # (1) ascending up to the key quantisation
-    tree = cKDTree(pts)
-    rng = np.random.default_rng(2)
-    for r in rng.choice(R, min(R, 4000), replace=False):
-        rho = float(np.sqrt(g["rho2"][r]))
-        want = set(tree.query_ball_point(centre[r].astype(np.float64), rho * (1 - 1e-5)))
-        got = g["ids"][r][:g["count"][r]].tolist()
-        assert len(set(got)) == len(got)                                       # each once
-        assert want <= set(got), (r, rho, sorted(want - set(got))[:4])         # (3)
+    check_cell_rows(gpu_ctx, 0, kind, sample=4000)
+
+
+PLANTED = ("lattice", "shell", "clusters", "grown")
+
+
+def _set_planted(gpu_ctx, name):
+    import knn5_ref as R
+    from lisreg import synth
+    c = R.case(name)
+    gpu_ctx.set_target(synth.to_pcl(R.to_f32(c["tgt"][0])), synth.to_pcl(R.to_f32(c["tgt"][1])))
+    return c
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", [0, 1])
+@pytest.mark.parametrize("name", PLANTED)
+def test_graph_rows_cover_their_radius_on_planted_clouds(gpu_ctx, name, kind):
+    """The same checks on the lattice clouds of tests/knn5_ref.py — whole rows of candidates at ONE distance, where the key quantisation
+    of the row sort meets rho — on EVERY row, the rho guarantee by brute force in integers (tests/row_checks.py).  `shell`: the row of a
+    point with more than k equidistant neighbours has rho no larger than their distance."""
+    from row_checks import check_graph_rows
+    _set_planted(gpu_ctx, name)
+    crowded = check_graph_rows(gpu_ctx, 0, kind, exact=True, shell=name == "shell")
+    assert name != "shell" or kind == 0 or crowded >= 1          # (surf: the centre point of the 72-shell; corner shells are halves)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", [0, 1])
+@pytest.mark.parametrize("name", PLANTED)
+def test_cell_rows_cover_their_radius_on_planted_clouds(gpu_ctx, name, kind):
+    """The cell rows of the planted clouds, every row; the grid is the one knn5_ref.grid_geometry restates (two-cell margin, grown cell).
+    `shell`: a row about a cell or octant centre with 72 points at one distance has rho no larger than that distance."""
+    import knn5_ref as R
+    from row_checks import check_cell_rows
+    c = _set_planted(gpu_ctx, name)
+    crowded = check_cell_rows(gpu_ctx, 0, kind, exact=True, shell=name == "shell")
+    idx, want = gpu_ctx.target_index(0, kind), R.grid_geometry(R.to_f32(c["tgt"][kind]))
+    assert (idx["nx"], idx["ny"], idx["nz"]) == want["dims"] and np.float32(idx["cell"]) == want["cell"], (idx["cell"], want)
+    assert np.array_equal(idx["origin"].astype(np.float32), want["o"])
+    assert name != "shell" or kind == 0 or crowded >= 2          # (surf: the cell-centre row and the octant-centre row of the 72-shells)
