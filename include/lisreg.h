@@ -1340,6 +1340,46 @@ int  lisreg_fgicp_default_params(int kind, lisreg_fgicp_params* p);
  * density; > 0 forces it: results do not depend on it. */
 int  lisreg_fgicp_set_target(lisreg_ctx* ctx, int slot, const void* cloud, int n, int stride_bytes, int fmt,
                              const lisreg_fgicp_params* params, lisreg_fgicp_info* info, float cell_edge);
+/* §7t: the targets of a whole candidate list as one call (detectLoopClosureForSubMap sets a different target submap for every
+ * candidate, src/node/subMapOptmizationNode.cpp:2793).  The slot of every job that comes back with status == LISREG_OK is, in every
+ * byte a later call can observe (the grid's geometry and dims, the bounding box, the points by cell, the cells' starts, the indices in
+ * the caller's cloud, the m x 6 covariances), what lisreg_fgicp_set_target(ctx, slot, cloud, n, 16, LISREG_FMT_DEVICE, params, &info,
+ * cell_edge) leaves for that cloud alone.  The clouds are device records, read where they lie.  The number of launches and of host
+ * synchronisations (two: one read-back of every target's finite count and bounding box, one at the end) does not depend on
+ * n_targets; the call runs on the context's stream and has returned when the slots are complete.
+ * A target with fewer finite points than k_correspondences, with an infinite coordinate or with an empty finite box fails alone:
+ * status = LISREG_ERR_ARG, its slot holds no target afterwards (whatever it held before), every other target is unaffected, the call
+ * returns LISREG_OK and lisreg_last_error names the first such job with the single call's text.
+ * Refused for the whole call (LISREG_ERR_ARG) before anything is launched, with no slot and no job field touched: NULL jobs with
+ * n_targets > 0, params lisreg_fgicp_set_target refuses, a slot outside 0 .. 65535, a slot named twice, n <= 0, a NULL cloud or a
+ * cell_edge that is negative or not finite in any job, n_targets outside 0 .. LISREG_FGICP_TARGET_BATCH_MAX, more than
+ * LISREG_FGICP_TARGET_BATCH_MAX_POINTS records in all.  n_targets == 0 is LISREG_OK. */
+#define LISREG_FGICP_TARGET_BATCH_MAX 1024
+#define LISREG_FGICP_TARGET_BATCH_MAX_POINTS 134217728          /* 2^27 */
+typedef struct lisreg_fgicp_target_job {
+    int         slot;        /* FastGICP slot 0 .. 65535 */
+    int         n;           /* records in cloud */
+    const void* cloud;       /* DEVICE lisreg_dpoint records (LISREG_FMT_DEVICE) */
+    float       cell_edge;   /* as the single call's: 0 = from the density, > 0 forced */
+    int         status;      /* out: LISREG_OK, or LISREG_ERR_ARG for this target alone */
+    lisreg_fgicp_info info;  /* out: what the single call writes to *info */
+} lisreg_fgicp_target_job;
+int  lisreg_fgicp_set_target_batch(lisreg_ctx* ctx, int n_targets, lisreg_fgicp_target_job* jobs,
+                                   const lisreg_fgicp_params* params);
+/* test hooks.  _get_target reads a slot back, whoever set it: info; geom = the grid's origin x y z, cell edge, its inverse, the
+ * bounding box [6]; sorted_xyzw [n_points][4] = the finite points by grid cell, ascending index inside a cell, the fourth word the
+ * point's index among the finite points as int bits; cell_start [cells + 1]; orig [n_points] = index among the finite points -> index
+ * in the caller's cloud; cov6 [n_points][6] by index among the finite points.  Any output pointer may be NULL.  A slot without a target,
+ * capacity_points < n_points with a per-point output wanted or capacity_cells < cells + 1 with cell_start wanted: LISREG_ERR_ARG (info
+ * and geom are filled all the same when the slot holds a target).  _grid_geometry: the search grid lisreg_fgicp_set_target[_batch]
+ * chooses for n_points finite points in the finite box bb (min x y z, max x y z) under cell_edge — dims [3], cell = {edge, 1 / edge};
+ * host arithmetic only, no device. */
+int  lisreg_fgicp_get_target(lisreg_ctx* ctx, int slot, lisreg_fgicp_info* info, float geom[11], float* sorted_xyzw, int* cell_start,
+                             int* orig, double* cov6, int capacity_points, int capacity_cells);
+int  lisreg_fgicp_grid_geometry(const float bb[6], int n_points, float cell_edge, int dims[3], float cell[2]);
+/* what the last lisreg_fgicp_set_target_batch of this context enqueued (its kernel launches and table copies, and one for every sort
+ * sequence) and how often it waited for the stream */
+int  lisreg_fgicp_target_batch_counts(const lisreg_ctx* ctx, int* enqueues, int* synchronisations);
 /* guess = row-major 4x4 or NULL for identity; aligned_out: NULL, or room for n points of the input layout (the source under
  * final_transform rounded to float).  Host PCL structs or LISREG_FMT_DEVICE records.  The slot must hold a target (LISREG_ERR_ARG
  * otherwise).  The source's distributions are made by every call; a source with fewer finite points than k_correspondences is

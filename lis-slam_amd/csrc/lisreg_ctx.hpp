@@ -411,6 +411,13 @@ struct lisreg_ctx {
     // correspondence rows of the test hook by the caller's index
     std::map<int, lisreg::FgicpTarget> fgicp;
     lisreg::DevBuf fg_pair, fg_M, fg_d2, fg_rows_i, fg_rows_d;
+    // lisreg_fgicp_set_target_batch (lisreg_fgicp_target_batch.hip): [job table | tile table] and, behind the read-back, [descriptors |
+    // sort segments | blocks] uploaded per call, with the per-target results the device writes; the tiles' finite counts, bases and
+    // boxes; the pinned host side of all of it.  The finite points of all targets are compacted into vg_pts; the sort runs in the sort
+    // scratch.  ft_enqueues / ft_syncs: what the last call enqueued and how often it waited (lisreg_fgicp_target_batch_counts)
+    lisreg::DevBuf ft_tab, ft_part;
+    lisreg::PinnedBuf ft_host;
+    int          ft_enqueues = 0, ft_syncs = 0;
     // lisreg_fgicp_align_batch (lisreg_fgicp_batch.hip), lisreg_vgicp_align_batch (lisreg_vgicp_batch.hip), lisreg_ndt_align_batch
     // (lisreg_ndt_batch.hip) and lisreg_gicp_align_batch (lisreg_gicp_batch.hip): a set of buffers each (a call of one family leaves the
     // others' alone; NDT's has no covariances), and the pairs and M FastGICP's items keep from a search to the sums after it
@@ -498,6 +505,12 @@ int  vg_distributions(lisreg_ctx* c, const char* who, const float4* raw, int n, 
 // min_points is refused.  mark >= 0: that profiling interval is opened in front of the gather.  *g: the grid, on the context's scratch.
 int  vg_search_grid(lisreg_ctx* c, const char* who, const float4* raw, int n, const float bb[6], float edge, int min_points, int mark,
                     int* m_out, GridIndex* g);
+// The geometry of the search grid over the finite bounding box bb of m > 0 finite points under `edge` (as vg_distributions'): what
+// vg_search_grid chooses, as a function of its own for lisreg_fgicp_set_target_batch.  Host arithmetic only.  A grid has at most
+// kVgGridMaxCells cells.
+constexpr long long kVgGridMaxCells = 1LL << 22;
+struct VgGrid { float ox, oy, oz, cell, inv_cell; int nx, ny, nz; };
+void vg_grid_geometry(const float bb[6], int m, float edge, VgGrid* g);
 // out[29] = the n_part partial records of 29 doubles added in a fixed order (one wavefront: sum_records of lisreg_fp64_sums.hpp)
 void launch_eval_total(const double* part, int n_part, double* out, hipStream_t st);
 // ---- lisreg_api_cloud.hip: the voxel sort of one cloud and the voxel table of a target ---------------------------------------------------

@@ -55,7 +55,8 @@ ABI_SYMBOLS = [
     "lisreg_vgicp_default_params", "lisreg_vgicp_set_target", "lisreg_vgicp_align", "lisreg_vgicp_covariances", "lisreg_vgicp_get_voxels",
     "lisreg_vgicp_linearize", "lisreg_vgicp_align_batch",
     "lisreg_fgicp_default_params", "lisreg_fgicp_set_target", "lisreg_fgicp_align", "lisreg_fgicp_correspondences", "lisreg_fgicp_linearize",
-    "lisreg_fgicp_align_batch",
+    "lisreg_fgicp_align_batch", "lisreg_fgicp_set_target_batch", "lisreg_fgicp_get_target", "lisreg_fgicp_grid_geometry",
+    "lisreg_fgicp_target_batch_counts",
     "lisreg_gicp_default_params", "lisreg_gicp_align", "lisreg_gicp_moments", "lisreg_gicp_inner", "lisreg_gicp_align_batch",
 ]
 
@@ -126,6 +127,16 @@ class FgicpParams(C.Structure):
 
 class FgicpInfo(C.Structure):
     _fields_ = [("grid_dims", C.c_int * 3), ("n_points", C.c_int)]
+
+
+class FgicpTargetJob(C.Structure):
+    """lisreg_fgicp_target_job"""
+    _fields_ = [("slot", C.c_int), ("n", C.c_int), ("cloud", C.c_void_p), ("cell_edge", C.c_float), ("status", C.c_int),
+                ("info", FgicpInfo)]
+
+
+FGICP_TARGET_BATCH_MAX = 1024
+FGICP_TARGET_BATCH_MAX_POINTS = 1 << 27
 
 
 class FgicpResult(VgicpResult):
@@ -657,6 +668,10 @@ def lib():
                                                C.POINTER(VgicpParams), C.POINTER(VgicpResult), dbl, C.POINTER(VgicpBatchInfo)]
         L.lisreg_fgicp_default_params.argtypes = [C.c_int, C.POINTER(FgicpParams)]
         L.lisreg_fgicp_set_target.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), C.POINTER(FgicpInfo), C.c_float]
+        L.lisreg_fgicp_set_target_batch.argtypes = [vp, C.c_int, C.POINTER(FgicpTargetJob), C.POINTER(FgicpParams)]
+        L.lisreg_fgicp_get_target.argtypes = [vp, C.c_int, C.POINTER(FgicpInfo), fp, fp, ip, ip, dbl, C.c_int, C.c_int]
+        L.lisreg_fgicp_grid_geometry.argtypes = [fp, C.c_int, C.c_float, ip, fp]
+        L.lisreg_fgicp_target_batch_counts.argtypes = [vp, ip, ip]
         L.lisreg_fgicp_align.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), fp, C.POINTER(FgicpResult), vp]
         L.lisreg_fgicp_correspondences.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), dbl, ip, dbl]
         L.lisreg_fgicp_align_batch.argtypes = [vp, C.POINTER(vp), ip, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpItemC), C.c_int,
@@ -683,6 +698,17 @@ def _default_params(struct, fn_name: str, kind: int, overrides: dict):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def fgicp_grid_geometry(bb, n_points: int, cell_edge: float = 0.0):
+    """lisreg_fgicp_grid_geometry: (dims [3], cell, inv_cell) of the search grid over the finite box bb [6]; needs no device"""
+    bb = np.ascontiguousarray(bb, np.float32).reshape(6)
+    dims = (C.c_int * 3)()
+    cell = (C.c_float * 2)()
+    rc = lib().lisreg_fgicp_grid_geometry(bb.ctypes.data_as(C.POINTER(C.c_float)), int(n_points), float(cell_edge), dims, cell)
+    if rc != OK:
+        raise LisregError(rc, "lisreg_fgicp_grid_geometry: bad arguments")
+    return list(dims), np.float32(cell[0]), np.float32(cell[1])
 
 
 def fgicp_default_params(kind: int = 0, **overrides) -> FgicpParams:
@@ -827,6 +853,10 @@ class Context:
         if rc not in allow:
             raise LisregError(rc, self._L.lisreg_last_error(self._h).decode())
         return rc
+
+    def last_error(self) -> str:
+        """lisreg_last_error: the text of the context's last failure (a call that returns OK may leave one: a failed job of a batch)"""
+        return self._L.lisreg_last_error(self._h).decode()
 
     @property
     def stream(self) -> int:
@@ -1966,6 +1996,38 @@ class Context:
         info = FgicpInfo()
         self._chk(self._L.lisreg_fgicp_set_target(self._h, slot, ptr, n, stride, fmt, C.byref(params), C.byref(info), cell_edge))
         return dict(grid_dims=list(info.grid_dims), n_points=info.n_points)
+
+    def fgicp_set_target_batch(self, jobs, params: "FgicpParams"):
+        """lisreg_fgicp_set_target_batch (§7t): jobs = a list of (slot, (device_ptr, n)) or (slot, (device_ptr, n), cell_edge).  Returns
+        a list of dicts, one per job: status, grid_dims, n_points (a failed job: status = ERR_ARG; last_error() names the first)."""
+        arr = (FgicpTargetJob * max(len(jobs), 1))()
+        for k, job in enumerate(jobs):
+            arr[k].slot, arr[k].cloud, arr[k].n = int(job[0]), job[1][0], int(job[1][1])
+            arr[k].cell_edge = float(job[2]) if len(job) > 2 else 0.0
+        self._chk(self._L.lisreg_fgicp_set_target_batch(self._h, len(jobs), arr, C.byref(params)))
+        return [dict(status=arr[k].status, grid_dims=list(arr[k].info.grid_dims), n_points=arr[k].info.n_points) for k in range(len(jobs))]
+
+    def fgicp_target_batch_counts(self):
+        """(enqueues, synchronisations) of the last fgicp_set_target_batch of this context"""
+        e, s = C.c_int(0), C.c_int(0)
+        self._chk(self._L.lisreg_fgicp_target_batch_counts(self._h, C.byref(e), C.byref(s)))
+        return e.value, s.value
+
+    def fgicp_get_target(self, slot: int) -> dict:
+        """lisreg_fgicp_get_target: the slot as it stands — grid_dims, n_points, geom [11] (origin, cell, 1 / cell, bounding box),
+        sorted [m, 4] float32 (the fourth word = index among the finite points, as bits), cell_start [cells + 1], orig [m], cov6 [m, 6]"""
+        info = FgicpInfo()
+        geom = np.zeros(11, np.float32)
+        gp = geom.ctypes.data_as(C.POINTER(C.c_float))
+        self._chk(self._L.lisreg_fgicp_get_target(self._h, slot, C.byref(info), gp, None, None, None, None, 0, 0))
+        m, cells = info.n_points, info.grid_dims[0] * info.grid_dims[1] * info.grid_dims[2]
+        srt = np.zeros((m, 4), np.float32)
+        cs, orig, cov = np.zeros(cells + 1, np.int32), np.zeros(m, np.int32), np.zeros((m, 6))
+        ip = C.POINTER(C.c_int)
+        self._chk(self._L.lisreg_fgicp_get_target(self._h, slot, C.byref(info), gp, srt.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  cs.ctypes.data_as(ip), orig.ctypes.data_as(ip), cov.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  m, cells + 1))
+        return dict(grid_dims=list(info.grid_dims), n_points=m, geom=geom, sorted=srt, cell_start=cs, orig=orig, cov6=cov)
 
     def fgicp_align(self, slot: int, source, params: "FgicpParams", guess=None, want_aligned: bool = False, out_ptr: int = 0) -> dict:
         """FastGICP::align against the FastGICP target in `slot`; returns the result dict (+ 'aligned')."""
