@@ -311,6 +311,28 @@ int  lisreg_get_counters(lisreg_ctx* ctx, unsigned long long* out, int n);
  * then surf of each item). */
 int  lisreg_get_neighbors(lisreg_ctx* ctx, int* out, int n_elems);
 
+/* Test hook, read-only (host code: no kernel, and no buffer of the production path is sized, cleared or kept for it): what the LAST
+ * executed GN iteration of the prepared batch left of the normal equations, one partial row per workgroup.  Call after
+ * lisreg_batch_run / lisreg_batch_fetch; available, like lisreg_get_neighbors, only if option "dump_neighbors" was 1 when the batch was
+ * prepared.  Synchronises the context's stream.  The rows are still there because only the next correspondence launch writes them: the
+ * solve reads them, and the finalize (also the one folded into the last solve of a fixed-iteration run) resets the registrations only.
+ *   *n_blocks                 workgroups of the row reduction (call with NULL buffers to learn it)
+ *   blocks[n_blocks][4]       item, kind (0 corner / 1 surf), the block's first query as a batch position (positions as for
+ *                             lisreg_get_neighbors; a batch that sorts its sources orders the positions inside a segment), count
+ *                             (<= 256) — the descriptors the row reduction ran with
+ *   rows[n_blocks][28]        21 upper-triangle AtA terms (row-major), 6 AtB, the correspondence count, summed over the block's
+ *                             queries.  UNSPECIFIED for the blocks of a registration that was through when the launch started (the
+ *                             feature-count guard): the kernels return before they write those rows.
+ *   capacity_blocks           blocks the two arrays above hold (>= n_blocks if either is given)
+ *   coef[n_elems][4], coef_ok[n_elems]   only for a batch that runs eight lanes per query ("lanes_per_query" reads 8): the coefficients
+ *                             (coeff.x, y, z, intensity) and the accept flag the search kernel handed to the row reduction, per batch
+ *                             position; LISREG_ERR_ARG if asked of a one-lane batch or with another n_elems than the batch's source
+ *                             point count.  UNSPECIFIED for the queries of a segment whose target has fewer than five points: the
+ *                             search kernel returns before it writes them (the rows of such a segment's blocks are zero).
+ * Any of blocks / rows / coef / coef_ok may be NULL and is skipped.  A refused call leaves every output untouched. */
+int  lisreg_get_partial_rows(lisreg_ctx* ctx, int* n_blocks, int* blocks, double* rows, int capacity_blocks, float* coef,
+                             int* coef_ok, int n_elems);
+
 /* Test hook: the DEVICE functions of the two residual models, one case per thread, on caller-given neighbourhoods — what the
  * correspondence kernel computes for a query once its five neighbours are known.  kind 1 = surfOptimization's body
  * (odomEstimationNode.cpp:776-821: plane through the five neighbours, |n.p + d| <= plane_tol test, point-to-plane residual, robust

@@ -723,6 +723,45 @@ int lisreg_get_neighbors(lisreg_ctx* c, int* out, int n_elems)
     return LISREG_OK;
 }
 
+// Host code only: nothing here is on the production path and no buffer is sized or cleared for it.  The partial rows outlive the run
+// because nothing but the next correspondence launch writes them: k_solve reads them as const, and the finalize — on its own
+// (k_finalize) or folded into the last solve (finalize_in_last_solve) — resets the registrations' ItemState and touches neither
+// `partials` nor `coef` / `coef_ok`.  An interleaved run joins its side stream into the context's stream before it returns.
+int lisreg_get_partial_rows(lisreg_ctx* c, int* n_blocks, int* blocks, double* rows, int capacity_blocks, float* coef, int* coef_ok,
+                            int n_elems)
+{
+    if (!c || !n_blocks) return LISREG_ERR_ARG;
+    const PreparedBatch& b = c->batch;
+    if (!b.live.prepared) return bad(c, "get_partial_rows: no prepared batch");
+    if (!c->opt.dump_neighbors || !c->dbg_nn.p || (b.mode_now != 1 && b.mode_now != 3 && b.mode_now != 5))
+        return bad(c, "get_partial_rows: set option dump_neighbors before preparing the batch (search modes 1, 3, 5)");
+    if ((blocks || rows) && capacity_blocks < b.n_blocks) return bad(c, "get_partial_rows: capacity_blocks too small");
+    if (coef || coef_ok) {
+        if (b.lanes_q <= 1) return bad(c, "get_partial_rows: the prepared batch runs one lane per query: it keeps no coefficients");
+        if (n_elems != b.n_elems) return bad(c, "get_partial_rows: n_elems must be the batch's source point count");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<BlockDesc> hb((size_t)b.n_blocks);
+    std::vector<Segment> hs((size_t)b.n_segs);
+    if (b.n_blocks) HIPCHK(c, hipMemcpy(hb.data(), c->blocks.p, sizeof(BlockDesc) * hb.size(), hipMemcpyDeviceToHost));
+    if (b.n_segs) HIPCHK(c, hipMemcpy(hs.data(), c->segs.p, sizeof(Segment) * hs.size(), hipMemcpyDeviceToHost));
+    for (const BlockDesc& d : hb)
+        if (d.seg < 0 || d.seg >= b.n_segs) return ctx_fail(c, LISREG_ERR_HIP, "get_partial_rows: the device block table names no segment of the batch");
+    if (rows && b.n_blocks) HIPCHK(c, hipMemcpy(rows, c->partials.p, sizeof(double) * kNumAcc * hb.size(), hipMemcpyDeviceToHost));
+    if (coef && b.n_elems) HIPCHK(c, hipMemcpy(coef, c->coef.p, sizeof(float4) * (size_t)b.n_elems, hipMemcpyDeviceToHost));
+    if (coef_ok && b.n_elems) HIPCHK(c, hipMemcpy(coef_ok, c->coef_ok.p, sizeof(int) * (size_t)b.n_elems, hipMemcpyDeviceToHost));
+    // (copied as they are: for a segment whose target has fewer than five points k_assoc_walk leaves before it searches (g.n < 5) and
+    // never writes its queries' coefficients — the buffers hold there whatever an earlier batch left, and include/lisreg.h says so)
+    if (blocks)
+        for (size_t i = 0; i < hb.size(); ++i) {
+            const Segment& s = hs[(size_t)hb[i].seg];
+            blocks[4 * i] = hb[i].item; blocks[4 * i + 1] = s.kind; blocks[4 * i + 2] = s.flat_base + hb[i].start; blocks[4 * i + 3] = hb[i].count;
+        }
+    *n_blocks = b.n_blocks;
+    return LISREG_OK;
+}
+
 int lisreg_test_fit_models(lisreg_ctx* c, int kind, int n, const float* neighbours, const float* queries, const lisreg_params* params,
                            int exact, float* out)
 {

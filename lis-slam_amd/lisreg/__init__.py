@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "lisreg_device_count", "lisreg_create", "lisreg_destroy", "lisreg_last_error", "lisreg_set_stream",
     "lisreg_get_stream", "lisreg_default_params", "lisreg_set_target", "lisreg_set_target_slot",
     "lisreg_target_from_classes", "lisreg_align", "lisreg_align_batch", "lisreg_batch_prepare", "lisreg_batch_run",
-    "lisreg_batch_fetch", "lisreg_stage_host_items", "lisreg_upload_cloud", "lisreg_concat_device", "lisreg_batch_result_device", "lisreg_set_option", "lisreg_get_option", "lisreg_get_counters", "lisreg_get_neighbors", "lisreg_test_fit_models", "lisreg_test_solve_steps", "lisreg_test_nn1", "lisreg_test_scan", "lisreg_get_map_grid", "lisreg_get_target_index", "lisreg_get_target_graph", "lisreg_get_target_cell_rows", "lisreg_keyframes_reset", "lisreg_keyframes_push", "lisreg_keyframes_target", "lisreg_get_trace",
+    "lisreg_batch_fetch", "lisreg_stage_host_items", "lisreg_upload_cloud", "lisreg_concat_device", "lisreg_batch_result_device", "lisreg_set_option", "lisreg_get_option", "lisreg_get_counters", "lisreg_get_neighbors", "lisreg_get_partial_rows", "lisreg_test_fit_models", "lisreg_test_solve_steps", "lisreg_test_nn1", "lisreg_test_scan", "lisreg_get_map_grid", "lisreg_get_target_index", "lisreg_get_target_graph", "lisreg_get_target_cell_rows", "lisreg_keyframes_reset", "lisreg_keyframes_push", "lisreg_keyframes_target", "lisreg_get_trace",
     "lisreg_set_profiling", "lisreg_get_timing", "lisreg_pose_to_matrix", "lisreg_transform_update",
     "lisreg_comm_unique_id", "lisreg_comm_init", "lisreg_gather_results", "lisreg_comm_destroy",
     "lisreg_voxel_downsample", "lisreg_voxel_downsample_multi", "lisreg_voxel_downsample_batch", "lisreg_transform_cloud",
@@ -536,6 +536,7 @@ def lib():
         L.lisreg_concat_device.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), vp, C.POINTER(C.c_int)]
         L.lisreg_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int)]
         L.lisreg_get_neighbors.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
+        L.lisreg_get_partial_rows.argtypes = [vp, ip, ip, C.POINTER(C.c_double), C.c_int, fp, ip, C.c_int]
         if hasattr(L, "lisreg_test_fit_models"): L.lisreg_test_fit_models.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Params), C.c_int, C.POINTER(C.c_float)]
         if hasattr(L, "lisreg_test_solve_steps"): L.lisreg_test_solve_steps.argtypes = [vp, C.c_int, C.c_int, ip, C.POINTER(C.c_double), fp, ip, ip, ip, C.POINTER(Imu), C.POINTER(Params), fp, fp, fp]
         L.lisreg_get_target_index.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -878,6 +879,27 @@ class Context:
         (-1: none), row 5 = 1 where the point contributed a correspondence."""
         out = np.full((6, n_elems), -1, np.int32)
         self._chk(self._L.lisreg_get_neighbors(self._h, out.ctypes.data_as(C.POINTER(C.c_int)), n_elems))
+        return out
+
+    def partial_rows(self, n_elems: int | None = None) -> dict:
+        """Test hook (lisreg_get_partial_rows): blocks[n_blocks, 4] (item, kind, first batch position, count) and rows[n_blocks, 28]
+        (float64) as the last executed GN iteration left them; with n_elems (the batch's source point count; eight lanes per query
+        only) also coef[n_elems, 4] and coef_ok[n_elems]."""
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        nb = C.c_int(-1)
+        self._chk(self._L.lisreg_get_partial_rows(self._h, C.byref(nb), None, None, 0, None, None, 0))
+        n = nb.value
+        out = dict(blocks=np.full((n, 4), -1, np.int32), rows=np.full((n, 28), np.nan, np.float64))
+        coef = coef_ok = None
+        if n_elems is not None:
+            out["coef"] = coef = np.full((n_elems, 4), np.nan, np.float32)
+            out["coef_ok"] = coef_ok = np.full(n_elems, -1, np.int32)
+        self._chk(self._L.lisreg_get_partial_rows(self._h, C.byref(nb), out["blocks"].ctypes.data_as(ip),
+                                                  out["rows"].ctypes.data_as(C.POINTER(C.c_double)), n,
+                                                  coef.ctypes.data_as(fp) if coef is not None else None,
+                                                  coef_ok.ctypes.data_as(ip) if coef_ok is not None else None,
+                                                  n_elems if n_elems is not None else 0))
+        assert nb.value == n
         return out
 
     def test_fit_models(self, kind: int, neighbours: np.ndarray, queries: np.ndarray, params, exact: bool = False) -> np.ndarray:
