@@ -1273,6 +1273,46 @@ int  lisreg_vgicp_get_voxels(lisreg_ctx* ctx, int slot, int* cell_ids, int* coun
 int  lisreg_vgicp_linearize(lisreg_ctx* ctx, int slot, const void* source, int n, int stride_bytes, int fmt,
                             const lisreg_vgicp_params* params, const double T[16], int with_hessian, double out[28],
                             long long* n_pairs);
+/* §7u: the targets of a whole candidate list as one call (detectLoopClosureForSubMap sets a different target submap for every
+ * candidate, src/node/subMapOptmizationNode.cpp:2793).  The slot of every job that comes back with status == LISREG_OK is, in every
+ * byte a later call can observe (dims, min_b, resolution, n_voxels, n_points, the voxel records in ascending cell id with their cell
+ * ids, the dense table, the bounding box, the search grid's geometry, points by cell and cells' starts), what
+ * lisreg_vgicp_set_target(ctx, slot, cloud, n, 16, LISREG_FMT_DEVICE, params, &info) leaves for that cloud alone.  resolution,
+ * k_correspondences and plane_epsilon of `params` apply to all jobs.  The clouds are device records, read where they lie.  The number
+ * of launches and of host synchronisations (two: one read-back of every target's finite count and bounding box, one at the end, with
+ * the voxel counts) does not depend on n_targets; the call runs on the context's stream and has returned when the slots are complete.
+ * A target with an infinite coordinate, with fewer finite points than k_correspondences or an empty finite box, or with a voxel grid
+ * of more than 2^26 cells fails alone: status = LISREG_ERR_ARG, its slot holds no target afterwards (whatever it held before), every
+ * other target is unaffected, the call returns LISREG_OK and lisreg_last_error names the first such job with the single call's text.
+ * Refused for the whole call (LISREG_ERR_ARG) before anything is launched, with no slot and no job field touched: NULL jobs with
+ * n_targets > 0, params lisreg_vgicp_set_target refuses, a slot outside 0 .. 65535, a slot named twice, n <= 0 or a NULL cloud in any
+ * job, n_targets outside 0 .. LISREG_VGICP_TARGET_BATCH_MAX, more than LISREG_VGICP_TARGET_BATCH_MAX_POINTS records in all.
+ * n_targets == 0 is LISREG_OK. */
+#define LISREG_VGICP_TARGET_BATCH_MAX 1024
+#define LISREG_VGICP_TARGET_BATCH_MAX_POINTS 134217728          /* 2^27 */
+typedef struct lisreg_vgicp_target_job {
+    int         slot;        /* VGICP slot 0 .. 65535 */
+    int         n;           /* records in cloud */
+    const void* cloud;       /* DEVICE lisreg_dpoint records (LISREG_FMT_DEVICE) */
+    int         status;      /* out: LISREG_OK, or LISREG_ERR_ARG for this target alone */
+    lisreg_vgicp_info info;  /* out: what the single call writes to *info */
+} lisreg_vgicp_target_job;
+int  lisreg_vgicp_set_target_batch(lisreg_ctx* ctx, int n_targets, lisreg_vgicp_target_job* jobs,
+                                   const lisreg_vgicp_params* params);
+/* test hook: reads a slot back, whoever set it: info; voxel_dims [3], voxel_min_b [3] and *resolution = the voxel grid; geom = the
+ * search grid's origin x y z, cell edge, its inverse, the bounding box [6]; grid_dims [3] = the search grid's cells per axis;
+ * sorted_xyzw [n_points][4] = the finite points by search-grid cell, ascending index inside a cell, the fourth word the point's index
+ * among the finite points as int bits; cell_start [grid cells + 1]; table [voxel cells] = cell -> voxel, -1 none.  (The voxel
+ * records: lisreg_vgicp_get_voxels.)  Any output pointer may be NULL.  A slot without a target, capacity_points < n_points with sorted_xyzw wanted, capacity_cells < grid cells + 1 with
+ * cell_start wanted or capacity_table < voxel cells with table wanted: LISREG_ERR_ARG (info, the voxel grid and geom are filled all the
+ * same when the slot holds a target). */
+int  lisreg_vgicp_get_target(lisreg_ctx* ctx, int slot, lisreg_vgicp_info* info, int voxel_dims[3], int voxel_min_b[3],
+                             double* resolution, float geom[11], int grid_dims[3], float* sorted_xyzw, int* cell_start, int* table,
+                             int capacity_points, int capacity_cells, int capacity_table);
+/* what the last lisreg_vgicp_set_target_batch of this context enqueued (its kernel launches, table copies and the one histogram
+ * clear, one more for every further sort sequence of the search grids, and the launches of the scans) and how often it waited for
+ * the stream */
+int  lisreg_vgicp_target_batch_counts(const lisreg_ctx* ctx, int* enqueues, int* synchronisations);
 
 /* ---- §7n: VGICP verification of a candidate list as one call -------------------------------------------------------------------
  * The candidate loop of detectLoopClosureForSubMap (src/node/subMapOptmizationNode.cpp:2779-2846) with the verifier its authors

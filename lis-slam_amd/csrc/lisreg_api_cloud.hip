@@ -34,28 +34,44 @@ int lisreg::voxel_sort_cloud(lisreg_ctx* c, const char* who, const float4* pts, 
     return LISREG_OK;
 }
 
+// The geometry of the dense voxel table over the finite box bb at `resolution`: pcl::VoxelGrid's min_b / div_b and the sort's keys
+// (d->span is left to the sort).  The one copy, for voxel_table_build below and for lisreg_vgicp_set_target_batch, which decides every
+// target's table on the host between its phases.  false: *why is the refusal's text behind "<who>: ".  Host arithmetic only.
+bool lisreg::voxel_table_geometry(const float bb[6], double resolution, const char* table_word, int min_b[3], int dims[3], VoxelDesc* d,
+                                  long long* total, std::string* why)
+{
+    const float inv = 1.0f / (float)resolution;
+    const long long max_cells = 1LL << 26;
+    for (int k = 0; k < 3; ++k) {
+        const double lo = floor((double)(bb[k] * inv)), hi = floor((double)(bb[3 + k] * inv));
+        if (!(fabs(lo) < 2.0e9 && fabs(hi) < 2.0e9)) { *why = "the grid has more than 2^26 cells (resolution too small for this cloud)"; return false; }
+    }
+    long long div_b[3];
+    voxel_bounds(bb, inv, min_b, div_b);
+    if (div_b[0] > max_cells || div_b[1] > max_cells || div_b[2] > max_cells || div_b[0] * div_b[1] > max_cells ||
+        div_b[0] * div_b[1] * div_b[2] > max_cells) {
+        *why = std::string("the grid has more than 2^26 cells (the ") + table_word + " is dense; resolution too small for this cloud)";
+        return false;
+    }
+    *total = div_b[0] * div_b[1] * div_b[2];
+    for (int k = 0; k < 3; ++k) dims[k] = (int)div_b[k];
+    memset(d, 0, sizeof *d);
+    d->inv_leaf = inv; d->min_b0 = min_b[0]; d->min_b1 = min_b[1]; d->min_b2 = min_b[2];
+    d->mul1 = dims[0]; d->mul2 = dims[0] * dims[1];
+    d->span = 1u;
+    return true;
+}
+
 // The shared build of the NDT and the VGICP target: pcl::VoxelGrid's keys, so both families see the voxels
 // lisreg_voxel_downsample sees, in the same order
 int lisreg::voxel_table_build(lisreg_ctx* c, const char* who, const char* table_word, const float4* pts, int n, const float bb[6],
                               double resolution, int mark, VoxelTable& T)
 {
     hipStream_t st = c->stream;
-    const float inv = 1.0f / (float)resolution;
-    const long long max_cells = 1LL << 26;
-    for (int k = 0; k < 3; ++k) {
-        const double lo = floor((double)(bb[k] * inv)), hi = floor((double)(bb[3 + k] * inv));
-        if (!(fabs(lo) < 2.0e9 && fabs(hi) < 2.0e9)) return bad(c, std::string(who) + ": the grid has more than 2^26 cells (resolution too small for this cloud)");
-    }
-    long long div_b[3];
-    voxel_bounds(bb, inv, T.min_b, div_b);
-    if (div_b[0] > max_cells || div_b[1] > max_cells || div_b[2] > max_cells || div_b[0] * div_b[1] > max_cells ||
-        div_b[0] * div_b[1] * div_b[2] > max_cells)
-        return bad(c, std::string(who) + ": the grid has more than 2^26 cells (the " + table_word + " is dense; resolution too small for this cloud)");
-    const long long total = div_b[0] * div_b[1] * div_b[2];
-    for (int k = 0; k < 3; ++k) T.dims[k] = (int)div_b[k];
     VoxelDesc d;
-    d.inv_leaf = inv; d.min_b0 = T.min_b[0]; d.min_b1 = T.min_b[1]; d.min_b2 = T.min_b[2];
-    d.mul1 = T.dims[0]; d.mul2 = T.dims[0] * T.dims[1];
+    long long total = 0;
+    std::string why;
+    if (!voxel_table_geometry(bb, resolution, table_word, T.min_b, T.dims, &d, &total, &why)) return bad(c, std::string(who) + ": " + why);
     int n_vox = 0;
     const int rc = voxel_sort_cloud(c, who, pts, n, d, total, mark, &n_vox);
     if (rc) return rc;

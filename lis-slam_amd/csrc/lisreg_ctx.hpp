@@ -418,6 +418,14 @@ struct lisreg_ctx {
     lisreg::DevBuf ft_tab, ft_part;
     lisreg::PinnedBuf ft_host;
     int          ft_enqueues = 0, ft_syncs = 0;
+    // lisreg_vgicp_set_target_batch (lisreg_vgicp_target_batch.hip) runs the same two phases on the same tables; besides: its own table
+    // of [voxel descriptors | fill chunks] uploaded per call with [first voxels | voxel counts] the device writes, the counter and the
+    // list of the voxels a wavefront sums, the pinned host side.  The covariances of all targets go to vg_cov, their indices to vg_idx,
+    // the voxel sort runs in the sort scratch and vox_order / vox_sidx / vox_head / vox_slot / vox_start.  vt_enqueues / vt_syncs: as above
+    // (lisreg_vgicp_target_batch_counts)
+    lisreg::DevBuf vt_tab, vt_big;
+    lisreg::PinnedBuf vt_host;
+    int          vt_enqueues = 0, vt_syncs = 0;
     // lisreg_fgicp_align_batch (lisreg_fgicp_batch.hip), lisreg_vgicp_align_batch (lisreg_vgicp_batch.hip), lisreg_ndt_align_batch
     // (lisreg_ndt_batch.hip) and lisreg_gicp_align_batch (lisreg_gicp_batch.hip): a set of buffers each (a call of one family leaves the
     // others' alone; NDT's has no covariances), and the pairs and M FastGICP's items keep from a search to the sums after it
@@ -523,6 +531,10 @@ int  voxel_sort_cloud(lisreg_ctx* c, const char* who, const float4* pts, int n, 
 // Refused: a grid of more than 2^26 cells (the table is dense; `table_word` names it in the text: "cell table", "voxel table").
 int  voxel_table_build(lisreg_ctx* c, const char* who, const char* table_word, const float4* pts, int n, const float bb[6], double resolution,
                        int mark, VoxelTable& T);
+// Its geometry alone (host arithmetic): min_b / dims, the sort's keys (d->span = 1: the sort chooses it) and the cells in all.  false:
+// the grid is refused and *why is voxel_table_build's text behind "<who>: "
+bool voxel_table_geometry(const float bb[6], double resolution, const char* table_word, int min_b[3], int dims[3], VoxelDesc* d,
+                          long long* total, std::string* why);
 VoxelView voxel_table_view(const VoxelTable& T);
 // the records of a table on the host, those with flag[v] != 0 only if `flag` is given ([n_voxels] ints on the device), at most `capacity`:
 // cell ids, point counts, means [3] and the six doubles behind them

@@ -90,4 +90,40 @@ void launch_voxel_stats(const Build& B, hipStream_t st)
     k_voxel_stats_big<Build><<<B.n_vox, 64, 0, st>>>(B);
 }
 
+// The same for the voxels of a whole batch of targets, whose number only the device knows (*B.n_vox, device memory): fixed grids that
+// stride.  Build is the family's record with the same static body, Build::voxel<WAVE>(B, v, lane), which finds voxel v's target itself.
+// Voxels above kVoxelBig points go into a list (an int counter, zero on entry; the list's order is irrelevant: every voxel has its own
+// output) that a fixed grid of wavefronts loops over; the voxel number is made wave-uniform, so what the body loads by it is scalar.
+template <class Build>
+__global__ __launch_bounds__(256) void k_voxel_stats_small_dev(Build B, int* __restrict__ big_count, int* __restrict__ big_list)
+{
+    const int n_vox = *B.n_vox;
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < n_vox; v += gridDim.x * 256) {
+        if (B.vstart[v + 1] - B.vstart[v] > kVoxelBig) { big_list[atomicAdd(big_count, 1)] = v; continue; }
+        Build::template voxel<false>(B, v, 0);
+    }
+}
+
+template <class Build>
+__global__ __launch_bounds__(64) void k_voxel_stats_big_dev(Build B, const int* __restrict__ big_count, const int* __restrict__ big_list)
+{
+    const int n_big = *big_count;
+    for (int i = blockIdx.x; i < n_big; i += gridDim.x) {
+        const int v = __builtin_amdgcn_readfirstlane(big_list[i]);
+        Build::template voxel<true>(B, v, (int)threadIdx.x);
+    }
+}
+
+// points: an upper bound of the voxels (every voxel holds a point); big_list has room for points / (kVoxelBig + 1) + 1 entries
+constexpr int kVoxelDevMaxBlocks = 4096, kVoxelDevMaxBigBlocks = 2048;
+inline int voxel_stats_big_capacity(int points) { return points / (kVoxelBig + 1) + 1; }
+template <class Build>
+void launch_voxel_stats_dev(const Build& B, int points, int* big_count, int* big_list, hipStream_t st)
+{
+    const int nb = std::max(1, std::min(kVoxelDevMaxBlocks, (points + 255) / 256));
+    const int nw = std::max(1, std::min(kVoxelDevMaxBigBlocks, voxel_stats_big_capacity(points)));
+    k_voxel_stats_small_dev<Build><<<nb, 256, 0, st>>>(B, big_count, big_list);
+    k_voxel_stats_big_dev<Build><<<nw, 64, 0, st>>>(B, big_count, big_list);
+}
+
 }  // namespace lisreg

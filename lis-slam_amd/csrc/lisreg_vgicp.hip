@@ -8,6 +8,7 @@
 // holds the one total kernel of the three verifiers (launch_eval_total).  No CPU fallback.
 #include "lisreg_vgicp_lane.hpp"
 #include "lisreg_vg_knn_lane.hpp"
+#include "lisreg_vg_voxel_lane.hpp"
 #include "lisreg_lm_stepper.hpp"
 #include "lisreg_jacobi3.hpp"
 
@@ -75,35 +76,12 @@ struct VgBuild {
     template <bool WAVE> static __device__ void voxel(const VgBuild& B, int v, int lane);
 };
 
-// WAVE: the 64 lanes of a wavefront share voxel v (every lane ends up with the same sums: the butterfly adds the same pairs everywhere)
+// the body is vg_voxel_lane (lisreg_vg_voxel_lane.hpp), which the batched target build inlines too
 template <bool WAVE>
 __device__ __forceinline__ void VgBuild::voxel(const VgBuild& B, int v, int lane)
 {
-    const int a = B.vstart[v], b = B.vstart[v + 1];
-    const int step = WAVE ? 64 : 1;
-    double s[9];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) s[e] = 0.0;
-    for (int j = a + lane; j < b; j += step) {
-        const int i = B.order[j];
-        const float4 p = B.pts[i];
-        const double* c = B.cov + (size_t)i * 6;
-        s[0] += (double)p.x; s[1] += (double)p.y; s[2] += (double)p.z;
-#pragma unroll
-        for (int e = 0; e < 6; ++e) s[3 + e] += c[e];
-    }
-    if (WAVE) {
-#pragma unroll
-        for (int e = 0; e < 9; ++e) s[e] = wave_sum(s[e]);
-    }
-    if (lane != 0) return;
-    const double cnt = (double)(b - a);
-    const uint32_t cid = B.sidx[a];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) B.stats[(size_t)v * kVoxelRec + e] = s[e] / cnt;
-    B.stats[(size_t)v * kVoxelRec + 9] = cnt;
-    B.cell[v] = (int)cid;
-    if ((long long)cid < B.n_cells) B.table[cid] = v;
+    vg_voxel_lane<WAVE>(B.pts, B.cov, B.order, B.sidx, B.vstart[v], B.vstart[v + 1], lane, v, B.n_cells,
+                        B.stats + (size_t)v * kVoxelRec, B.cell + v, B.table);
 }
 
 // ---- one linearisation ------------------------------------------------------------------------------------------------------------

@@ -53,7 +53,8 @@ ABI_SYMBOLS = [
     "lisreg_ndt_default_params", "lisreg_ndt_set_target", "lisreg_ndt_align", "lisreg_ndt_get_voxels", "lisreg_ndt_derivatives",
     "lisreg_ndt_align_batch",
     "lisreg_vgicp_default_params", "lisreg_vgicp_set_target", "lisreg_vgicp_align", "lisreg_vgicp_covariances", "lisreg_vgicp_get_voxels",
-    "lisreg_vgicp_linearize", "lisreg_vgicp_align_batch",
+    "lisreg_vgicp_linearize", "lisreg_vgicp_align_batch", "lisreg_vgicp_set_target_batch", "lisreg_vgicp_get_target",
+    "lisreg_vgicp_target_batch_counts",
     "lisreg_fgicp_default_params", "lisreg_fgicp_set_target", "lisreg_fgicp_align", "lisreg_fgicp_correspondences", "lisreg_fgicp_linearize",
     "lisreg_fgicp_align_batch", "lisreg_fgicp_set_target_batch", "lisreg_fgicp_get_target", "lisreg_fgicp_grid_geometry",
     "lisreg_fgicp_target_batch_counts",
@@ -107,6 +108,15 @@ class VgicpParams(C.Structure):
 
 class VgicpInfo(C.Structure):
     _fields_ = [("dims", C.c_int * 3), ("n_voxels", C.c_int), ("n_points", C.c_int)]
+
+
+class VgicpTargetJob(C.Structure):
+    """lisreg_vgicp_target_job"""
+    _fields_ = [("slot", C.c_int), ("n", C.c_int), ("cloud", C.c_void_p), ("status", C.c_int), ("info", VgicpInfo)]
+
+
+VGICP_TARGET_BATCH_MAX = 1024
+VGICP_TARGET_BATCH_MAX_POINTS = 1 << 27
 
 
 class VgicpResult(C.Structure):
@@ -667,6 +677,9 @@ def lib():
                                              C.POINTER(C.c_longlong)]
         L.lisreg_vgicp_align_batch.argtypes = [vp, C.POINTER(vp), ip, C.c_int, C.c_int, C.c_int, C.POINTER(VgicpItemC), C.c_int,
                                                C.POINTER(VgicpParams), C.POINTER(VgicpResult), dbl, C.POINTER(VgicpBatchInfo)]
+        L.lisreg_vgicp_set_target_batch.argtypes = [vp, C.c_int, C.POINTER(VgicpTargetJob), C.POINTER(VgicpParams)]
+        L.lisreg_vgicp_get_target.argtypes = [vp, C.c_int, C.POINTER(VgicpInfo), ip, ip, dbl, fp, ip, fp, ip, ip, C.c_int, C.c_int, C.c_int]
+        L.lisreg_vgicp_target_batch_counts.argtypes = [vp, ip, ip]
         L.lisreg_fgicp_default_params.argtypes = [C.c_int, C.POINTER(FgicpParams)]
         L.lisreg_fgicp_set_target.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FgicpParams), C.POINTER(FgicpInfo), C.c_float]
         L.lisreg_fgicp_set_target_batch.argtypes = [vp, C.c_int, C.POINTER(FgicpTargetJob), C.POINTER(FgicpParams)]
@@ -2010,6 +2023,42 @@ class Context:
     def vgicp_linearize(self, slot: int, source, params: "VgicpParams", T, with_hessian: bool = True):
         """one linearisation at T (4x4): (out [28] = error, b, H upper triangle; pairs)"""
         return self._sums_at(self._L.lisreg_vgicp_linearize, slot, source, params, [np.reshape(T, 16)], with_hessian)
+
+    def vgicp_set_target_batch(self, jobs, params: "VgicpParams"):
+        """lisreg_vgicp_set_target_batch (§7u): jobs = a list of (slot, (device_ptr, n)).  Returns a list of dicts, one per job: status,
+        dims, n_voxels, n_points (a failed job: status = ERR_ARG; last_error() names the first)."""
+        arr = (VgicpTargetJob * max(len(jobs), 1))()
+        for k, job in enumerate(jobs):
+            arr[k].slot, arr[k].cloud, arr[k].n = int(job[0]), job[1][0], int(job[1][1])
+        self._chk(self._L.lisreg_vgicp_set_target_batch(self._h, len(jobs), arr, C.byref(params)))
+        return [dict(status=arr[k].status, dims=list(arr[k].info.dims), n_voxels=arr[k].info.n_voxels, n_points=arr[k].info.n_points)
+                for k in range(len(jobs))]
+
+    def vgicp_target_batch_counts(self):
+        """(enqueues, synchronisations) of the last vgicp_set_target_batch of this context"""
+        e, s = C.c_int(0), C.c_int(0)
+        self._chk(self._L.lisreg_vgicp_target_batch_counts(self._h, C.byref(e), C.byref(s)))
+        return e.value, s.value
+
+    def vgicp_get_target(self, slot: int) -> dict:
+        """lisreg_vgicp_get_target: the slot as it stands — dims, n_voxels, n_points, min_b [3], resolution, geom [11] (the search grid's
+        origin, cell, 1 / cell, the bounding box), grid_dims [3], sorted [m, 4] float32 (the fourth word = index among the finite points, as bits),
+        cell_start [grid cells + 1], table [voxel cells]"""
+        info = VgicpInfo()
+        dims, min_b, res = (C.c_int * 3)(), (C.c_int * 3)(), C.c_double(0)
+        geom = np.zeros(11, np.float32)
+        gp = geom.ctypes.data_as(C.POINTER(C.c_float))
+        gd = (C.c_int * 3)()
+        self._chk(self._L.lisreg_vgicp_get_target(self._h, slot, C.byref(info), dims, min_b, C.byref(res), gp, gd, None, None, None, 0, 0, 0))
+        m, cells, n_table = info.n_points, gd[0] * gd[1] * gd[2], dims[0] * dims[1] * dims[2]
+        srt = np.zeros((m, 4), np.float32)
+        cs, tab = np.zeros(cells + 1, np.int32), np.zeros(n_table, np.int32)
+        ip = C.POINTER(C.c_int)
+        self._chk(self._L.lisreg_vgicp_get_target(self._h, slot, C.byref(info), dims, min_b, C.byref(res), gp, gd,
+                                                  srt.ctypes.data_as(C.POINTER(C.c_float)), cs.ctypes.data_as(ip), tab.ctypes.data_as(ip),
+                                                  m, cells + 1, n_table))
+        return dict(dims=list(dims), n_voxels=info.n_voxels, n_points=m, min_b=list(min_b), resolution=res.value, geom=geom,
+                    grid_dims=list(gd), sorted=srt, cell_start=cs, table=tab)
 
     # -- §7l: FastGICP registration ----------------------------------------------------------------------
     def fgicp_set_target(self, slot: int, cloud, params: "FgicpParams", cell_edge: float = 0.0) -> dict:
