@@ -96,7 +96,9 @@ __device__ void icp_solve_step(const double* tot, IcpState* st, int max_iters, d
     const double cos_angle = 0.5 * ((double)Tm[0] + (double)Tm[5] + (double)Tm[10] - 1.0);
     const double tr2 = (double)Tm[3] * Tm[3] + (double)Tm[7] * Tm[7] + (double)Tm[11] * Tm[11];
     if (cos_angle >= 1.0 - eps_t && tr2 <= eps_t) { st->state = LISREG_ICP_TRANSFORM; st->converged = 1; st->done = 1; return; }
-    const double cur = tot[16] * inv, prev = st->prev_mse;
+    // calculateMSE divides (default_convergence_criteria.hpp): tot[16] * inv is up to one ulp off it, which decides the absolute test
+    // when an alignment starts from the value the one before it left behind
+    const double cur = tot[16] / cnt, prev = st->prev_mse;
     st->cur_mse = cur;
     if (iters == 1) st->first_mse = cur;                 // the MSE test of the first iteration was reached (chained batches)
     // chained batch (the reference's `static` ICP object, subMapOptmizationNode.cpp:2763): this item's correspondences_prev_mse_ is the
