@@ -846,7 +846,10 @@ int  lisreg_localmap_default_params(lisreg_localmap_params* p);
 int  lisreg_localmap_reset(lisreg_ctx* ctx, int map_id);
 /* clouds[5] / n[5]: the key frame's UN-downsampled class clouds in the sensor frame (semantic_dynamic, _pole, _ground, _building,
  * _outlier); host PointXYZIL structs or LISREG_FMT_DEVICE records.  pose = the frame's optimized_pose {roll,pitch,yaw,x,y,z}.
- * The outlier cloud is accepted and ignored, exactly as the reference leaves its transform commented out (subMap.h:1003). */
+ * The outlier cloud is accepted and ignored, exactly as the reference leaves its transform commented out (subMap.h:1003).
+ * While the map's dynamic class is empty the dynamic removal does not run, whatever feature_point_num is: every dynamic point of
+ * the frame is appended (the reference reads distances_square[0] of an empty vector there, which is undefined; the same holds for
+ * lisreg_submap_insert). */
 int  lisreg_localmap_insert(lisreg_ctx* ctx, int map_id, const void* const clouds[5], const int n[5], int stride_bytes, int fmt,
                             const float pose[6], const lisreg_localmap_params* params, lisreg_localmap_info* info);
 int  lisreg_localmap_extract(lisreg_ctx* ctx, int map_id, const float cur_pose[6], const lisreg_localmap_params* params,

@@ -329,6 +329,7 @@ def test_keyframe_ring_target_equals_oracle_bitwise(oracle, gpu_ctx):
     drops its oldest frames beyond max_keep."""
     import replay_oracle as ro
     from lisreg import replay, synth
+    from map_store_ref import ring_push, ring_target
     frames, truth = zip(*replay.synthetic_raw_drive(5, h=32, w=900))
     fp = oracle.FeatureParams(32, 900, 1, 0.0, 70.0, 1.0, 0.1)
     gpu_ctx.keyframes_reset(2)
@@ -338,12 +339,10 @@ def test_keyframe_ring_target_equals_oracle_bitwise(oracle, gpu_ctx):
         corner, surf = ro._xyzi(sw, f["corner"]), ro._xyzi(sw, f["surface"])
         T = T.astype(np.float32)
         info = gpu_ctx.keyframes_push(2, corner, surf, T, max_keep=3)
-        kc.append(oracle.transform_cloud(corner, T)); ks.append(oracle.transform_cloud(surf, T))
-        kc, ks = kc[-3:], ks[-3:]
+        kc, ks = ring_push(oracle, kc, ks, corner, surf, T, 3)
         assert info["n_keyframes"] == len(kc)
         tinfo = gpu_ctx.keyframes_target(2, 0.2, 0.4, target_slot=0)
-        want_c = oracle.voxel_grid(ro.cat(kc[::-1]), 0.2)[1]
-        want_s = oracle.voxel_grid(ro.cat(ks[::-1]), 0.4)[1]
+        want_c, want_s, _ = ring_target(oracle, kc, ks, 0.2, 0.4)
         assert (tinfo["n_target_corner"], tinfo["n_target_surf"]) == (len(want_c), len(want_s))
         for kind, want in ((0, want_c), (1, want_s)):
             idx = gpu_ctx.target_index(0, kind)
@@ -363,7 +362,7 @@ def test_keyframe_ring_target_equals_oracle_bitwise(oracle, gpu_ctx):
     assert gpu_ctx.keyframes_target(2, 0.2, 0.4, target_slot=0) == tinfo           # ... and is rebuilt from the ring
     assert all(np.array_equal(a["sorted"], b["sorted"]) for a, b in zip(first, slot0()))
     coarse = gpu_ctx.keyframes_target(2, 0.4, 0.8, target_slot=0)
-    assert coarse["n_target_surf"] == len(oracle.voxel_grid(ro.cat(ks[::-1]), 0.8)[1]) < tinfo["n_target_surf"]
+    assert coarse["n_target_surf"] == len(ring_target(oracle, kc, ks, 0.4, 0.8)[1]) < tinfo["n_target_surf"]
 
 
 @pytest.mark.gpu
