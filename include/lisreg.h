@@ -1208,6 +1208,55 @@ int  lisreg_ndt_align_batch(lisreg_ctx* ctx, const void* const* sources, const i
                             const lisreg_ndt_item* items, int n_items, const lisreg_ndt_params* params,
                             lisreg_ndt_result* results, double* fitness, lisreg_ndt_batch_info* info);
 
+/* ---- §7v: the NDT targets of a whole candidate list as one call ------------------------------------------------------------------
+ * detectLoopClosureForSubMap sets a different target submap for every candidate (src/node/subMapOptmizationNode.cpp:2793).  The slot
+ * of every job that comes back with status == LISREG_OK is, in every byte a later call can observe (dims, min_b, resolution, the voxel
+ * records of ALL voxels in ascending cell id with their cell ids and flags — those that did not become a Gaussian included —, their
+ * number as the table counts them, the occupied and the valid voxels, the dense table with the voxel numbers it holds, the bounding
+ * box, the search grid's geometry, points by cell and cells' starts), what
+ * lisreg_ndt_set_target(ctx, slot, cloud, n, 16, LISREG_FMT_DEVICE, params, &info) leaves for that cloud alone.  resolution,
+ * min_points_per_voxel and min_covar_eigvalue_mult of `params` apply to all jobs.  The clouds are device records, read where they lie.
+ * The number of launches and of host synchronisations (two: one read-back of every target's finite count and bounding box, one at the
+ * end, with every target's three counts: voxel records, occupied, valid) does not depend on n_targets; the call runs on the context's
+ * stream and has returned when the slots are complete.
+ * A target with an infinite coordinate, without a finite coordinate box, with a finite box but no record finite in all three
+ * coordinates, with a voxel grid of more than 2^26 cells or without a valid voxel fails alone: status = LISREG_ERR_ARG (the last kind
+ * with `info` filled as the single call fills it before it refuses, n_valid == 0), its slot holds no target afterwards (whatever it
+ * held before), every other target is unaffected, the call returns LISREG_OK and lisreg_last_error names the first such job with the
+ * single call's text ("ndt_set_target_batch: job <t>: ndt_set_target: <text>").
+ * Refused for the whole call (LISREG_ERR_ARG) before anything is launched, with no slot and no job field touched: NULL jobs with
+ * n_targets > 0, params lisreg_ndt_set_target refuses, a slot outside 0 .. 65535, a slot named twice, n <= 0 or a NULL cloud in any
+ * job, n_targets outside 0 .. LISREG_NDT_TARGET_BATCH_MAX, more than LISREG_NDT_TARGET_BATCH_MAX_POINTS records in all.
+ * n_targets == 0 is LISREG_OK. */
+#define LISREG_NDT_TARGET_BATCH_MAX 1024
+#define LISREG_NDT_TARGET_BATCH_MAX_POINTS 134217728          /* 2^27 */
+typedef struct lisreg_ndt_target_job {
+    int         slot;        /* NDT slot 0 .. 65535 */
+    int         n;           /* records in cloud */
+    const void* cloud;       /* DEVICE lisreg_dpoint records (LISREG_FMT_DEVICE) */
+    int         status;      /* out: LISREG_OK, or LISREG_ERR_ARG for this target alone */
+    lisreg_ndt_info info;    /* out: what the single call writes to *info */
+} lisreg_ndt_target_job;
+int  lisreg_ndt_set_target_batch(lisreg_ctx* ctx, int n_targets, lisreg_ndt_target_job* jobs, const lisreg_ndt_params* params);
+/* test hook: reads a slot back, whoever set it: info; voxel_dims [3], voxel_min_b [3] and *resolution = the voxel grid; geom = the
+ * search grid's origin x y z, cell edge, its inverse, the bounding box [6]; grid_dims [3] = the search grid's cells per axis;
+ * *n_points = the finite points; *n_records = the voxel records (every voxel that holds a record of the cloud: a NaN record sits in
+ * cell 0, so this may be one more than info->n_voxels); sorted_xyzw [n_points][4] = the finite points by search-grid cell, ascending
+ * index inside a cell, the fourth word the point's index among the finite points as int bits; cell_start [grid cells + 1]; table
+ * [voxel cells] = cell -> voxel record, -1 none (valid voxels only); record_cells / record_flags [n_records] = every record's cell
+ * id and whether it became a Gaussian; records [n_records][10] = mean [3], inverse covariance xx xy xz yy yz zz, finite points.  Any
+ * output pointer may be NULL.  A slot without a target, capacity_points < n_points with sorted_xyzw wanted, capacity_cells < grid
+ * cells + 1 with cell_start wanted, capacity_table < voxel cells with table wanted or capacity_records < n_records with any of the
+ * three record outputs wanted: LISREG_ERR_ARG (info, the voxel grid, geom and the two numbers are filled all the same when the slot
+ * holds a target). */
+int  lisreg_ndt_get_target(lisreg_ctx* ctx, int slot, lisreg_ndt_info* info, int voxel_dims[3], int voxel_min_b[3],
+                           double* resolution, float geom[11], int grid_dims[3], int* n_points, int* n_records, float* sorted_xyzw,
+                           int* cell_start, int* table, int* record_cells, int* record_flags, double* records, int capacity_points,
+                           int capacity_cells, int capacity_table, int capacity_records);
+/* what the last lisreg_ndt_set_target_batch of this context enqueued (its kernel launches, table copies and the two clears, one more
+ * for every further sort sequence of the search grids, and the launches of the scans) and how often it waited for the stream */
+int  lisreg_ndt_target_batch_counts(const lisreg_ctx* ctx, int* enqueues, int* synchronisations);
+
 /* ---- §7k: voxelised GICP registration (loop-closure verification) ----------------------------------------------------
  * select_registration_method("FAST_VGICP") is the verifier detectLoopClosureForSubMap's authors chose last
  * (src/node/subMapOptmizationNode.cpp:2771, commented out); src/core/registration.cpp:156-187 carries the whole fast_gicp family

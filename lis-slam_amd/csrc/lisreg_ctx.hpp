@@ -426,6 +426,11 @@ struct lisreg_ctx {
     lisreg::DevBuf vt_tab, vt_big;
     lisreg::PinnedBuf vt_host;
     int          vt_enqueues = 0, vt_syncs = 0;
+    // lisreg_ndt_set_target_batch (lisreg_ndt_target_batch.hip): the same two phases without the distributions, and the voxel half on
+    // the tables above (a context is single-threaded and every such call ends in a wait, so the families share them): [voxel descriptors
+    // | fill chunks | blocks of the raw records] uploaded per call with [first voxels | voxel counts | occupied and valid counts] the
+    // device writes.  nt_enqueues / nt_syncs: as above (lisreg_ndt_target_batch_counts)
+    int          nt_enqueues = 0, nt_syncs = 0;
     // lisreg_fgicp_align_batch (lisreg_fgicp_batch.hip), lisreg_vgicp_align_batch (lisreg_vgicp_batch.hip), lisreg_ndt_align_batch
     // (lisreg_ndt_batch.hip) and lisreg_gicp_align_batch (lisreg_gicp_batch.hip): a set of buffers each (a call of one family leaves the
     // others' alone; NDT's has no covariances), and the pairs and M FastGICP's items keep from a search to the sums after it

@@ -9,6 +9,7 @@
 // lisreg_ndt_batch.hip).  No CPU fallback.
 #include "lisreg_fp64_sums.hpp"
 #include "lisreg_ndt_lane.hpp"
+#include "lisreg_ndt_voxel_lane.hpp"
 #include "lisreg_ndt_stepper.hpp"
 #include "lisreg_jacobi3.hpp"
 
@@ -34,28 +35,6 @@ __global__ __launch_bounds__(256) void k_ndt_clean(const float4* __restrict__ in
     out[i] = bad ? make_float4(lx, ly, lz, 1.0f) : make_float4(p.x, p.y, p.z, 0.0f);
 }
 
-// the Gaussian of one voxel from its mean-centred second moments S (already divided by n - 1): eigen-decomposition, the two smaller
-// eigenvalues raised to mult * the largest, inverse = V diag(1 / lambda) V^T.  False: not a valid voxel.
-__device__ bool ndt_gaussian(double a00, double a01, double a02, double a11, double a12, double a22, double mult, double ic[6])
-{
-    double v00, v01, v02, v10, v11, v12, v20, v21, v22;
-    jacobi3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
-    const double lmax = fmax(a00, fmax(a11, a22));
-    if (a00 < 0.0 || a11 < 0.0 || a22 < 0.0 || !(lmax > 0.0)) return false;
-    const double fl = mult * lmax;
-    const double i0 = 1.0 / fmax(a00, fl), i1 = 1.0 / fmax(a11, fl), i2 = 1.0 / fmax(a22, fl);
-    ic[0] = (i0 * v00 * v00 + i1 * v01 * v01) + i2 * v02 * v02;
-    ic[1] = (i0 * v00 * v10 + i1 * v01 * v11) + i2 * v02 * v12;
-    ic[2] = (i0 * v00 * v20 + i1 * v01 * v21) + i2 * v02 * v22;
-    ic[3] = (i0 * v10 * v10 + i1 * v11 * v11) + i2 * v12 * v12;
-    ic[4] = (i0 * v10 * v20 + i1 * v11 * v21) + i2 * v12 * v22;
-    ic[5] = (i0 * v20 * v20 + i1 * v21 * v21) + i2 * v22 * v22;
-    bool fin = true;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) fin = fin && isfinite(ic[k]);
-    return fin;
-}
-
 struct NdtBuild {
     const float4*   pts;        // cleaned records
     const int*      order;      // sorted position -> record
@@ -72,53 +51,12 @@ struct NdtBuild {
     template <bool WAVE> static __device__ void voxel(const NdtBuild& B, int v, int lane);
 };
 
-// WAVE: the 64 lanes of a wavefront share voxel v (every lane ends up with the same sums: the butterfly adds the same pairs everywhere)
+// the body is ndt_voxel_lane (lisreg_ndt_voxel_lane.hpp), which the batched target build inlines too
 template <bool WAVE>
 __device__ __forceinline__ void NdtBuild::voxel(const NdtBuild& B, int v, int lane)
 {
-    const int a = B.vstart[v], b = B.vstart[v + 1];
-    const int step = WAVE ? 64 : 1;
-    double s0 = 0, s1 = 0, s2 = 0, cnt = 0;
-    for (int k = a + lane; k < b; k += step) {
-        const float4 p = B.pts[B.order[k]];
-        if (p.w != 0.0f) continue;
-        s0 += (double)p.x; s1 += (double)p.y; s2 += (double)p.z; cnt += 1.0;
-    }
-    if (WAVE) { s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); cnt = wave_sum(cnt); }
-    const int n = (int)cnt;
-    const uint32_t cid = B.sidx[a];
-    double rec[kVoxelRec];
-#pragma unroll
-    for (int k = 0; k < kVoxelRec; ++k) rec[k] = 0.0;
-    rec[9] = cnt;
-    bool ok = n >= B.min_pts && n >= 2;
-    if (ok) {                                                  // uniform across the wavefront: no lane leaves the shuffles below alone
-        const double m0 = s0 / cnt, m1 = s1 / cnt, m2 = s2 / cnt;
-        double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
-        for (int k = a + lane; k < b; k += step) {
-            const float4 p = B.pts[B.order[k]];
-            if (p.w != 0.0f) continue;
-            const double d0 = (double)p.x - m0, d1 = (double)p.y - m1, d2 = (double)p.z - m2;
-            c00 += d0 * d0; c01 += d0 * d1; c02 += d0 * d2; c11 += d1 * d1; c12 += d1 * d2; c22 += d2 * d2;
-        }
-        if (WAVE) { c00 = wave_sum(c00); c01 = wave_sum(c01); c02 = wave_sum(c02); c11 = wave_sum(c11); c12 = wave_sum(c12); c22 = wave_sum(c22); }
-        const double inv = 1.0 / (cnt - 1.0);
-        double ic[6];
-        ok = ndt_gaussian(c00 * inv, c01 * inv, c02 * inv, c11 * inv, c12 * inv, c22 * inv, B.mult, ic);
-        rec[0] = m0; rec[1] = m1; rec[2] = m2;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) rec[3 + k] = ok ? ic[k] : 0.0;
-    }
-    if (lane != 0) return;
-#pragma unroll
-    for (int k = 0; k < kVoxelRec; ++k) B.stats[(size_t)v * kVoxelRec + k] = rec[k];
-    B.vflag[v] = ok ? 1 : 0;
-    B.cell[v] = (int)cid;
-    if (n > 0) atomicAdd(&B.counters[0], 1);
-    if (ok) {
-        atomicAdd(&B.counters[1], 1);
-        if ((long long)cid < B.n_cells) B.table[cid] = v;
-    }
+    ndt_voxel_lane<WAVE, NdtSkipMarked>(B.pts, B.order, B.sidx, B.vstart[v], B.vstart[v + 1], lane, v, B.n_cells, B.min_pts, B.mult,
+                                        B.stats + (size_t)v * kVoxelRec, B.vflag + v, B.cell + v, B.table, B.counters);
 }
 
 // ---- one evaluation --------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
-// lisreg_target_batch_shared.hpp — phases A and B of a batched target build, one copy for the two units that run
-// them: lisreg_fgicp_set_target_batch (lisreg_fgicp_target_batch.hip) and lisreg_vgicp_set_target_batch
-// (lisreg_vgicp_target_batch.hip).  Phase A: the finite count and the bounding box of every target, one read-back.  The host between the
+// lisreg_target_batch_shared.hpp — phases A and B of a batched target build, one copy for the three units that
+// run them: lisreg_fgicp_set_target_batch (lisreg_fgicp_target_batch.hip), lisreg_vgicp_set_target_batch
+// (lisreg_vgicp_target_batch.hip) and lisreg_ndt_set_target_batch (lisreg_ndt_target_batch.hip), which leaves the distributions out.  Phase A: the finite count and the bounding box of every target, one read-back.  The host between the
 // phases: every target's verdict and search grid (vg_grid_geometry, the single call's function), one table of descriptors.  Phase B: the
 // finite points compacted in input order, all search grids in one bucket sort (launch_build_targets_batched) and the distributions of
 // all targets in one launch (vg_knn_lane, the single kernel's body).  Where the sorted points, the cells, the indices and the
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(64) void k_ft_stats(const FtJob* __restrict__ jobs,
 
 // ---- phase B -----------------------------------------------------------------------------------------------------------------------
 // One tile: its finite points, in input order, behind those of the target's tiles in front of it; their indices in the caller's cloud
-// go to the descriptor's `orig_out`.  Tiles of a dropped target return at once.
+// go to the descriptor's `orig_out` (if it has one).  Tiles of a dropped target return at once.
 __global__ __launch_bounds__(kFtTile) void k_ft_compact(const FtJob* __restrict__ jobs, const FtTile* __restrict__ tiles,
                                                         const FtDesc* __restrict__ descs, const int* __restrict__ tile_base)
 {
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kFtTile) void k_ft_compact(const FtJob* __restrict_
     for (int w = 0; w < wave; ++w) dst += s_cnt[w];
     if (dst >= m) return;                                           // (cannot happen: m is the sum of the counts this repeats)
     pts_out[dst] = p;
-    orig_out[dst] = t.start + (int)threadIdx.x;
+    if (orig_out) orig_out[dst] = t.start + (int)threadIdx.x;   // (null: a family that keeps no indices, lisreg_ndt_set_target_batch)
 }
 
 // The distributions of all targets: one query per lane, 64-lane workgroups, four of them to a 256-point block of one target (the sort's
@@ -282,8 +282,8 @@ inline void ft_grid_index(const VgGrid& vg, int m, const float4* sorted, const i
     g->pts = sorted; g->cell_start = cells;
 }
 
-// Phase B of the targets added (at least one): one table up, the compaction, one sort per sequence, the distributions; nothing is
-// waited for.  lisreg_get_timing: "index" opens in front of the compaction (the caller closes it)
+// Phase B of the targets added (at least one): one table up, the compaction, one sort per sequence, the distributions (k == 0: none,
+// and orig / cov of ft_add_target may be null); nothing is waited for.  lisreg_get_timing: "index" opens in front of the compaction (the caller closes it)
 inline int ft_phase_b(lisreg_ctx* c, FtBatch& F, int k, FtEnq enq)
 {
     hipStream_t st = c->stream;
@@ -298,6 +298,7 @@ inline int ft_phase_b(lisreg_ctx* c, FtBatch& F, int k, FtEnq enq)
         launch_build_targets_batched(F.d_blk + g.blk0, g.n_blks, F.d_tseg + g.seg0, g.n_segs, g.elems, (int)g.cells, sort_buffers(c), st);
         enq();
     }
+    if (k == 0) return LISREG_OK;                                  // a family without distributions: the search grids are all it wants
     if (k <= 20) k_ft_knn<20><<<F.n_blk * 4, 64, 0, st>>>(F.d_blk, F.d_desc);
     else         k_ft_knn<32><<<F.n_blk * 4, 64, 0, st>>>(F.d_blk, F.d_desc);
     enq();

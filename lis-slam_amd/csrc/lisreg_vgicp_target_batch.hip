@@ -8,7 +8,8 @@
 // What this unit adds is the voxel half:
 //  - the host decides every target's voxel geometry between the phases with the single call's function (voxel_table_geometry), so the
 //    third per-target failure (a grid beyond 2^26 cells) needs no device work either;
-//  - ONE voxel sort over the finite points of all targets, keyed by (target, the target's own pcl::VoxelGrid index): every target owns a
+//  - ONE voxel sort over the finite points of all targets (lisreg_voxel_sort_batch.hpp, which lisreg_ndt_set_target_batch runs over all
+//    records of its targets), keyed by (target, the target's own pcl::VoxelGrid index): every target owns a
 //    range of buckets, so the sorted sequence is target by target, each "ascending cell id, ties by index among the finite points" — the
 //    total order launch_voxel_sort gives the single call;
 //  - one launch fills every dense table with -1 (a table of (pointer, length) chunks; no workgroup spans two targets);
@@ -19,7 +20,7 @@
 #include "lisreg_vgicp_lane.hpp"
 #include "lisreg_target_batch_shared.hpp"
 #include "lisreg_vg_voxel_lane.hpp"
-#include "lisreg_voxel_shared.hpp"
+#include "lisreg_voxel_sort_batch.hpp"
 
 #include <algorithm>
 #include <set>
@@ -27,15 +28,6 @@
 using namespace lisreg;
 
 namespace {
-
-// The bucket budget of the voxel sort, as lisreg_voxel_downsample_batch's (lisreg_voxel_batch_plan.hpp): a target of m finite points asks
-// for kVtBucketsPerPoint * m buckets (at least kVtMinBuckets, never more than its grid has cells); only if the batch asks for more than
-// kVtBucketCap in all does every share shrink in proportion.  The rank pass is quadratic inside a bucket, so the share per POINT is what
-// matters, and that does not shrink with n_targets until the cap binds (2 M points).
-constexpr long long kVtBucketsPerPoint = 8;
-constexpr long long kVtMinBuckets      = 64;
-constexpr long long kVtBucketCap       = 1LL << 24;
-constexpr int       kVtFillChunk       = 8192;        // table entries one workgroup of k_vt_fill sets
 
 // One target of the batch as the voxel kernels read it (by job index; m == 0: dropped)
 struct VtTarget {
@@ -49,131 +41,10 @@ struct VtTarget {
     int           pbase, m;    // first sorted position (the live targets' finite points end to end), finite points
     int           bucket_base, n_buckets;
     int           cap;         // records `stats` / `cell` hold: min(m, n_cells)
+    // the sort's key of the target's finite point e (lisreg_voxel_sort_batch.hpp)
+    static __device__ __forceinline__ uint32_t key(const VtTarget& T, int e) { return voxel_index(T.pts[e], T.d); }
 };
-struct VtChunk { int* p; int count, pad_; };
-static_assert(sizeof(VtTarget) == 96 && sizeof(VtChunk) == 16, "table layout");
-
-// sort keys: bucket = the target's first bucket + index / span, sub-key = the target's own voxel index; and the point's arrival rank in its
-// bucket, drawn from the histogram's counter here so that the scatter needs no atomic (k_vb_keys' scheme: a run of equal buckets among
-// neighbouring lanes sends ONE integer atomic; which rank a point draws is irrelevant, the rank pass fixes the order inside a bucket)
-__global__ __launch_bounds__(kBlockQ) void k_vt_keys(const BlockDesc* __restrict__ blocks, const VtTarget* __restrict__ tg,
-                                                     uint32_t* __restrict__ elem_bucket, uint32_t* __restrict__ elem_sub,
-                                                     int* __restrict__ elem_rank, int* __restrict__ hist)
-{
-    const BlockDesc bd = blocks[blockIdx.x];
-    const VtTarget& T = tg[bd.item];
-    const int lane = threadIdx.x & 63;
-    const bool valid = (int)threadIdx.x < bd.count;
-    const int e = bd.start + (int)threadIdx.x;
-    uint32_t b = 0xffffffffu - (uint32_t)lane, idx = 0u;            // a lane without a point: a bucket no other lane names
-    if (valid) {
-        const VoxelDesc d = T.d;
-        idx = voxel_index(T.pts[e], d);
-        uint32_t lb = idx / d.span;
-        if (lb >= (uint32_t)T.n_buckets) lb = (uint32_t)T.n_buckets - 1u;      // (cannot happen: a finite point lies inside its box)
-        b = (uint32_t)T.bucket_base + lb;
-    }
-    const uint32_t left = (uint32_t)__shfl_up((int)b, 1);
-    const bool first = lane == 0 || left != b;                      // first lane of a run of equal buckets
-    const unsigned long long firsts = __ballot(first);
-    const int start = 63 - __clzll((long long)(firsts & ((2ull << lane) - 1ull)));          // my run's first lane
-    const unsigned long long above = lane == 63 ? 0ull : firsts >> (lane + 1);
-    const int behind = above ? __ffsll((long long)above) - 1 : 63 - lane;                   // lanes of my run behind me
-    int base = 0;
-    if (first && valid) base = atomicAdd(&hist[b], 1 + behind);
-    base = __shfl(base, start);
-    if (!valid) return;
-    const int i = T.pbase + e;
-    elem_bucket[i] = b;
-    elem_sub[i] = idx;
-    elem_rank[i] = base + (lane - start);
-}
-
-// scatter into the buckets at the rank drawn above; the point's index among its target's finite points travels along
-__global__ __launch_bounds__(kBlockQ) void k_vt_scatter(const BlockDesc* __restrict__ blocks, const VtTarget* __restrict__ tg,
-                                                        const uint32_t* __restrict__ elem_bucket, const uint32_t* __restrict__ elem_sub,
-                                                        const int* __restrict__ elem_rank, const int* __restrict__ bucket_start,
-                                                        uint32_t* __restrict__ tmp_bucket, uint32_t* __restrict__ tmp_sub, int* __restrict__ tmp_idx)
-{
-    const BlockDesc bd = blocks[blockIdx.x];
-    if ((int)threadIdx.x >= bd.count) return;
-    const int e = bd.start + (int)threadIdx.x, i = tg[bd.item].pbase + e;
-    const uint32_t b = elem_bucket[i];
-    const int pos = bucket_start[b] + elem_rank[i];
-    tmp_bucket[pos] = b;
-    tmp_sub[pos] = elem_sub[i];
-    tmp_idx[pos] = e;
-}
-
-// final position inside the bucket: rank by (cell id, index) — a bucket holds points of one target only, so the sorted sequence is,
-// target by target, "ascending cell id, ties by index among the finite points"
-__global__ __launch_bounds__(256) void k_vt_rank(int n, const uint32_t* __restrict__ tmp_bucket, const uint32_t* __restrict__ tmp_sub,
-                                                 const int* __restrict__ tmp_idx, const int* __restrict__ bucket_start,
-                                                 int* __restrict__ order, uint32_t* __restrict__ sidx)
-{
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= n) return;
-    const uint32_t b = tmp_bucket[p];
-    const int s = bucket_start[b], e = bucket_start[b + 1];
-    const uint32_t sub = tmp_sub[p];
-    const int idx = tmp_idx[p];
-    int rank = 0;
-#pragma unroll 8
-    for (int j = s; j < e; ++j) {
-        const uint32_t sj = tmp_sub[j];
-        const int ij = tmp_idx[j];
-        rank += (sj < sub || (sj == sub && ij < idx)) ? 1 : 0;
-    }
-    order[s + rank] = idx;
-    sidx[s + rank] = sub;
-}
-
-// a voxel begins where a target begins or the cell id changes
-__global__ __launch_bounds__(kBlockQ) void k_vt_heads(const BlockDesc* __restrict__ blocks, const VtTarget* __restrict__ tg,
-                                                      const uint32_t* __restrict__ sidx, int* __restrict__ head)
-{
-    const BlockDesc bd = blocks[blockIdx.x];
-    if ((int)threadIdx.x >= bd.count) return;
-    const int e = bd.start + (int)threadIdx.x, p = tg[bd.item].pbase + e;
-    head[p] = (e == 0 || sidx[p] != sidx[p - 1]) ? 1 : 0;
-}
-
-// One thread per target (and one more), after the scan of the heads (slot[p] = voxels in front of sorted position p, slot[n_points] =
-// all of them): the target's first voxel in the batch-wide numbering and its voxel count; vox_base[n_targets] = the voxels of the
-// batch, which the statistics launches read; the end of the last voxel; the counter of the wavefront voxels' list back to zero
-__global__ __launch_bounds__(256) void k_vt_finish(int n_targets, int n_points, const VtTarget* __restrict__ tg, const int* __restrict__ slot,
-                                                   int* __restrict__ vox_base, int* __restrict__ n_vox, int* __restrict__ vstart,
-                                                   int* __restrict__ big_count)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t == n_targets) { const int all = slot[n_points]; vox_base[t] = all; vstart[all] = n_points; *big_count = 0; }
-    if (t >= n_targets) return;
-    const VtTarget& T = tg[t];
-    const int base = slot[T.pbase];
-    vox_base[t] = base;
-    n_vox[t] = slot[T.pbase + T.m] - base;
-}
-
-__global__ __launch_bounds__(kBlockQ) void k_vt_starts(const BlockDesc* __restrict__ blocks, const VtTarget* __restrict__ tg,
-                                                       const int* __restrict__ head, const int* __restrict__ slot, int* __restrict__ vstart)
-{
-    const BlockDesc bd = blocks[blockIdx.x];
-    if ((int)threadIdx.x >= bd.count) return;
-    const int p = tg[bd.item].pbase + bd.start + (int)threadIdx.x;
-    if (head[p]) vstart[slot[p]] = p;
-}
-
-// every dense table all -1: one workgroup per chunk of one table.  A chunk starts at a multiple of kVtFillChunk entries of an
-// allocation, so its first entry is 16-byte aligned
-__global__ __launch_bounds__(256) void k_vt_fill(const VtChunk* __restrict__ chunks)
-{
-    const VtChunk ch = chunks[blockIdx.x];
-    int4* q = reinterpret_cast<int4*>(ch.p);
-    const int n4 = ch.count >> 2;
-    for (int i = threadIdx.x; i < n4; i += 256) q[i] = make_int4(-1, -1, -1, -1);
-    const int rest = (n4 << 2) + (int)threadIdx.x;
-    if (rest < ch.count) ch.p[rest] = -1;
-}
+static_assert(sizeof(VtTarget) == 96, "table layout");
 
 // The family's record for launch_voxel_stats_dev (lisreg_fp64_sums.hpp): voxel v of the batch belongs to the last target whose first voxel
 // is not behind v (targets without voxels share the next one's base and lose); the body is the single kernels'
@@ -187,11 +58,7 @@ struct VtBuild {
     const uint32_t* sidx;
     template <bool WAVE> static __device__ __forceinline__ void voxel(const VtBuild& B, int v, int lane)
     {
-        int lo = 0, hi = B.n_targets - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (B.vox_base[mid] <= v) lo = mid; else hi = mid - 1;
-        }
+        const int lo = vt_target_of(B.vox_base, B.n_targets, v);
         const VtTarget& T = B.tg[lo];
         const int vl = v - B.vox_base[lo];
         if (vl >= T.cap) return;                                    // (cannot happen: a target has at most min(m, n_cells) voxels)
@@ -272,7 +139,7 @@ int lisreg_vgicp_set_target_batch(lisreg_ctx* c, int n_targets, lisreg_vgicp_tar
             continue;
         }
         p.live = true;
-        p.want = std::min(p.total, std::max(kVtMinBuckets, kVtBucketsPerPoint * (long long)S.m));
+        p.want = vt_buckets_wanted(p.total, S.m);
         want_all += p.want;
         n_chunks += (p.total + kVtFillChunk - 1) / kVtFillChunk;
         M += S.m;
@@ -320,12 +187,10 @@ int lisreg_vgicp_set_target_batch(lisreg_ctx* c, int n_targets, lisreg_vgicp_tar
             double* cov = c->vg_cov.as<double>() + 6 * (size_t)p.pbase;
             ft_add_target(c, F, t, vg, k, P->plane_epsilon, G.sorted.as<float4>(), G.cells.as<int>(), c->vg_idx.as<int>() + F.hj[(size_t)t].off, cov);
             // the voxel sort's share of the buckets and the span that follows from it
-            long long share = p.want;
-            if (want_all > kVtBucketCap) share = std::max(1LL, share * kVtBucketCap / want_all);
-            const long long span = (p.total + share - 1) / share;
-            p.d.span = (uint32_t)span;
+            int nbk = 0;
+            p.d.span = vt_bucket_span(p.total, p.want, want_all, &nbk);
             V.pts = F.hd[t].pts_out; V.cov = cov; V.stats = G.stats.as<double>(); V.cell = G.cell.as<int>(); V.table = G.table.as<int>();
-            V.n_cells = p.total; V.d = p.d; V.m = m; V.n_buckets = (int)((p.total + span - 1) / span); V.cap = (int)cap;
+            V.n_cells = p.total; V.d = p.d; V.m = m; V.n_buckets = nbk; V.cap = (int)cap;
             n_buckets += V.n_buckets;
             for (long long s0 = 0; s0 < p.total; s0 += kVtFillChunk)
                 hc[ic++] = VtChunk{ V.table + s0, (int)std::min((long long)kVtFillChunk, p.total - s0), 0 };
@@ -354,14 +219,8 @@ int lisreg_vgicp_set_target_batch(lisreg_ctx* c, int n_targets, lisreg_vgicp_tar
         HIPCHK(c, hipMemcpyAsync(c->vt_tab.p, c->vt_host.p, z_up, hipMemcpyHostToDevice, st)); enq();
         HIPCHK(c, hipMemsetAsync(sb.hist, 0, sizeof(int) * (size_t)B, st)); enq();          // the extent this call uses, once
         k_vt_fill<<<(unsigned)n_chunks, 256, 0, st>>>(d_ch); enq();
-        k_vt_keys<<<nb, kBlockQ, 0, st>>>(blk, d_tg, sb.elem_bucket, sb.elem_sub, head /* the ranks, until the heads are made */, sb.hist); enq();
-        launch_exclusive_scan(sb.hist, sb.bucket_start, sb.scan_tmp, B, st); enq();
-        k_vt_scatter<<<nb, kBlockQ, 0, st>>>(blk, d_tg, sb.elem_bucket, sb.elem_sub, head, sb.bucket_start, sb.tmp_bucket, sb.tmp_sub, sb.tmp_idx); enq();
-        k_vt_rank<<<(Mi + 255) / 256, 256, 0, st>>>(Mi, sb.tmp_bucket, sb.tmp_sub, sb.tmp_idx, sb.bucket_start, order, sidx); enq();
-        k_vt_heads<<<nb, kBlockQ, 0, st>>>(blk, d_tg, sidx, head); enq();
-        launch_exclusive_scan(head, slot, sb.scan_tmp, Mi, st); enq();
-        k_vt_finish<<<(N + 256) / 256, 256, 0, st>>>(N, Mi, d_tg, slot, vox_base, n_vox, vstart, big_count); enq();
-        k_vt_starts<<<nb, kBlockQ, 0, st>>>(blk, d_tg, head, slot, vstart); enq();
+        launch_voxel_sort_targets(blk, nb, d_tg, N, Mi, B, sb, order, sidx, head, slot, vstart, vox_base, n_vox, big_count, st);
+        enq(kVtSortEnqueues);
         VtBuild Bd;
         Bd.tg = d_tg; Bd.n_targets = N; Bd.vox_base = vox_base; Bd.n_vox = vox_base + N; Bd.vstart = vstart; Bd.order = order; Bd.sidx = sidx;
         launch_voxel_stats_dev(Bd, Mi, big_count, big_list, st); enq(2);

@@ -51,7 +51,7 @@ ABI_SYMBOLS = [
     "lisreg_rangenet_label_batch",
     "lisreg_default_rangenet_knn_params", "lisreg_rangenet_knn_weights", "lisreg_rangenet_label_knn", "lisreg_rangenet_label_knn_batch",
     "lisreg_ndt_default_params", "lisreg_ndt_set_target", "lisreg_ndt_align", "lisreg_ndt_get_voxels", "lisreg_ndt_derivatives",
-    "lisreg_ndt_align_batch",
+    "lisreg_ndt_align_batch", "lisreg_ndt_set_target_batch", "lisreg_ndt_get_target", "lisreg_ndt_target_batch_counts",
     "lisreg_vgicp_default_params", "lisreg_vgicp_set_target", "lisreg_vgicp_align", "lisreg_vgicp_covariances", "lisreg_vgicp_get_voxels",
     "lisreg_vgicp_linearize", "lisreg_vgicp_align_batch", "lisreg_vgicp_set_target_batch", "lisreg_vgicp_get_target",
     "lisreg_vgicp_target_batch_counts",
@@ -87,6 +87,15 @@ class NdtParams(C.Structure):
 
 class NdtInfo(C.Structure):
     _fields_ = [("dims", C.c_int * 3), ("n_voxels", C.c_int), ("n_valid", C.c_int), ("reserved", C.c_int)]
+
+
+class NdtTargetJob(C.Structure):
+    """lisreg_ndt_target_job"""
+    _fields_ = [("slot", C.c_int), ("n", C.c_int), ("cloud", C.c_void_p), ("status", C.c_int), ("info", NdtInfo)]
+
+
+NDT_TARGET_BATCH_MAX = 1024
+NDT_TARGET_BATCH_MAX_POINTS = 1 << 27
 
 
 class NdtResult(C.Structure):
@@ -677,6 +686,10 @@ def lib():
                                              C.POINTER(C.c_longlong)]
         L.lisreg_vgicp_align_batch.argtypes = [vp, C.POINTER(vp), ip, C.c_int, C.c_int, C.c_int, C.POINTER(VgicpItemC), C.c_int,
                                                C.POINTER(VgicpParams), C.POINTER(VgicpResult), dbl, C.POINTER(VgicpBatchInfo)]
+        L.lisreg_ndt_set_target_batch.argtypes = [vp, C.c_int, C.POINTER(NdtTargetJob), C.POINTER(NdtParams)]
+        L.lisreg_ndt_get_target.argtypes = [vp, C.c_int, C.POINTER(NdtInfo), ip, ip, dbl, fp, ip, ip, ip, fp, ip, ip, ip, ip, dbl,
+                                            C.c_int, C.c_int, C.c_int, C.c_int]
+        L.lisreg_ndt_target_batch_counts.argtypes = [vp, ip, ip]
         L.lisreg_vgicp_set_target_batch.argtypes = [vp, C.c_int, C.POINTER(VgicpTargetJob), C.POINTER(VgicpParams)]
         L.lisreg_vgicp_get_target.argtypes = [vp, C.c_int, C.POINTER(VgicpInfo), ip, ip, dbl, fp, ip, fp, ip, ip, C.c_int, C.c_int, C.c_int]
         L.lisreg_vgicp_target_batch_counts.argtypes = [vp, ip, ip]
@@ -1994,6 +2007,48 @@ class Context:
     def ndt_derivatives(self, slot: int, source, params: "NdtParams", p, with_hessian: bool = True):
         """one evaluation at p = (tx, ty, tz, a, b, c): (out [28] = score, gradient, Hessian upper triangle; pairs)"""
         return self._sums_at(self._L.lisreg_ndt_derivatives, slot, source, params, [p], with_hessian)
+
+    def ndt_set_target_batch(self, jobs, params: "NdtParams"):
+        """lisreg_ndt_set_target_batch (§7v): jobs = a list of (slot, (device_ptr, n)).  Returns a list of dicts, one per job: status,
+        dims, n_voxels, n_valid (a failed job: status = ERR_ARG; last_error() names the first)."""
+        arr = (NdtTargetJob * max(len(jobs), 1))()
+        for k, job in enumerate(jobs):
+            arr[k].slot, arr[k].cloud, arr[k].n = int(job[0]), job[1][0], int(job[1][1])
+        self._chk(self._L.lisreg_ndt_set_target_batch(self._h, len(jobs), arr, C.byref(params)))
+        return [dict(status=arr[k].status, dims=list(arr[k].info.dims), n_voxels=arr[k].info.n_voxels, n_valid=arr[k].info.n_valid)
+                for k in range(len(jobs))]
+
+    def ndt_target_batch_counts(self):
+        """(enqueues, synchronisations) of the last ndt_set_target_batch of this context"""
+        e, s = C.c_int(0), C.c_int(0)
+        self._chk(self._L.lisreg_ndt_target_batch_counts(self._h, C.byref(e), C.byref(s)))
+        return e.value, s.value
+
+    def ndt_get_target(self, slot: int) -> dict:
+        """lisreg_ndt_get_target: the slot as it stands — dims, n_voxels (occupied), n_valid, n_points, n_records, min_b [3], resolution,
+        geom [11] (the search grid's origin, cell, 1 / cell, the bounding box), grid_dims [3], sorted [m, 4] float32 (the fourth word =
+        index among the finite points, as bits), cell_start [grid cells + 1], table [voxel cells], and of every voxel record, valid or
+        not: record_cells, record_flags, records [n_records, 10]"""
+        info = NdtInfo()
+        dims, min_b, res = (C.c_int * 3)(), (C.c_int * 3)(), C.c_double(0)
+        geom = np.zeros(11, np.float32)
+        gp = geom.ctypes.data_as(C.POINTER(C.c_float))
+        gd = (C.c_int * 3)()
+        m_, nv_ = C.c_int(0), C.c_int(0)
+        self._chk(self._L.lisreg_ndt_get_target(self._h, slot, C.byref(info), dims, min_b, C.byref(res), gp, gd, C.byref(m_), C.byref(nv_),
+                                                None, None, None, None, None, None, 0, 0, 0, 0))
+        m, nv, cells, n_table = m_.value, nv_.value, gd[0] * gd[1] * gd[2], dims[0] * dims[1] * dims[2]
+        srt = np.zeros((m, 4), np.float32)
+        cs, tab = np.zeros(cells + 1, np.int32), np.zeros(n_table, np.int32)
+        rc, rf, rec = np.zeros(nv, np.int32), np.zeros(nv, np.int32), np.zeros((nv, 10))
+        ip = C.POINTER(C.c_int)
+        self._chk(self._L.lisreg_ndt_get_target(self._h, slot, C.byref(info), dims, min_b, C.byref(res), gp, gd, C.byref(m_), C.byref(nv_),
+                                                srt.ctypes.data_as(C.POINTER(C.c_float)), cs.ctypes.data_as(ip), tab.ctypes.data_as(ip),
+                                                rc.ctypes.data_as(ip), rf.ctypes.data_as(ip), rec.ctypes.data_as(C.POINTER(C.c_double)),
+                                                m, cells + 1, n_table, nv))
+        return dict(dims=list(dims), n_voxels=info.n_voxels, n_valid=info.n_valid, n_points=m, n_records=nv, min_b=list(min_b),
+                    resolution=res.value, geom=geom, grid_dims=list(gd), sorted=srt, cell_start=cs, table=tab, record_cells=rc,
+                    record_flags=rf, records=rec)
 
     # -- §7k: VGICP registration -------------------------------------------------------------------------
     def vgicp_set_target(self, slot: int, cloud, params: "VgicpParams") -> dict:
