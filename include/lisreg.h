@@ -1262,14 +1262,28 @@ int  lisreg_ndt_target_batch_counts(const lisreg_ctx* ctx, int* enqueues, int* s
  * (src/node/subMapOptmizationNode.cpp:2771, commented out); src/core/registration.cpp:156-187 carries the whole fast_gicp family
  * as a comment because it would not link.  The method (Koide et al. 2021): every point of either cloud gets a distribution from
  * its k nearest points within its own cloud, regularised to a plane (eigenvalues 1, 1, plane_epsilon); the target is cut into
- * voxels of edge `resolution` holding the mean of their points and of their points' covariances; a source point is paired with the
- * voxel it falls into (DIRECT1) and a Levenberg-Marquardt loop minimises the sum of sqrt(N) d^T (C_voxel + R C_a R^T)^-1 d over
- * the pairs.  The DEFINITION is tests/vgicp_ref.py (fast_gicp's source is not available to this project); DESIGN.md §7k lists where
- * it picks a reading of fast_gicp it cannot verify.  NaN points are no points: never a neighbour, in no voxel, in no pair.
+ * voxels of edge `resolution` holding the mean of their points and of their points' covariances; a source point x' = R a + t with
+ * the cell f = floor(x' / resolution) - grid origin is paired with every voxel among the cells f + o of its neighbourhood
+ * (neighbor_search, the last int of params, §7w: DIRECT1 o = (0, 0, 0), the voxel it falls into; DIRECT7 the offsets in {-1, 0, 1}^3 with
+ * |dx| + |dy| + |dz| <= 1; DIRECT27 all of them; every offset is tested against the grid on its own, so a point one cell outside
+ * the grid still pairs with the voxels inside; the offsets are walked in ascending cell id) and a Levenberg-Marquardt loop minimises
+ * the sum of sqrt(N) d^T (C_voxel + R C_a R^T)^-1 d over the pairs; n_pairs counts pairs, not points.  The neighbourhood belongs to
+ * the alignment: a slot serves all three, and the calls that only build or read a target check the field and otherwise ignore it.
+ * The DEFINITION is tests/vgicp_ref.py with the pairing of tests/vgicp_nb_ref.py (fast_gicp's source is not available to this
+ * project); DESIGN.md §7k and §7w list where it picks a reading of fast_gicp it cannot verify.  NaN points are no points: never a
+ * neighbour, in no voxel, in no pair.
  * The GPU makes the distributions (an exact k-nearest search, one query per lane), the voxel statistics and every linearisation
  * (fp64, fixed-order sums: two evaluations of the same input give the same bits); the 6 x 6 solve and the LM loop run on the host in
  * double.  A single alignment has no fitness score (a caller who wants one has aligned_out and lisreg_nearest); the batch form below
  * (§7n) computes one per item. */
+/* neighbor_search, fast_gicp's setNeighborSearchMethod: the last int of lisreg_vgicp_params.  The struct member keeps the name it had
+ * while it was unused, `reserved` (tests/test_vgicp_ref.py compares the member names of the struct with the Python mirror's, whose
+ * list of fields is pinned by the same file); the C++ mirror's setNeighborSearchMethod and the Python mirror's neighbor_search property
+ * write it.  0 means DIRECT1 (what lisreg_vgicp_default_params writes, and a zero-initialised struct); any other value than these is
+ * refused (LISREG_ERR_ARG) by every lisreg_vgicp_* call that takes params */
+#define LISREG_VGICP_DIRECT1  1
+#define LISREG_VGICP_DIRECT7  7
+#define LISREG_VGICP_DIRECT27 27
 typedef struct lisreg_vgicp_params {
     double resolution;                  /* voxel edge */
     double transformation_epsilon;      /* a step is converged when max|exp(delta).t| is below this ... */
@@ -1279,7 +1293,7 @@ typedef struct lisreg_vgicp_params {
     int    k_correspondences;           /* points per distribution, 4 .. 32 */
     int    max_iters;                   /* outer iterations (linearisations) */
     int    lm_max_iterations;           /* trials per outer iteration */
-    int    reserved;
+    int    reserved;                    /* neighbor_search: 0 or LISREG_VGICP_DIRECT1, LISREG_VGICP_DIRECT7, LISREG_VGICP_DIRECT27 (§7w) */
 } lisreg_vgicp_params;
 typedef struct lisreg_vgicp_info {
     int dims[3];                        /* voxel grid of the target */

@@ -85,14 +85,16 @@ __device__ __forceinline__ void VgBuild::voxel(const VgBuild& B, int v, int lane
 }
 
 // ---- one linearisation ------------------------------------------------------------------------------------------------------------
-// one lane per source point (vg_linearize_lane of lisreg_vgicp_lane.hpp), one wavefront per workgroup, one partial record per workgroup
-template <bool HESS>
+// one lane per source point (vg_linearize_lane of lisreg_vgicp_lane.hpp), one wavefront per workgroup, one partial record per workgroup;
+// NB: the neighbourhood (1, 7 or 27 cells, §7w)
+template <bool HESS, int NB>
 __global__ __launch_bounds__(64) void k_vgicp_linearize(const float4* __restrict__ src, const double* __restrict__ cov, int n, VoxelView G,
                                                         VgPose P, double* __restrict__ part)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
     double acc[28], pairs;
-    vg_linearize_lane<HESS>(i < n, src + i, cov + (size_t)i * 6, G, P, acc, pairs);
+    if constexpr (NB == 1) vg_linearize_lane<HESS>(i < n, src + i, cov + (size_t)i * 6, G, P, acc, pairs);
+    else                   vg_linearize_lane_nb<HESS, NB>(i < n, src + i, cov + (size_t)i * 6, G, P, acc, pairs);
     if (threadIdx.x == 0) {
         double* o = part + (size_t)blockIdx.x * kOut;
 #pragma unroll
@@ -120,6 +122,9 @@ int check_params(lisreg_ctx* c, const lisreg_vgicp_params* P, const char* who)
     if (!(P->transformation_epsilon > 0) || !(P->rotation_epsilon > 0) || !(P->lm_init_lambda_factor > 0) || P->max_iters < 0 ||
         P->lm_max_iterations < 1 || !(P->plane_epsilon > 0 && P->plane_epsilon <= 1))
         return bad(c, std::string(who) + ": bad transformation_epsilon / rotation_epsilon / lm_init_lambda_factor / max_iters / lm_max_iterations / plane_epsilon");
+    const int nbs = vg_neighbor_search(*P);
+    if (nbs != 0 && nbs != LISREG_VGICP_DIRECT1 && nbs != LISREG_VGICP_DIRECT7 && nbs != LISREG_VGICP_DIRECT27)
+        return bad(c, std::string(who) + ": neighbor_search (the last int of params) is none of 0, 1, 7, 27");
     return LISREG_OK;
 }
 
@@ -262,8 +267,20 @@ struct VgRun {
     const float4*      src;      // the source's finite points
     const double*      cov;
     int                n;
+    int                neighbors = 0;       // vg_neighbor_search of the call's params
     int                n_evals = 0;
 };
+
+template <bool HESS>
+void launch_linearize(const VgRun& r, int nb, const VoxelView& G, const VgPose& P, double* part)
+{
+    hipStream_t st = r.c->stream;
+    switch (r.neighbors) {
+    case LISREG_VGICP_DIRECT7:  k_vgicp_linearize<HESS, 7><<<nb, 64, 0, st>>>(r.src, r.cov, r.n, G, P, part); break;
+    case LISREG_VGICP_DIRECT27: k_vgicp_linearize<HESS, 27><<<nb, 64, 0, st>>>(r.src, r.cov, r.n, G, P, part); break;
+    default:                    k_vgicp_linearize<HESS, 1><<<nb, 64, 0, st>>>(r.src, r.cov, r.n, G, P, part); break;     // 0 and 1 (check_params)
+    }
+}
 
 int evaluate(VgRun& r, const double T[16], bool hess, double out[kOut])
 {
@@ -273,8 +290,8 @@ int evaluate(VgRun& r, const double T[16], bool hess, double out[kOut])
     const int nb = (r.n + 63) / 64;
     const int rc = eval_totals(c, nb, [&](double* part) {
         ctx_prof_mark(c, 0);                                       // "assoc" = the linearisations (both launches), one interval each
-        if (hess) k_vgicp_linearize<true><<<nb, 64, 0, c->stream>>>(r.src, r.cov, r.n, G, P, part);
-        else      k_vgicp_linearize<false><<<nb, 64, 0, c->stream>>>(r.src, r.cov, r.n, G, P, part);
+        if (hess) launch_linearize<true>(r, nb, G, P, part);
+        else      launch_linearize<false>(r, nb, G, P, part);
     }, true, out);
     if (!rc) ++r.n_evals;
     return rc;
@@ -299,6 +316,7 @@ int stage_source(lisreg_ctx* c, const char* who, int slot, const void* source, i
     rc = distributions(c, who, *raw, n, P->k_correspondences, P->plane_epsilon, 0.f, bb, &m, nullptr);
     if (rc) return rc;
     r->c = c; r->T = T; r->src = c->vg_pts.as<float4>(); r->cov = c->vg_cov.as<double>(); r->n = m;
+    r->neighbors = vg_neighbor_search(*P);
     return LISREG_OK;
 }
 

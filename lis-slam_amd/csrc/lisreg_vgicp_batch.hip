@@ -31,8 +31,8 @@ struct VgWork {
 
 // The evaluations of the entries [e_lo, e_hi) of the round (the linearising ones with HESS, the error evaluations without): lanes
 // 64 b .. 64 b + 63 of the entry's source, one partial record per workgroup, as k_vgicp_linearize.  Launched over the workgroups
-// wg_start[e_lo] .. wg_start[e_hi].
-template <bool HESS>
+// wg_start[e_lo] .. wg_start[e_hi].  NB: the neighbourhood of the batch (1, 7 or 27 cells, §7w).
+template <bool HESS, int NB>
 __global__ __launch_bounds__(64) void k_vgicp_linearize_batch(const VgWork* __restrict__ work, const int* __restrict__ wg_start, int e_lo, int e_hi,
                                                               const float4* __restrict__ src, const double* __restrict__ cov,
                                                               double* __restrict__ part)
@@ -46,7 +46,8 @@ __global__ __launch_bounds__(64) void k_vgicp_linearize_batch(const VgWork* __re
     const VgPose P = w->P;
     const size_t s = (size_t)w->src_off + (size_t)i;
     double acc[28], pairs;
-    vg_linearize_lane<HESS>(i < n, src + s, cov + s * 6, G, P, acc, pairs);
+    if constexpr (NB == 1) vg_linearize_lane<HESS>(i < n, src + s, cov + s * 6, G, P, acc, pairs);
+    else                   vg_linearize_lane_nb<HESS, NB>(i < n, src + s, cov + s * 6, G, P, acc, pairs);
     if (threadIdx.x == 0) {
         double* o = part + (size_t)g * kOut;
 #pragma unroll
@@ -89,11 +90,22 @@ struct VgBatch : LmBatchFamily<lisreg_vgicp_params, lisreg_vgicp_result> {
         w->src_off = src_off; w->n = n; w->reserved = 0;
     }
 
-    static void launch_round(lisreg_ctx* c, const Params&, const BatchRound<Work>& r)
+    template <int NB>
+    static void launch_round_nb(const BatchRound<Work>& r)
+    {
+        if (r.n_lin) k_vgicp_linearize_batch<true, NB><<<r.g_lin, 64, 0, r.st>>>(r.work, r.start, 0, r.n_lin, r.src, r.cov, r.part);
+        if (r.ne > r.n_lin) k_vgicp_linearize_batch<false, NB><<<r.g - r.g_lin, 64, 0, r.st>>>(r.work, r.start, r.n_lin, r.ne, r.src, r.cov, r.part);
+    }
+
+    // a batch has one neighbourhood, that of its params
+    static void launch_round(lisreg_ctx* c, const Params& P, const BatchRound<Work>& r)
     {
         ctx_prof_mark(c, 0);                                       // lisreg_get_timing: "assoc" = the evaluations of a round (with the totals), one interval
-        if (r.n_lin) k_vgicp_linearize_batch<true><<<r.g_lin, 64, 0, r.st>>>(r.work, r.start, 0, r.n_lin, r.src, r.cov, r.part);
-        if (r.ne > r.n_lin) k_vgicp_linearize_batch<false><<<r.g - r.g_lin, 64, 0, r.st>>>(r.work, r.start, r.n_lin, r.ne, r.src, r.cov, r.part);
+        switch (vg_neighbor_search(P)) {
+        case LISREG_VGICP_DIRECT7:  launch_round_nb<7>(r); break;
+        case LISREG_VGICP_DIRECT27: launch_round_nb<27>(r); break;
+        default:                    launch_round_nb<1>(r); break;                                 // 0 and 1 (vg_check_params)
+        }
     }
 };
 

@@ -555,6 +555,8 @@ public:
     void setTransformationEpsilon(double e) { prm_.transformation_epsilon = e; }
     void setRotationEpsilon(double e) { prm_.rotation_epsilon = e; }
     void setMaximumIterations(int n) { prm_.max_iters = n; }
+    // fast_gicp's setNeighborSearchMethod (§7w): LISREG_VGICP_DIRECT1 / 7 / 27; of the alignment, so the target is not built again
+    void setNeighborSearchMethod(int mode) { prm_.reserved = mode; }
     void setInputTarget(const PointCloud<PointT>& cloud) {
         target_ = &cloud;
         check(lisreg_vgicp_set_target(tree_.ctx(), vgicp_slot_, cloud.points.data(), (int)cloud.size(), (int)sizeof(PointT), SearchTree<PointT>::fmt(), &prm_, &info_));
@@ -780,6 +782,8 @@ public:
     void setTransformationEpsilon(double e) { prm_.transformation_epsilon = e; }
     void setRotationEpsilon(double e) { prm_.rotation_epsilon = e; }
     void setMaximumIterations(int n) { prm_.max_iters = n; }
+    // fast_gicp's setNeighborSearchMethod (§7w): LISREG_VGICP_DIRECT1 / 7 / 27, one for all candidates of a batch
+    void setNeighborSearchMethod(int mode) { prm_.reserved = mode; }
     const lisreg_vgicp_params& params() const { return prm_; }
     // the submap of a candidate into its slot (a submap that stays resident between key frames is set once)
     void setCandidateTarget(int slot, const PointCloud<PointT>& cloud) {

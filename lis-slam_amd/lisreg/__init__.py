@@ -114,6 +114,19 @@ class VgicpParams(C.Structure):
                 ("lm_init_lambda_factor", C.c_double), ("plane_epsilon", C.c_double), ("k_correspondences", C.c_int),
                 ("max_iters", C.c_int), ("lm_max_iterations", C.c_int), ("reserved", C.c_int)]
 
+    # neighbor_search (§7w) is the struct's last int, whose member is named `reserved` in include/lisreg.h and here
+    @property
+    def neighbor_search(self) -> int:
+        """0 or VGICP_DIRECT1, VGICP_DIRECT7, VGICP_DIRECT27: the voxel neighbourhood of an alignment"""
+        return self.reserved
+
+    @neighbor_search.setter
+    def neighbor_search(self, mode: int):
+        self.reserved = int(mode)
+
+
+VGICP_DIRECT1, VGICP_DIRECT7, VGICP_DIRECT27 = 1, 7, 27
+
 
 class VgicpInfo(C.Structure):
     _fields_ = [("dims", C.c_int * 3), ("n_voxels", C.c_int), ("n_points", C.c_int)]

@@ -52,9 +52,9 @@ def small_motion(rng):
     return M
 
 
-def measure(lisreg, ctx, hip, tgt, src, guess, candidates, reps):
+def measure(lisreg, ctx, hip, tgt, src, guess, candidates, reps, neighbors=1):
     d_tgt, d_src = lisreg.DeviceArray(tgt), lisreg.DeviceArray(src)
-    P = lisreg.vgicp_default_params()
+    P = lisreg.vgicp_default_params() if neighbors == 1 else lisreg.vgicp_default_params(neighbor_search=neighbors)
     stream = C.c_void_p(ctx.stream)
     source = (d_src.ptr, len(src))
 
@@ -148,6 +148,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1000)
     ap.add_argument("--out", default=None)
     ap.add_argument("--md", default=None)
+    ap.add_argument("--neighbors", type=int, choices=(1, 7, 27), default=1,
+                    help="the voxel neighbourhood of the batch and of the single calls (DIRECT1 / 7 / 27, DESIGN.md section 7w)")
     a = ap.parse_args()
     cand = [int(v) for v in a.candidates.split(",")]
     import lisreg
@@ -157,23 +159,26 @@ def main():
     c = synth.make_case(h=16, w=225, m_points=300000, scan_seed=1000, local_radius=12, trans=0.3, rot_deg=2.0, pose_xy=(32, 31))
     scene = measure(lisreg, ctx, hip, records(np.concatenate([synth.pcl_xyz(c["tgt_corner"]), synth.pcl_xyz(c["tgt_surf"])])),
                     records(np.concatenate([synth.pcl_xyz(c["src_corner"]), synth.pcl_xyz(c["src_surf"])])),
-                    synth.pose_matrix(c["T_init"]).astype(np.float32), cand, a.reps)
+                    synth.pose_matrix(c["T_init"]).astype(np.float32), cand, a.reps, a.neighbors)
     tc, ts = synth.make_submap(a.target_points)
     sc = synth.make_scan(a.h, a.w, a.seed)
     T0 = synth.perturb_pose(sc["T_true"], np.random.default_rng(a.seed + 7919), 0.3, 2.0)
     bench = measure(lisreg, ctx, hip, records(np.concatenate([synth.pcl_xyz(x) for x in (tc, ts)])),
                     records(np.concatenate([synth.pcl_xyz(x) for x in (sc["corner"], sc["surf"])])),
-                    synth.pose_matrix(T0).astype(np.float32), cand, a.reps)
+                    synth.pose_matrix(T0).astype(np.float32), cand, a.reps, a.neighbors)
     line = dict(workload="vgicp_batch", reps=a.reps, candidates=cand, slots=N_SLOTS, scene=scene, bench=bench,
                 what="timings only: host clock around calls that end in a synchronise, the library's HIP-event intervals inside them; the loop of "
                      "single calls computes no fitness score; no counters, nothing tuned")
+    nb = "" if a.neighbors == 1 else f" --neighbors {a.neighbors}"          # (the default's output is the one it always was)
+    if nb:
+        line["neighbors"] = a.neighbors
     text = json.dumps(line)
     print(text)
     with open(a.out or os.path.join(ROOT, "profiles", "vgicp_batch_bench.json"), "w") as f:
         f.write(text + "\n")
     with open(a.md or os.path.join(ROOT, "profiles", "vgicp_batch.md"), "w") as f:
         f.write("# VGICP verification of a candidate list: the batch against the loop of single calls\n\n"
-                f"`python tools/vgicp_batch_bench.py --candidates {a.candidates} --reps {a.reps}` on one MI355X, medians over {a.reps} repetitions "
+                f"`python tools/vgicp_batch_bench.py --candidates {a.candidates} --reps {a.reps}{nb}` on one MI355X, medians over {a.reps} repetitions "
                 "(host clock around calls that end in a synchronise; the event columns are the library's HIP-event intervals added up over a "
                 "call).  The loop computes no fitness score, the batch does; its time without the fitness pass is in brackets.  The results of "
                 "the two are equal bit for bit (asserted by the tool).  Timings only: nothing was promised in advance or tuned to them.\n\n"

@@ -44,6 +44,8 @@ def main():
     ap.add_argument("--w", type=int, default=1800)
     ap.add_argument("--seed", type=int, default=1000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--neighbors", type=int, choices=(1, 7, 27), default=1,
+                    help="the voxel neighbourhood of the linearisations and alignments (DIRECT1 / 7 / 27, DESIGN.md section 7w)")
     a = ap.parse_args()
     import lisreg
     from lisreg import synth
@@ -61,7 +63,7 @@ def main():
     ctx = lisreg.Context(0)
     hip = lisreg.hip_runtime()
     d_tgt, d_src, d_out = lisreg.DeviceArray(tgt), lisreg.DeviceArray(src), lisreg.DeviceArray(np.zeros_like(src))
-    P = lisreg.vgicp_default_params()
+    P = lisreg.vgicp_default_params() if a.neighbors == 1 else lisreg.vgicp_default_params(neighbor_search=a.neighbors)
     stream = C.c_void_p(ctx.stream)
 
     def sync():
@@ -125,6 +127,8 @@ def main():
                 icp_align_ms=med_iqr(t_icp)[0], icp_align_iqr_ms=med_iqr(t_icp)[1], icp_iters=ricp["iters"], icp_end_from_truth_m=off(ricp["T"]),
                 guess_from_truth_m=off(guess),
                 what="timings only: host clock around calls that end in a synchronise, the library's HIP-event intervals inside them; no counters, nothing tuned")
+    if a.neighbors != 1:                                               # (the default's line is the one it always was)
+        line["neighbors"] = a.neighbors
     text = json.dumps(line)
     print(text)
     out = a.out or os.path.join(ROOT, "profiles", "vgicp_bench.json")
